@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- QP-subproblem solves/sec of the MI355X-native engine (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch: every rank solves its shard of
 independent hs071-scale QPs (the derived hs071 first QP and seeded 1 % perturbations of it,
@@ -12,7 +12,17 @@ independent (no data-path collective) -> weak scaling; `value` = QPs of all rank
 `--gpus N` with N > 1 and no torchrun environment: bench.py starts the N ranks itself (a child
 `python -m torch.distributed.run`, before anything touches the GPU) and exits with its code.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the headline line: the contract keys
+(`value`, `ms_per_step` = wall milliseconds per timed step, ...) and `config` (workload, engine).
+`--dump-outputs DIR` writes what the last timed step handed its caller, rank 0's batch, as
+DIR/<name>.npy (float64: x, y, working sets, status, nWSR, objective); the inputs are seeded, so
+two builds run with the same arguments can be compared output for output.
+
+`--full` adds everything else below (per-launch statistics, the correctness guard, the scaling,
+gather and CPU legs, the secondary rooflines, the large configurations; `--no-extras` /
+`--no-large` trim it), prints the compact line of `compact_line` and writes the sidecar.
+
+With `--full` the JSON line also carries
   roofline       -- the dominant kernel of the timed region (the batched QP kernel): algorithmic
                     HBM bytes per launch / its HIP-event duration. The kernel is LDS/latency
                     bound, so the fraction is small by nature; see DESIGN.md.
@@ -189,6 +199,52 @@ def compact_line(full):
     text = json.dumps(line)
     assert len(text) < MAX_LINE_BYTES and json.loads(text)["metric"], "bench line %d bytes: must stay below %d" % (len(text), MAX_LINE_BYTES)
     return text
+
+
+def headline(args, world, elapsed, engine):
+    """The figure a plain run exists for: the QP solves of all ranks over the K timed steps / the slowest rank's wall time."""
+    B = args.batch_per_gpu
+    return {
+        "metric": "QP-subproblem solves/sec", "value": world * B * args.steps / elapsed, "unit": "QP solves/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": "hs071-scale QP batch (derived hs071 first QP + seeded 1 %% perturbations, "
+                               "nV=8 x nC=2 via QPhandler [J I -I]), cold start, %d QPs/GPU per step" % B,
+                   "qps_per_gpu": B, "engine": engine,
+                   "keep_state": bool(args.keep_state)},
+    }
+
+
+def headline_line(line):
+    """The ONE line of a plain run: the headline record, numbers rounded as compact_line rounds them."""
+    out = {k: _r(v, 7) for k, v in line.items() if k != "config"}
+    out["config"] = line["config"]
+    text = json.dumps(out)
+    assert len(text) < MAX_LINE_BYTES, "bench line %d bytes: must stay below %d" % (len(text), MAX_LINE_BYTES)
+    return text
+
+
+MAX_DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(batch, out_dir):
+    """What the timed path hands its caller after the last timed step (the batch's results, as Batch.results() returns them),
+    one float64 array per field in out_dir/<name>.npy, a row per QP. A batch whose arrays would pass MAX_DUMP_BYTES is cut to
+    a fixed, seeded sample of its members; member.npy then names them. Returns the names written."""
+    res = batch.results()
+    fields = ("x", "y", "ws_b", "ws_c", "status", "nWSR", "obj")
+    per_member = 8 * sum(np.size(res[0][k]) for k in fields) if res else 0
+    keep = np.arange(len(res))
+    if per_member * len(res) > MAX_DUMP_BYTES:
+        rng = np.random.default_rng(20260103)
+        keep = np.sort(rng.choice(len(res), MAX_DUMP_BYTES // (per_member + 8), replace=False))   # (+ 8: member.npy)
+    arrays = {k: np.array([res[i][k] for i in keep], dtype=np.float64) for k in fields}
+    if len(keep) < len(res):
+        arrays["member"] = keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return sorted(arrays)
 
 
 def write_extras(full):
@@ -933,7 +989,13 @@ def main():
                     help="never run hipcc / make (profiled runs: build first, outside rocprofv3 -- tools/*.sh)")
     ap.add_argument("--keep-state", type=int, default=0,
                     help="1: every cold solve also writes the hot-start image (1.7 KB/QP) back to HBM")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step (rank 0's batch) as DIR/<name>.npy, float64")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beside the headline (statistics, guard, CPU and secondary legs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     NO_BUILD = args.no_build
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1017,7 +1079,21 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # launch-by-launch statistics (each launch bracketed by its own HIP events; outside the timed region)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(batch, args.dump_outputs)
+    if not args.full:
+        if rank == 0:
+            kdesc = HEADLINE_KERNELS.get(batch.last_kernel(), HEADLINE_KERNELS[1])[2]
+            text = headline_line(headline(args, world, elapsed, kdesc))
+            sys.stdout.flush()
+            sys.stderr.flush()
+            os.write(result_fd, (text + "\n").encode())
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # --full from here on. launch-by-launch statistics (each launch bracketed by its own HIP events; outside the timed region)
     per_launch = []
     for _ in range(args.stat_launches):
         batch.solve(capi.MODE_COLD, 1000, sync=True)
@@ -1078,7 +1154,6 @@ def main():
         n_bad = int(tb.item())
 
     if rank == 0:
-        total = world * B * args.steps
         k_ms = kernel_ms_total / args.steps   # average launch duration over the timed region
         bytes_launch = float(sum(qp_algorithmic_bytes(q) for q in probs))
         achieved = bytes_launch / (k_ms * 1e-3) / 1e9
@@ -1088,15 +1163,9 @@ def main():
         if batch.last_kernel() == 2 and args.keep_state:      # (the build that writes the state blocks back)
             kname = kkey = "lane_qp_kernel<2, true, true>"
         traffic, tfile = pmc_traffic(kkey, ffac) if B == 65536 else (None, None)
-        line = {
-            "metric": "QP-subproblem solves/sec", "value": total / elapsed, "unit": "QP solves/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": "hs071-scale QP batch (derived hs071 first QP + seeded 1 %% perturbations, "
-                                   "nV=8 x nC=2 via QPhandler [J I -I]), cold start, %d QPs/GPU per step" % B,
-                       "qps_per_gpu": B, "engine": kdesc,
-                       "keep_state": bool(args.keep_state),
-                       "mean_nWSR": float(np.mean([r["nWSR"] for r in res])), "unsolved_or_kkt_fail": n_bad},
+        line = headline(args, world, elapsed, kdesc)
+        line["config"].update({"mean_nWSR": float(np.mean([r["nWSR"] for r in res])), "unsolved_or_kkt_fail": n_bad})
+        line.update({
             "roofline": {"kernel": kname, "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": tfile,
                          "traffic_note": "from the committed rocprofv3 --pmc passes of this command, not measured in this run: "
@@ -1108,7 +1177,7 @@ def main():
                          "kernel_ms": k_ms, "algorithmic_bytes_per_launch": bytes_launch,
                          "note": knote},
             "kernel_ms_stats": quartiles(per_launch),
-        }
+        })
         issue = pmc_issue_roofline(kkey) if B == 65536 else None
         if issue:
             line["roofline_lds"] = issue

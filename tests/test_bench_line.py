@@ -1,10 +1,12 @@
-"""The line bench.py prints must survive the driver's record: one JSON object, below 4 KB, with the contract keys, `roofline`
+"""The line `bench.py --full` prints must survive the driver's record: one JSON object, below 4 KB, with the contract keys, `roofline`
 and `cpu_baseline` (the 20 KB line of round 4 was cut and parsed as nothing). Built here from canned numbers --
-the full record of round 4's last builder run (tests/golden/bench_full_record_r04.json) -- no GPU involved."""
+the full record of round 4's last builder run (tests/golden/bench_full_record_r04.json) -- no GPU involved. The same for
+the headline line of a plain run and for the arrays of --dump-outputs."""
 import json
 import os
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -60,3 +62,48 @@ def test_oversized_line_is_refused():
     full["config"]["workload"] = "w" * 5000
     with pytest.raises(AssertionError):
         bench.compact_line(full)
+
+
+def test_plain_line_carries_the_headline_keys():
+    import argparse
+    args = argparse.Namespace(batch_per_gpu=65536, steps=20, warmup=5, keep_state=0)
+    line = json.loads(bench.headline_line(bench.headline(args, 1, 0.9, "lane_qp_kernel<2, false, true>")))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus"):
+        assert k in line, k
+    assert line["metric"] == "QP-subproblem solves/sec" and line["unit"] == "QP solves/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f64" and line["steps"] == 20 and line["warmup"] == 5
+    assert line["value"] == pytest.approx(65536 * 20 / 0.9, rel=1e-6)
+    assert line["ms_per_step"] == pytest.approx(1e3 * 0.9 / 20, rel=1e-6)
+    assert line["config"]["qps_per_gpu"] == 65536 and "roofline" not in line and "extras" not in line
+
+
+class _FakeBatch:
+    def __init__(self, nq):
+        rng = np.random.default_rng(7)
+        self.res = [dict(x=rng.normal(size=8), y=rng.normal(size=10), ws_b=rng.integers(-1, 2, 8).astype(np.int32),
+                         ws_c=rng.integers(-1, 2, 2).astype(np.int32), status=20, nWSR=2, obj=float(q)) for q in range(nq)]
+
+    def results(self):
+        return self.res
+
+
+def test_dump_outputs_writes_one_float64_array_per_field(tmp_path):
+    b = _FakeBatch(300)
+    names = bench.dump_outputs(b, str(tmp_path))
+    assert names == ["nWSR", "obj", "status", "ws_b", "ws_c", "x", "y"]
+    x = np.load(tmp_path / "x.npy")
+    assert x.dtype == np.float64 and x.shape == (300, 8) and np.array_equal(x[17], b.res[17]["x"])
+    assert np.load(tmp_path / "ws_c.npy").shape == (300, 2) and np.array_equal(np.load(tmp_path / "obj.npy"), np.arange(300.0))
+
+
+def test_dump_outputs_samples_a_large_batch_within_the_cap(tmp_path, monkeypatch):
+    monkeypatch.setattr(bench, "MAX_DUMP_BYTES", 64 * 1024)
+    b = _FakeBatch(2000)
+    bench.dump_outputs(b, str(tmp_path / "a"))
+    bench.dump_outputs(b, str(tmp_path / "b"))
+    total = sum(np.load(p).nbytes for p in (tmp_path / "a").iterdir())
+    assert total <= 64 * 1024
+    member = np.load(tmp_path / "a" / "member.npy").astype(int)
+    assert 0 < len(member) < 2000 and np.array_equal(member, np.sort(member))
+    assert np.array_equal(member, np.load(tmp_path / "b" / "member.npy").astype(int))      # the same sample every run
+    assert np.array_equal(np.load(tmp_path / "a" / "obj.npy"), member.astype(float))
