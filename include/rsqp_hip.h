@@ -227,7 +227,13 @@ int rsqp_read_qore_dump(const char *path, double *lb, double *ub, double *lbA, d
 /* ------------------------------------------------------------------------------------ */
 /* nq problems of individual size; nV[q], nC[q], and per problem CSC matrices given as
  * concatenated arrays with offsets: Ajc_off[q] indexes into Ajc (length sum(nV+1)),
- * Annz_off[q] into Air/Aval; likewise H. Everything is copied to the device once. */
+ * Annz_off[q] into Air/Aval; likewise H. Everything is copied to the device once.
+ * Size limit: every member has at most RSQP_BATCH_MAX_V variables and RSQP_BATCH_MAX_C constraints; a larger
+ * member, or a state block the device cannot allocate, gives RSQP_ERR_TOO_LARGE. Batches whose largest member's
+ * solver image fits the LDS of a CU (about 90 variables) run the LDS-resident kernels; any other batch runs ALL its
+ * members on the HBM-resident kernel (rsqp_batch_get_last_kernel() == 3). */
+#define RSQP_BATCH_MAX_V 512
+#define RSQP_BATCH_MAX_C 512
 int rsqp_batch_create(int nq, const int *nV, const int *nC, const int *Ajc, const int *Air,
                       const double *Aval, const int *Hjc, const int *Hir, const double *Hval,
                       int device, rsqp_batch **out);
@@ -250,7 +256,8 @@ int rsqp_batch_set_keep_state(rsqp_batch *b, int keep);
 /* which kernel the last rsqp_batch_solve launched (diagnostics; all of them stand in for the SQProblem::init / hotstart calls of
  * qpOASESInterface.cpp:155,180-206): 0 = the LDS-resident null-space kernels (+ the mid-size tableau kernel), 1 = the hs071-scale
  * tableau kernel with 8 lanes per problem, 2 = the lane-per-problem kernel (cold starts of one-shape batches of at most 8 x 2
- * with more than 16 384 members; RSQP_LANE); -1 before the first solve */
+ * with more than 16 384 members; RSQP_LANE), 3 = the HBM-resident null-space kernel (one workgroup per problem, its image in
+ * the batch state block: batches whose largest member does not fit the LDS-resident kernels); -1 before the first solve */
 int rsqp_batch_get_last_kernel(const rsqp_batch *b);
 /* device time of the last rsqp_batch_solve in milliseconds (HIP events on its stream) */
 float rsqp_batch_last_solve_ms(rsqp_batch *b);

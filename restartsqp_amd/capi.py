@@ -465,7 +465,8 @@ class Batch:
         check(lib().rsqp_batch_set_keep_state(self._h, int(bool(keep))))
 
     def last_kernel(self):
-        """0 LDS null-space kernels, 1 tableau kernel with 8 lanes per problem, 2 lane-per-problem kernel (rsqp_batch_get_last_kernel)"""
+        """0 LDS null-space kernels, 1 tableau kernel with 8 lanes per problem, 2 lane-per-problem kernel, 3 HBM-resident
+        null-space kernel (batches beyond the LDS fit) (rsqp_batch_get_last_kernel)"""
         return lib().rsqp_batch_get_last_kernel(self._h)
 
     def last_solve_ms(self):

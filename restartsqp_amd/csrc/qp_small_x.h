@@ -1,4 +1,4 @@
-// qp_small_x.h -- included by qp_small.hip inside its anonymous namespace.
+// qp_small_x.h -- included by qp_small.hip and qp_small_hbm.hip inside their anonymous namespaces (after qp_small_engine.h).
 //
 // EngineX: the LDS-resident engine in the EXPLICIT-INVERSE formulation of qp_large.hip
 // (orthonormal Z / Y, Minv = (A_AC,FR Y)^-1, Wz = (Z'HZ)^-1, one Householder reflection aimed at

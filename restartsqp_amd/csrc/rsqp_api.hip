@@ -1348,6 +1348,7 @@ extern "C" int rsqp_H_times(rsqp_solver *s, const double *p, double *result) {
 // =====================================================================================
 // batch of independent QPs
 // =====================================================================================
+static_assert(RSQP_BATCH_MAX_V == RSQP_HBM_MAX_V && RSQP_BATCH_MAX_C == RSQP_HBM_MAX_C, "batch size limits of rsqp_hip.h and rsqp_internal.h");
 struct rsqp_batch {
     int nq = 0, device = 0, nVmax = 0, nCmax = 0, uniV = -1, uniC = -1;
     bool uni_pat = false; int uni_annz = 0, uni_hnnz = 0; long long uni_state = 0;     // (QPPools::uni_pat)
@@ -1356,6 +1357,7 @@ struct rsqp_batch {
     SmallKnobs kn = rsqp_small_knobs_from_env();
     int state_engine = -1;                // kernel family that wrote the members' hot-start states (see rsqp_solver::state_engine)
     int last_kernel = -1;                 // rsqp_batch_get_last_kernel
+    bool hbm = false;                     // images beyond the LDS of a CU: every member on the HBM-resident kernel (qp_small_hbm.hip)
     bool h_sym = true;                    // every H symmetric value by value (the tableau kernel of qp_tiny.hip may take the batch)
     std::vector<int> h_Hjc, h_Hir;        // host copy of the H patterns (re-examined when the values change), small batches only
     std::vector<QPDesc> desc;
@@ -1449,8 +1451,19 @@ extern "C" int rsqp_batch_create(int nq, const int *nV, const int *nC, const int
         }
         offState += rsqp_state_bytes(d.nV, d.nC) / 8;
     }
-    if (!rsqp_small_qp_fits(b->nVmax, b->nCmax))
-        return fail(RSQP_ERR_TOO_LARGE, "rsqp_batch_create: a problem exceeds the LDS-resident engine");
+    if (!rsqp_small_qp_fits(b->nVmax, b->nCmax)) {
+        // the whole batch runs the HBM-resident kernel: its state slices are the images used in place (plus the dense
+        // matrices), with no extension for the KKT-tableau kernel
+        if (!rsqp_hbm_qp_fits(b->nVmax, b->nCmax))
+            return fail(RSQP_ERR_TOO_LARGE, "rsqp_batch_create: a problem exceeds the batch limit of " + std::to_string(RSQP_HBM_MAX_V) +
+                                                " variables and " + std::to_string(RSQP_HBM_MAX_C) + " constraints");
+        b->hbm = true;
+        offState = 0;
+        for (int q = 0; q < nq; q++) {
+            b->desc[q].offState = offState;
+            offState += rsqp_hbm_state_bytes(b->desc[q].nV, b->desc[q].nC) / 8;
+        }
+    }
     if (b->haveH && b->nVmax <= 8) {
         b->h_Hjc.assign(Hjc, Hjc + offHjc); b->h_Hir.assign(Hir, Hir + offHnz);
         for (int q = 0; q < nq && b->h_sym; q++) {
@@ -1463,7 +1476,8 @@ extern "C" int rsqp_batch_create(int nq, const int *nV, const int *nC, const int
     b->uni_pat = b->uniV > 0 && b->uniC >= 0;
     if (b->uni_pat) {
         const QPDesc &d0 = b->desc[0];
-        b->uni_annz = d0.annz; b->uni_hnnz = d0.hnnz; b->uni_state = rsqp_state_bytes(d0.nV, d0.nC) / 8;
+        b->uni_annz = d0.annz; b->uni_hnnz = d0.hnnz;
+        b->uni_state = (b->hbm ? rsqp_hbm_state_bytes(d0.nV, d0.nC) : rsqp_state_bytes(d0.nV, d0.nC)) / 8;
         for (int q = 1; q < nq && b->uni_pat; q++) {
             const QPDesc &d = b->desc[q];
             b->uni_pat = d.annz == d0.annz && d.hnnz == d0.hnnz &&
@@ -1495,7 +1509,16 @@ extern "C" int rsqp_batch_create(int nq, const int *nV, const int *nC, const int
     HIPCHK(b->x.alloc(offV)); HIPCHK(b->y.alloc(offV + offC)); HIPCHK(b->obj.alloc(nq));
     HIPCHK(b->ws_b.alloc(offV)); HIPCHK(b->ws_c.alloc(offC));
     HIPCHK(b->status.alloc(nq)); HIPCHK(b->ret.alloc(nq)); HIPCHK(b->nwsr.alloc(nq)); HIPCHK(b->nflips.alloc(nq));
-    HIPCHK(b->state.alloc((size_t)offState));
+    if (b->hbm) {
+        const hipError_t e = b->state.alloc((size_t)offState);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(RSQP_ERR_TOO_LARGE, "rsqp_batch_create: the state block of the batch (" + std::to_string(8 * offState) +
+                                                " bytes) cannot be allocated: " + hipGetErrorString(e));
+        }
+    } else {
+        HIPCHK(b->state.alloc((size_t)offState));
+    }
     HIPCHK(hipStreamSynchronize(b->stream));
     guard.b = nullptr;
     *out = b;
@@ -1540,6 +1563,16 @@ extern "C" int rsqp_batch_solve(rsqp_batch *b, int mode, int max_nWSR) {
     HIPCHK(hipSetDevice(b->device));
     QPPools p = pools_of(b);
     if (!b->timing) HIPCHK(hipEventRecord(b->ev0, b->stream));
+    if (b->hbm) {
+        // state family 3: images in place in HBM (another layout than the LDS-resident kernels' copies)
+        if ((mode == RSQP_MODE_HOT_VECTORS || mode == RSQP_MODE_HOT_MATRICES) && b->state_engine != 3) mode = RSQP_MODE_COLD;
+        b->state_engine = 3;
+        b->last_kernel = 3;
+        hipError_t e = rsqp_launch_small_qp_hbm(b->kn, p, b->nq, b->nVmax, b->nCmax, mode, max_nWSR, b->stream);
+        if (e != hipSuccess) return fail(RSQP_ERR_DEVICE, std::string("QP kernel launch: ") + hipGetErrorString(e));
+        if (!b->timing) HIPCHK(hipEventRecord(b->ev1, b->stream));
+        return RSQP_OK;
+    }
     {
         const int fam = rsqp_small_launch_is_tiny(b->kn, p, b->nVmax, b->nCmax);
         if ((mode == RSQP_MODE_HOT_VECTORS || mode == RSQP_MODE_HOT_MATRICES) && b->state_engine != fam) mode = RSQP_MODE_COLD;

@@ -115,6 +115,15 @@ __host__ __device__ inline long long rsqp_state_bytes(int nV, int nC) {
     return b;
 }
 
+// batches whose images exceed the LDS of a CU (qp_small_hbm.hip): limits of the members' sizes, and the state slice of one
+// member -- the image used in place, 8 x 256 bytes of cross-wave partial sums, dense copies of A and H. No KKT-tableau
+// extension: the mid-size tableau kernel never sees these batches.
+#define RSQP_HBM_MAX_V 512   // = RSQP_BATCH_MAX_V / _C of rsqp_hip.h (checked in rsqp_api.hip)
+#define RSQP_HBM_MAX_C 512
+__host__ __device__ inline long long rsqp_hbm_state_bytes(int nV, int nC) {
+    return rsqp_image_bytes(nV, nC) + 8LL * 256 + 8LL * ((long long)nV * nV + (long long)nC * nV);
+}
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE attribute of a kernel: set it once per
 // (kernel, device) -- `mask` is the kernel's own bitmask of devices already done (thread-safe)
 inline void rsqp_allow_full_lds(const void *fn, std::atomic<unsigned long long> &mask, int bytes) {
@@ -142,3 +151,8 @@ hipError_t rsqp_launch_lane_qp(const QPPools &p, int nq, int maxWSR, hipStream_t
 // handle or batch
 int rsqp_small_launch_is_tiny(const SmallKnobs &kn, const QPPools &p, int nVmax, int nCmax);
 hipError_t rsqp_launch_tiny_qp(const SmallKnobs &kn, const QPPools &p, int nq, int nVmax, int nCmax, int mode, int maxWSR, hipStream_t stream);
+// qp_small_hbm.hip: the null-space engines with their images in HBM, one workgroup per problem, for batches beyond
+// rsqp_small_qp_fits (every member of such a batch, the small ones included); members up to RSQP_HBM_MAX_V x RSQP_HBM_MAX_C
+int rsqp_hbm_qp_fits(int nVmax, int nCmax);
+hipError_t rsqp_launch_small_qp_hbm(const SmallKnobs &kn, const QPPools &p, int nq, int nVmax, int nCmax, int mode, int maxWSR,
+                                    hipStream_t stream);
