@@ -101,7 +101,7 @@ k_dgemm(int ta, int tb, int m, int n, int kfull, int kc, double alpha, const dou
     extern __shared__ __attribute__((aligned(16))) double gemm_lds[];
     // RSQP_GEMM_DB=1 (tuning build, tools/gemm_pad_variants.sh): two LDS buffers, the tiles of step i + 1 stored while step i is
     // still being multiplied, one barrier per K step instead of two -- measured SLOWER (51.3 vs 53.1 TFLOP/s on 4096^3, QR
-    // 100.4 vs 97.8 ms): the barriers are not what keeps the MFMA pipe at 67 % busy. Row paddings 2 .. 20 doubles: no difference. Other tile shapes (RSQP_GEMM_TILE), K step 32
+    // 100.4 vs 97.8 ms): the barriers are not what keeps the MFMA pipe at 67 % busy. Row paddings 2 .. 20 doubles: no difference. Other tile shapes, K step 32
     // (spills), the AGPR form of the MFMAs (a 64 / 64 register split: spills, 16 TFLOP/s): all slower or equal.
     constexpr int NBUF = RSQP_GEMM_DB ? 2 : 1;
     constexpr int TILE_DOUBLES = GK * ((TM + GPAD) + (TN + GPAD));
@@ -232,12 +232,9 @@ static hipError_t dgemm_ws(bool transA, bool transB, int m, int n, int k, double
         TN = n <= 64 || (long long)((m + TM - 1) / TM) * ((n + 127) / 128) * std::max(batch, 1) < 512 ? 64 : 128;
     }
     // a block of reflectors against a wide matrix (W = V'C: 256 x n with an inner dimension of thousands): the large tile,
-    // and K split so that the chip has work -- 64 x 64 tiles ran these at 29-35 TFLOP/s (RSQP_GEMM_SKINNY=0: as before)
-    static const int skinny = getenv("RSQP_GEMM_SKINNY") ? atoi(getenv("RSQP_GEMM_SKINNY")) : 1;
-    const bool skinny_case = skinny && ws && m <= 512 && m >= 128 && n >= 1024 && k >= 2048 && ws_cap >= 2LL * m * n;
-    if (skinny_case) { TM = 128; TN = skinny == 2 ? 64 : 128; }
-    static const int force_tile = getenv("RSQP_GEMM_TILE") ? atoi(getenv("RSQP_GEMM_TILE")) : 0;      // tuning: 12864 / 64128 / 6464
-    if (force_tile == 12864) { TM = 128; TN = 64; } else if (force_tile == 64128) { TM = 64; TN = 128; } else if (force_tile == 6464) { TM = 64; TN = 64; }
+    // and K split so that the chip has work -- 64 x 64 tiles ran these at 29-35 TFLOP/s
+    const bool skinny_case = ws && m <= 512 && m >= 128 && n >= 1024 && k >= 2048 && ws_cap >= 2LL * m * n;
+    if (skinny_case) { TM = 128; TN = 128; }
     const int bx = (m + TM - 1) / TM, by = (n + TN - 1) / TN;
     // a long inner dimension over few output tiles: split K so that the chip has work
     int splits = 1;
@@ -252,7 +249,6 @@ static hipError_t dgemm_ws(bool transA, bool transB, int m, int n, int k, double
     double *Cout = splits > 1 ? ws : C;
     const long long ldo = splits > 1 ? m : ldc;
     const double al = splits > 1 ? 1.0 : alpha, be = splits > 1 ? 0.0 : beta;
-    static const int nw_big = getenv("RSQP_GEMM_WAVES") ? atoi(getenv("RSQP_GEMM_WAVES")) : 8;
 #define GEMM_LAUNCH(a, b, nw, mw, gk)                                                                              \
     do {                                                                                                           \
         const size_t lds_ = sizeof(double) * gk * ((a + GPAD) + (b + GPAD)) * (RSQP_GEMM_DB ? 2 : 1);               \
@@ -262,12 +258,9 @@ static hipError_t dgemm_ws(bool transA, bool transB, int m, int n, int k, double
                            lda, B, ldb, be, Cout, ldo, upper, ktri, batch > 1 ? sA : 0LL, batch > 1 ? sB : 0LL,    \
                            batch > 1 ? sC : 0LL);                                                                  \
     } while (0)
-    if (TM == 128 && TN == 128) {
-        // measured on 4096^3: 8 waves (4 resident per SIMD, 122 VGPRs) 53.5 TFLOP/s; 4 waves x 2 resident
-        // 51.5; 4 waves x 1 resident (the compiler's default allocation) 37.8; K step 32 is slower (spills)
-        if (nw_big == 8) GEMM_LAUNCH(128, 128, 8, 4, RSQP_GEMM_GK);
-        else GEMM_LAUNCH(128, 128, 4, 2, 16);
-    }
+    // measured on 4096^3: 8 waves (4 resident per SIMD, 122 VGPRs) 53.5 TFLOP/s; 4 waves x 2 resident
+    // 51.5; 4 waves x 1 resident (the compiler's default allocation) 37.8; K step 32 is slower (spills)
+    if (TM == 128 && TN == 128) GEMM_LAUNCH(128, 128, 8, 4, RSQP_GEMM_GK);
     else if (TM == 64 && TN == 128) GEMM_LAUNCH(64, 128, 4, 3, 16);
     else if (TM == 128 && TN == 64) GEMM_LAUNCH(128, 64, 4, 3, 16);
     else GEMM_LAUNCH(64, 64, 4, 4, 16);
@@ -860,55 +853,6 @@ __global__ void k_zero_block_batched(int m, int n, double *__restrict__ X, long 
     if (i < m && j < n) X[(long long)blockIdx.z * stride + i + (long long)j * ldx] = 0.0;
 }
 
-// unblocked Cholesky (upper, G = U'U) of one NB x NB diagonal block in LDS with the definiteness
-// test of the engine; also returns the inverse of the block's factor in Uinv (upper)
-__global__ void __launch_bounds__(64)
-k_potf2(int nb, double *__restrict__ G, long long ldg, const double *__restrict__ diag0, double pd_rel, double pd_abs,
-        double *__restrict__ Uinv, int *__restrict__ flag) {
-    __shared__ double Gs[NB][NB + 1], Xs[NB][NB + 1];
-    __shared__ int bad;
-    const int t = threadIdx.x;
-    if (t == 0) bad = 0;
-    for (int e = t; e < NB * NB; e += 64) {
-        const int r = e % NB, c = e / NB;
-        Gs[r][c] = (r < nb && c < nb && r <= c) ? G[r + (long long)c * ldg] : (r == c ? 1.0 : 0.0);
-        Xs[r][c] = 0.0;
-    }
-    __syncthreads();
-    for (int j = 0; j < nb; j++) {
-        // pivot: d2 = g_jj - sum_k u_kj^2 (the part of the sum from earlier panels is already in g_jj)
-        double d2 = Gs[j][j];
-        for (int k = 0; k < j; k++) d2 -= Gs[k][j] * Gs[k][j];
-        const double g0 = diag0[j], sum = g0 - d2;
-        const bool ok = d2 > pd_rel * (fabs(g0) + (sum > 0.0 ? sum : 0.0)) + pd_abs;
-        if (!ok && t == 0) bad = 1;
-        const double d = ok ? sqrt(d2) : 1.0;
-        __syncthreads();
-        // row j of U: u_jc = (g_jc - sum_k u_kj u_kc) / d, c > j
-        if (t > j && t < nb) {
-            double s = Gs[j][t];
-            for (int k = 0; k < j; k++) s -= Gs[k][j] * Gs[k][t];
-            Gs[j][t] = s / d;
-        }
-        if (t == j) Gs[j][j] = d;
-        __syncthreads();
-    }
-    if (t < nb) {
-        for (int r = t; r >= 0; r--) {
-            double s = r == t ? 1.0 : 0.0;
-            for (int c = r + 1; c <= t; c++) s -= Gs[r][c] * Xs[c][t];
-            Xs[r][t] = s / Gs[r][r];
-        }
-    }
-    __syncthreads();
-    for (int e = t; e < NB * NB; e += 64) {
-        const int r = e % NB, c = e / NB;
-        if (r < nb && c < nb) G[r + (long long)c * ldg] = r <= c ? Gs[r][c] : 0.0;
-        Uinv[e] = Xs[r][c];
-    }
-    if (t == 0 && bad) atomicAdd(flag, 1);
-}
-
 __global__ void k_get_diag(int n, const double *__restrict__ G, long long ldg, double *__restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = G[i + (long long)i * ldg];
@@ -966,14 +910,12 @@ hipError_t rsqp_dgeqrf(int m, int n, double *B, long long ldb, double eps_li, Rs
         for (int k0 = K0; k0 < K0 + ob; k0 += NB, p++) {
             const int jb = std::min(NB, K0 + ob - k0), mt = m - k0, nin = K0 + ob - k0 - jb;
             double *Vp = w->V + (k0 - K0) + (long long)(k0 - K0) * ldv;     // panel p inside the outer block's V
-            // (tried in round 3, RSQP_QR_WIDE_PANEL=1: apply a column's reflector to every remaining column of the OUTER block in
-            //  the same launch -- up to 256 workgroups instead of 64 -- and drop the three small-output products below, which run
-            //  at a few per cent of anything (64 x 192 results from an inner dimension of 10 000): 149 ms instead of 138 ms for
-            //  10 000 x 7 670, the column launches turn bandwidth-bound at ~15 us)
-            static const bool wide = getenv("RSQP_QR_WIDE_PANEL") != nullptr;
-            static const bool no_cholqr = getenv("RSQP_QR_NO_CHOLQR") != nullptr;
+            // (tried in round 3: apply a column's reflector to every remaining column of the OUTER block in the same launch -- up
+            //  to 256 workgroups instead of 64 -- and drop the three small-output products below, which run at a few per cent of
+            //  anything (64 x 192 results from an inner dimension of 10 000): 149 ms instead of 138 ms for 10 000 x 7 670, the
+            //  column launches turn bandwidth-bound at ~15 us)
             double *Tp = w->T + (long long)p * NB * NB;
-            if (w->panel_cholqr && !no_cholqr && !wide && jb == NB && mt >= 2 * NB) {
+            if (w->panel_cholqr && jb == NB && mt >= 2 * NB) {
                 // the panel in a dozen launches (see k_cholqr_pass2): Q1 lives in w->W (free until the panel is applied)
                 double *P = B + k0 + (long long)k0 * ldb, *Q1 = w->W, *X1 = w->hr, *R1 = w->hr + NB * NB, *Mx = w->hr + 2 * NB * NB;
                 const long long ldq = w->mmax;
@@ -989,7 +931,7 @@ hipError_t rsqp_dgeqrf(int m, int n, double *B, long long ldb, double eps_li, Rs
                 DCHK(rsqp_dgemm(false, false, mt - NB, NB, NB, 1.0, Q1 + NB, ldq, Mx, NB, 0.0, Vp + NB, ldv, st));          // V below the block
             } else {
                 for (int j = k0; j < k0 + jb; j++)
-                    hipLaunchKernelGGL(k_qr_col, dim3((wide ? K0 + ob : k0 + jb) - j), dim3(QC), 0, st, B, ldb, m, j, k0, Vp, ldv, w->tau, rdiag,
+                    hipLaunchKernelGGL(k_qr_col, dim3(k0 + jb - j), dim3(QC), 0, st, B, ldb, m, j, k0, Vp, ldv, w->tau, rdiag,
                                        w->norm2, eps_li, w->flag);
                 // S = V'V (jb x jb, long inner dimension: split K), T factor
                 DCHK(dgemm_ws(true, false, jb, jb, mt, 1.0, Vp, ldv, Vp, ldv, 0.0, S, jb, ws, 64LL * NB * NB, st));
@@ -997,7 +939,7 @@ hipError_t rsqp_dgeqrf(int m, int n, double *B, long long ldb, double eps_li, Rs
             }
             // reflectors back into B
             hipLaunchKernelGGL(k_panel_writeback, dim3((mt + 255) / 256, jb), dim3(256), 0, st, B, ldb, m, k0, jb, Vp, ldv, rdiag);
-            if (nin > 0 && !wide) {      // the rest of the outer block
+            if (nin > 0) {      // the rest of the outer block
                 double *Ct = B + k0 + (long long)(k0 + jb) * ldb;
                 DCHK(dgemm_ws(true, false, jb, nin, mt, 1.0, Vp, ldv, Ct, ldb, 0.0, w->W, NB, w->ws, w->ws_cap, st));   // W = V'C
                 DCHK(rsqp_dgemm(true, false, jb, nin, jb, 1.0, w->T + (long long)p * NB * NB, NB, w->W, NB, 0.0, w->W2, NB, st));   // T'W
@@ -1104,14 +1046,12 @@ hipError_t rsqp_dpotrf_upper(int n, double *G, long long ldg, double pd_rel, dou
     // (profiles/r05_j_kernel_stats_setup_full.csv). Inside an outer block the panels are right-looking on the block ROW only
     // (COB x remaining columns: a few MB).
     constexpr int COB = 256;
-    static const bool old_potf2 = getenv("RSQP_POTF2_OLD") != nullptr;
     for (int K0 = 0; K0 < n; K0 += COB) {
         const int ob = std::min(COB, n - K0), K1 = K0 + ob;
         for (int k0 = K0; k0 < K1; k0 += NB) {
             const int jb = std::min(NB, K1 - k0), nt = n - k0 - jb, mrest = K1 - k0 - jb;
             double *Gd = G + k0 + (long long)k0 * ldg;
-            if (old_potf2) hipLaunchKernelGGL(k_potf2, dim3(1), dim3(64), 0, st, jb, Gd, ldg, w->norm2 + k0, pd_rel, pd_abs, Uinv, w->flag + 1);
-            else hipLaunchKernelGGL(k_potf2_elim, dim3(1), dim3(256), CHOLQR_LDS1, st, jb, Gd, ldg, w->norm2 + k0, pd_rel, pd_abs, Uinv, w->flag + 1);
+            hipLaunchKernelGGL(k_potf2_elim, dim3(1), dim3(256), CHOLQR_LDS1, st, jb, Gd, ldg, w->norm2 + k0, pd_rel, pd_abs, Uinv, w->flag + 1);
             if (nt > 0) {
                 double *G12 = G + k0 + (long long)(k0 + jb) * ldg;
                 // U12 = Ujj^-T G12  (jb x nt): via W, then copied back

@@ -195,6 +195,8 @@ int trajectory_bench(const char *path, int reps) {
     auto options = std::make_shared<Options>();
     double us_all = 0.0, us_first = 0.0, xlast[8] = {0}, ylast[10] = {0};
     int qp_iter_last = 0;
+    // (RSQP_TRAJ_PHASES=1: where the first iteration's time goes -- structure analysis + upload of A, of H, vectors, solve)
+    const bool phases = std::getenv("RSQP_TRAJ_PHASES") != nullptr;
     for (int r = 0; r < reps; r++) {
         auto stats = std::make_shared<Stats>();
         Handler myQP(info, QP, options, nullptr);          // (Algorithm::allocate_memory: outside the reference's clock as well)
@@ -205,8 +207,6 @@ int trajectory_bench(const char *path, int reps) {
             const auto t0 = std::chrono::steady_clock::now();
             Hs071 nlp(t + 2, t + 6);
             if (k == 0) {
-                // (RSQP_TRAJ_PHASES=1: where the first iteration's time goes -- structure analysis + upload of A, of H, vectors, solve)
-                static const bool phases = std::getenv("RSQP_TRAJ_PHASES") != nullptr;
                 auto now = [] { return std::chrono::steady_clock::now(); };
                 auto us_since = [&](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::micro>(now() - a).count(); };
                 auto p0 = now();

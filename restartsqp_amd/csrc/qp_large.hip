@@ -485,8 +485,8 @@ __global__ void __launch_bounds__(NT) k_ger_gemv_t(double *__restrict__ M, long 
     }
 }
 // Everything behind the two products of a carried constraint REMOVAL (t = Y v, s' = v'Minv) in ONE launch over max(nV, n) entries
-// (n = nAC before the removal, kk = n - 1): k_keep_removal, the reflection of the last column of Y (it becomes the new column of Z:
-// written to both) and of the last column of Minv (which then fills the slot k of the removed constraint), the carried range-space
+// (n = nAC before the removal, kk = n - 1): the operands the deferred reflections keep, the reflection of the last column of Y (it
+// becomes the new column of Z: written to both) and of the last column of Minv (which then fills the slot k of the removed constraint), the carried range-space
 // part -- wY <- (1 - tau)(P wY)[0..kk), omega = (P wY)[kk], xY <- (1 - tau)(xY - omega z_new) -- and the working-set bookkeeping
 // (k_ws_remove_c). Every workgroup forms the dot product v'wY itself (same loop, same tree: the same bits in all of them);
 // workgroup 0 writes the new wY into wYout (the OTHER half of the double buffer: the others may still be reading wY).
@@ -527,14 +527,6 @@ __global__ void __launch_bounds__(NT) k_remove_tail(int n, int nV, int k, double
         znew[i] = m;
         xY[i] = om * (xY[i] - omega * m);
     }
-}
-// what the deferred reflections of Y and Minv behind a removed constraint need later (remove_constraint_tq): v twice (Y's column
-// coefficients = Minv's row coefficients), s = v'Minv with the entry of the column that is refilled zeroed, beta
-__global__ void k_keep_removal(int n, const double *__restrict__ v, const double *__restrict__ srow, int kzero, double *__restrict__ keep_v,
-                               double *__restrict__ keep_s, double *__restrict__ scal, int from, int to) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) { keep_v[i] = v[i]; keep_s[i] = i == kzero ? 0.0 : srow[i]; }
-    if (i == 0) scal[to] = scal[from];
 }
 // what a deferred reflection needs later: the Householder vector and its beta out of the way of the next products
 __global__ void k_keep_reflector(const double *__restrict__ v, int n, double *__restrict__ keep, double *__restrict__ scal, int from,
@@ -1498,34 +1490,10 @@ __global__ void __launch_bounds__(NT) k_dual_carry_remove(int k, int j, double o
         if (i != j) dyv[i] = om * (dyv[i] - f * v[i]);
     if (threadIdx.x == 0 && j != last) dyv[j] = tl;
 }
-// the border of Sinv behind an added constraint (after Sinv += u u' / s): row and column nAC = -u / s, corner 1 / s; thread nAC
-// records the working-set entry and the multiplier of the incoming constraint (yidx >= 0)
-__global__ void k_dual_border(double *Sinv, long long ldm, int nAC, const double *__restrict__ u, const double *__restrict__ scal,
-                              int *AC, int *posAC, int *Sc, int r, int side, double *y, int yidx, double yval) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j > nAC) return;
-    const double is = scal[8];
-    if (j == nAC) {
-        AC[nAC] = r; posAC[r] = nAC; Sc[r] = side;
-        if (yidx >= 0) y[yidx] = yval;
-        Sinv[(long long)nAC * ldm + nAC] = is;
-    } else {
-        const double b = -u[j] * is;
-        Sinv[(long long)j * ldm + nAC] = b;
-        Sinv[(long long)nAC * ldm + j] = b;
-    }
-}
-// the rank-1 part of a bordering is DEFERRED (it rides on the next product with Sinv, k_ger_gemv_n1): u and 1 / s out of the way
-// of the next products, zero behind the block it applies to (the kernel then updates rows / columns 0..n) only)
-__global__ void k_dual_keep_u(int n, const double *__restrict__ u, double *__restrict__ keep, double *__restrict__ scal, int to) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < n) keep[j] = u[j];
-    if (j == n) { keep[n] = 0.0; keep[n + 1] = 0.0; scal[to] = scal[8]; }
-}
 // ---- Sinv is symmetric: stored in its UPPER triangle only (entry (i, j), i <= j, at M[j ld + i]), so that a rank-1 update and a
 // product touch half the bytes. One workgroup per 64 x 64 tile (I <= J) of the triangle: optional update M += coef u u', optional
 // contributions to y = M w -- the tile's rows against w_J (into P1[J][.]) and, transposed, its columns against w_I (into
-// P2[I][.]; a diagonal tile holds i <= j only and gives its diagonal to the row part). k_sym_reduce adds the partials in tile
+// P2[I][.]; a diagonal tile holds i <= j only and gives its diagonal to the row part). k_sym_reduce_lz adds the partials in tile
 // order (deterministic). The tile passes through LDS once: coalesced column loads / stores, both products from there.
 constexpr int SYT = 64;
 __device__ __forceinline__ void sym_tile_of(int t, int &I, int &J) {
@@ -1606,28 +1574,6 @@ __global__ void __launch_bounds__(256) k_sym_tile(double *__restrict__ M, long l
     if (threadIdx.x < SYT) { if (i < n) P1[(long long)J * n + i] = rp[0][threadIdx.x] + rp[1][threadIdx.x]; }
     else if (threadIdx.x < 2 * SYT) { const int j = J * SYT + e; if (j < n) P2[(long long)I * n + j] = cp[0][e] + cp[1][e]; }
 }
-// (R / full: the result scattered by row id as well -- the multiplier step of the general range-space path)
-__global__ void k_sym_reduce(int n, int nt, const double *__restrict__ P1, const double *__restrict__ P2, double *__restrict__ y,
-                             const int *__restrict__ R = nullptr, double *__restrict__ full = nullptr) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int Ti = i / SYT;
-    // (four independent accumulators per sum: up to 2 x 120 partials per entry, one dependent load chain each measured 22 us)
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, b0 = 0.0, b1 = 0.0, b2 = 0.0, b3 = 0.0;
-    int J = Ti;
-    for (; J + 3 < nt; J += 4) {
-        a0 += P1[(long long)J * n + i]; a1 += P1[(long long)(J + 1) * n + i]; a2 += P1[(long long)(J + 2) * n + i]; a3 += P1[(long long)(J + 3) * n + i];
-    }
-    for (; J < nt; J++) a0 += P1[(long long)J * n + i];
-    int I = 0;
-    for (; I + 3 <= Ti; I += 4) {
-        b0 += P2[(long long)I * n + i]; b1 += P2[(long long)(I + 1) * n + i]; b2 += P2[(long long)(I + 2) * n + i]; b3 += P2[(long long)(I + 3) * n + i];
-    }
-    for (; I <= Ti; I++) b0 += P2[(long long)I * n + i];
-    const double val = ((a0 + a1) + (a2 + a3)) + ((b0 + b1) + (b2 + b3));
-    y[i] = val;
-    if (R) full[R[i]] = val;
-}
 // The same tile scheme for Wz = (Z'HZ)^-1 of the NULL-space path (symmetric as well; upper triangle from wz_sym_min variables on).
 // UPD 2: the elimination step behind a reflected null space (k_wz_shrink's expression) on the leading l x l block; UPD 3: the
 // rank-1 part of a bordering, u u' / rho^2, under the kernel's own definiteness guard (scal[i0] > scal[i0 + 1]: k_wz_grow's);
@@ -1703,30 +1649,8 @@ __global__ void k_wz_grow_col_sym(double *__restrict__ Wz, long long ld, int nZ,
     if (!(r2 > scal[sr + 1])) return;
     Wz[(long long)nZ * ld + a] = a == nZ ? 1.0 / r2 : -u[a] / r2;
 }
-// (upper-triangle storage) column j of the symmetric matrix and the coefficient of its removal
-__global__ void k_dual_colcoef_sym(const double *__restrict__ Sinv, long long ldm, int k, int j, double *__restrict__ v, double *__restrict__ scal) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < k) v[i] = i <= j ? Sinv[(long long)j * ldm + i] : Sinv[(long long)i * ldm + j];
-    if (i == 0) { const double d = Sinv[(long long)j * ldm + j]; scal[9] = d != 0.0 ? -1.0 / d : 0.0; }
-}
-// (keep != nullptr: k_dual_keep_u in the same launch -- u and 1 / s kept for the deferred rank-1 part, zero behind the block)
-__global__ void k_dual_border_sym(double *Sinv, long long ldm, int nAC, const double *__restrict__ u, double *__restrict__ scal,
-                                  int *AC, int *posAC, int *Sc, int r, int side, double *y, int yidx, double yval,
-                                  double *__restrict__ keep, int to) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j > nAC) return;
-    const double is = scal[8];
-    if (j == nAC) {
-        AC[nAC] = r; posAC[r] = nAC; Sc[r] = side;
-        if (yidx >= 0) y[yidx] = yval;
-        Sinv[(long long)nAC * ldm + nAC] = is;
-        if (keep) { keep[nAC] = 0.0; keep[nAC + 1] = 0.0; scal[to] = is; }
-    } else {
-        const double uj = u[j];
-        Sinv[(long long)nAC * ldm + j] = -uj * is;
-        if (keep) keep[j] = uj;
-    }
-}
+// removal of the constraint at position j (upper-triangle storage): the last row / column (k - 1) moves into the freed slot j,
+// the working set follows
 __global__ void k_dual_move_last_sym(double *Sinv, long long ldm, int k, int j, int *AC, int *posAC, int *Sc, int r, double *y, int yidx) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     const int last = k - 1;
@@ -1739,26 +1663,6 @@ __global__ void k_dual_move_last_sym(double *Sinv, long long ldm, int k, int j, 
     const double val = c == j ? Sinv[(long long)last * ldm + last] : Sinv[(long long)last * ldm + c];
     const int lo_ = c < j ? c : j, hi_ = c < j ? j : c;
     Sinv[(long long)hi_ * ldm + lo_] = val;
-}
-// removal of the constraint at position j: v = column j of Sinv, coef = -1 / v_j  (Sinv += coef v v' zeroes row and column j)
-__global__ void k_dual_colcoef(const double *__restrict__ Sinv, long long ldm, int k, int j, double *__restrict__ v, double *__restrict__ scal) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < k) v[i] = Sinv[(long long)j * ldm + i];
-    if (i == 0) { const double d = Sinv[(long long)j * ldm + j]; scal[9] = d != 0.0 ? -1.0 / d : 0.0; }
-}
-// ... then the last row / column (k - 1) moves into the freed slot j (Sinv symmetric: both from column k - 1), working set follows
-__global__ void k_dual_move_last(double *Sinv, long long ldm, int k, int j, int *AC, int *posAC, int *Sc, int r, double *y, int yidx) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    const int last = k - 1;
-    if (c == 0) {
-        if (j != last) { const int rl = AC[last]; AC[j] = rl; posAC[rl] = j; }
-        posAC[r] = -1; Sc[r] = 0;
-        y[yidx] = 0.0;
-    }
-    if (j == last || c >= last) return;
-    const double val = c == j ? Sinv[(long long)last * ldm + last] : Sinv[(long long)last * ldm + c];
-    Sinv[(long long)c * ldm + j] = val;
-    Sinv[(long long)j * ldm + c] = val;
 }
 // a variable is freed: S gains a_v a_v' / d_v, Sinv -= w w' / (d_v + a_v'w) with w = Sinv a_v: the coefficient (one workgroup)
 __global__ void __launch_bounds__(NT) k_dual_free_coef(int k, const double *__restrict__ av, const double *__restrict__ w,
@@ -1826,12 +1730,47 @@ static hipError_t dalloc(T **p, size_t n) {
     return hipMemset(*p, 0, std::max<size_t>(n, 1) * sizeof(T));
 }
 
+// The environment switches of this engine, read ONCE when the engine of a handle is created (Impl's first member) and kept with
+// it. Apart from NO_DUAL / NO_RSH (bench.py --full: the null-space path at scale) and the diagnostics, each forces onto small
+// problems a path the default dispatch takes only at scale, on odd leading dimensions or after some event: the tests set them
+// for that coverage. Table: INTEGRATION.md 6.
+struct LargeKnobs {
+    bool no_dual;          // RSQP_LARGE_NO_DUAL        no range-space path for a diagonal H: the null-space factors
+    bool no_rsh;           // RSQP_LARGE_NO_RSH         no general range-space path (banded / dense H^-1): the null-space factors
+    bool rsh_dense;        // RSQP_LARGE_RSH_DENSE      the dense H^-1 operator on a banded H as well
+    bool no_tableau;       // RSQP_LARGE_NO_TABLEAU     no static tableau WW on a small dense problem (the default above WW_MAX)
+    bool band_1wg;         // RSQP_LARGE_BAND_1WG       the one-workgroup banded kernel for single vectors as well (the path of blocks)
+    bool no_carry;         // RSQP_LARGE_NO_CARRY       the step direction exact at every change (the default every CARRY_REFRESH)
+    bool no_carry_null;    // RSQP_LARGE_NO_CARRY_NULL  its null-space part exact at every change (the default above nV 16 384)
+    bool no_fuse;          // RSQP_LARGE_NO_FUSE        deferred reflections applied on their own (the default on an odd ld)
+    int fuse_wz_min;       // RSQP_LARGE_FUSE_WZ_MIN    nZ from which the shrinking of Wz rides on its product (3072; tests: 0)
+    int wz_sym_min;        // RSQP_LARGE_WZ_SYM_MIN     nV from which Wz is kept as its upper triangle (4096; tests: 0)
+    bool no_blocked_setup; // RSQP_NO_BLOCKED_SETUP     sequential set-up of a guessed working set (the default below BLOCKED_MIN)
+    bool no_spin;          // RSQP_LARGE_NO_SPIN        block in hipStreamSynchronize for publications (the default after 16 spin misses)
+    bool debug;            // RSQP_DEBUG                synchronise and check after every launch
+    bool profile;          // RSQP_PROFILE              per kernel class HIP-event time and bytes (serialises the stream)
+    bool waitstat;         // RSQP_LARGE_WAITSTAT       the homotopy's host waits and the solve's set-up times on stderr
+};
+static LargeKnobs large_knobs_from_env() {
+    auto on = [](const char *name) { return getenv(name) != nullptr; };
+    auto num = [](const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; };
+    LargeKnobs k;
+    k.no_dual = on("RSQP_LARGE_NO_DUAL"); k.no_rsh = on("RSQP_LARGE_NO_RSH"); k.rsh_dense = on("RSQP_LARGE_RSH_DENSE");
+    k.no_tableau = on("RSQP_LARGE_NO_TABLEAU"); k.band_1wg = on("RSQP_LARGE_BAND_1WG");
+    k.no_carry = on("RSQP_LARGE_NO_CARRY"); k.no_carry_null = on("RSQP_LARGE_NO_CARRY_NULL"); k.no_fuse = on("RSQP_LARGE_NO_FUSE");
+    k.fuse_wz_min = num("RSQP_LARGE_FUSE_WZ_MIN", 3072); k.wz_sym_min = num("RSQP_LARGE_WZ_SYM_MIN", 4096);
+    k.no_blocked_setup = on("RSQP_NO_BLOCKED_SETUP"); k.no_spin = on("RSQP_LARGE_NO_SPIN");
+    k.debug = on("RSQP_DEBUG"); k.profile = on("RSQP_PROFILE"); k.waitstat = on("RSQP_LARGE_WAITSTAT");
+    return k;
+}
+
 struct RsqpLargeEngine::Impl {
+    const LargeKnobs kn = large_knobs_from_env();
     int nV = 0, nC = 0, nAmax = 0;
     long long ld = 0, ldm = 0;
     // (sizes below 256 keep their own leading dimension: alignment buys nothing there, and the even-ld kernel variants sum in
     //  another order -- on the reference's non-convex dump hs107 that changed which side a flip takes and the run cycled)
-    static long long pad16(long long n) { const bool off = getenv("RSQP_LARGE_NO_PAD") != nullptr; return (off || n < 256) ? n : ((n + 15) & ~15LL); }      // (read where a handle is created: init / bytes_needed)
+    static long long pad16(long long n) { return n < 256 ? n : ((n + 15) & ~15LL); }
     hipStream_t st = nullptr;
     hipError_t err_ = hipSuccess;
     RsqpLargeMatrices M;
@@ -1855,7 +1794,7 @@ struct RsqpLargeEngine::Impl {
     double *h_ctl = nullptr, *d_ctl = nullptr;   // host-mapped decision block written by kernels
     unsigned long long ctl_seq = 0;              // number of the last publication launched (see publish())
     int spin_misses = 0;                         // publications that only became visible at the end of the kernel's stream
-    bool spin_wait = getenv("RSQP_LARGE_NO_SPIN") == nullptr;
+    bool spin_wait = !kn.no_spin;
     double next_seq() { return (double)(++ctl_seq); }
     // wait for the last launched publication: spin on its sequence number for up to 5 ms, then (or when spinning is
     // off) block in hipStreamSynchronize. A platform on which the number never shows up early turns the spinning off.
@@ -1887,7 +1826,7 @@ struct RsqpLargeEngine::Impl {
     // next hot start falls back to a full set-up
     int wait_failed() {
         status = QPS_NOTINITIALISED;
-        pendZ.on = pendW.on = pendY.on = pendM.on = pendS.on = pendR.on = false;
+        pendZ.on = pendW.on = pendY.on = pendM.on = false;
         lz_n = 0;
         return RET_SETUP_FAILED;
     }
@@ -1904,16 +1843,12 @@ struct RsqpLargeEngine::Impl {
     RsqpDenseWork dw;
     double *big = nullptr;    // 2 nV^2 scratch, allocated by the first blocked set-up
     int *d_fpos = nullptr, *d_cand = nullptr, *d_freev = nullptr;
-    bool blocked_setup = getenv("RSQP_NO_BLOCKED_SETUP") == nullptr;
     // rows up to which y = M w runs as ONE launch (k_gemv_n1); beyond, chunks + a reduction launch. Measured
     // (tools/large_kernel_bench.py): 4096 x 4096 19.8 vs 27.8 us, 5000 x 5000 44.2 vs 35.6 us, 7670 x 7670 116.9 vs 84.5 us
-    int n1_maxrows = getenv("RSQP_GEMV_N1_MAXROWS") ? atoi(getenv("RSQP_GEMV_N1_MAXROWS")) : 4096;
+    static constexpr int N1_MAXROWS = 4096;
     bool dx_ready = false;
     bool house_done = false;      // wz2 / scal[0..3] hold the Householder data of the current wz1 (constraint_products / bound_products)
-    bool live_skip = getenv("RSQP_LARGE_NO_LIVE_SKIP") == nullptr;
-    bool extra_sync = getenv("RSQP_LARGE_EXTRA_SYNC") != nullptr;
-    int n1_threads = getenv("RSQP_GEMV_N1_THREADS") ? atoi(getenv("RSQP_GEMV_N1_THREADS")) : 0;   // tuning: force 256 / 512 threads in k_gemv_n1
-    int gemv_wgs = getenv("RSQP_GEMV_WGS") ? atoi(getenv("RSQP_GEMV_WGS")) : 4096;     // workgroups the chunked y = M w aims for
+    static constexpr int GEMV_WGS = 4096;     // workgroups the chunked y = M w aims for
     bool reinit_from_y0 = false;
     // the last blocked set-up (rsqp_get_setup_profile): HIP-event time and algorithmic flops of its two parts
     struct SetupStat { int valid = 0, m = 0, n = 0, nZ = 0, dual = 0; float ms_tq = 0.f, ms_wz = 0.f; double flops_tq = 0.0, flops_wz = 0.0; };
@@ -1923,8 +1858,8 @@ struct RsqpLargeEngine::Impl {
 
     ~Impl() {
         double *dv[] = {Z, Y, Minv, Wz, x, g, lb, ub, gN, lbN, ubN, dx, w1, w2, w3, w4, w5, w6, wz1, wz2, wz3, Ax, lbA, ubA,
-                        lbAN, ubAN, dAx, c1, c2, c3, a1, a2, a3, a4, y, dy, part, scal, pt, res_t, ATy, Hx, Hdx, ATdy, pz_t, pz_v, pw_s, pw_col, c_wY, c_wY2, c_xY, c_xi, c_wZ, py_t, py_v, pm_s, hinv, ps_u, sym_part, wz_part,
-                        rs_p, ra1, ra2, ra3, ra4, rs_dl, rs_ps_u, rs_G, band_buf, rs_WW, rs_dA, lz_vec, lz_c, lz_d};
+                        lbAN, ubAN, dAx, c1, c2, c3, a1, a2, a3, a4, y, dy, part, scal, pt, res_t, ATy, Hx, Hdx, ATdy, pz_t, pz_v, pw_s, pw_col, c_wY, c_wY2, c_xY, c_xi, c_wZ, py_t, py_v, pm_s, hinv, sym_part, wz_part,
+                        rs_p, ra1, ra2, ra3, ra4, rs_dl, rs_G, band_buf, rs_WW, rs_dA, lz_vec, lz_c, lz_d};
         for (double *p : dv) if (p) (void)hipFree(p);
         if (big) (void)hipFree(big);
         rsqp_dense_work_free(&dw);
@@ -1937,9 +1872,9 @@ struct RsqpLargeEngine::Impl {
     }
 
     // ---- launch helpers -----------------------------------------------------------
-    bool debug = getenv("RSQP_DEBUG") != nullptr;
-    // RSQP_PROFILE=1: per kernel class, HIP-event time and algorithmic bytes (serialises the stream)
-    bool profile = getenv("RSQP_PROFILE") != nullptr;
+    bool debug = kn.debug;
+    // per kernel class, HIP-event time and algorithmic bytes (serialises the stream); also profile_enable()
+    bool profile = kn.profile;
     struct Prof { double ms = 0, bytes = 0; long long calls = 0; };
     Prof prof[10];
     hipEvent_t pe0 = nullptr, pe1 = nullptr;
@@ -1999,12 +1934,12 @@ struct RsqpLargeEngine::Impl {
             return;
         }
         pbegin();
-        if (nrows <= n1_maxrows || mSb) {   // launch-bound sizes: one kernel, no partials (k_gemv_n1)
+        if (nrows <= N1_MAXROWS || mSb) {   // launch-bound sizes: one kernel, no partials (k_gemv_n1)
             const bool vec1 = ((l & 1) == 0) && ((reinterpret_cast<unsigned long long>(Mx) & 15) == 0);
             // 16-row workgroups: up to 3072 rows they cover at most 192 of the 256 CUs, so each gets 512 threads (64 column
             // groups, twice the loads in flight: 2048 x 2048 8.7 -> 6.7 us); taller matrices fill the chip with 256 (4096 x
             // 4096: 19.9 us vs 21.4 with 512). 1024 threads measured 2x slower. (tools/large_kernel_bench.py)
-            if (vec1 && (n1_threads == 512 || (n1_threads == 0 && nrows <= 3072))) hipLaunchKernelGGL((k_gemv_n1<true, 512>), dim3((nrows + 15) / 16), dim3(512), 0, st, Mx, l, nrows, ncols, wv, alpha, beta, base, out, mSb, mdst);
+            if (vec1 && nrows <= 3072) hipLaunchKernelGGL((k_gemv_n1<true, 512>), dim3((nrows + 15) / 16), dim3(512), 0, st, Mx, l, nrows, ncols, wv, alpha, beta, base, out, mSb, mdst);
             else if (vec1) hipLaunchKernelGGL((k_gemv_n1<true, NT>), dim3((nrows + 15) / 16), dim3(NT), 0, st, Mx, l, nrows, ncols, wv, alpha, beta, base, out, mSb, mdst);
             else hipLaunchKernelGGL((k_gemv_n1<false, NT>), dim3((nrows + 7) / 8), dim3(NT), 0, st, Mx, l, nrows, ncols, wv, alpha, beta, base, out, mSb, mdst);
             pend(0, 8.0 * nrows * (double)ncols + 8.0 * nrows + 8.0 * ncols);
@@ -2015,7 +1950,7 @@ struct RsqpLargeEngine::Impl {
         // 768 workgroups 152 us, 2048 145 us, 4096 (capped: 2528) 136 us = 5.9 TB/s -- more loads in flight per CU
         const bool vec = ((l & 1) == 0) && ((reinterpret_cast<unsigned long long>(Mx) & 15) == 0) && nrows >= 128;
         const int rb = vec ? (nrows + 127) / 128 : (nrows + 63) / 64;
-        int nch = std::max(1, std::min(std::min((gemv_wgs + rb - 1) / rb, 32), (ncols + 15) / 16));
+        int nch = std::max(1, std::min(std::min((GEMV_WGS + rb - 1) / rb, 32), (ncols + 15) / 16));
         while ((long long)nch * nrows > part_cap) nch = (nch + 1) / 2;
         const int chunk = (ncols + nch - 1) / nch;
         nch = (ncols + chunk - 1) / chunk;
@@ -2036,90 +1971,39 @@ struct RsqpLargeEngine::Impl {
     // (nAC x nAC, symmetric, in the buffer of Minv) replace Z, Y, Minv, Wz: per working-set change one rank-1 update of Sinv and
     // one or two products with it -- nAC^2 entries instead of nV nZ + nZ^2 + nAC^2 + nV nAC. Same homotopy, ratio tests, exchange
     // rule and drift correction; the definiteness guard of a removal never fires (Z'DZ is positive definite for every Z).
-    struct { bool on = false; int n = 0; } pendS;      // Sinv[0..n) x [0..n) += scal[S_KEEP_S] ps_u ps_u' not applied yet
-    static constexpr int S_KEEP_S = 45;
-    double *ps_u = nullptr;
-    bool dual_defer = getenv("RSQP_LARGE_NO_FUSE") == nullptr;
-    // Sinv symmetric: upper triangle only (k_sym_tile); RSQP_LARGE_NO_SYM=1: full storage with the GEMV / GER kernels of the null-space path
-    bool dual_sym = getenv("RSQP_LARGE_NO_SYM") == nullptr;
+    // Sinv symmetric: upper triangle only (k_sym_tile), its rank-1 updates kept as lazy terms (qp_rs_kernels.h: LzP)
     double *sym_part = nullptr;      // partial sums of the tiled symmetric product: [2][tiles per side][nAmax]
     static int sym_tiles(int n) { const int nt = (n + SYT - 1) / SYT; return nt * (nt + 1) / 2; }
-    // Sinv[0..n)^2 += (cs scal[slot]) v v'
-    void dual_rank1(int n, const double *v, int slot, double cs) {
-        if (n <= 0) return;
-        if (!dual_sym) { ger(Minv, ldm, n, n, v, v, slot, cs); return; }
-        pbegin();
-        hipLaunchKernelGGL((k_sym_tile<true, false>), dim3(sym_tiles(n)), dim3(256), 0, st, Minv, ldm, n, v, scal, slot, cs, (const double *)nullptr,
-                           (double *)nullptr, (double *)nullptr);
-        pend(2, 8.0 * n * (double)n);
-    }
-    bool dual_lazy() const { return lz_enabled && dual_sym; }      // lazy rank-1 terms (qp_rs_kernels.h: LzP) on the triangle storage
     void dual_flush() {
         if (rsh) return;      // (the pending terms belong to the general path's matrix: rs_flush)
-        if (lz_n > 0 && nAC > 0 && dual_lazy()) {
+        if (lz_n > 0 && nAC > 0) {
             pbegin();
             hipLaunchKernelGGL(k_sym_tile_lz, dim3(sym_tiles(nAC)), dim3(256), 0, st, Minv, ldm, nAC, lz_p());
             pend(2, 8.0 * nAC * (double)nAC);
         }
         lz_n = 0;
-        if (!pendS.on) return;
-        pendS.on = false;
-        dual_rank1(pendS.n, ps_u, S_KEEP_S, 1.0);
     }
-    // out = Sinv w, the deferred rank-1 update applied on the way (one read + one write of Sinv instead of read + write + read)
+    // out = Sinv w: one read of the triangle; the pending terms in the reduction
     void dual_sinv_times(const double *wv, double *out) {
-        if (dual_sym) {
-            if (nAC <= 0) return;
-            const int nt = (nAC + SYT - 1) / SYT;
-            double *P1 = sym_part, *P2 = sym_part + (size_t)nt * nAC;
-            if (dual_lazy()) {      // one read of the triangle; the pending terms in the reduction
-                if (lz_n > 0) hipLaunchKernelGGL(k_lz_dots, dim3(lz_n), dim3(NT), 0, st, lz_p(), nAC, wv, lz_d);
-                pbegin();
-                hipLaunchKernelGGL((k_sym_tile<false, true>), dim3(sym_tiles(nAC)), dim3(256), 0, st, Minv, ldm, nAC, (const double *)nullptr, scal, 0, 0.0,
-                                   wv, P1, P2);
-                pend(0, 4.0 * nAC * (double)nAC);
-                hipLaunchKernelGGL(k_sym_reduce_lz, g1(nAC), dim3(NT), 0, st, nAC, nt, P1, P2, out, (const int *)nullptr, (double *)nullptr, lz_p(), lz_d);
-                chk("dual lazy product");
-                return;
-            }
-            pbegin();
-            if (pendS.on && nAC == pendS.n + 1) {     // (ps_u is zero behind pendS.n: the update leaves the new border alone)
-                pendS.on = false;
-                hipLaunchKernelGGL((k_sym_tile<true, true>), dim3(sym_tiles(nAC)), dim3(256), 0, st, Minv, ldm, nAC, ps_u, scal, S_KEEP_S, 1.0, wv, P1, P2);
-                pend(8, 8.0 * nAC * (double)nAC);
-            } else {
-                dual_flush();
-                hipLaunchKernelGGL((k_sym_tile<false, true>), dim3(sym_tiles(nAC)), dim3(256), 0, st, Minv, ldm, nAC, (const double *)nullptr, scal, 0, 0.0,
-                                   wv, P1, P2);
-                pend(0, 4.0 * nAC * (double)nAC);
-            }
-            hipLaunchKernelGGL(k_sym_reduce, g1(nAC), dim3(NT), 0, st, nAC, nt, P1, P2, out);
-            chk("dual sym product");
-            return;
-        }
-        if (pendS.on && nAC == pendS.n + 1 && (ldm & 1) == 0 && ((reinterpret_cast<unsigned long long>(Minv) | reinterpret_cast<unsigned long long>(ps_u)) & 15) == 0) {
-            pendS.on = false;
-            pbegin();
-            hipLaunchKernelGGL((k_ger_gemv_n1<NT>), dim3((nAC + 15) / 16), dim3(NT), 0, st, Minv, ldm, nAC, nAC, ps_u, ps_u, scal, S_KEEP_S, 1.0, wv,
-                               1.0, 0.0, (const double *)nullptr, out, (const int *)nullptr, (double *)nullptr);
-            pend(8, 16.0 * nAC * (double)nAC);
-            chk("dual ger_gemv_n1");
-            return;
-        }
-        dual_flush();
-        gemv_n(Minv, ldm, nAC, nAC, wv, 1.0, 0.0, nullptr, out);
+        if (nAC <= 0) return;
+        const int nt = (nAC + SYT - 1) / SYT;
+        double *P1 = sym_part, *P2 = sym_part + (size_t)nt * nAC;
+        if (lz_n > 0) hipLaunchKernelGGL(k_lz_dots, dim3(lz_n), dim3(NT), 0, st, lz_p(), nAC, wv, lz_d);
+        pbegin();
+        hipLaunchKernelGGL((k_sym_tile<false, true>), dim3(sym_tiles(nAC)), dim3(256), 0, st, Minv, ldm, nAC, (const double *)nullptr, scal, 0, 0.0,
+                           wv, P1, P2);
+        pend(0, 4.0 * nAC * (double)nAC);
+        hipLaunchKernelGGL(k_sym_reduce_lz, g1(nAC), dim3(NT), 0, st, nAC, nt, P1, P2, out, (const int *)nullptr, (double *)nullptr, lz_p(), lz_d);
+        chk("dual lazy product");
     }
-    bool dual_enabled = getenv("RSQP_LARGE_NO_DUAL") == nullptr;
     bool dual = false;               // the factors of this handle are Sinv (set by setup_aux; a hot start on new vectors keeps it)
     double *hinv = nullptr;          // 1 / (diag(H) + hreg)
     int *dflag = nullptr;
-    bool pair_enabled = getenv("RSQP_LARGE_NO_PAIR") == nullptr;
-    bool tail_fused = getenv("RSQP_LARGE_NO_TAIL") == nullptr;      // (k_remove_tail; off: the separate kernels)
     bool gemv_n1_pair(const double *M0, long long l0, int r0, int c0, const double *w0, double *o0, const double *M1, long long l1,
                       int r1, int c1, const double *w1, double *o1, bool skip0 = false, int live = 0) {
-        if (!pair_enabled || r0 <= 0 || r1 <= 0 || c0 <= 0 || c1 <= 0 || r0 > n1_maxrows || r1 > n1_maxrows) return false;
+        if (r0 <= 0 || r1 <= 0 || c0 <= 0 || c1 <= 0 || r0 > N1_MAXROWS || r1 > N1_MAXROWS) return false;
         if ((l0 & 1) || (l1 & 1) || ((reinterpret_cast<unsigned long long>(M0) | reinterpret_cast<unsigned long long>(M1)) & 15)) return false;
-        const bool t512 = n1_threads == 512 || (n1_threads == 0 && std::max(r0, r1) <= 3072);
+        const bool t512 = std::max(r0, r1) <= 3072;
         const int nb0 = (r0 + 15) / 16, nb1 = (r1 + 15) / 16;
         pbegin();
         if (skip0) {
@@ -2237,13 +2121,9 @@ struct RsqpLargeEngine::Impl {
     struct { bool on = false; int nZold = 0; } pendW;
     struct { bool on = false; int n = 0; } pendY, pendM;      // reflections of Y (n columns) / Minv (n x n) behind a removed constraint
     static constexpr int S_KEEP_BETA2 = 44;
-    bool fuse_passes = getenv("RSQP_LARGE_NO_FUSE") == nullptr;
-    int fuse_wz_min = getenv("RSQP_LARGE_FUSE_WZ_MIN") ? atoi(getenv("RSQP_LARGE_FUSE_WZ_MIN")) : 3072;   // (tests force 0: both fused kernels on small problems)
     static constexpr int S_KEEP_BETA = 40, S_KEEP_THETA = 41;
     // Wz symmetric: upper triangle only from wz_sym_min variables on (k_symw_tile: half the bytes of every update and product; below
     // that size the matrices are cache-resident and the single-launch kernels win). Decided per set-up (setup_aux), kept by hot starts.
-    bool wz_sym_enabled = getenv("RSQP_LARGE_NO_WZ_SYM") == nullptr;
-    int wz_sym_min = getenv("RSQP_LARGE_WZ_SYM_MIN") ? atoi(getenv("RSQP_LARGE_WZ_SYM_MIN")) : 4096;   // (tests force 0)
     bool wz_sym = false;
     double *wz_part = nullptr;
     // out = alpha Wz[0..n)^2 w, upper storage; upd: 0 plain, 2 the deferred shrinking applied on the way (q), n = the block it leaves
@@ -2263,7 +2143,7 @@ struct RsqpLargeEngine::Impl {
         else gemv_n(Wz, ld, nZ, nZ, wv, alpha, 0.0, nullptr, out);
     }
     bool can_defer() const {
-        return fuse_passes && wz_enabled && (ld & 1) == 0 && nZ > 1 && pz_t &&
+        return !kn.no_fuse && wz_enabled && (ld & 1) == 0 && nZ > 1 && pz_t &&
                (((reinterpret_cast<unsigned long long>(Z) | reinterpret_cast<unsigned long long>(Wz)) & 15) == 0);
     }
     void flush_pending_ZW() {
@@ -2354,7 +2234,7 @@ struct RsqpLargeEngine::Impl {
             wz_sym_times(nZ, wv, alpha, out, 2, q);
             return;
         }
-        if (!(pendW.on && pendW.nZold - 1 == nZ && nZ >= fuse_wz_min && nZ > 0) || wz_sym) {
+        if (!(pendW.on && pendW.nZold - 1 == nZ && nZ >= kn.fuse_wz_min && nZ > 0) || wz_sym) {
             if (pendW.on) { pendW.on = false; wz_shrink_now(pendW.nZold, pw_s, pz_v, pw_col, S_KEEP_BETA, S_KEEP_THETA); }
             wz_times(wv, alpha, out);
             return;
@@ -2362,7 +2242,7 @@ struct RsqpLargeEngine::Impl {
         pendW.on = false;
         pbegin();
         const int rb = (nZ + 127) / 128;
-        int nch = std::max(1, std::min(std::min((gemv_wgs + rb - 1) / rb, 32), (nZ + 15) / 16));
+        int nch = std::max(1, std::min(std::min((GEMV_WGS + rb - 1) / rb, 32), (nZ + 15) / 16));
         while ((long long)nch * nZ > part_cap) nch = (nch + 1) / 2;
         const int chunk = (nZ + nch - 1) / nch;
         nch = (nZ + chunk - 1) / chunk;
@@ -2377,10 +2257,8 @@ struct RsqpLargeEngine::Impl {
     // with the old Y are in a1 (wY) and with the new column in scal[eta_slot]
     // The step direction's wY = Minv bA and xY = Y wY are CARRIED over an incoming constraint (k_carry_add: one
     // O(n) kernel instead of one pass over Minv and one over Y) and recomputed exactly after any other change, at the first
-    // step, and every CARRY_REFRESH carried steps (RSQP_LARGE_NO_CARRY=1: always exactly).
+    // step, and every CARRY_REFRESH carried steps (kn.no_carry: always exactly).
     static constexpr int S_KEEP_ETA = 43, S_KEEP_WLAST = 42, CARRY_REFRESH = 8;
-    bool carry_enabled = getenv("RSQP_LARGE_NO_CARRY") == nullptr;
-    bool carry_null_enabled = getenv("RSQP_LARGE_NO_CARRY_NULL") == nullptr;   // (the null-space part as well)
     bool carry_valid = false;        // c_wY / c_xY are those of the last step direction, nothing but a homotopy step since
     bool carry_pending = false;      // ... and the change behind it was a plain added constraint (border kept in c_xi, S_KEEP_ETA)
     bool carry_ready = false;        // ... or a plain removed constraint: c_wY / c_xY already transformed (remove_constraint_tq)
@@ -2411,7 +2289,7 @@ struct RsqpLargeEngine::Impl {
             dot(w1, Zc(nZ - 1), nV, 5);
         }
         nZ--;
-        const bool keep = defer && !skipZ && plain_add && carry_enabled && carry_valid && carried < CARRY_REFRESH;
+        const bool keep = defer && !skipZ && plain_add && !kn.no_carry && carry_valid && carried < CARRY_REFRESH;
         minv_append(5, !skipZ, r, side, keep, yidx, yval);
         carry_pending = keep;
         hAC[nAC] = r; hSc[r] = side;
@@ -2494,12 +2372,12 @@ struct RsqpLargeEngine::Impl {
         // a plain removal whose step direction will be carried (below) does not need Y and Minv before that step direction's LAST
         // two products (Y'r, Minv'(Y'r)): their reflections wait and ride on those (k_ger_gemv_t) -- only the last column of each is
         // reflected now (it moves to Z / into the slot of the removed constraint)
-        const bool will_carry = plain_removal && carry_enabled && carry_valid && carried < CARRY_REFRESH && nAC > 1;
-        const bool dfr = will_carry && fuse_passes && (ld & 1) == 0 && (ldm & 1) == 0 &&
+        const bool will_carry = plain_removal && !kn.no_carry && carry_valid && carried < CARRY_REFRESH && nAC > 1;
+        const bool dfr = will_carry && !kn.no_fuse && (ld & 1) == 0 && (ldm & 1) == 0 &&
                          (((reinterpret_cast<unsigned long long>(Y) | reinterpret_cast<unsigned long long>(Minv)) & 15) == 0);
         gemv_n(Y, ld, nV, nAC, a2, 1.0, 0.0, nullptr, dfr ? py_t : w5);  // t = Y v
         gemv_t(Minv, ldm, nAC, nAC, a2, a3);                             // s' = v' Minv
-        if (dfr && tail_fused) {
+        if (dfr) {
             // (dfr implies will_carry) everything that follows in one launch
             hipLaunchKernelGGL(k_remove_tail, g1(std::max(nV, nAC)), dim3(NT), 0, st, nAC, nV, k, 1.0 - last_tau, a2, a3, py_t, py_v, pm_s, scal, 1,
                                S_KEEP_BETA2, S_KEEP_WLAST, Yc(nAC - 1), Zc(nZ), Minv + (long long)(nAC - 1) * ldm,
@@ -2513,16 +2391,8 @@ struct RsqpLargeEngine::Impl {
             nAC--;
             return;
         }
-        if (dfr) {
-            hipLaunchKernelGGL(k_keep_removal, g1(nAC), dim3(NT), 0, st, nAC, a2, a3, k, py_v, pm_s, scal, 1, S_KEEP_BETA2);
-            ger(Yc(nAC - 1), ld, nV, 1, py_t, a2 + (nAC - 1), 1, -1.0);
-            ger(Minv + (long long)(nAC - 1) * ldm, ldm, nAC, 1, a2, a3 + (nAC - 1), 1, -1.0);
-            pendY.on = true; pendY.n = nAC - 1;
-            pendM.on = true; pendM.n = nAC - 1;
-        } else {
-            ger(Y, ld, nV, nAC, w5, a2, 1, -1.0);                        // Y -= beta t v'
-            ger(Minv, ldm, nAC, nAC, a2, a3, 1, -1.0);                   // Minv -= beta v s'
-        }
+        ger(Y, ld, nV, nAC, w5, a2, 1, -1.0);                            // Y -= beta t v'
+        ger(Minv, ldm, nAC, nAC, a2, a3, 1, -1.0);                       // Minv -= beta v s'
         copy(Yc(nAC - 1), Zc(nZ), nV);                                   // new null-space column
         if (will_carry) {
             const double om = 1.0 - last_tau;
@@ -2653,14 +2523,13 @@ struct RsqpLargeEngine::Impl {
         return RET_OK;
     }
 
-    bool dual_carry_enabled = getenv("RSQP_LARGE_NO_CARRY") == nullptr;
     int dual_carry_row = -1;         // the constraint a carried plain addition brought in (position nAC - 1)
     int dual_change_active_set(int kind, int idx, int side) {
         carry_pending = carry_ready = false;
         if (kind == 1) {
             const int k = position_of(idx);
             // a plain removal: the multiplier step is carried (c_wY transformed here, with column k of Sinv as it is before the update)
-            const bool will_carry = dual_carry_enabled && carry_valid && carried < CARRY_REFRESH && nAC > 1;
+            const bool will_carry = !kn.no_carry && carry_valid && carried < CARRY_REFRESH && nAC > 1;
             dual_remove_constraint(k, will_carry);
             carry_ready = will_carry;
             return RET_OK;
@@ -2687,7 +2556,7 @@ struct RsqpLargeEngine::Impl {
         if (kind == 3) {
             dual_add_constraint(idx, side, nV + idx, ynew);
             // a plain addition (no exchange before it: c in a1, u in a2, 1 / s in scal[8] are those of the bordering)
-            carry_pending = dual_carry_enabled && ynew == 0.0 && li && carry_valid && carried < CARRY_REFRESH && !dual_exchanged;
+            carry_pending = !kn.no_carry && ynew == 0.0 && li && carry_valid && carried < CARRY_REFRESH && !dual_exchanged;
             dual_carry_row = idx;
         } else {
             dual_add_bound(idx, side);
@@ -2747,7 +2616,7 @@ struct RsqpLargeEngine::Impl {
     // M.diagH), every d + hreg > 0 (device check here; one host round trip per set-up)
     int dual_prepare(bool *ok) {
         *ok = false;
-        if (!dual_enabled || !M.diagH || !M.haveH || nC <= 0) return RET_OK;
+        if (kn.no_dual || !M.diagH || !M.haveH || nC <= 0) return RET_OK;
         LCHK(hipMemsetAsync(dflag, 0, sizeof(int), st));
         hipLaunchKernelGGL(k_dual_hinv, g1(nV), dim3(NT), 0, st, nV, M.Hval, M.hreg, hinv, dflag);
         LCHK(hipMemcpyAsync(h_pinned_i, dflag, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -2807,32 +2676,16 @@ struct RsqpLargeEngine::Impl {
         lz_n++;
     }
     void dual_add_constraint(int r, int side, int yidx = -1, double yval = 0.0) {
-        if (dual_lazy()) {
-            if (lz_n >= LZK) dual_flush();
-            hipLaunchKernelGGL(k_lz_border, g1(nAC + 1), dim3(NT), 0, st, Minv, ldm, nAC, a2, scal, AC, posAC, Sc, r, side, y, yidx, yval, lz_vec, lz_stride, lz_n, lz_c);
-            lz_n++;
-            hAC[nAC] = r; hSc[r] = side;
-            nAC++;
-            nZ = nFR - nAC;
-            return;
-        }
-        dual_flush();       // (none is pending here: the products of this row have applied it)
-        const bool defer = dual_defer && nAC > 0;
-        if (defer) {
-            if (!dual_sym) hipLaunchKernelGGL(k_dual_keep_u, g1(nAC + 1), dim3(NT), 0, st, nAC, a2, ps_u, scal, S_KEEP_S);
-            pendS.on = true; pendS.n = nAC;
-        } else dual_rank1(nAC, a2, 8, 1.0);
-        if (dual_sym) hipLaunchKernelGGL(k_dual_border_sym, g1(nAC + 1), dim3(NT), 0, st, Minv, ldm, nAC, a2, scal, AC, posAC, Sc, r, side, y, yidx, yval,
-                                         defer ? ps_u : (double *)nullptr, S_KEEP_S);
-        else hipLaunchKernelGGL(k_dual_border, g1(nAC + 1), dim3(NT), 0, st, Minv, ldm, nAC, a2, scal, AC, posAC, Sc, r, side, y, yidx, yval);
+        if (lz_n >= LZK) dual_flush();
+        hipLaunchKernelGGL(k_lz_border, g1(nAC + 1), dim3(NT), 0, st, Minv, ldm, nAC, a2, scal, AC, posAC, Sc, r, side, y, yidx, yval, lz_vec, lz_stride, lz_n, lz_c);
+        lz_n++;
         hAC[nAC] = r; hSc[r] = side;
         nAC++;
         nZ = nFR - nAC;
     }
     // a variable joins the fixed set: S loses a_v a_v'/d_v, Sinv += u u'/s with the same u and s as a bordering would use
     void dual_add_bound(int v, int side) {
-        if (dual_lazy()) { if (nAC > 0) lz_push(nAC, a2, 8); }
-        else { dual_flush(); dual_rank1(nAC, a2, 8, 1.0); }
+        if (nAC > 0) lz_push(nAC, a2, 8);
         hipLaunchKernelGGL(k_set_Sb, dim3(1), dim3(1), 0, st, Sb, v, side);
         hSb[v] = side;
         nFR--;
@@ -2840,21 +2693,12 @@ struct RsqpLargeEngine::Impl {
     }
     void dual_remove_constraint(int k, bool carry) {
         const int r = hAC[k];
-        if (dual_lazy()) {
-            if (lz_n >= LZK) dual_flush();
-            hipLaunchKernelGGL(k_lz_colcoef, g1(nAC), dim3(NT), 0, st, Minv, ldm, nAC, k, lz_p(), a3, scal);
-            if (carry) hipLaunchKernelGGL(k_dual_carry_remove, dim3(1), dim3(NT), 0, st, nAC, k, 1.0 - last_tau, a3, c_wY);
-            hipLaunchKernelGGL(k_lz_remove_fix, g1(std::max(nAC, 1)), dim3(NT), 0, st, nAC, k, a3, scal, lz_vec, lz_stride, lz_n, lz_c);
-            lz_n++;
-        } else {
-        dual_flush();
-        if (dual_sym) hipLaunchKernelGGL(k_dual_colcoef_sym, g1(nAC), dim3(NT), 0, st, Minv, ldm, nAC, k, a3, scal);
-        else hipLaunchKernelGGL(k_dual_colcoef, g1(nAC), dim3(NT), 0, st, Minv, ldm, nAC, k, a3, scal);
+        if (lz_n >= LZK) dual_flush();
+        hipLaunchKernelGGL(k_lz_colcoef, g1(nAC), dim3(NT), 0, st, Minv, ldm, nAC, k, lz_p(), a3, scal);
         if (carry) hipLaunchKernelGGL(k_dual_carry_remove, dim3(1), dim3(NT), 0, st, nAC, k, 1.0 - last_tau, a3, c_wY);
-        dual_rank1(nAC, a3, 9, 1.0);
-        }
-        if (dual_sym) hipLaunchKernelGGL(k_dual_move_last_sym, g1(std::max(nAC - 1, 1)), dim3(NT), 0, st, Minv, ldm, nAC, k, AC, posAC, Sc, r, y, nV + r);
-        else hipLaunchKernelGGL(k_dual_move_last, g1(std::max(nAC - 1, 1)), dim3(NT), 0, st, Minv, ldm, nAC, k, AC, posAC, Sc, r, y, nV + r);
+        hipLaunchKernelGGL(k_lz_remove_fix, g1(std::max(nAC, 1)), dim3(NT), 0, st, nAC, k, a3, scal, lz_vec, lz_stride, lz_n, lz_c);
+        lz_n++;
+        hipLaunchKernelGGL(k_dual_move_last_sym, g1(std::max(nAC - 1, 1)), dim3(NT), 0, st, Minv, ldm, nAC, k, AC, posAC, Sc, r, y, nV + r);
         if (k != nAC - 1) hAC[k] = hAC[nAC - 1];
         hSc[r] = 0;
         nAC--;
@@ -2870,7 +2714,7 @@ struct RsqpLargeEngine::Impl {
         hipLaunchKernelGGL(k_col_of_A_active, dim3(4), dim3(NT), 0, st, M.Ajc, M.Air, M.Aval, v, posAC, a4);  // a_v
         dual_sinv_times(a4, a3);                                         // w = Sinv a_v
         hipLaunchKernelGGL(k_dual_free_coef, dim3(1), dim3(NT), 0, st, nAC, a4, a3, M.Hval, M.hreg, v, scal);
-        if (dual_lazy()) lz_push(nAC, a3, 9); else dual_rank1(nAC, a3, 9, 1.0);
+        lz_push(nAC, a3, 9);
     }
     // factors for a guessed working set: S = B'B with B = D^-1/2 A_cand,FR' (GEMM), Cholesky, inverse. RET_FALLBACK: dependent rows
     // in the guess (or too few candidates): the caller adds them one by one
@@ -2899,7 +2743,6 @@ struct RsqpLargeEngine::Impl {
         if (h_pinned_i[1] != 0) return RET_FALLBACK;
         LCHK(rsqp_dtrtri_upper(n, G, lg, Ui, lg, &dw, st));
         LCHK(rsqp_dtrmmt_upper(n, 1.0, Ui, lg, Minv, ldm, st));
-        if (!dual_sym) LCHK(rsqp_mirror_upper(n, Minv, ldm, st));
         (void)hipEventRecord(se2, st);
         {   // what the matrix cores were asked for (algorithmic: the symmetric results counted once): Gram matrix n^2 m, Cholesky
             // n^3/3, triangular inverse n^3/3, U^-1 U^-T n^3/3
@@ -2948,7 +2791,7 @@ struct RsqpLargeEngine::Impl {
         }
         carry_pending = carry_ready = false;
         carry_valid = true;
-        if (fuse_passes && nC > 0 && !M.denseA) {
+        if (!kn.no_fuse && nC > 0 && !M.denseA) {
             // (sparse A: the dx kernel rides behind the product, in the thread that has just formed the entry -- same bits, a launch less)
             RsqpSpmvDualDx e;
             e.Sb = Sb; e.hinv = hinv; e.Hval = M.Hval; e.hreg = M.hreg; e.gN = gN; e.g = g; e.dx = dx; e.Hdx = Hdx;
@@ -2974,14 +2817,14 @@ struct RsqpLargeEngine::Impl {
         const bool was_ready = carry_ready && carry_valid;
         const bool carry_add = !was_ready && carry_pending && carry_valid && nAC > 0;
         if (carry_add)
-            carry_null = carry_null_enabled && pendZ.on && pendZ.ncols == nZ && pendW.on && pendW.nZold - 1 == nZ && nZ > 0 && nV <= 16384 &&
+            carry_null = !kn.no_carry_null && pendZ.on && pendZ.ncols == nZ && pendW.on && pendW.nZold - 1 == nZ && nZ > 0 && nV <= 16384 &&
                          (((reinterpret_cast<unsigned long long>(pz_t)) & 15) == 0);
-        const bool carry_null_grow = was_ready && carry_null_enabled && nZ > 0 && 1.0 - last_tau > 1e-6;
+        const bool carry_null_grow = was_ready && !kn.no_carry_null && nZ > 0 && 1.0 - last_tau > 1e-6;
         // A dx_FX, H dx_FX: dx is zero on the free variables here (mean over the dense 2048 x 4096 cold start: 196 of
         // 2048 entries live), so the column-major products read the live columns only. A removed constraint with both parts carried
         // needs neither product (no right-hand side is formed), an added one with both parts carried only A dx_FX
         if (carry_null_grow) {
-        } else if (live_skip && M.denseA && M.haveH && M.denseH && M.hreg == 0.0 && 4 * (nV - nFR) < nV) {
+        } else if (M.denseA && M.haveH && M.denseH && M.hreg == 0.0 && 4 * (nV - nFR) < nV) {
             if (!gemv_n1_pair(M.denseA, nC, nC, nV, dx, c1, M.denseH, nV, nV, nV, dx, w2, true, nV - nFR)) {
                 gemv_n_live(M.denseA, nC, nC, nV, dx, c1, nV - nFR);
                 gemv_n_live(M.denseH, nV, nV, nV, dx, w2, nV - nFR);       // H symmetric
@@ -3101,14 +2944,14 @@ struct RsqpLargeEngine::Impl {
         double sum_nFR = 0.0, sum_nAC = 0.0, sum_nZ = 0.0;      // reported by RSQP_PROFILE: the sizes the products run on
         status = QPS_PERFORMINGHOMOTOPY;
         dx_ready = false;
-        pendZ.on = pendW.on = pendY.on = pendM.on = pendS.on = false;      // (nothing is deferred across solves; a solve that failed half-way leaves nothing behind)
+        pendZ.on = pendW.on = pendY.on = pendM.on = false;      // (nothing is deferred across solves; a solve that failed half-way leaves nothing behind)
         lz_n = 0;
         carry_valid = carry_pending = carry_ready = false;
         carried = 0;
         refresh_products();
         hipLaunchKernelGGL(k_rerelax, g1(nV), dim3(NT), 0, st, nV, Sb, x, lbN, ubN, lb, ub);
         if (nC > 0) hipLaunchKernelGGL(k_rerelax, g1(nC), dim3(NT), 0, st, nC, Sc, Ax, lbAN, ubAN, lbA, ubA);
-        if (rsh) { pendR.on = false; lz_n = 0; rs_refresh_p(); }
+        if (rsh) { lz_n = 0; rs_refresh_p(); }
         for (;;) {
             step_direction();
             hipLaunchKernelGGL(k_ratio1, dim3(nblk_ratio), dim3(NT), 0, st, nV, nC, Sb, Sc, x, y, dx, dy, Ax, dAx, lb, ub,
@@ -3131,7 +2974,6 @@ struct RsqpLargeEngine::Impl {
             } else tau = 1.0;
             const int done = kind == 0;
             (void)tau;
-            if (extra_sync) (void)hipStreamSynchronize(st);      // tuning: what one more host round trip per change costs
             if (done) { A_times(x, Ax); status = QPS_SOLVED; break; }
             if (iter >= maxit) { rcode = RET_MAX_NWSR; break; }
             last_tau = tau;
@@ -3145,7 +2987,7 @@ struct RsqpLargeEngine::Impl {
             sum_nFR += nFR; sum_nAC += nAC; sum_nZ += nZ;
             drift_correction();
         }
-        if ((profile || getenv("RSQP_LARGE_WAITSTAT")) && iter > 0)
+        if ((profile || kn.waitstat) && iter > 0)
             fprintf(stderr, "[rsqp profile] homotopy: %d changes, mean nFR %.1f nAC %.1f nZ %.1f (nV %d nC %d); host waited %.3f s in %lld round trips; return code %d, final nFR %d nAC %d\n", iter,
                     sum_nFR / iter, sum_nAC / iter, sum_nZ / iter, nV, nC, wait_seconds, wait_calls, rcode, nFR, nAC);
         if (profile && iter > 0)
@@ -3154,7 +2996,7 @@ struct RsqpLargeEngine::Impl {
         flush_pending();
         dual_flush();
         rs_flush();
-        if (rsh && rs_refine_enabled && status == QPS_SOLVED && rcode == RET_OK && iter > 0) rs_refine();      // (no change, nothing accumulated: a hot start on unchanged data returns the same bits)
+        if (rsh && status == QPS_SOLVED && rcode == RET_OK && iter > 0) rs_refine();      // (no change, nothing accumulated: a hot start on unchanged data returns the same bits)
         *nWSR = iter;
         return rcode;
     }
@@ -3163,14 +3005,11 @@ struct RsqpLargeEngine::Impl {
     // ---- GENERAL range-space path (rsh; DESIGN 4.5, kernels in qp_rs_kernels.h, bodies in qp_rs_path.h) ----------------------------
     // any symmetric positive definite H: active bounds AND constraints are rows of C, Sinv = (C H^-1 C')^-1 (upper triangle, in the
     // buffer of Wz, leading dimension ld), H^-1 an operator built once per Hessian (banded LDL' / explicit dense inverse in Z)
-    bool rsh_enabled = getenv("RSQP_LARGE_NO_RSH") == nullptr;
     bool force_null_space = false;   // this solve is the null-space retry of a range-space attempt that failed numerically (solve())
-    bool rs_force_dense = getenv("RSQP_LARGE_RSH_DENSE") != nullptr;      // (tests: the dense operator on a banded Hessian)
     bool rsh = false;
     int rs_kind = 0;                 // 1: banded factor (k_band_apply), 2: explicit dense inverse in Z, 3: 2 + the static tableau
                                      // WW = [I; A] H^-1 [I A'] of small dense problems (nV + nC <= WW_MAX)
     static constexpr int WW_MAX = 8192, S_WW_AD = 47;
-    bool rs_no_ww = getenv("RSQP_LARGE_NO_TABLEAU") != nullptr;
     double *rs_WW = nullptr, *rs_dA = nullptr;
     long long ldw = 0;
     int rs_cur_id = -1;
@@ -3178,18 +3017,13 @@ struct RsqpLargeEngine::Impl {
     int nR = 0;                      // active rows: (nV - nFR) + nAC
     int *R = nullptr, *posR = nullptr;
     std::vector<int> hR, hposR;
-    double *rs_p = nullptr, *rs_Ap = nullptr, *ra1 = nullptr, *ra2 = nullptr, *ra3 = nullptr, *ra4 = nullptr, *rs_dl = nullptr, *rs_ps_u = nullptr;
+    double *rs_p = nullptr, *rs_Ap = nullptr, *ra1 = nullptr, *ra2 = nullptr, *ra3 = nullptr, *ra4 = nullptr, *rs_dl = nullptr;
     double *rs_G = nullptr;          // ld x ld scratch of the blocked set-up (allocated on first use)
     double *band_buf = nullptr;      // the nine arrays of the banded operator
     BandOp band{};
     bool band_attr_set = false;
-    bool band_hinv = false;          // Z holds the explicit inverse of the banded H as well (products of incoming rows)
-    bool rs_band_columns = getenv("RSQP_LARGE_BAND_NO_COLUMNS") == nullptr;
     double band_seq = 0.0;           // tag of the last multi-workgroup product (k_band_apply_mw)
-    bool band_mw = getenv("RSQP_LARGE_BAND_1WG") == nullptr;      // (tests / tuning: the one-workgroup kernel for single vectors as well)
-    struct { bool on = false; int n = 0; } pendR;
     // lazy rank-1 terms of Sinv (qp_rs_kernels.h): vectors lz_vec[k] (stride lz_stride), coefficients lz_c[k], dots lz_d[k]
-    bool lz_enabled = getenv("RSQP_LARGE_NO_LAZY") == nullptr;
     double *lz_vec = nullptr, *lz_c = nullptr, *lz_d = nullptr;
     long long lz_stride = 0;
     int lz_n = 0;
@@ -3199,10 +3033,8 @@ struct RsqpLargeEngine::Impl {
     int rs_build_dense(bool *ok);
     void rs_hinv_apply(const double *in, const double *sub, double *out, bool fix_dx);
     void band_launch(int ncols, const double *in, const double *sub, double *out, long long ldc, bool qmode);
-    void rs_rank1(int n, const double *v, int slot, double cs);
     void rs_flush();
     void rs_sinv_times(const double *wv, double *out, bool scatter_dy = false);
-    bool rs_carry_enabled = getenv("RSQP_LARGE_NO_CARRY") == nullptr;
     int rs_carry_id = -1;
     void rs_products(int id);
     void rs_residual();
@@ -3213,7 +3045,6 @@ struct RsqpLargeEngine::Impl {
     void rs_step_direction();
     void rs_refresh_p();
     void rs_refine();
-    bool rs_refine_enabled = getenv("RSQP_LARGE_NO_REFINE") == nullptr;
     int rs_setup_rows(const std::vector<int> &rows, const std::vector<int> &gb, const std::vector<int> &gc);
     int rs_setup(const std::vector<int> &gb, const std::vector<int> &gc);
     void rs_count(int id, int delta);
@@ -3334,7 +3165,7 @@ struct RsqpLargeEngine::Impl {
             std::vector<int> cand;
             for (int r = 0; r < nC; r++) if (gc[r] != 0) cand.push_back(r);
             bool done = cand.empty();
-            if (!done && blocked_setup && (int)cand.size() >= BLOCKED_MIN && (int)cand.size() <= nFR) {
+            if (!done && !kn.no_blocked_setup && (int)cand.size() >= BLOCKED_MIN && (int)cand.size() <= nFR) {
                 const int rcb = dual_setup_blocked(gc, freev, cand);
                 if (rcb == RET_OK) done = true;
                 else if (rcb != RET_FALLBACK) return rcb;
@@ -3351,7 +3182,7 @@ struct RsqpLargeEngine::Impl {
             nZ = nFR - nAC;
             if (profile) { (void)hipStreamSynchronize(st); fprintf(stderr, "[rsqp profile] setup_aux (range-space path): nFR %d nAC %d, t=%.3f s\n", nFR, nAC, now_s() - t_setup0); }
         } else {
-        wz_sym = wz_sym_enabled && nV >= wz_sym_min;
+        wz_sym = nV >= kn.wz_sym_min;
         if (nZ > 0) {
             LCHK(hipMemsetAsync(Z, 0, sizeof(double) * (size_t)ld * nZ, st));
             // free-variable index list staged in dy (read as ints; dy is rewritten before its next use)
@@ -3365,7 +3196,7 @@ struct RsqpLargeEngine::Impl {
         std::vector<int> cand;
         for (int r = 0; r < nC; r++) if (gc[r] != 0) cand.push_back(r);
         bool tq_done = false;
-        if (blocked_setup && (int)cand.size() >= BLOCKED_MIN && (int)cand.size() <= nFR) {
+        if (!kn.no_blocked_setup && (int)cand.size() >= BLOCKED_MIN && (int)cand.size() <= nFR) {
             setup_stat = SetupStat();
             if (!se0) { (void)hipEventCreate(&se0); (void)hipEventCreate(&se1); (void)hipEventCreate(&se2); }
             (void)hipEventRecord(se0, st);
@@ -3397,7 +3228,7 @@ struct RsqpLargeEngine::Impl {
         if (profile) { (void)hipStreamSynchronize(st); fprintf(stderr, "[rsqp profile] setup_aux: TQ part done (%s), nFR %d nAC %d nZ %d, t=%.3f s\n", tq_done ? "blocked QR" : "sequential", nFR, nAC, nZ, now_s() - t_setup0); }
         // 3. Wz = (Z'HZ)^-1: blocked Cholesky + inverse, or bordering over the null-space columns
         bool wz_done = false;
-        if (blocked_setup && nZ >= BLOCKED_MIN) {
+        if (!kn.no_blocked_setup && nZ >= BLOCKED_MIN) {
             if (!se0) { (void)hipEventCreate(&se0); (void)hipEventCreate(&se1); (void)hipEventCreate(&se2); }
             (void)hipEventRecord(se1, st);
             const int rcw = setup_wz_blocked();
@@ -3479,11 +3310,11 @@ hipError_t RsqpLargeEngine::init(int nV, int nC, hipStream_t stream) {
     DA(R, nV + 1); DA(posR, nV + nC + 1);
     if ((e = hipMemsetAsync(P.res_id, 0, 2 * sizeof(int), stream)) != hipSuccess) return e;      // res_id[0]: ticket counter of k_ratio1
     DA(d_fpos, nV); DA(d_cand, nC); DA(d_freev, nV);
-    DA(hinv, nV); DA(dflag, 4); DA(ps_u, P.nAmax + 4);
+    DA(hinv, nV); DA(dflag, 4);
     DA(sym_part, 2 * (size_t)((P.nAmax + SYT - 1) / SYT + 1) * (size_t)std::max(P.nAmax, 1));
     P.lz_stride = Impl::pad16(nV + 4); DA(lz_vec, (size_t)LZK * P.lz_stride); DA(lz_c, LZK); DA(lz_d, LZK);
     DA(rs_p, nV + std::max(nC, 1)); P.rs_Ap = P.rs_p + nV;      // ([p; A p] contiguous: one product with the tableau refreshes both)
-    DA(ra1, nV + 4); DA(ra2, nV + 4); DA(ra3, nV + 4); DA(ra4, nV + 4); DA(rs_dl, nV + 4); DA(rs_ps_u, nV + 4);
+    DA(ra1, nV + 4); DA(ra2, nV + 4); DA(ra3, nV + 4); DA(ra4, nV + 4); DA(rs_dl, nV + 4);
     DA(wz_part, 2 * (size_t)((nV + SYT - 1) / SYT + 1) * (size_t)nV);
 #undef DA
     if ((e = rsqp_dense_work_alloc(&P.dw, nV)) != hipSuccess) return e;
@@ -3506,7 +3337,7 @@ int RsqpLargeEngine::solve(int mode, const double *d_g, const double *d_lb, cons
     P.err_ = hipSuccess;
     const int maxit = *nWSR;
     *nWSR = 0;
-    const bool tstat = P.profile || getenv("RSQP_LARGE_WAITSTAT") != nullptr;
+    const bool tstat = P.profile || P.kn.waitstat;
     const double t_solve0 = Impl::now_s();
     if (mode != RSQP_LMODE_COLD && P.status == QPS_NOTINITIALISED) mode = RSQP_LMODE_COLD;
     // targets, clamped to +-INFTY

@@ -79,13 +79,9 @@ int Impl::rs_build_band(const std::vector<double> &hv, bool *ok) {
     // the explicit inverse as well (in Z: n^2 doubles, 0.8 GB at n = 10 000): H^-1 c' of an incoming row -- a unit vector or a few
     // entries -- is then a combination of a few of its columns (k_rs_hinv_row, every lane busy) instead of a banded product whose
     // two scans and two cross-workgroup hand-offs take 20 us whatever the vector holds. One banded product per column, all at once.
-    band_hinv = false;
-    if (rs_band_columns) {
-        LCHK(hipMemsetAsync(Z, 0, sizeof(double) * (size_t)ld * nV, st));
-        hipLaunchKernelGGL(k_rs_unit_diag, g1(nV), dim3(NT), 0, st, nV, Z, ld);
-        band_launch(nV, Z, nullptr, Z, ld, false);
-        band_hinv = true;
-    }
+    LCHK(hipMemsetAsync(Z, 0, sizeof(double) * (size_t)ld * nV, st));
+    hipLaunchKernelGGL(k_rs_unit_diag, g1(nV), dim3(NT), 0, st, nV, Z, ld);
+    band_launch(nV, Z, nullptr, Z, ld, false);
     *ok = true;
     return RET_OK;
 }
@@ -129,7 +125,7 @@ int Impl::rs_build_ww() {
 }
 int Impl::rs_prepare(bool *ok) {
     *ok = false;
-    if (!rsh_enabled || !M.haveH || !M.h_Hjc || !M.h_Hir || M.Hnnz <= 0 || nV > BAND_MAX_N) return RET_OK;
+    if (kn.no_rsh || !M.haveH || !M.h_Hjc || !M.h_Hir || M.Hnnz <= 0 || nV > BAND_MAX_N) return RET_OK;
     // symmetry (pattern and values) and band width: on the device, two words back
     LCHK(hipMemsetAsync(dflag + 2, 0, 2 * sizeof(int), st));
     hipLaunchKernelGGL(k_rs_sym_check, dim3(nV), dim3(NT), 0, st, nV, M.Hjc, M.Hir, M.Hval, dflag + 2);
@@ -138,17 +134,17 @@ int Impl::rs_prepare(bool *ok) {
     const int hb = h_pinned_i[0];
     if (h_pinned_i[1] != 0) return RET_OK;
     std::vector<double> hv;
-    if (hb <= 2 && !rs_force_dense) {      // the banded factor is built on the host: its few values come over
+    if (hb <= 2 && !kn.rsh_dense) {      // the banded factor is built on the host: its few values come over
         hv.resize(M.Hnnz);
         LCHK(hipMemcpyAsync(hv.data(), M.Hval, sizeof(double) * M.Hnnz, hipMemcpyDeviceToHost, st));
         LCHK(hipStreamSynchronize(st));
     }
     bool built = false;
-    if (hb <= 2 && !rs_force_dense) { if (rs_build_band(hv, &built) != RET_OK) return RET_SETUP_FAILED; if (built) rs_kind = 1; }
+    if (hb <= 2 && !kn.rsh_dense) { if (rs_build_band(hv, &built) != RET_OK) return RET_SETUP_FAILED; if (built) rs_kind = 1; }
     if (!built) {
         if (rs_build_dense(&built) != RET_OK) return RET_SETUP_FAILED;
         if (built) rs_kind = 2;
-        if (built && !rs_no_ww && nV + nC <= WW_MAX) { if (rs_build_ww() != RET_OK) return RET_SETUP_FAILED; rs_kind = 3; }
+        if (built && !kn.no_tableau && nV + nC <= WW_MAX) { if (rs_build_ww() != RET_OK) return RET_SETUP_FAILED; rs_kind = 3; }
     }
     *ok = built;
     return RET_OK;
@@ -157,7 +153,7 @@ void Impl::band_launch(int ncols, const double *in, const double *sub, double *o
     BandQ q{};
     if (qmode) { q.Sb = Sb; q.ATdy = ATdy; q.dy = dy; q.gN = gN; q.g = g; q.Hdx = Hdx; }
     const int c = band.c;
-    if (ncols == 1 && band_mw) {       // one vector: 16 single-wave workgroups
+    if (ncols == 1 && !kn.band_1wg) {       // one vector: 16 single-wave workgroups
         const double seq = (band_seq += 1.0);
 #define RS_MW(CC) hipLaunchKernelGGL(k_band_apply_mw<CC>, dim3(BAND_MW), dim3(64), 0, st, band, in, sub, out, q, seq)
         if (c <= 4) RS_MW(4); else if (c <= 8) RS_MW(8); else if (c <= 10) RS_MW(10); else if (c <= 12) RS_MW(12); else RS_MW(16);
@@ -188,13 +184,6 @@ void Impl::rs_hinv_apply(const double *in, const double *sub, double *out, bool 
 }
 
 // ---- Sinv ------------------------------------------------------------------------------------------------------------------------
-void Impl::rs_rank1(int n, const double *v, int slot, double cs) {
-    if (n <= 0) return;
-    pbegin();
-    hipLaunchKernelGGL((k_sym_tile<true, false>), dim3(sym_tiles(n)), dim3(256), 0, st, Wz, ld, n, v, scal, slot, cs, (const double *)nullptr,
-                       (double *)nullptr, (double *)nullptr);
-    pend(2, 8.0 * n * (double)n);
-}
 void Impl::rs_flush() {
     if (!rsh) return;
     if (lz_n > 0 && nR > 0) {      // all pending terms in one pass over the triangle
@@ -203,38 +192,19 @@ void Impl::rs_flush() {
         pend(2, 8.0 * nR * (double)nR);
     }
     lz_n = 0;
-    if (!pendR.on) return;
-    pendR.on = false;
-    rs_rank1(pendR.n, rs_ps_u, S_KEEP_S, 1.0);
 }
-// out = Sinv w. Lazy form: one read of the triangle, the pending terms in the reduction; otherwise the deferred rank-1 part of the
-// last bordering is applied on the way
+// out = Sinv w: one read of the triangle, the pending terms in the reduction
 void Impl::rs_sinv_times(const double *wv, double *out, bool scatter_dy) {
     if (nR <= 0) return;
     const int nt = (nR + SYT - 1) / SYT;
     double *P1 = wz_part, *P2 = wz_part + (size_t)nt * nR;
-    if (lz_enabled) {
-        if (lz_n > 0) hipLaunchKernelGGL(k_lz_dots, dim3(lz_n), dim3(NT), 0, st, lz_p(), nR, wv, lz_d);
-        pbegin();
-        hipLaunchKernelGGL((k_sym_tile<false, true>), dim3(sym_tiles(nR)), dim3(256), 0, st, Wz, ld, nR, (const double *)nullptr, scal, 0, 0.0, wv, P1, P2);
-        pend(0, 4.0 * nR * (double)nR);
-        hipLaunchKernelGGL(k_sym_reduce_lz, g1(nR), dim3(NT), 0, st, nR, nt, P1, P2, out, scatter_dy ? R : (const int *)nullptr,
-                           scatter_dy ? dy : (double *)nullptr, lz_p(), lz_d);
-        chk("rs lazy product");
-        return;
-    }
+    if (lz_n > 0) hipLaunchKernelGGL(k_lz_dots, dim3(lz_n), dim3(NT), 0, st, lz_p(), nR, wv, lz_d);
     pbegin();
-    if (pendR.on && nR == pendR.n + 1) {
-        pendR.on = false;
-        hipLaunchKernelGGL((k_sym_tile<true, true>), dim3(sym_tiles(nR)), dim3(256), 0, st, Wz, ld, nR, rs_ps_u, scal, S_KEEP_S, 1.0, wv, P1, P2);
-        pend(8, 8.0 * nR * (double)nR);
-    } else {
-        rs_flush();
-        hipLaunchKernelGGL((k_sym_tile<false, true>), dim3(sym_tiles(nR)), dim3(256), 0, st, Wz, ld, nR, (const double *)nullptr, scal, 0, 0.0, wv, P1, P2);
-        pend(0, 4.0 * nR * (double)nR);
-    }
-    hipLaunchKernelGGL(k_sym_reduce, g1(nR), dim3(NT), 0, st, nR, nt, P1, P2, out, scatter_dy ? R : (const int *)nullptr, scatter_dy ? dy : (double *)nullptr);
-    chk("rs sym product");
+    hipLaunchKernelGGL((k_sym_tile<false, true>), dim3(sym_tiles(nR)), dim3(256), 0, st, Wz, ld, nR, (const double *)nullptr, scal, 0, 0.0, wv, P1, P2);
+    pend(0, 4.0 * nR * (double)nR);
+    hipLaunchKernelGGL(k_sym_reduce_lz, g1(nR), dim3(NT), 0, st, nR, nt, P1, P2, out, scatter_dy ? R : (const int *)nullptr,
+                       scatter_dy ? dy : (double *)nullptr, lz_p(), lz_d);
+    chk("rs lazy product");
 }
 void Impl::rs_count(int id, int delta) {       // delta +1: the row joined, -1: it left
     if (id < nV) nFR -= delta; else nAC += delta;
@@ -253,7 +223,7 @@ void Impl::rs_products(int id) {
         return;
     }
     hipLaunchKernelGGL(k_rs_row, dim3(1), dim3(NT), 0, st, nV, id, M.Arp, M.Aci, M.Arv, M.denseAT, w1);
-    if ((rs_kind == 2 || (rs_kind == 1 && band_hinv)) && !M.denseAT) hipLaunchKernelGGL(k_rs_hinv_row, g1(nV), dim3(NT), 0, st, nV, id, M.Arp, M.Aci, M.Arv, Z, ld, w5);
+    if ((rs_kind == 1 || rs_kind == 2) && !M.denseAT) hipLaunchKernelGGL(k_rs_hinv_row, g1(nV), dim3(NT), 0, st, nV, id, M.Arp, M.Aci, M.Arv, Z, ld, w5);
     else rs_hinv_apply(w1, nullptr, w5, false);
     A_times(w5, c3);
     if (nR > 0) hipLaunchKernelGGL(k_rs_gather, g1(nR), dim3(NT), 0, st, nR, R, nV, w5, c3, ra1);
@@ -283,20 +253,12 @@ int Impl::rs_li_decision(bool *li) {
     *li = nR < nV && a2n > 0.0 && std::sqrt(r2) > RSQP_EPS_LI * std::sqrt(a2n) && sp > 0.0;
     return RET_OK;
 }
-// Sinv <- [[Sinv + u u'/s, -u/s], [-u'/s, 1/s]]  (u in ra2, 1/s in scal[8]); the rank-1 part rides on the next product
+// Sinv <- [[Sinv + u u'/s, -u/s], [-u'/s, 1/s]]  (u in ra2, 1/s in scal[8]); the rank-1 part joins the lazy terms
 void Impl::rs_add_row(int id, int side, int yidx, double yval) {
-    if (lz_enabled) {
-        if (lz_n >= LZK) rs_flush();
-        // (nR = 0: no rank-1 part; the term is recorded with an empty vector all the same)
-        hipLaunchKernelGGL(k_lz_border, g1(nR + 1), dim3(NT), 0, st, Wz, ld, nR, ra2, scal, R, posR, Sall, id, side, y, yidx, yval, lz_vec, lz_stride, lz_n, lz_c);
-        lz_n++;
-    } else {
-        rs_flush();
-        const bool defer = nR > 0;
-        if (defer) { pendR.on = true; pendR.n = nR; }
-        hipLaunchKernelGGL(k_dual_border_sym, g1(nR + 1), dim3(NT), 0, st, Wz, ld, nR, ra2, scal, R, posR, Sall, id, side, y, yidx, yval,
-                           defer ? rs_ps_u : (double *)nullptr, S_KEEP_S);
-    }
+    if (lz_n >= LZK) rs_flush();
+    // (nR = 0: no rank-1 part; the term is recorded with an empty vector all the same)
+    hipLaunchKernelGGL(k_lz_border, g1(nR + 1), dim3(NT), 0, st, Wz, ld, nR, ra2, scal, R, posR, Sall, id, side, y, yidx, yval, lz_vec, lz_stride, lz_n, lz_c);
+    lz_n++;
     hR[nR] = id; hposR[id] = nR;
     if (id < nV) hSb[id] = side; else hSc[id - nV] = side;
     nR++;
@@ -304,18 +266,11 @@ void Impl::rs_add_row(int id, int side, int yidx, double yval) {
 }
 void Impl::rs_remove_row(int k, bool carry) {
     const int id = hR[k];
-    if (lz_enabled) {
-        if (lz_n >= LZK) rs_flush();
-        hipLaunchKernelGGL(k_lz_colcoef, g1(nR), dim3(NT), 0, st, Wz, ld, nR, k, lz_p(), ra3, scal);
-        if (carry) hipLaunchKernelGGL(k_dual_carry_remove, dim3(1), dim3(NT), 0, st, nR, k, 1.0 - last_tau, ra3, rs_dl);
-        hipLaunchKernelGGL(k_lz_remove_fix, g1(std::max(nR, 1)), dim3(NT), 0, st, nR, k, ra3, scal, lz_vec, lz_stride, lz_n, lz_c);
-        lz_n++;
-    } else {
-        rs_flush();
-        hipLaunchKernelGGL(k_dual_colcoef_sym, g1(nR), dim3(NT), 0, st, Wz, ld, nR, k, ra3, scal);
-        if (carry) hipLaunchKernelGGL(k_dual_carry_remove, dim3(1), dim3(NT), 0, st, nR, k, 1.0 - last_tau, ra3, rs_dl);
-        rs_rank1(nR, ra3, 9, 1.0);
-    }
+    if (lz_n >= LZK) rs_flush();
+    hipLaunchKernelGGL(k_lz_colcoef, g1(nR), dim3(NT), 0, st, Wz, ld, nR, k, lz_p(), ra3, scal);
+    if (carry) hipLaunchKernelGGL(k_dual_carry_remove, dim3(1), dim3(NT), 0, st, nR, k, 1.0 - last_tau, ra3, rs_dl);
+    hipLaunchKernelGGL(k_lz_remove_fix, g1(std::max(nR, 1)), dim3(NT), 0, st, nR, k, ra3, scal, lz_vec, lz_stride, lz_n, lz_c);
+    lz_n++;
     hipLaunchKernelGGL(k_dual_move_last_sym, g1(std::max(nR - 1, 1)), dim3(NT), 0, st, Wz, ld, nR, k, R, posR, Sall, id, y, id);
     if (k != nR - 1) { hR[k] = hR[nR - 1]; hposR[hR[k]] = k; }
     hposR[id] = -1;
@@ -328,7 +283,7 @@ int Impl::rs_change_active_set(int kind, int idx, int side) {
     const int id = (kind == 1 || kind == 3) ? nV + idx : idx;
     if (kind == 1 || kind == 2) {
         // a row leaves: the multiplier step is carried (rs_dl transformed here, with the column of Sinv as it is before the update)
-        const bool will_carry = rs_carry_enabled && carry_valid && carried < CARRY_REFRESH && nR > 1;
+        const bool will_carry = !kn.no_carry && carry_valid && carried < CARRY_REFRESH && nR > 1;
         rs_remove_row(hposR[id], will_carry);
         carry_ready = will_carry;
         return RET_OK;
@@ -351,7 +306,7 @@ int Impl::rs_change_active_set(int kind, int idx, int side) {
     }
     rs_add_row(id, side, id, ynew);
     // a plain addition (no exchange before it: cv in ra1, u in ra2, 1 / s in scal[8] are those of the bordering)
-    carry_pending = rs_carry_enabled && ynew == 0.0 && li && carry_valid && carried < CARRY_REFRESH && !exchanged;
+    carry_pending = !kn.no_carry && ynew == 0.0 && li && carry_valid && carried < CARRY_REFRESH && !exchanged;
     rs_carry_id = id;
     return RET_OK;
 }
@@ -483,7 +438,6 @@ int Impl::rs_setup_rows(const std::vector<int> &rows, const std::vector<int> &gb
 }
 // the factors of a guessed working set (gb: bounds, gc: constraints; Sb already holds gb, Sc is zero, x is set)
 int Impl::rs_setup(const std::vector<int> &gb, const std::vector<int> &gc) {
-    pendR.on = false;
     lz_n = 0;
     A_times(x, Ax);
     std::vector<int> rows, cons;
@@ -505,7 +459,7 @@ int Impl::rs_setup(const std::vector<int> &gb, const std::vector<int> &gc) {
         // (no constraint can join while no variable is free: the guessed ones, if any, are dropped like dependent rows)
         cons.clear();
     }
-    if (!rows_done && blocked_setup && nFX + (int)cons.size() >= BLOCKED_MIN && nFX + (int)cons.size() <= nV) {
+    if (!rows_done && !kn.no_blocked_setup && nFX + (int)cons.size() >= BLOCKED_MIN && nFX + (int)cons.size() <= nV) {
         std::vector<int> all(rows);
         all.insert(all.end(), cons.begin(), cons.end());
         int rcb = rs_setup_rows(all, gb, gc);

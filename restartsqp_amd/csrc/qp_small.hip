@@ -239,13 +239,10 @@ static int env_int(const char *name, int dflt) {
 
 SmallKnobs rsqp_small_knobs_from_env() {
     SmallKnobs k;
-    k.engine = env_int("RSQP_SMALL_ENGINE", -1); k.k_debug_bail = env_int("RSQP_K_DEBUG_BAIL", -1); k.noshape = env_int("RSQP_SMALL_NOSHAPE", 0);
-    k.lanes = env_int("RSQP_SMALL_LANES", -1); k.waves = env_int("RSQP_SMALL_WAVES", -1); k.wide = env_int("RSQP_SMALL_WIDE", -1);
-    k.wide_lanes = env_int("RSQP_SMALL_WIDE_LANES", 256) == 512 ? 512 : 256; k.nospread = env_int("RSQP_SMALL_NOSPREAD", 0);
-    k.no_kkt = env_int("RSQP_SMALL_NO_KKT", 0); k.kkt_only = env_int("RSQP_SMALL_KKT_ONLY", 0); k.no_tiny = env_int("RSQP_SMALL_NO_TINY", 0);
-    k.tiny_lds = env_int("RSQP_TINY_LDS", 0); k.lane = env_int("RSQP_LANE", -1); k.exp_matglobal = env_int("RSQP_EXP_MATGLOBAL", 0);
-    k.arena_mapped = env_int("RSQP_ARENA_MAPPED", -1);
-    k.no_spin = getenv("RSQP_NO_SPIN") != nullptr; k.no_spec_cert = getenv("RSQP_NO_SPEC_CERT") != nullptr;
+    k.engine = env_int("RSQP_SMALL_ENGINE", -1); k.k_debug_bail = env_int("RSQP_K_DEBUG_BAIL", -1);
+    k.lanes = env_int("RSQP_SMALL_LANES", -1); k.waves = env_int("RSQP_SMALL_WAVES", -1);
+    k.lane = env_int("RSQP_LANE", -1); k.arena_mapped = env_int("RSQP_ARENA_MAPPED", -1);
+    k.no_spin = getenv("RSQP_NO_SPIN") != nullptr;
     return k;
 }
 int rsqp_small_launch_is_tiny(const SmallKnobs &kn, const QPPools &p, int nVmax, int nCmax) {
@@ -270,22 +267,15 @@ hipError_t rsqp_launch_small_qp(const SmallKnobs &kn, const QPPools &p_in, int n
     if (eng == 1 && mat_bytes_max >= 0) mat_bytes_max = 8LL * ((long long)nVmax * nVmax + (long long)nCmax * nVmax);
     // uniform hs071-scale batches (8 x 2 through the QPhandler formulation; parameter scans of one NLP iterate) run
     // the build with the shape as a compile-time constant and the target vectors in registers (see RegVec)
-    const int noshape = kn.noshape, forcedL0 = kn.lanes;
-    const bool shape82 = eng == 0 && p.uniV == 8 && p.uniC == 2 && !noshape && mat_bytes_max >= 0 &&
+    const int forcedL0 = kn.lanes;
+    const bool shape82 = eng == 0 && p.uniV == 8 && p.uniC == 2 && mat_bytes_max >= 0 &&
                          (forcedL0 < 0 || forcedL0 == 8);        // only the 8-lane build has the shape instantiation
     // LDS image of the chosen formulation (the persistent copy in HBM is sized for the larger one)
     const long long imgd = eng == 1 ? EngineX<64, true>::image_doubles(nVmax, nCmax)
                                     : (shape82 ? Engine<8, true, true>::image_doubles(nVmax, nCmax) : Engine<64, true>::image_doubles(nVmax, nCmax));
     const long long imgi = eng == 1 ? EngineX<64, true>::image_ints(nVmax, nCmax) : Engine<64, true>::image_ints(nVmax, nCmax);
     const long long img = (8 * imgd + 2 * imgi + 7) & ~7LL;
-#if defined(RSQP_SMALL_EXPERIMENT) && RSQP_SMALL_EXPERIMENT == 1
-    // tuning build only: the 8-lane shape kernel with the matrices left in global memory (L2) -- a smaller LDS image per problem,
-    // more resident waves (RSQP_EXP_MATGLOBAL=1 with RSQP_SMALL_WAVES=3)
-    const int exp_nomat = kn.exp_matglobal;
-#else
-    constexpr int exp_nomat = 0;
-#endif
-    const bool mat_lds = mat_bytes_max >= 0 && align16(img + mat_bytes_max) <= kMaxLds && !exp_nomat;
+    const bool mat_lds = mat_bytes_max >= 0 && align16(img + mat_bytes_max) <= kMaxLds;
     // LDS of one problem: image, then its staged matrices, 16-byte granular.
     long long stride = align16(img + (mat_lds ? mat_bytes_max : 0));
     // (an odd number of 16-byte units would spread the problems of a wave over the banks, but the LDS is
@@ -298,21 +288,16 @@ hipError_t rsqp_launch_small_qp(const SmallKnobs &kn, const QPPools &p_in, int n
     int L = nmax <= 8 ? 8 : (nmax <= 16 ? 16 : (nmax <= 32 ? 32 : 64));
     if ((forcedL == 8 || forcedL == 16 || forcedL == 32 || forcedL == 64) && forcedL >= L) L = forcedL;   // never fewer lanes than entries
     if (eng == 1 && L < 16) L = 16;   // the explicit-inverse build has no 8-lane instantiation
-    if (!mat_lds && !exp_nomat) L = 64;
+    if (!mat_lds) L = 64;
     while (L < 64 && (64 / L) * stride > kMaxLds) L *= 2;
     if (L == 64 && stride > kMaxLds) stride = align16(mat_lds ? img + mat_bytes_max : img);
-    const int forcedWide0 = kn.wide;
-    const bool wide0 = eng == 1 && mat_lds && L == 64 && (forcedWide0 >= 0 ? forcedWide0 != 0 : nVmax > 32);
+    const bool wide0 = eng == 1 && mat_lds && L == 64 && nVmax > 32;
     bool wide = false;
     // several waves per problem: four (256 lanes, one wave per SIMD). The kernel keeps ~430 values live per lane
-    // (256 VGPRs + AGPRs), so an eight-wave build (RSQP_SMALL_WIDE_LANES=512, tuning builds only) spills 233 of them.
+    // (256 VGPRs + AGPRs), so an eight-wave build spills 233 of them (measured).
     // With one wave per SIMD every wave instruction costs its full 4+ cycles: the four-wave kernel is bound by the
     // instruction count per wave (~350 per 69 x 69 product stage), not by LDS bandwidth or barriers.
-#if defined(RSQP_SMALL_EXPERIMENT) && RSQP_SMALL_EXPERIMENT == 2
-    const int wideL = kn.wide_lanes;
-#else
     constexpr int wideL = 256;
-#endif
     if (wide0 && stride + 8 * wideL <= kMaxLds) { stride += 8 * wideL; wide = true; }   // one double per lane of the wide build
     // bank spread of packed waves: a 32-lane LDS access group holds 32 / L problems, each touching 2 L consecutive
     // banks of the 64 (ds_read_b64: bank = dword address mod 64; stores: 16-lane groups, mod 32). Their images must
@@ -320,11 +305,10 @@ hipError_t rsqp_launch_small_qp(const SmallKnobs &kn, const QPPools &p_in, int n
     // every vector access of an 8-lane build is a 4-way conflict (measured: 54 % of the LDS-array cycles, LDS busy
     // 73 % of the kernel). The stride is padded to the next such value when that does not cost a resident workgroup.
     if (L < 64) {
-        const int nospread = kn.nospread;
         long long s1 = stride;
         while ((s1 & 255) != ((8 * L) & 255)) s1 += 16;
         auto wgs = [&](long long st) { const long long a = (((64 / L) * st) + 511) / 512 * 512; return a > 0 ? kMaxLds / a : 0; };
-        if (!nospread && wgs(s1) == wgs(stride) && (64 / L) * s1 <= kMaxLds) stride = s1;
+        if (wgs(s1) == wgs(stride) && (64 / L) * s1 <= kMaxLds) stride = s1;
     }
     const int G = 64 / L, nblk = (nq + G - 1) / G;
     const size_t lds = (size_t)(G * stride);
@@ -339,13 +323,12 @@ hipError_t rsqp_launch_small_qp(const SmallKnobs &kn, const QPPools &p_in, int n
     // ---- batches of mid-size problems (cold starts and hot starts on new vectors): the tableau kernel first (qp_small_g.h: 3 phases
     // per working-set change instead of ~50); members it cannot carry (non-symmetric H, LP, undecidable tests) come back with
     // ret == RET_BAIL and are solved by the null-space kernel launched right behind it, which skips everybody else
-    const int noK = kn.no_kkt;
     // 32 row blocks x 8 column blocks of lanes: up to 72 variables x 32 constraints -- the 69 x 28 class of the hs0xx batch.
     typedef EngineG<3, 1, 9, 4> EK;      // up to 72 variables x 32 constraints
     typedef EngineG<2, 2, 8, 8> EK2;     // up to 64 variables x 64 constraints
     // (only where the null-space kernel would give a problem four waves as well: batches of SMALL problems are throughput-bound
     //  and better served by 16 / 32 lanes per problem, several problems per wave)
-    if (!noK && forcedE < 0 && eng == 1 && (nVmax > 32 || nCmax > 32) && (mode == 0 || mode == 1) && !p.done_flag) {
+    if (forcedE < 0 && eng == 1 && (nVmax > 32 || nCmax > 32) && (mode == 0 || mode == 1) && !p.done_flag) {
 #define KK_LAUNCH(RV_, RC_, CV_, CC_)                                                                                            \
         do {                                                                                                                     \
             hipLaunchKernelGGL((small_qpg_kernel<RV_, RC_, CV_, CC_>), dim3(nq), dim3(256), 0, stream, p, nq, mode, maxWSR);     \
@@ -355,8 +338,6 @@ hipError_t rsqp_launch_small_qp(const SmallKnobs &kn, const QPPools &p_in, int n
         else if (nVmax <= EK2::MAXV && nCmax <= EK2::MAXC) KK_LAUNCH(2, 2, 8, 8);
 #undef KK_LAUNCH
     }
-    const int konly = kn.kkt_only;     // diagnostics: no second pass (bailed members keep ret = 9, nflips = reason)
-    if (konly && p.only_bailed) return hipGetLastError();
 #define SQ_LAUNCH_U(ENG, LL, ML, W, U)                                                                        \
     do {                                                                                                      \
         static std::atomic<unsigned long long> set_{0};                                                       \
@@ -385,31 +366,13 @@ hipError_t rsqp_launch_small_qp(const SmallKnobs &kn, const QPPools &p_in, int n
     // explicit-inverse kernel (mid-size problems, BASELINE configs[4])
     {
         if (!(eng == 1 && wide)) return hipErrorInvalidValue;
-        if (wideL == 512) SQ_LAUNCH_E(EngineX, 512, true, 1);
-        else SQ_LAUNCH_E(EngineX, 256, true, 1);
+        SQ_LAUNCH_E(EngineX, 256, true, 1);
         return hipGetLastError();
     }
 #elif defined(RSQP_SMALL_EXPERIMENT)
     // quick-turnaround build for tuning (tools/small_experiment.sh): only the 8-lane Givens / TQ kernel
     {
         const bool fixed = shape82;
-#ifdef RSQP_EXP_L16W6
-        // the build the launcher refuses (qp_small.hip "Packed builds with W=6"): 16 lanes per problem, 6 waves per
-        // SIMD = 80 VGPRs with ~180 spilled values; kept reachable only here, for the root-cause hunt
-        if (L == 16 && eng == 0 && mat_lds) { SQ_LAUNCH_U(Engine, 16, true, 6, 0); return hipGetLastError(); }
-#endif
-        if (exp_nomat && L == 8 && eng == 0 && fixed) {
-#define SQ_LAUNCH_SHAPE_G(W)                                                                                                  \
-            do {                                                                                                              \
-                static std::atomic<unsigned long long> set_{0};                                                               \
-                rsqp_allow_full_lds(reinterpret_cast<const void *>(&small_qp_kernel<Engine<8, false, true>, 8, false, W, 8 * 256 + 2>), set_, (int)kMaxLds); \
-                hipLaunchKernelGGL((small_qp_kernel<Engine<8, false, true>, 8, false, W, 8 * 256 + 2>), dim3(nblk), dim3(64), lds, stream, p, nq, \
-                                   (int)stride, mode, maxWSR);                                                                \
-            } while (0)
-            switch (waves) { case 3: SQ_LAUNCH_SHAPE_G(3); break; case 4: SQ_LAUNCH_SHAPE_G(4); break; default: SQ_LAUNCH_SHAPE_G(2); }
-#undef SQ_LAUNCH_SHAPE_G
-            return hipGetLastError();
-        }
         if (L != 8 || eng != 0 || !mat_lds) return hipErrorInvalidValue;
         if (fixed) { switch (waves) { case 3: SQ_LAUNCH_SHAPE(8, 3, 8, 2); break; case 4: SQ_LAUNCH_SHAPE(8, 4, 8, 2); break; default: SQ_LAUNCH_SHAPE(8, 2, 8, 2); } }
         else { switch (waves) { case 3: SQ_LAUNCH_U(Engine, 8, true, 3, 0); break; case 4: SQ_LAUNCH_U(Engine, 8, true, 4, 0); break; default: SQ_LAUNCH_U(Engine, 8, true, 2, 0); } }

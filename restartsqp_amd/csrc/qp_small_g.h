@@ -807,7 +807,7 @@ __global__ void __launch_bounds__(256, 1) small_qpg_kernel(QPPools P, int nq, in
     const int tid = (int)threadIdx.x;
     if (rcode == RET_BAIL) {
         if (tid == 0) { P.ret[q] = RET_BAIL; P.nflips[q] = E.bail_reason; P.nwsr[q] = 1000 + E.bail_reason; }    // the null-space kernel takes this member over
-        //                                  (nwsr: overwritten by it; read by tools/bail_hist.py under RSQP_SMALL_KKT_ONLY=1)
+        //                                  (nwsr: overwritten by it)
         return;
     }
     E.write_results(P, d);

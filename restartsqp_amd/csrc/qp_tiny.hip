@@ -105,6 +105,8 @@ constexpr int TB = TINY_BLOCK, TG = TINY_BLOCK / 8;
 // beside the dense K), every lane reads / updates its own two rows there and reads any other row directly -- no permutes for the
 // pivot rows, no select chains for "entry q of my rows", and ~80 VGPRs less: a third wave per SIMD. A wave of this kernel takes
 // its ~45 k cycles whatever runs beside it (the same count for 1 QP and for 65 536), so throughput is resident waves / that latency.
+// (The launcher no longer builds GL = true: it was never the default, DESIGN 8. The parameter stays because dropping it moves the
+//  register allocation of the shipped GL = false builds.)
 template <int MC, bool GL = false>
 struct EngineT {
     static constexpr int N = MV + MC, REFRESH = 8;
@@ -788,13 +790,10 @@ hipError_t rsqp_launch_tiny_qp(const SmallKnobs &kn, const QPPools &p, int nq, i
     if (nq <= 0) return hipSuccess;
     if (!rsqp_tiny_fits(kn, nVmax, nCmax)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((nq + TG - 1) / TG)), block(TB);
-    // RSQP_TINY_LDS=1: the tableau in LDS, three waves per SIMD (tuning: default decided by measurement)
-    const int glds = kn.tiny_lds;
-    if (nCmax <= 2 && glds) hipLaunchKernelGGL((tiny_qp_kernel<2, 3, true>), grid, block, 0, stream, p, nq, mode, maxWSR);
     // (launches of at most one workgroup per CU -- the single QP of an SQP iteration above all -- get the builds for ONE wave per SIMD:
     //  268 instead of 256 registers, none spilled to scratch, whose round trips sit in the chain of a lone wave: cold solve of the hs071 QP 30.5 ->
     //  28.8 us through the Python loop, the solveQP replay 23.0 -> 22.6 us through the C++ boundary, batches of up to 8 192 QPs 3 % faster)
-    else if (nCmax <= 2 && nq <= 32 * 256) hipLaunchKernelGGL((tiny_qp_kernel<2, 1>), grid, block, 0, stream, p, nq, mode, maxWSR);
+    if (nCmax <= 2 && nq <= 32 * 256) hipLaunchKernelGGL((tiny_qp_kernel<2, 1>), grid, block, 0, stream, p, nq, mode, maxWSR);
     else if (nCmax <= 2) hipLaunchKernelGGL((tiny_qp_kernel<2, 2>), grid, block, 0, stream, p, nq, mode, maxWSR);
     else if (nCmax <= 4 && nq <= 32 * 256) hipLaunchKernelGGL((tiny_qp_kernel<4, 1>), grid, block, 0, stream, p, nq, mode, maxWSR);
     else if (nCmax <= 4) hipLaunchKernelGGL((tiny_qp_kernel<4, 2>), grid, block, 0, stream, p, nq, mode, maxWSR);

@@ -974,7 +974,7 @@ extern "C" int rsqp_solve(rsqp_solver *s, int mode, int *nWSR, const double *x0,
     }
     if (s->d_done && !s->kn.no_spin) { p.done_flag = s->d_done; p.done_val = ++s->done_seq; }
     // the hs071-scale tableau kernel forms the certificate QPhandler::solveQP asks for at the end of the SAME launch
-    const bool fused_cert = p.done_flag && p.tiny_ok && rsqp_tiny_fits(s->kn, s->nV, s->nC) && !s->kn.no_spec_cert && !s->lp_mode &&
+    const bool fused_cert = p.done_flag && p.tiny_ok && rsqp_tiny_fits(s->kn, s->nV, s->nC) && !s->lp_mode &&
                             s->A.initialised == (s->nC > 0) && s->kn.engine < 0;
     if (fused_cert) { p.cert_out = s->d_kkt.p; p.cert_Wb = s->d_Wb.p; p.cert_Wc = s->d_Wc.p; }
     {   // the tableau kernel and the LDS-resident kernels keep different layouts in the same state block: a solve that changes
@@ -1249,7 +1249,7 @@ void fill_kkt_args(rsqp_solver *s, RsqpKktArgs &a) {
 // the fused products + certificate kernel of an LDS-scale QP right behind its solve kernel (same stream), see rsqp_solver::spec_cert
 void launch_speculative_certificate(rsqp_solver *s, const QPPools &p) {
     s->spec_cert = false;
-    if (s->kn.no_spec_cert || s->lp_mode || !p.done_flag || !(s->fits_small && s->A.initialised == (s->nC > 0))) return;
+    if (s->lp_mode || !p.done_flag || !(s->fits_small && s->A.initialised == (s->nC > 0))) return;
     RsqpKktArgs a;
     fill_kkt_args(s, a);
     a.done_flag = s->d_done; a.done_val = ++s->done_seq;

@@ -33,27 +33,18 @@ struct QPDesc {
     long long offState;   // persistent engine image (doubles) for hot starts
 };
 
-// The RSQP_SMALL_* / RSQP_TINY_* / RSQP_K_* / RSQP_NO_SPIN / RSQP_NO_SPEC_CERT environment switches, read ONCE PER HANDLE (rsqp_create /
+// The RSQP_SMALL_* / RSQP_K_* / RSQP_LANE / RSQP_ARENA_MAPPED / RSQP_NO_SPIN environment switches, read ONCE PER HANDLE (rsqp_create /
 // rsqp_batch_create) and kept with it: a handle's behaviour does not depend on what another handle's first use found in the
 // environment. Table of every switch: INTEGRATION.md 6.
 struct SmallKnobs {
     int engine = -1;          // RSQP_SMALL_ENGINE      0 / 1: force the Givens-TQ / the explicit-inverse LDS kernel (no tableau kernels)
     int k_debug_bail = -1;    // RSQP_K_DEBUG_BAIL      test hook: the mid-size tableau kernel bails out of a hot start before its n-th change
-    int noshape = 0;          // RSQP_SMALL_NOSHAPE     no compile-time 8 x 2 shape build
     int lanes = -1;           // RSQP_SMALL_LANES       lanes per problem (8 / 16 / 32 / 64)
     int waves = -1;           // RSQP_SMALL_WAVES       waves per SIMD the build is compiled for
-    int wide = -1;            // RSQP_SMALL_WIDE        0 / 1: never / always four waves per problem
-    int wide_lanes = 256;     // RSQP_SMALL_WIDE_LANES  (tuning builds) 512
-    int nospread = 0;         // RSQP_SMALL_NOSPREAD    no bank-spreading pad of the LDS stride
-    int no_kkt = 0;           // RSQP_SMALL_NO_KKT      no mid-size tableau kernel
-    int kkt_only = 0;         // RSQP_SMALL_KKT_ONLY    diagnostics: no second pass for bailed members
-    int no_tiny = 0;          // RSQP_SMALL_NO_TINY     no hs071-scale tableau kernel
+    int no_tiny = 0;          // (set by the single-QP rescue, rsqp_api.hip) no hs071-scale tableau kernel
     int lane = -1;            // RSQP_LANE              0: never the lane-per-problem kernel (qp_lane.hip); n > 0: from n members on (default 16 385)
-    int tiny_lds = 0;         // RSQP_TINY_LDS          the hs071-scale kernel with its tableau in LDS, three waves per SIMD
-    int exp_matglobal = 0;    // RSQP_EXP_MATGLOBAL     (tuning builds) matrices left in global memory
     int arena_mapped = -1;    // RSQP_ARENA_MAPPED      single-QP handles: patterns / plans in host-mapped memory, no upload at set_A / set_H (-1: hs071 scale only)
     int no_spin = 0;          // RSQP_NO_SPIN           single-QP waits block in hipStreamSynchronize instead of spinning on a mapped word
-    int no_spec_cert = 0;     // RSQP_NO_SPEC_CERT      the certificate of a single LDS-scale QP only on demand
 };
 SmallKnobs rsqp_small_knobs_from_env();      // qp_small.hip
 

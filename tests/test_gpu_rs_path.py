@@ -53,7 +53,7 @@ def all_call_shapes(capi, oracle, rng, q, want_path):
 
 
 @pytest.mark.parametrize("knob", [None, "RSQP_LARGE_RSH_DENSE", "RSQP_LARGE_RSH_DENSE+RSQP_LARGE_NO_TABLEAU", "RSQP_NO_BLOCKED_SETUP", "RSQP_LARGE_BAND_1WG",
-                                  "RSQP_LARGE_NO_CARRY", "RSQP_LARGE_NO_LAZY"])
+                                  "RSQP_LARGE_NO_CARRY"])
 def test_banded_hessian_all_call_shapes(capi, oracle, monkeypatch, knob):
     for k in (knob or "").split("+"):
         if k:
@@ -183,7 +183,7 @@ def test_infeasible_qp_is_reported_infeasible_on_every_path(capi, oracle, monkey
     qp.init(q.g, q.lb, q.ub, q.lbA, q.ubA, 100000)
     qp.hotstart(q2.g, q2.lb, q2.ub, q2.lbA, q2.ubA, 100000)
     assert qp.exitflag() == 22
-    for knob in (None, "RSQP_LARGE_NO_TABLEAU", "RSQP_LARGE_NO_LAZY", "RSQP_LARGE_NO_RSH"):
+    for knob in (None, "RSQP_LARGE_NO_TABLEAU", "RSQP_LARGE_NO_RSH"):
         if knob:
             monkeypatch.setenv(knob, "1")
         s = load(capi, q)
