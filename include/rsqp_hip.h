@@ -126,6 +126,13 @@ int rsqp_set_reinit_guess(rsqp_solver *s, int from_y0);
 /* Options fields the adapter reads: qp_maxiter, lp_maxiter (Options.cpp:45,54) */
 int rsqp_set_options(rsqp_solver *s, int qp_maxiter, int lp_maxiter);
 
+/* Matrix input, every entry point below (triplet and CSC setters, rsqp_batch_create): the input describes the SUM of
+ * its entries, as SpHbMat::times does. Positions may repeat (triplet lists, or a row given twice within a CSC column),
+ * rows within a CSC column may come in any order, and repeats that cancel stay as a stored 0.0. Every engine, product
+ * and certificate reads that matrix; the library folds it to canonical CSC (rows strictly ascending, one entry per
+ * position) once, at structure upload -- canonical input is used as it is. What the API shows keeps the caller's
+ * layout: rsqp_get_*_csc, `order`, rsqp_get_*_nnz, and the value arrays of later refresh calls. A CSC array whose
+ * jc[0] != 0, whose column pointers decrease or whose rows are out of range is refused with RSQP_ERR_ARG. */
 /* set_A (qpOASESInterface.cpp:426-442): first call = SpHbMat::setStructure(rhs, I_info)
  * (SpHbMat.cpp:196-268) -- 1-based COO + identity blocks -> CSC on the device; later
  * calls = SpHbMat::setMatVal (:368-380), a device scatter through `order`. */
@@ -231,7 +238,9 @@ int rsqp_read_qore_dump(const char *path, double *lb, double *ub, double *lbA, d
  * Size limit: every member has at most RSQP_BATCH_MAX_V variables and RSQP_BATCH_MAX_C constraints; a larger
  * member, or a state block the device cannot allocate, gives RSQP_ERR_TOO_LARGE. Batches whose largest member's
  * solver image fits the LDS of a CU (about 90 variables) run the LDS-resident kernels; any other batch runs ALL its
- * members on the HBM-resident kernel (rsqp_batch_get_last_kernel() == 3). */
+ * members on the HBM-resident kernel (rsqp_batch_get_last_kernel() == 3). The matrices follow the contract of the
+ * setters above (sums of the entries, any row order; malformed CSC of A or H refused with RSQP_ERR_ARG), and
+ * rsqp_batch_set_matrix_values takes the values in the layout given here. */
 #define RSQP_BATCH_MAX_V 512
 #define RSQP_BATCH_MAX_C 512
 int rsqp_batch_create(int nq, const int *nV, const int *nC, const int *Ajc, const int *Air,

@@ -15,10 +15,10 @@
 
 static const double sqrt_m_eps = 1.0e-8; /* include/sqphot/Utils.hpp:37 */
 
-int orc_kkt_get_working_set(int nV, int nC, const int *Ajc, const int *Air, const double *Aval,
-                            const double *x, const double *lb, const double *ub,
-                            const double *lbA, const double *ubA, const int *ws_b,
-                            const int *ws_c, int *W_b, int *W_c) {
+static int kkt_get_working_set(int nV, int nC, const int *Ajc, const int *Air, const double *Aval,
+                               const double *x, const double *lb, const double *ub,
+                               const double *lbA, const double *ubA, const int *ws_b,
+                               const int *ws_c, int *W_b, int *W_c) {
     /* bounds (:846-868): solver +1 maps to ACTIVE_ABOVE, -1 to ACTIVE_BELOW */
     for (int i = 0; i < nV; i++) {
         switch (ws_b[i]) {
@@ -59,12 +59,12 @@ int orc_kkt_get_working_set(int nV, int nC, const int *Ajc, const int *Air, cons
     return 0;
 }
 
-int orc_kkt_test_optimality(int nV, int nC, const int *Ajc, const int *Air, const double *Aval,
-                            const int *Hjc, const int *Hir, const double *Hval,
-                            const double *g, const double *lb, const double *ub,
-                            const double *lbA, const double *ubA, const double *x,
-                            const double *y, const int *W_b, const int *W_c,
-                            orc_optimality_status *out) {
+static int kkt_test_optimality(int nV, int nC, const int *Ajc, const int *Air, const double *Aval,
+                               const int *Hjc, const int *Hir, const double *Hval,
+                               const double *g, const double *lb, const double *ub,
+                               const double *lbA, const double *ubA, const double *x,
+                               const double *y, const int *W_b, const int *W_c,
+                               orc_optimality_status *out) {
     double primal = 0.0, dual = 0.0, compl = 0.0, stat = 0.0;
     double *Ax = (double *)calloc((size_t)(nC > 0 ? nC : 1), sizeof(double));
     double *gap = (double *)calloc((size_t)(nV > 0 ? nV : 1), sizeof(double));
@@ -134,5 +134,43 @@ done:
     free(Ax);
     free(gap);
     free(Hx);
+    return rc;
+}
+
+static int csc_is_canonical(int ncol, const int *jc, const int *ir) {
+    for (int c = 0; c < ncol; c++)
+        for (int k = jc[c] + 1; k < jc[c + 1]; k++)
+            if (ir[k] <= ir[k - 1]) return 0;
+    return 1;
+}
+
+/* the public forms take any CSC array and read the matrix it describes (orc_csc_canonical), as the HIP certificate does */
+int orc_kkt_get_working_set(int nV, int nC, const int *Ajc, const int *Air, const double *Aval,
+                            const double *x, const double *lb, const double *ub,
+                            const double *lbA, const double *ubA, const int *ws_b,
+                            const int *ws_c, int *W_b, int *W_c) {
+    if (csc_is_canonical(nV, Ajc, Air)) return kkt_get_working_set(nV, nC, Ajc, Air, Aval, x, lb, ub, lbA, ubA, ws_b, ws_c, W_b, W_c);
+    int *jc, *ir;
+    double *val;
+    (void)orc_csc_canonical(nC, nV, Ajc, Air, Aval, &jc, &ir, &val);
+    const int rc = kkt_get_working_set(nV, nC, jc, ir, val, x, lb, ub, lbA, ubA, ws_b, ws_c, W_b, W_c);
+    free(jc); free(ir); free(val);
+    return rc;
+}
+
+int orc_kkt_test_optimality(int nV, int nC, const int *Ajc, const int *Air, const double *Aval,
+                            const int *Hjc, const int *Hir, const double *Hval,
+                            const double *g, const double *lb, const double *ub,
+                            const double *lbA, const double *ubA, const double *x,
+                            const double *y, const int *W_b, const int *W_c,
+                            orc_optimality_status *out) {
+    if (csc_is_canonical(nV, Ajc, Air) && (!Hjc || csc_is_canonical(nV, Hjc, Hir)))
+        return kkt_test_optimality(nV, nC, Ajc, Air, Aval, Hjc, Hir, Hval, g, lb, ub, lbA, ubA, x, y, W_b, W_c, out);
+    int *jc, *ir, *hjc = NULL, *hir = NULL;
+    double *val, *hval = NULL;
+    (void)orc_csc_canonical(nC, nV, Ajc, Air, Aval, &jc, &ir, &val);
+    if (Hjc) (void)orc_csc_canonical(nV, nV, Hjc, Hir, Hval, &hjc, &hir, &hval);
+    const int rc = kkt_test_optimality(nV, nC, jc, ir, val, hjc, hir, hval, g, lb, ub, lbA, ubA, x, y, W_b, W_c, out);
+    free(jc); free(ir); free(val); free(hjc); free(hir); free(hval);
     return rc;
 }

@@ -126,15 +126,13 @@ void orc_qp_destroy(orc_qp *qp) {
     free(qp);
 }
 
-int orc_qp_set_A_csc(orc_qp *qp, const int *jc, const int *ir, const double *val) {
-    int nV = qp->nV, nC = qp->nC, nnz = jc[nV];
+int orc_qp_set_A_csc(orc_qp *qp, const int *jc_in, const int *ir_in, const double *val_in) {
+    int nV = qp->nV, nC = qp->nC;
     free(qp->Ajc); free(qp->Air); free(qp->Aval); free(qp->Arp); free(qp->Aci); free(qp->Arv);
-    qp->Ajc = (int *)xcalloc((size_t)nV + 1, sizeof(int));
-    qp->Air = (int *)xcalloc((size_t)nnz, sizeof(int));
-    qp->Aval = (double *)xcalloc((size_t)nnz, sizeof(double));
-    memcpy(qp->Ajc, jc, sizeof(int) * ((size_t)nV + 1));
-    memcpy(qp->Air, ir, sizeof(int) * (size_t)nnz);
-    memcpy(qp->Aval, val, sizeof(double) * (size_t)nnz);
+    /* the matrix the array describes: rows sorted, repeated positions summed (every row gather below assigns) */
+    int nnz = orc_csc_canonical(nC, nV, jc_in, ir_in, val_in, &qp->Ajc, &qp->Air, &qp->Aval);
+    const int *jc = qp->Ajc, *ir = qp->Air;
+    const double *val = qp->Aval;
     /* CSR copy (columns ascending within each row) */
     qp->Arp = (int *)xcalloc((size_t)nC + 1, sizeof(int));
     qp->Aci = (int *)xcalloc((size_t)nnz, sizeof(int));
@@ -159,13 +157,7 @@ int orc_qp_set_H_csc(orc_qp *qp, const int *jc, const int *ir, const double *val
     qp->Hjc = NULL; qp->Hir = NULL; qp->Hval = NULL;
     qp->haveH = 0;
     if (!jc) return 0;
-    int nnz = jc[nV];
-    qp->Hjc = (int *)xcalloc((size_t)nV + 1, sizeof(int));
-    qp->Hir = (int *)xcalloc((size_t)nnz, sizeof(int));
-    qp->Hval = (double *)xcalloc((size_t)nnz, sizeof(double));
-    memcpy(qp->Hjc, jc, sizeof(int) * ((size_t)nV + 1));
-    memcpy(qp->Hir, ir, sizeof(int) * (size_t)nnz);
-    memcpy(qp->Hval, val, sizeof(double) * (size_t)nnz);
+    (void)orc_csc_canonical(nV, nV, jc, ir, val, &qp->Hjc, &qp->Hir, &qp->Hval);
     qp->haveH = 1;
     return 0;
 }

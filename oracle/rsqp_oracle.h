@@ -62,6 +62,12 @@ void orc_sphb_transposed_times(int nrow, int ncol, int compressed_row, const int
                                const int *idx, const double *val, const double *p,
                                double *result);
 
+/* The matrix a CSC array describes, in canonical form: rows strictly ascending within every column, the entries
+ * that repeat a position summed in the order they are given (SpHbMat::times sums them as well). Returns the number
+ * of canonical entries and sets *ojc (ncol + 1), *oir, *oval (malloc'ed, the caller frees them). */
+int orc_csc_canonical(int nrow, int ncol, const int *jc, const int *ir, const double *val, int **ojc, int **oir,
+                      double **oval);
+
 /* SpHbMat dense ctor src/SpHbMat.cpp:59-165 (row_oriented data -> CSC / CSR). */
 int orc_sphb_from_dense(const double *data, int nrow, int ncol, int row_oriented,
                         int compressed_row, int *ptr, int *idx, double *val);

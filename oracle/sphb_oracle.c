@@ -263,3 +263,39 @@ void orc_handler_update_bounds(int n, int m, double delta, const double *x_l,
 void orc_handler_set_g(int n, int m, const double *grad, double rho, double *g) {
     for (int i = 0; i < n + 2 * m; i++) g[i] = i < n ? grad[i] : rho;
 }
+
+/* ---------------------------------------------------------------------- */
+/* canonical form of a CSC array (see rsqp_oracle.h)                       */
+/* ---------------------------------------------------------------------- */
+static int cmp_int(const void *a, const void *b) {
+    const int x = *(const int *)a, y = *(const int *)b;
+    return (x > y) - (x < y);
+}
+
+int orc_csc_canonical(int nrow, int ncol, const int *jc, const int *ir, const double *val, int **ojc, int **oir,
+                      double **oval) {
+    const int nnz = jc[ncol];
+    int *cjc = (int *)calloc((size_t)ncol + 1, sizeof(int));
+    int *cir = (int *)calloc((size_t)(nnz > 0 ? nnz : 1), sizeof(int));
+    double *cval = (double *)calloc((size_t)(nnz > 0 ? nnz : 1), sizeof(double));
+    int *slot = (int *)malloc(sizeof(int) * (size_t)(nrow > 0 ? nrow : 1));
+    for (int r = 0; r < nrow; r++) slot[r] = -1;
+    int n = 0;
+    for (int c = 0; c < ncol; c++) {
+        const int c0 = n;
+        for (int k = jc[c]; k < jc[c + 1]; k++)       /* the distinct rows of the column, ascending */
+            if (slot[ir[k]] < 0) { slot[ir[k]] = 0; cir[n++] = ir[k]; }
+        qsort(cir + c0, (size_t)(n - c0), sizeof(int), cmp_int);
+        for (int p = c0; p < n; p++) slot[cir[p]] = p;
+        for (int k = jc[c]; k < jc[c + 1]; k++) {     /* first occurrence sets, later ones add, in the given order */
+            const int p = slot[ir[k]];
+            if (p >= 0) { cval[p] = val[k]; slot[ir[k]] = -2 - p; }
+            else cval[-2 - p] += val[k];
+        }
+        for (int p = c0; p < n; p++) slot[cir[p]] = -1;
+        cjc[c + 1] = n;
+    }
+    free(slot);
+    *ojc = cjc; *oir = cir; *oval = cval;
+    return n;
+}

@@ -85,6 +85,7 @@ struct DevBuf {
 struct Compressed {
     int nrow = 0, ncol = 0;
     std::vector<int> jc, ir, order, tmap;  // CSC; order[ext] = position; tmap[ext] = triplet index
+    std::vector<int> slot_of;              // canonical form of a non-canonical layout (canonicalise): caller slot -> canonical slot
     std::vector<double> val;
     int nnz() const { return (int)ir.size(); }
 };
@@ -126,6 +127,39 @@ void csr_from_csc(int nrow, int ncol, const int *jc, const int *ir, CsrCopy &out
             out.ci[p] = c;
             out.perm[p] = k;
         }
+}
+
+// The matrix a CSC array or a triplet list describes is the SUM of its entries (SpHbMat::times; contract of rsqp_hip.h). Every
+// consumer -- products, certificate, CSR copy, dense copies, the engines' staging of A and H -- reads the canonical form: rows
+// strictly ascending within each column, one entry per position. A caller's layout that is not canonical (rows out of order,
+// repeated positions) is folded ONCE, here, at structure upload. Returns false when `c` is canonical already: nothing is built,
+// the handle takes the path it always took. Otherwise `k` is the canonical matrix (with the caller's order / tmap and slot_of)
+// and its slot j the sum of the caller's slots cidx[cptr[j] .. cptr[j+1]), in the caller's order -- what fold_values of
+// sparse.hip and fold_host below add up on a value refresh.
+bool canonicalise(const Compressed &c, Compressed &k, std::vector<int> &cptr, std::vector<int> &cidx) {
+    bool canon = true;
+    for (int col = 0; col < c.ncol && canon; col++)
+        for (int p = c.jc[col] + 1; p < c.jc[col + 1] && canon; p++) canon = c.ir[p] > c.ir[p - 1];
+    if (canon) return false;
+    const int n = c.nnz();
+    k.nrow = c.nrow; k.ncol = c.ncol; k.order = c.order; k.tmap = c.tmap;
+    k.jc.assign(c.ncol + 1, 0); k.ir.clear(); k.val.clear(); k.ir.reserve(n); k.val.reserve(n); k.slot_of.assign(n, 0);
+    cptr.assign(1, 0); cidx.resize(n);
+    std::vector<int> idx(n);
+    for (int col = 0; col < c.ncol; col++) {
+        const int b = c.jc[col], e = c.jc[col + 1];
+        std::iota(idx.begin() + b, idx.begin() + e, b);
+        std::stable_sort(idx.begin() + b, idx.begin() + e, [&](int x, int y) { return c.ir[x] < c.ir[y]; });
+        for (int p = b; p < e; p++) {
+            const int u = idx[p];
+            if (p == b || c.ir[u] != c.ir[idx[p - 1]]) { k.ir.push_back(c.ir[u]); k.val.push_back(c.val[u]); cptr.push_back(cptr.back()); }
+            else k.val.back() += c.val[u];
+            k.slot_of[u] = (int)k.ir.size() - 1;
+            cidx[cptr.back()++] = u;
+        }
+        k.jc[col + 1] = (int)k.ir.size();
+    }
+    return true;
 }
 
 // blocks of consecutive majors with at most `chunk` entries; a longer major stands alone
@@ -200,11 +234,22 @@ int exitflag_of(int status_word, int ret) {
 // one matrix on the device (CSC + optional CSR copy + spmv blocks)
 // =====================================================================================
 struct DevMatrix {
-    int nrow = 0, ncol = 0, nnz = 0;
+    int nrow = 0, ncol = 0, nnz = 0;   // nnz: entries of the canonical form, the one every consumer reads (canonicalise)
+    int unnz = 0;                      // entries of the caller's layout: rsqp_get_*_nnz, rsqp_get_*_csc, order_ (= nnz when canonical)
+    bool canon = true;                 // the caller's layout is canonical: the arrays below ARE the caller's, nothing else is kept
+    bool dense = false;                // the canonical pattern stores every entry: the CSR copy is a tiled transpose of the values
     bool initialised = false, symmetric = false, from_triplet = false;
     int n_ident_entries = 0, n_triplet = 0;
     double structure_seconds = 0.0;   // one-off structure analysis (setStructure: sort + CSC / CSR / SpMV plan + upload), rsqp_get_structure_seconds
-    std::vector<int> h_jc, h_ir, h_order;  // host mirror of the pattern
+    std::vector<int> h_jc, h_ir, h_order;  // host mirror of the (canonical) pattern; order[triplet entry] = slot of the caller's layout
+    // a non-canonical caller layout: its pattern, the fold map (canonical slot j = sum of caller slots h_cidx[h_cptr[j] ..)) and its
+    // values -- in h_uval where the values are host-mapped (pin), else in uval on the device; get_*_csc and every refresh work on them
+    std::vector<int> h_ujc, h_uir, h_cptr, h_cidx;
+    std::vector<double> h_uval;
+    DevBuf<double> uval;
+    DevBuf<int> cptr, cidx;
+    const std::vector<int> &caller_jc() const { return canon ? h_jc : h_ujc; }
+    const std::vector<int> &caller_ir() const { return canon ? h_ir : h_uir; }
     DevBuf<int> jc, ir, order, tmap;                 // CSC
     DevBuf<int4> blk_c, blk_r;
     DevBuf<double> val, tv;                          // tv: staging for triplet values
@@ -341,6 +386,32 @@ struct rsqp_solver {
 
 namespace {
 
+// the CSR copy of A from its (canonical) CSC values
+hipError_t gather_csr(DevMatrix &M, hipStream_t stream) {
+    return M.dense ? rsqp_launch_gather_dense(M.nrow, M.ncol, M.val.p, M.rval.p, stream)
+                   : rsqp_launch_gather(M.nnz, M.perm.p, M.val.p, M.rval.p, stream);
+}
+
+// the canonical values of a non-canonical matrix after its caller-layout values changed: host-mapped values are summed by a host
+// loop (the sums of fold_values, in the same order), device-resident ones by one fold launch; then the CSR copy
+void fold_host(DevMatrix &M) {
+    double *v = M.val.host;
+    for (int j = 0; j < M.nnz; j++) {
+        int k = M.h_cptr[j];
+        double t = M.h_uval[M.h_cidx[k]];
+        for (k++; k < M.h_cptr[j + 1]; k++) t += M.h_uval[M.h_cidx[k]];
+        v[j] = t;
+    }
+    if (M.have_csr) for (int k = 0; k < M.nnz; k++) M.rval.host[k] = v[M.h_perm[k]];
+}
+hipError_t fold_dev(DevMatrix &M, hipStream_t stream) {
+    hipError_t e = rsqp_launch_fold(M.nnz, M.cptr.p, M.cidx.p, M.uval.p, M.val.p, stream);
+    if (e == hipSuccess && M.have_csr) e = gather_csr(M, stream);
+    return e;
+}
+
+int upload_canonical(DevMatrix &M, const Compressed &c, bool want_csr, bool zero_copy, hipStream_t stream);
+
 // arena form of the function below (LDS-scale single-QP handles whose arena holds the matrix): no allocation, one copy
 int upload_matrix_arena(DevMatrix &M, const Compressed &c, bool want_csr, hipStream_t stream) {
     M.arena_used = 0;
@@ -352,8 +423,8 @@ int upload_matrix_arena(DevMatrix &M, const Compressed &c, bool want_csr, hipStr
     M.rval.map(static_cast<double *>(dev) + n, static_cast<double *>(M.pin) + n, n);
     std::memset(M.pin, 0, 2 * n * sizeof(double));
     HIPCHK(M.val.upload(c.val.data(), c.val.size()));
-    bool ok = M.take(M.jc, c.jc.size()) && M.take(M.ir, (size_t)M.nnz + 2) && M.take(M.order, std::max(M.nnz, 1)) &&
-              M.take(M.tv, std::max(M.nnz, 1));
+    bool ok = M.take(M.jc, c.jc.size()) && M.take(M.ir, (size_t)M.nnz + 2) && M.take(M.order, std::max<size_t>(c.order.size(), 1)) &&
+              M.take(M.tv, std::max(M.unnz, 1));
     if (ok && !c.tmap.empty()) ok = M.take(M.tmap, c.tmap.size());
     std::vector<int4> blk = build_blocks(M.ncol, c.jc.data(), rsqp_spmv_chunk());
     M.nblk_c = (int)blk.size();
@@ -367,9 +438,9 @@ int upload_matrix_arena(DevMatrix &M, const Compressed &c, bool want_csr, hipStr
     if (want_csr) {
         CsrCopy r;
         csr_from_csc(M.nrow, M.ncol, c.jc.data(), c.ir.data(), r);
-        std::vector<int> inv(std::max(M.nnz, 1), 0), ro(std::max(M.nnz, 1), 0);
+        std::vector<int> inv(std::max(M.nnz, 1), 0), ro(std::max<size_t>(c.order.size(), 1), 0);
         for (int k = 0; k < M.nnz; k++) inv[r.perm[k]] = k;
-        for (size_t i = 0; i < c.order.size(); i++) ro[i] = inv[c.order[i]];
+        for (size_t i = 0; i < c.order.size(); i++) ro[i] = inv[c.slot_of.empty() ? c.order[i] : c.slot_of[c.order[i]]];
         std::vector<int4> blr = build_blocks(M.nrow, r.rp.data(), rsqp_spmv_chunk());
         M.nblk_r = (int)blr.size();
         ok = M.take(M.rp, r.rp.size()) && M.take(M.ci, (size_t)M.nnz + 2) && M.take(M.perm, std::max(M.nnz, 1)) &&
@@ -386,9 +457,29 @@ int upload_matrix_arena(DevMatrix &M, const Compressed &c, bool want_csr, hipStr
     return RSQP_OK;
 }
 
-int upload_matrix(DevMatrix &M, const Compressed &c, bool want_csr, bool zero_copy = false, hipStream_t stream = nullptr) {
-    M.nrow = c.nrow; M.ncol = c.ncol; M.nnz = c.nnz();
+// `cu` is the caller's layout; the device receives its canonical form (canonicalise)
+int upload_matrix(DevMatrix &M, const Compressed &cu, bool want_csr, bool zero_copy = false, hipStream_t stream = nullptr) {
+    Compressed ck;
+    std::vector<int> cptr, cidx;
+    const bool folded = canonicalise(cu, ck, cptr, cidx);
+    const Compressed &c = folded ? ck : cu;
+    M.nrow = c.nrow; M.ncol = c.ncol; M.nnz = c.nnz(); M.unnz = cu.nnz(); M.canon = !folded;
+    M.dense = (long long)M.nnz == (long long)M.nrow * M.ncol;   // (canonical: every position of every column, rows in order)
     M.h_jc = c.jc; M.h_ir = c.ir; M.h_order = c.order; M.h_tmap = c.tmap;
+    M.uval.release(); M.cptr.release(); M.cidx.release();
+    if (folded) { M.h_ujc = cu.jc; M.h_uir = cu.ir; M.h_cptr = std::move(cptr); M.h_cidx = std::move(cidx); }
+    else { M.h_ujc.clear(); M.h_uir.clear(); M.h_cptr.clear(); M.h_cidx.clear(); }
+    M.h_uval.clear();
+    const int rc = upload_canonical(M, c, want_csr, zero_copy, stream);
+    if (rc != RSQP_OK || !folded) return rc;
+    // the caller's values: next to the host-mapped canonical ones, or on the device with the fold map
+    if (M.pin) { M.h_uval = cu.val; return RSQP_OK; }
+    HIPCHK(M.uval.alloc(std::max(M.unnz, 1), false)); HIPCHK(M.uval.upload(cu.val.data(), cu.val.size()));
+    HIPCHK(M.cptr.from(M.h_cptr)); HIPCHK(M.cidx.from(M.h_cidx));
+    return RSQP_OK;
+}
+
+int upload_canonical(DevMatrix &M, const Compressed &c, bool want_csr, bool zero_copy, hipStream_t stream) {
     if (zero_copy && M.arena_dev && M.pin && (size_t)M.nnz + 2 <= M.pin_cap) {
         // (an earlier copy of the staging mirror may still be on its way -- or, mapped arena, a kernel may still be reading the old
         //  structure; nothing can be when the matrix is set for the first time)
@@ -417,9 +508,9 @@ int upload_matrix(DevMatrix &M, const Compressed &c, bool want_csr, bool zero_co
     } else {
         HIPCHK(M.val.alloc(M.nnz + 2, true)); HIPCHK(M.val.upload(c.val.data(), c.val.size()));
     }
-    HIPCHK(M.order.alloc(std::max(M.nnz, 1), true)); HIPCHK(M.order.upload(c.order.data(), c.order.size()));
+    HIPCHK(M.order.alloc(std::max<size_t>(c.order.size(), 1), true)); HIPCHK(M.order.upload(c.order.data(), c.order.size()));
     if (!c.tmap.empty()) { HIPCHK(M.tmap.from(c.tmap)); }
-    HIPCHK(M.tv.alloc(std::max(M.nnz, 1), true));
+    HIPCHK(M.tv.alloc(std::max(M.unnz, 1), true));
     std::vector<int4> blk = build_blocks(M.ncol, c.jc.data(), rsqp_spmv_chunk());
     M.nblk_c = (int)blk.size();
     HIPCHK(M.blk_c.from(blk));
@@ -432,9 +523,9 @@ int upload_matrix(DevMatrix &M, const Compressed &c, bool want_csr, bool zero_co
         HIPCHK(M.perm.alloc(std::max(M.nnz, 1), true)); HIPCHK(M.perm.upload(r.perm.data(), r.perm.size()));
         if (!M.pin) HIPCHK(M.rval.alloc(M.nnz + 2, true));
         {   // rorder = (CSC slot -> CSR slot) o order: where a refreshed triplet value lands in the CSR copy
-            std::vector<int> inv(std::max(M.nnz, 1), 0), ro(std::max(M.nnz, 1), 0);
+            std::vector<int> inv(std::max(M.nnz, 1), 0), ro(std::max<size_t>(c.order.size(), 1), 0);
             for (int k = 0; k < M.nnz; k++) inv[r.perm[k]] = k;
-            for (size_t i = 0; i < c.order.size(); i++) ro[i] = inv[c.order[i]];
+            for (size_t i = 0; i < c.order.size(); i++) ro[i] = inv[c.slot_of.empty() ? c.order[i] : c.slot_of[c.order[i]]];
             HIPCHK(M.rorder.from(ro));
             M.h_rorder = ro; M.h_perm = r.perm;
         }
@@ -442,22 +533,24 @@ int upload_matrix(DevMatrix &M, const Compressed &c, bool want_csr, bool zero_co
         M.nblk_r = (int)blr.size();
         HIPCHK(M.blk_r.from(blr));
         if (M.pin) { for (int k = 0; k < M.nnz; k++) M.rval.host[k] = M.val.host[r.perm[k]]; }
-        else if (((long long)M.nnz == (long long)M.nrow * M.ncol ? rsqp_launch_gather_dense(M.nrow, M.ncol, M.val.p, M.rval.p, nullptr)
-                                                                 : rsqp_launch_gather(M.nnz, M.perm.p, M.val.p, M.rval.p, nullptr)) != hipSuccess)
-            return fail(RSQP_ERR_DEVICE, "gather launch failed");
+        else if (gather_csr(M, nullptr) != hipSuccess) return fail(RSQP_ERR_DEVICE, "gather launch failed");
     }
     M.initialised = true;
     return RSQP_OK;
 }
 
-// is the CSC matrix (n <= 8 columns) symmetric, value by value? (eligibility of the tableau kernel of qp_tiny.hip)
+// is the matrix of a CSC array (n <= 8 columns) symmetric, value by value? (eligibility of the tableau kernel of qp_tiny.hip)
+// (any layout: entries that repeat a position are summed in their order, as canonicalise sums them)
 bool small_csc_symmetric(int n, const int *jc, const int *ir, const double *val) {
     if (n > 8) return false;
     double d[64] = {0.0};
+    bool seen[64] = {false};
     for (int c = 0; c < n; c++)
         for (int k = jc[c]; k < jc[c + 1]; k++) {
             if (ir[k] < 0 || ir[k] >= n) return false;
-            d[ir[k] * 8 + c] = val[k];
+            const int i = ir[k] * 8 + c;
+            d[i] = seen[i] ? d[i] + val[k] : val[k];
+            seen[i] = true;
         }
     for (int r = 0; r < n; r++)
         for (int c = 0; c < r; c++)
@@ -718,6 +811,18 @@ extern "C" int rsqp_set_A_triplet(rsqp_solver *s, int nnz, const int *irow, cons
     }
     if (!M.from_triplet || nnz != M.n_triplet) return fail(RSQP_ERR_ARG, "rsqp_set_A_triplet: pattern changed");
     // SpHbMat::setMatVal(rhs, I_info): only the first nnz(J) entries are rewritten
+    if (!M.canon) {   // repeated positions: the values land in the caller's layout, the canonical ones are their sums
+        if (M.pin) {
+            if (s->cert_pending) { HIPCHK(hipStreamSynchronize(s->stream)); s->cert_pending = false; }
+            for (int i = 0; i < nnz; i++) M.h_uval[M.h_order[i]] = val[i];
+            fold_host(M);
+            return RSQP_OK;
+        }
+        HIPCHK(M.tv.upload(val, nnz));
+        if (rsqp_launch_scatter(nnz, M.order.p, nullptr, M.tv.p, M.uval.p, s->stream) != hipSuccess || fold_dev(M, s->stream) != hipSuccess)
+            return fail(RSQP_ERR_DEVICE, "value refresh launch failed");
+        return RSQP_OK;
+    }
     if (M.pin) {
         // host-mapped values: the scatter through order_ is a host loop (no kernel of this handle is running: every solve and
         // certificate of the single-QP boundary is waited for before its call returns)
@@ -755,7 +860,7 @@ extern "C" int rsqp_set_H_triplet(rsqp_solver *s, int nnz, const int *irow, cons
         Compressed cs;
         csc_from_entries(s->nV, s->nV, r, c, v, cs);
         cs.tmap = tmap;
-        s->h_sym = is_symmetric != 0 || (s->nV <= 8 && small_csc_symmetric(s->nV, cs.jc.data(), cs.ir.data(), cs.val.data()));
+        s->h_sym = is_symmetric != 0 || (s->nV <= 8 && small_csc_symmetric(s->nV, cs.jc.data(), cs.ir.data(), cs.val.data()));   // (sums repeats)
         M.from_triplet = true; M.n_triplet = nnz; M.symmetric = is_symmetric != 0;
         int rc = upload_matrix(M, cs, false, s->fits_small, s->stream);
         if (rc != RSQP_OK) return rc;
@@ -768,13 +873,15 @@ extern "C" int rsqp_set_H_triplet(rsqp_solver *s, int nnz, const int *irow, cons
     if (!M.symmetric) s->h_sym = false;       // (values of a general triplet matrix: re-examined below where they are at hand)
     if (M.pin) {
         if (s->cert_pending) { HIPCHK(hipStreamSynchronize(s->stream)); s->cert_pending = false; }
-        double *v = M.val.host;
-        for (int j = 0; j < M.nnz; j++) v[M.h_order[j]] = val[M.h_tmap.empty() ? j : M.h_tmap[j]];
-        if (!M.symmetric) s->h_sym = s->nV <= 8 && small_csc_symmetric(s->nV, M.h_jc.data(), M.h_ir.data(), v);
+        double *v = M.canon ? M.val.host : M.h_uval.data();     // (repeated positions: the caller's layout, then the sums)
+        for (int j = 0; j < M.unnz; j++) v[M.h_order[j]] = val[M.h_tmap.empty() ? j : M.h_tmap[j]];
+        if (!M.canon) fold_host(M);
+        if (!M.symmetric) s->h_sym = s->nV <= 8 && small_csc_symmetric(s->nV, M.h_jc.data(), M.h_ir.data(), M.val.host);
         return RSQP_OK;
     }
     HIPCHK(M.tv.upload(val, nnz));
-    if (rsqp_launch_scatter(M.nnz, M.order.p, M.tmap.p, M.tv.p, M.val.p, s->stream) != hipSuccess)
+    if (rsqp_launch_scatter(M.unnz, M.order.p, M.tmap.p, M.tv.p, M.canon ? M.val.p : M.uval.p, s->stream) != hipSuccess ||
+        (!M.canon && fold_dev(M, s->stream) != hipSuccess))
         return fail(RSQP_ERR_DEVICE, "value refresh launch failed");
     return RSQP_OK;
 }
@@ -785,27 +892,34 @@ int set_csc(rsqp_solver *s, DevMatrix &M, int nrow, int ncol, const int *jc, con
     if (!s || !jc || (jc[ncol] > 0 && (!ir || !val))) return fail(RSQP_ERR_ARG, "rsqp_set_*_csc");
     if (s->firstQPsolved && !*flag) *flag = true;
     const int nnz = jc[ncol];
-    // same pattern (compared entry by entry, not just by count): refresh values
-    if (M.initialised && nnz == M.nnz && !M.from_triplet && M.nrow == nrow && M.ncol == ncol &&
-        std::equal(jc, jc + ncol + 1, M.h_jc.begin()) && std::equal(ir, ir + nnz, M.h_ir.begin())) {
+    // same pattern as the caller's layout of the last call (compared entry by entry, not just by count): refresh values
+    if (M.initialised && nnz == M.unnz && !M.from_triplet && M.nrow == nrow && M.ncol == ncol &&
+        std::equal(jc, jc + ncol + 1, M.caller_jc().begin()) && std::equal(ir, ir + nnz, M.caller_ir().begin())) {
         if (M.pin && s->cert_pending) { HIPCHK(hipStreamSynchronize(s->stream)); s->cert_pending = false; }
+        if (!M.canon) {   // rows out of order or repeated: the caller's values, then their canonical sums
+            if (M.pin) { std::copy(val, val + nnz, M.h_uval.begin()); fold_host(M); }
+            else {
+                HIPCHK(M.uval.upload(val, nnz));
+                if (fold_dev(M, s->stream) != hipSuccess) return fail(RSQP_ERR_DEVICE, "value refresh launch failed");
+            }
+            return RSQP_OK;
+        }
         HIPCHK(M.val.upload(val, nnz));
         if (M.pin) { if (M.have_csr) for (int k = 0; k < M.nnz; k++) M.rval.host[k] = val[M.h_perm[k]]; }
-        else if (M.have_csr && ((long long)M.nnz == (long long)M.nrow * M.ncol ? rsqp_launch_gather_dense(M.nrow, M.ncol, M.val.p, M.rval.p, s->stream)
-                                                                                : rsqp_launch_gather(M.nnz, M.perm.p, M.val.p, M.rval.p, s->stream)) != hipSuccess)
-            return fail(RSQP_ERR_DEVICE, "gather launch failed");
+        else if (M.have_csr && gather_csr(M, s->stream) != hipSuccess) return fail(RSQP_ERR_DEVICE, "gather launch failed");
         return RSQP_OK;
+    }
+    if (jc[0] != 0) return fail(RSQP_ERR_ARG, "rsqp_set_*_csc: column pointers must start at 0");
+    for (int c = 0; c < ncol; c++) {
+        if (jc[c] > jc[c + 1]) return fail(RSQP_ERR_ARG, "rsqp_set_*_csc: column pointers not monotone");
+        for (int k = jc[c]; k < jc[c + 1]; k++)
+            if (ir[k] < 0 || ir[k] >= nrow) return fail(RSQP_ERR_ARG, "rsqp_set_*_csc: row index out of range");
     }
     Compressed cs;
     cs.nrow = nrow; cs.ncol = ncol;
     cs.jc.assign(jc, jc + ncol + 1); cs.ir.assign(ir, ir + nnz); cs.val.assign(val, val + nnz);
     cs.order.resize(nnz);
     std::iota(cs.order.begin(), cs.order.end(), 0);
-    for (int c = 0; c < ncol; c++) {
-        if (jc[c] > jc[c + 1]) return fail(RSQP_ERR_ARG, "rsqp_set_*_csc: column pointers not monotone");
-        for (int k = jc[c]; k < jc[c + 1]; k++)
-            if (ir[k] < 0 || ir[k] >= nrow) return fail(RSQP_ERR_ARG, "rsqp_set_*_csc: row index out of range");
-    }
     // a new pattern on an initialised matrix: everything derived from the old one (CSR copy, SpMV
     // blocks, host mirror) is rebuilt; the dirty flag set above makes optimizeQP re-factorise
     M.from_triplet = false;
@@ -820,12 +934,15 @@ int set_csc(rsqp_solver *s, DevMatrix &M, int nrow, int ncol, const int *jc, con
 }
 int get_csc(const DevMatrix &M, hipStream_t stream, int *jc, int *ir, double *val, int *order) {
     if (!M.initialised) return fail(RSQP_ERR_ARG, "matrix not set");
-    if (jc) std::copy(M.h_jc.begin(), M.h_jc.end(), jc);
-    if (ir) std::copy(M.h_ir.begin(), M.h_ir.end(), ir);
+    // (the caller's layout, as it was given: a non-canonical one is kept beside the canonical form)
+    if (jc) std::copy(M.caller_jc().begin(), M.caller_jc().end(), jc);
+    if (ir) std::copy(M.caller_ir().begin(), M.caller_ir().end(), ir);
     if (order) std::copy(M.h_order.begin(), M.h_order.end(), order);
     if (val) {
         HIPCHK(hipStreamSynchronize(stream));   // the value refresh kernels of this handle
-        HIPCHK(M.val.download(val, M.nnz));
+        if (M.canon) HIPCHK(M.val.download(val, M.nnz));
+        else if (M.pin) std::copy(M.h_uval.begin(), M.h_uval.end(), val);
+        else HIPCHK(M.uval.download(val, M.unnz));
     }
     return RSQP_OK;
 }
@@ -842,8 +959,8 @@ extern "C" int rsqp_set_H_csc(rsqp_solver *s, const int *jc, const int *ir, cons
     if (jc && (jc[s->nV] == 0 || (ir && val))) s->h_sym = s->nV <= 8 && small_csc_symmetric(s->nV, jc, ir, val);
     return set_csc(s, s->H, s->nV, s->nV, jc, ir, val, false, &s->upd_H);
 }
-extern "C" int rsqp_get_A_nnz(const rsqp_solver *s) { return s && s->A.initialised ? s->A.nnz : -1; }
-extern "C" int rsqp_get_H_nnz(const rsqp_solver *s) { return s && s->H.initialised ? s->H.nnz : -1; }
+extern "C" int rsqp_get_A_nnz(const rsqp_solver *s) { return s && s->A.initialised ? s->A.unnz : -1; }
+extern "C" int rsqp_get_H_nnz(const rsqp_solver *s) { return s && s->H.initialised ? s->H.unnz : -1; }
 extern "C" int rsqp_get_A_csc(const rsqp_solver *s, int *jc, int *ir, double *val, int *order) {
     if (!s) return fail(RSQP_ERR_ARG, "null solver");
     return get_csc(s->A, s->stream, jc, ir, val, order);
@@ -1360,6 +1477,12 @@ struct rsqp_batch {
     bool hbm = false;                     // images beyond the LDS of a CU: every member on the HBM-resident kernel (qp_small_hbm.hip)
     bool h_sym = true;                    // every H symmetric value by value (the tableau kernel of qp_tiny.hip may take the batch)
     std::vector<int> h_Hjc, h_Hir;        // host copy of the H patterns (re-examined when the values change), small batches only
+    std::vector<long long> h_Huoff;       //   (the caller's layout: member q's entries start at h_Huoff[q])
+    // members given in a non-canonical layout (BatchPool): the pools hold the canonical form; the caller's values and the fold maps
+    bool A_canon = true, H_canon = true;
+    long long sumAnz_u = 0, sumHnz_u = 0;
+    DevBuf<double> Auval, Huval;
+    DevBuf<int> Acptr, Acidx, Hcptr, Hcidx;
     std::vector<QPDesc> desc;
     std::vector<int> h_csr_perm;
     hipStream_t stream = nullptr;
@@ -1386,6 +1509,68 @@ struct rsqp_batch {
 };
 
 namespace {
+// the pooled CSC matrices of a batch (member q: nrow[q] x ncol[q]; its column pointers start at 0 and index its own slice), checked
+// as set_csc checks one matrix; when some member's layout is not canonical, the canonical pools are built (canonicalise, member by
+// member) and jc / ir / val point at them, else at the caller's arrays. Canonical slot j of the pool = sum of the caller's slots
+// cidx[cptr[j] .. cptr[j+1]).
+struct BatchPool {
+    const int *jc = nullptr, *ir = nullptr;
+    const double *val = nullptr;
+    bool canon = true;
+    long long unnz = 0;                  // entries of the caller's pool
+    std::vector<long long> uoff;         // member q's entries in the caller's pool start at uoff[q]
+    std::vector<int> kjc, kir, cptr, cidx;
+    std::vector<double> kval;
+};
+int batch_pool(int nq, const int *nrow, const int *ncol, const int *jc, const int *ir, const double *val, const char *what,
+               BatchPool &P) {
+    const std::string name = std::string("rsqp_batch_create: ") + what;
+    long long ojc = 0, onz = 0;
+    P.uoff.resize(nq);
+    for (int q = 0; q < nq; q++) {
+        const int *j = jc + ojc, *r = ir + onz;
+        if (j[0] != 0) return fail(RSQP_ERR_ARG, name + " column pointers must start at 0");
+        for (int c = 0; c < ncol[q]; c++) {
+            if (j[c] > j[c + 1]) return fail(RSQP_ERR_ARG, name + " column pointers not monotone");
+            for (int k = j[c]; k < j[c + 1]; k++) {
+                if (r[k] < 0 || r[k] >= nrow[q]) return fail(RSQP_ERR_ARG, name + " row index");
+                if (k > j[c] && r[k] <= r[k - 1]) P.canon = false;
+            }
+        }
+        P.uoff[q] = onz;
+        ojc += ncol[q] + 1; onz += j[ncol[q]];
+    }
+    P.unnz = onz;
+    P.jc = jc; P.ir = ir; P.val = val;
+    if (P.canon) return RSQP_OK;
+    if (!val) return fail(RSQP_ERR_ARG, name + " values missing");
+    P.cptr.assign(1, 0);
+    ojc = 0;
+    for (int q = 0; q < nq; q++) {
+        Compressed cu, ck;
+        std::vector<int> cp, ci;
+        const int *j = jc + ojc;
+        const long long u0 = P.uoff[q];
+        cu.nrow = nrow[q]; cu.ncol = ncol[q];
+        cu.jc.assign(j, j + ncol[q] + 1); cu.ir.assign(ir + u0, ir + u0 + j[ncol[q]]); cu.val.assign(val + u0, val + u0 + j[ncol[q]]);
+        const long long cbase = (long long)P.cidx.size();
+        const bool folded = canonicalise(cu, ck, cp, ci);
+        if (folded) {
+            for (size_t t = 1; t < cp.size(); t++) P.cptr.push_back((int)(cbase + cp[t]));
+            for (int u : ci) P.cidx.push_back((int)(u0 + u));
+        } else {
+            for (int t = 0; t < cu.nnz(); t++) { P.cidx.push_back((int)(u0 + t)); P.cptr.push_back((int)(cbase + t + 1)); }
+        }
+        const Compressed &c = folded ? ck : cu;
+        P.kjc.insert(P.kjc.end(), c.jc.begin(), c.jc.end());
+        P.kir.insert(P.kir.end(), c.ir.begin(), c.ir.end());
+        P.kval.insert(P.kval.end(), c.val.begin(), c.val.end());
+        ojc += ncol[q] + 1;
+    }
+    P.jc = P.kjc.data(); P.ir = P.kir.data(); P.val = P.kval.data();
+    return RSQP_OK;
+}
+
 QPPools pools_of(rsqp_batch *b) {
     QPPools p;
     std::memset(&p, 0, sizeof(p));
@@ -1407,12 +1592,21 @@ QPPools pools_of(rsqp_batch *b) {
 }
 }  // namespace
 
-extern "C" int rsqp_batch_create(int nq, const int *nV, const int *nC, const int *Ajc, const int *Air,
-                                 const double *Aval, const int *Hjc, const int *Hir, const double *Hval,
+extern "C" int rsqp_batch_create(int nq, const int *nV, const int *nC, const int *Ajc_in, const int *Air_in,
+                                 const double *Aval_in, const int *Hjc_in, const int *Hir_in, const double *Hval_in,
                                  int device, rsqp_batch **out) {
-    if (!out || nq <= 0 || !nV || !nC || !Ajc) return fail(RSQP_ERR_ARG, "rsqp_batch_create");
+    if (!out || nq <= 0 || !nV || !nC || !Ajc_in) return fail(RSQP_ERR_ARG, "rsqp_batch_create");
     if (rsqp_device_count() <= 0) return fail(RSQP_ERR_DEVICE, "rsqp_batch_create: no HIP device visible");
     if (device >= 0) HIPCHK(hipSetDevice(device));
+    for (int q = 0; q < nq; q++)
+        if (nV[q] <= 0 || nC[q] < 0) return fail(RSQP_ERR_ARG, "rsqp_batch_create: bad sizes");
+    // from here on Ajc ... Hval are the canonical pools: the caller's arrays where they are canonical (BatchPool)
+    BatchPool PA, PH;
+    int prc = batch_pool(nq, nC, nV, Ajc_in, Air_in, Aval_in, "A", PA);
+    if (prc == RSQP_OK && Hjc_in) prc = batch_pool(nq, nV, nV, Hjc_in, Hir_in, Hval_in, "H", PH);
+    if (prc != RSQP_OK) return prc;
+    const int *Ajc = PA.jc, *Air = PA.ir, *Hjc = Hjc_in ? PH.jc : nullptr, *Hir = Hjc_in ? PH.ir : nullptr;
+    const double *Aval = PA.val, *Hval = Hjc_in ? PH.val : nullptr;
     rsqp_batch *b = new rsqp_batch();
     struct Guard { rsqp_batch *b; ~Guard() { delete b; } } guard{b};
     b->nq = nq;
@@ -1422,7 +1616,6 @@ extern "C" int rsqp_batch_create(int nq, const int *nV, const int *nC, const int
     std::vector<int> h_Arp, h_Aci, h_perm;
     long long offV = 0, offC = 0, offAjc = 0, offAnz = 0, offArp = 0, offHjc = 0, offHnz = 0, offState = 0;
     for (int q = 0; q < nq; q++) {
-        if (nV[q] <= 0 || nC[q] < 0) return fail(RSQP_ERR_ARG, "rsqp_batch_create: bad sizes");
         QPDesc &d = b->desc[q];
         d.nV = nV[q]; d.nC = nC[q];
         d.offV = (int)offV; d.offC = (int)offC; d.offAjc = (int)offAjc; d.offAnz = (int)offAnz;
@@ -1431,8 +1624,6 @@ extern "C" int rsqp_batch_create(int nq, const int *nV, const int *nC, const int
         const int *jc = Ajc + offAjc;
         const int annz = jc[d.nV];
         d.annz = annz; d.hnnz = b->haveH ? Hjc[offHjc + d.nV] : 0;
-        for (int k = 0; k < annz; k++)
-            if (Air[offAnz + k] < 0 || Air[offAnz + k] >= d.nC) return fail(RSQP_ERR_ARG, "rsqp_batch_create: A row index");
         CsrCopy r;
         csr_from_csc(d.nC, d.nV, jc, Air + offAnz, r);
         h_Arp.insert(h_Arp.end(), r.rp.begin(), r.rp.end());
@@ -1445,8 +1636,6 @@ extern "C" int rsqp_batch_create(int nq, const int *nV, const int *nC, const int
         b->mat_bytes_max = std::max(b->mat_bytes_max, rsqp_mat_lds_bytes(d.nV, d.nC, annz, b->haveH ? Hjc[offHjc + d.nV] : 0));
         if (b->haveH) {
             const int hnnz = Hjc[offHjc + d.nV];
-            for (int k = 0; k < hnnz; k++)
-                if (Hir[offHnz + k] < 0 || Hir[offHnz + k] >= d.nV) return fail(RSQP_ERR_ARG, "rsqp_batch_create: H row index");
             offHjc += d.nV + 1; offHnz += hnnz;
         }
         offState += rsqp_state_bytes(d.nV, d.nC) / 8;
@@ -1465,7 +1654,8 @@ extern "C" int rsqp_batch_create(int nq, const int *nV, const int *nC, const int
         }
     }
     if (b->haveH && b->nVmax <= 8) {
-        b->h_Hjc.assign(Hjc, Hjc + offHjc); b->h_Hir.assign(Hir, Hir + offHnz);
+        // (rsqp_batch_set_matrix_values gets the caller's layout: its pattern is kept)
+        b->h_Hjc.assign(Hjc_in, Hjc_in + offHjc); b->h_Hir.assign(Hir_in, Hir_in + PH.unnz); b->h_Huoff = PH.uoff;
         for (int q = 0; q < nq && b->h_sym; q++) {
             const QPDesc &d = b->desc[q];
             b->h_sym = small_csc_symmetric(d.nV, Hjc + d.offHjc, Hir + d.offHnz, Hval + d.offHnz);
@@ -1504,6 +1694,11 @@ extern "C" int rsqp_batch_create(int nq, const int *nV, const int *nC, const int
     if (b->haveH) {
         HIPCHK(b->Hjc.upload(Hjc, offHjc)); HIPCHK(b->Hir.upload(Hir, offHnz)); HIPCHK(b->Hval.upload(Hval, offHnz));
     }
+    // non-canonical layouts: the caller's values and the fold maps, for rsqp_batch_set_matrix_values
+    b->A_canon = PA.canon; b->sumAnz_u = PA.unnz;
+    if (!PA.canon) { HIPCHK(b->Auval.alloc(PA.unnz, false)); HIPCHK(b->Acptr.from(PA.cptr)); HIPCHK(b->Acidx.from(PA.cidx)); }
+    b->H_canon = PH.canon; b->sumHnz_u = b->haveH ? PH.unnz : 0;
+    if (b->haveH && !PH.canon) { HIPCHK(b->Huval.alloc(PH.unnz, false)); HIPCHK(b->Hcptr.from(PH.cptr)); HIPCHK(b->Hcidx.from(PH.cidx)); }
     HIPCHK(b->g.alloc(offV)); HIPCHK(b->lb.alloc(offV)); HIPCHK(b->ub.alloc(offV));
     HIPCHK(b->lbA.alloc(offC)); HIPCHK(b->ubA.alloc(offC));
     HIPCHK(b->x.alloc(offV)); HIPCHK(b->y.alloc(offV + offC)); HIPCHK(b->obj.alloc(nq));
@@ -1539,18 +1734,29 @@ extern "C" int rsqp_batch_set_vectors(rsqp_batch *b, const double *g, const doub
 extern "C" int rsqp_batch_set_matrix_values(rsqp_batch *b, const double *Aval, const double *Hval) {
     if (!b) return fail(RSQP_ERR_ARG, "null batch");
     HIPCHK(hipSetDevice(b->device));
+    // (the caller's layout of rsqp_batch_create; a non-canonical one is folded into the canonical pools by one launch)
     if (Aval) {
-        HIPCHK(b->Aval.upload(Aval, b->sumAnz));
+        if (b->A_canon) HIPCHK(b->Aval.upload(Aval, b->sumAnz));
+        else {
+            HIPCHK(b->Auval.upload(Aval, b->sumAnz_u));
+            if (rsqp_launch_fold((int)b->sumAnz, b->Acptr.p, b->Acidx.p, b->Auval.p, b->Aval.p, b->stream) != hipSuccess)
+                return fail(RSQP_ERR_DEVICE, "value fold launch failed");
+        }
         if (rsqp_launch_gather((int)b->sumAnz, b->perm.p, b->Aval.p, b->Arv.p, b->stream) != hipSuccess)
             return fail(RSQP_ERR_DEVICE, "gather launch failed");
     }
     if (Hval && b->haveH) {
-        HIPCHK(b->Hval.upload(Hval, b->sumHnz));
+        if (b->H_canon) HIPCHK(b->Hval.upload(Hval, b->sumHnz));
+        else {
+            HIPCHK(b->Huval.upload(Hval, b->sumHnz_u));
+            if (rsqp_launch_fold((int)b->sumHnz, b->Hcptr.p, b->Hcidx.p, b->Huval.p, b->Hval.p, b->stream) != hipSuccess)
+                return fail(RSQP_ERR_DEVICE, "value fold launch failed");
+        }
         if (!b->h_Hjc.empty()) {
             b->h_sym = true;
             for (int q = 0; q < b->nq && b->h_sym; q++) {
                 const QPDesc &d = b->desc[q];
-                b->h_sym = small_csc_symmetric(d.nV, b->h_Hjc.data() + d.offHjc, b->h_Hir.data() + d.offHnz, Hval + d.offHnz);
+                b->h_sym = small_csc_symmetric(d.nV, b->h_Hjc.data() + d.offHjc, b->h_Hir.data() + b->h_Huoff[q], Hval + b->h_Huoff[q]);
             }
         }
     }
@@ -1758,6 +1964,7 @@ int rsqp_batch_nq_internal(const rsqp_batch *b) { return b ? b->nq : 0; }
 extern "C" int rsqp_time_value_refresh_fused(rsqp_solver *s, int repeats, float *ms) {
     if (!s || repeats <= 0 || !ms || !s->A.initialised || !s->A.from_triplet || !s->A.have_csr) return fail(RSQP_ERR_ARG, "rsqp_time_value_refresh_fused");
     if (s->A.pin) return fail(RSQP_ERR_ARG, "rsqp_time_value_refresh_fused: this handle refreshes its values on the host (no kernel to time)");
+    if (!s->A.canon) return fail(RSQP_ERR_ARG, "rsqp_time_value_refresh_fused: the matrix repeats positions (its refresh folds)");
     HIPCHK(hipSetDevice(s->device));
     hipEvent_t e0, e1;
     HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
@@ -1777,6 +1984,7 @@ extern "C" int rsqp_time_value_refresh_fused(rsqp_solver *s, int repeats, float 
 extern "C" int rsqp_time_value_refresh(rsqp_solver *s, int repeats, float *ms_scatter, float *ms_gather) {
     if (!s || repeats <= 0 || !s->A.initialised || !s->A.from_triplet) return fail(RSQP_ERR_ARG, "rsqp_time_value_refresh");
     if (s->A.pin) return fail(RSQP_ERR_ARG, "rsqp_time_value_refresh: this handle refreshes its values on the host (no kernel to time)");
+    if (!s->A.canon) return fail(RSQP_ERR_ARG, "rsqp_time_value_refresh: the matrix repeats positions (its refresh folds)");
     HIPCHK(hipSetDevice(s->device));
     hipEvent_t e0, e1;
     HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));

@@ -673,6 +673,19 @@ __global__ void gather_values(int n, const int *__restrict__ perm, const double 
     if (i < n) dst[i] = src[perm[i]];
 }
 
+// canonical values of a matrix given in a non-canonical layout (rows out of order, repeated positions): slot j is the sum of the
+// caller's slots idx[ptr[j] .. ptr[j+1]) (at least one), in the caller's order -- the host loop of rsqp_api.hip (fold_host) sums alike
+__global__ void fold_values(int n, const int *__restrict__ ptr, const int *__restrict__ idx, const double *__restrict__ src,
+                            double *__restrict__ dst) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const int e = ptr[j + 1];
+    int k = ptr[j];
+    double s = src[idx[k]];
+    for (k++; k < e; k++) s += src[idx[k]];
+    dst[j] = s;
+}
+
 // ---------------------------------------------------------------------------------
 // KKT certificate. One workgroup of 256 threads per QP; products come from Ax / ATy / Hx
 // computed beforehand (large QPs: csx_stream_spmv) or inside (small QPs, batched).
@@ -977,6 +990,12 @@ hipError_t rsqp_launch_gather_dense(int nrow, int ncol, const double *src, doubl
 hipError_t rsqp_launch_gather(int n, const int *perm, const double *src, double *dst, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(gather_values, dim3((n + 255) / 256), dim3(256), 0, stream, n, perm, src, dst);
+    return hipGetLastError();
+}
+
+hipError_t rsqp_launch_fold(int n, const int *ptr, const int *idx, const double *src, double *dst, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(fold_values, dim3((n + 255) / 256), dim3(256), 0, stream, n, ptr, idx, src, dst);
     return hipGetLastError();
 }
 

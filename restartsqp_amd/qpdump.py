@@ -46,10 +46,11 @@ class QPData:
 
 
 def csc_to_dense(nrow, ncol, jc, ir, val):
+    """The matrix a CSC array describes: entries that repeat a position are summed (as SpHbMat::times does)."""
     M = np.zeros((nrow, ncol))
     for c in range(ncol):
         for k in range(jc[c], jc[c + 1]):
-            M[ir[k], c] = val[k]
+            M[ir[k], c] += val[k]
     return M
 
 
