@@ -2,9 +2,9 @@
 //
 // Host logic restated from the reference adapter src/qpOASESInterface.cpp: the
 // FIXED/VARIED warm-start dispatch (:137-224, :817-833), dirty flags (:361-496),
-// handle_error (:686-758), status mapping (:332-357). Structure analysis of
-// SpHbMat::setStructure (src/SpHbMat.cpp:196-355) runs once on the host (a sort); every
-// per-iteration operation (value refresh, products, certificate, QP solve) is a kernel.
+// handle_error (:686-758), status mapping (:332-357). How a matrix becomes device arrays
+// (SpHbMat::setStructure, setMatVal) is rsqp_matrix.h; every other per-iteration operation
+// (products, certificate, QP solve) is a kernel.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -17,6 +17,7 @@
 
 #include "../../include/rsqp_hip.h"
 #include "rsqp_large.h"
+#include "rsqp_matrix.h"
 #include "rsqp_sparse.h"
 
 namespace {
@@ -26,155 +27,6 @@ int fail(int code, const std::string &msg) {
     g_err = msg;
     return code;
 }
-#define HIPCHK(call)                                                                         \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return fail(RSQP_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-template <class T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t n = 0;
-    T *host = nullptr;   // non-null: p is the device view of host-mapped pinned memory owned elsewhere
-    T *stage = nullptr;  // non-null: p is a slice of a device arena owned elsewhere and `stage` the same slice of its pinned staging
-                         // mirror -- uploads are written there, the owner copies the arena to the device in ONE piece (DevMatrix)
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { release(); }
-    void release() {
-        if (p && !host && !stage) (void)hipFree(p);
-        p = nullptr;
-        host = nullptr;
-        stage = nullptr;
-        n = 0;
-    }
-    void map(T *dev, T *hst, size_t count) { release(); p = dev; host = hst; n = count; }
-    void carve(T *dev, T *stg, size_t count) { release(); p = dev; stage = stg; n = count; }
-    hipError_t alloc(size_t count, bool zero = true) {
-        release();
-        n = count;
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(&p), std::max<size_t>(count, 1) * sizeof(T));
-        if (e != hipSuccess) { p = nullptr; return e; }
-        if (zero) e = hipMemset(p, 0, std::max<size_t>(count, 1) * sizeof(T));
-        return e;
-    }
-    hipError_t upload(const T *h, size_t count) {
-        if (count == 0) return hipSuccess;
-        if (host) { std::memcpy(host, h, count * sizeof(T)); return hipSuccess; }
-        if (stage) { std::memcpy(stage, h, count * sizeof(T)); return hipSuccess; }     // (reaches the device with the arena)
-        return hipMemcpy(p, h, count * sizeof(T), hipMemcpyHostToDevice);
-    }
-    hipError_t from(const std::vector<T> &h) {
-        hipError_t e = alloc(h.size(), false);
-        if (e != hipSuccess) return e;
-        return upload(h.data(), h.size());
-    }
-    hipError_t download(T *h, size_t count) const {
-        if (count == 0) return hipSuccess;
-        if (host) { std::memcpy(h, host, count * sizeof(T)); return hipSuccess; }   // caller has synchronised
-        return hipMemcpy(h, p, count * sizeof(T), hipMemcpyDeviceToHost);
-    }
-};
-
-// ---------------------------------------------------------------------------------
-// structure analysis (host, one-off)
-// ---------------------------------------------------------------------------------
-struct Compressed {
-    int nrow = 0, ncol = 0;
-    std::vector<int> jc, ir, order, tmap;  // CSC; order[ext] = position; tmap[ext] = triplet index
-    std::vector<int> slot_of;              // canonical form of a non-canonical layout (canonicalise): caller slot -> canonical slot
-    std::vector<double> val;
-    int nnz() const { return (int)ir.size(); }
-};
-
-// SpHbMat::setStructure: sort the (extended) triplet list by (col,row); ties by position.
-void csc_from_entries(int nrow, int ncol, const std::vector<int> &row1, const std::vector<int> &col1,
-                      const std::vector<double> &v, Compressed &out) {
-    const int n = (int)v.size();
-    std::vector<int> perm(n);
-    std::iota(perm.begin(), perm.end(), 0);
-    std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) {
-        if (col1[a] != col1[b]) return col1[a] < col1[b];
-        return row1[a] < row1[b];
-    });
-    out.nrow = nrow; out.ncol = ncol;
-    out.jc.assign(ncol + 1, 0); out.ir.resize(n); out.val.resize(n); out.order.resize(n);
-    for (int p = 0; p < n; p++) {
-        int e = perm[p];
-        out.ir[p] = row1[e] - 1;
-        out.val[p] = v[e];
-        out.order[e] = p;
-        out.jc[col1[e]]++;  // 1-based col -> slot col (= 0-based col + 1)
-    }
-    for (int c = 0; c < ncol; c++) out.jc[c + 1] += out.jc[c];
-}
-
-struct CsrCopy {
-    std::vector<int> rp, ci, perm;  // perm[p] = CSC position of CSR entry p
-};
-void csr_from_csc(int nrow, int ncol, const int *jc, const int *ir, CsrCopy &out) {
-    const int nnz = jc[ncol];
-    out.rp.assign(nrow + 1, 0); out.ci.resize(nnz); out.perm.resize(nnz);
-    for (int k = 0; k < nnz; k++) out.rp[ir[k] + 1]++;
-    for (int r = 0; r < nrow; r++) out.rp[r + 1] += out.rp[r];
-    std::vector<int> fill(nrow, 0);
-    for (int c = 0; c < ncol; c++)
-        for (int k = jc[c]; k < jc[c + 1]; k++) {
-            int r = ir[k], p = out.rp[r] + fill[r]++;
-            out.ci[p] = c;
-            out.perm[p] = k;
-        }
-}
-
-// The matrix a CSC array or a triplet list describes is the SUM of its entries (SpHbMat::times; contract of rsqp_hip.h). Every
-// consumer -- products, certificate, CSR copy, dense copies, the engines' staging of A and H -- reads the canonical form: rows
-// strictly ascending within each column, one entry per position. A caller's layout that is not canonical (rows out of order,
-// repeated positions) is folded ONCE, here, at structure upload. Returns false when `c` is canonical already: nothing is built,
-// the handle takes the path it always took. Otherwise `k` is the canonical matrix (with the caller's order / tmap and slot_of)
-// and its slot j the sum of the caller's slots cidx[cptr[j] .. cptr[j+1]), in the caller's order -- what fold_values of
-// sparse.hip and fold_host below add up on a value refresh.
-bool canonicalise(const Compressed &c, Compressed &k, std::vector<int> &cptr, std::vector<int> &cidx) {
-    bool canon = true;
-    for (int col = 0; col < c.ncol && canon; col++)
-        for (int p = c.jc[col] + 1; p < c.jc[col + 1] && canon; p++) canon = c.ir[p] > c.ir[p - 1];
-    if (canon) return false;
-    const int n = c.nnz();
-    k.nrow = c.nrow; k.ncol = c.ncol; k.order = c.order; k.tmap = c.tmap;
-    k.jc.assign(c.ncol + 1, 0); k.ir.clear(); k.val.clear(); k.ir.reserve(n); k.val.reserve(n); k.slot_of.assign(n, 0);
-    cptr.assign(1, 0); cidx.resize(n);
-    std::vector<int> idx(n);
-    for (int col = 0; col < c.ncol; col++) {
-        const int b = c.jc[col], e = c.jc[col + 1];
-        std::iota(idx.begin() + b, idx.begin() + e, b);
-        std::stable_sort(idx.begin() + b, idx.begin() + e, [&](int x, int y) { return c.ir[x] < c.ir[y]; });
-        for (int p = b; p < e; p++) {
-            const int u = idx[p];
-            if (p == b || c.ir[u] != c.ir[idx[p - 1]]) { k.ir.push_back(c.ir[u]); k.val.push_back(c.val[u]); cptr.push_back(cptr.back()); }
-            else k.val.back() += c.val[u];
-            k.slot_of[u] = (int)k.ir.size() - 1;
-            cidx[cptr.back()++] = u;
-        }
-        k.jc[col + 1] = (int)k.ir.size();
-    }
-    return true;
-}
-
-// blocks of consecutive majors with at most `chunk` entries; a longer major stands alone
-std::vector<int4> build_blocks(int nmajor, const int *ptr, int chunk) {
-    std::vector<int4> blk;
-    int start = 0;
-    while (start < nmajor) {
-        int end = start + 1;
-        while (end < nmajor && ptr[end + 1] - ptr[start] <= chunk && end - start < 4096) end++;
-        blk.push_back(make_int4(start, end, ptr[start], ptr[end]));
-        start = end;
-    }
-    return blk;
-}
-
 // entry-parallel SpMV variant (sparse.hip csx_ldsvec_segscan): chunks of whole majors with at most 512 entries and 128 majors, one
 // "starts a major" bit per entry (16 words per chunk), the non-empty majors in order, the empty ones
 struct SegHost {
@@ -229,96 +81,6 @@ int exitflag_of(int status_word, int ret) {
 }
 
 }  // namespace
-
-// =====================================================================================
-// one matrix on the device (CSC + optional CSR copy + spmv blocks)
-// =====================================================================================
-struct DevMatrix {
-    int nrow = 0, ncol = 0, nnz = 0;   // nnz: entries of the canonical form, the one every consumer reads (canonicalise)
-    int unnz = 0;                      // entries of the caller's layout: rsqp_get_*_nnz, rsqp_get_*_csc, order_ (= nnz when canonical)
-    bool canon = true;                 // the caller's layout is canonical: the arrays below ARE the caller's, nothing else is kept
-    bool dense = false;                // the canonical pattern stores every entry: the CSR copy is a tiled transpose of the values
-    bool initialised = false, symmetric = false, from_triplet = false;
-    int n_ident_entries = 0, n_triplet = 0;
-    double structure_seconds = 0.0;   // one-off structure analysis (setStructure: sort + CSC / CSR / SpMV plan + upload), rsqp_get_structure_seconds
-    std::vector<int> h_jc, h_ir, h_order;  // host mirror of the (canonical) pattern; order[triplet entry] = slot of the caller's layout
-    // a non-canonical caller layout: its pattern, the fold map (canonical slot j = sum of caller slots h_cidx[h_cptr[j] ..)) and its
-    // values -- in h_uval where the values are host-mapped (pin), else in uval on the device; get_*_csc and every refresh work on them
-    std::vector<int> h_ujc, h_uir, h_cptr, h_cidx;
-    std::vector<double> h_uval;
-    DevBuf<double> uval;
-    DevBuf<int> cptr, cidx;
-    const std::vector<int> &caller_jc() const { return canon ? h_jc : h_ujc; }
-    const std::vector<int> &caller_ir() const { return canon ? h_ir : h_uir; }
-    DevBuf<int> jc, ir, order, tmap;                 // CSC
-    DevBuf<int4> blk_c, blk_r;
-    DevBuf<double> val, tv;                          // tv: staging for triplet values
-    DevBuf<int> rp, ci, perm, rorder;                // CSR copy (A only); rorder[i] = CSR position of triplet entry i (fused value refresh)
-    DevBuf<double> rval;
-    int nblk_c = 0, nblk_r = 0;
-    bool have_csr = false;
-    // LDS-scale single-QP handles: the VALUES (CSC and CSR copy) live in host-mapped pinned memory that the kernels read
-    // directly -- a value refresh (SpHbMat::setMatVal through order_) is then a host loop over a few dozen entries, no copy
-    // and no launch (a blocking hipMemcpy + a scatter launch cost ~15 us per matrix per SQP iteration of hs071)
-    void *pin = nullptr;
-    size_t pin_cap = 0;                    // entries each of the two value arrays in `pin` can hold
-    std::vector<int> h_rorder, h_tmap, h_perm;
-    // ... and everything else the structure analysis uploads (pattern, permutations, SpMV plan) is a slice of ONE device arena
-    // with a pinned staging mirror, both allocated by rsqp_create -- where the reference allocates as well
-    // (Algorithm::allocate_memory), outside the first SQP iteration: set_A / set_H of that iteration then cost one asynchronous
-    // copy instead of 17 hipMalloc + 15 blocking hipMemcpy + 2 hipHostMalloc (365 -> ~90 us for the first iteration of hs071)
-    char *arena_dev = nullptr, *arena_stage = nullptr;
-    size_t arena_cap = 0, arena_used = 0;
-    bool arena_mapped = false;             // the arena IS its staging mirror (host-mapped memory): no copy at all -- the kernels read the few
-                                           // dozen pattern words of an hs071-scale matrix over the link, as they read its values already
-    hipError_t reserve(int nrow_, int ncol_, bool mapped = false) {
-        const size_t cap = (size_t)nrow_ * (size_t)ncol_ + 2 * (size_t)(nrow_ + ncol_) + 8;      // dense + an identity block or two
-        arena_cap = 64 * cap + 64 * (size_t)(nrow_ + ncol_) + 4096;
-        hipError_t e;
-        arena_mapped = mapped;
-        if (mapped) {
-            e = hipHostMalloc(reinterpret_cast<void **>(&arena_stage), arena_cap, hipHostMallocMapped);
-            if (e != hipSuccess) { arena_stage = nullptr; arena_cap = 0; return e; }
-            e = hipHostGetDevicePointer(reinterpret_cast<void **>(&arena_dev), arena_stage, 0);
-            if (e != hipSuccess) { arena_dev = nullptr; return e; }
-        } else {
-        e = hipMalloc(reinterpret_cast<void **>(&arena_dev), arena_cap);
-        if (e != hipSuccess) { arena_dev = nullptr; arena_cap = 0; return e; }
-        e = hipHostMalloc(reinterpret_cast<void **>(&arena_stage), arena_cap, hipHostMallocDefault);
-        if (e != hipSuccess) { arena_stage = nullptr; return e; }
-        }
-        std::memset(arena_stage, 0, arena_cap);
-        e = hipHostMalloc(&pin, 2 * (cap + 2) * sizeof(double), hipHostMallocMapped);
-        if (e != hipSuccess) { pin = nullptr; return e; }
-        std::memset(pin, 0, 2 * (cap + 2) * sizeof(double));
-        pin_cap = cap + 2;
-        return hipSuccess;
-    }
-    void release_arena() {     // undo a partial reserve(): without an arena every array is allocated on its own
-        if (pin) { (void)hipHostFree(pin); pin = nullptr; pin_cap = 0; }
-        if (arena_dev && !arena_mapped) (void)hipFree(arena_dev);
-        arena_dev = nullptr;
-        if (arena_stage) { (void)hipHostFree(arena_stage); arena_stage = nullptr; }
-        arena_cap = arena_used = 0;
-    }
-    template <class T> bool take(DevBuf<T> &b, size_t count) {      // next slice of the arena (16-byte aligned, zero-filled)
-        const size_t bytes = (std::max<size_t>(count, 1) * sizeof(T) + 15) & ~(size_t)15;
-        if (!arena_dev || arena_used + bytes > arena_cap) return false;
-        std::memset(arena_stage + arena_used, 0, bytes);
-        b.carve(reinterpret_cast<T *>(arena_dev + arena_used), reinterpret_cast<T *>(arena_stage + arena_used), count);
-        arena_used += bytes;
-        return true;
-    }
-    void drop_slices() {
-        jc.release(); ir.release(); order.release(); tmap.release(); tv.release(); blk_c.release(); blk_r.release();
-        rp.release(); ci.release(); perm.release(); rorder.release();
-    }
-    ~DevMatrix() {
-        if (pin) { val.release(); rval.release(); (void)hipHostFree(pin); }
-        if (arena_dev) { drop_slices(); if (!arena_mapped) (void)hipFree(arena_dev); }
-        if (arena_stage) (void)hipHostFree(arena_stage);
-    }
-};
 
 struct rsqp_solver {
     int nV = 0, nC = 0, device = 0;
@@ -386,176 +148,21 @@ struct rsqp_solver {
 
 namespace {
 
-// the CSR copy of A from its (canonical) CSC values
-hipError_t gather_csr(DevMatrix &M, hipStream_t stream) {
-    return M.dense ? rsqp_launch_gather_dense(M.nrow, M.ncol, M.val.p, M.rval.p, stream)
-                   : rsqp_launch_gather(M.nnz, M.perm.p, M.val.p, M.rval.p, stream);
-}
-
-// the canonical values of a non-canonical matrix after its caller-layout values changed: host-mapped values are summed by a host
-// loop (the sums of fold_values, in the same order), device-resident ones by one fold launch; then the CSR copy
-void fold_host(DevMatrix &M) {
-    double *v = M.val.host;
-    for (int j = 0; j < M.nnz; j++) {
-        int k = M.h_cptr[j];
-        double t = M.h_uval[M.h_cidx[k]];
-        for (k++; k < M.h_cptr[j + 1]; k++) t += M.h_uval[M.h_cidx[k]];
-        v[j] = t;
-    }
-    if (M.have_csr) for (int k = 0; k < M.nnz; k++) M.rval.host[k] = v[M.h_perm[k]];
-}
-hipError_t fold_dev(DevMatrix &M, hipStream_t stream) {
-    hipError_t e = rsqp_launch_fold(M.nnz, M.cptr.p, M.cidx.p, M.uval.p, M.val.p, stream);
-    if (e == hipSuccess && M.have_csr) e = gather_csr(M, stream);
-    return e;
-}
-
-int upload_canonical(DevMatrix &M, const Compressed &c, bool want_csr, bool zero_copy, hipStream_t stream);
-
-// arena form of the function below (LDS-scale single-QP handles whose arena holds the matrix): no allocation, one copy
-int upload_matrix_arena(DevMatrix &M, const Compressed &c, bool want_csr, hipStream_t stream) {
-    M.arena_used = 0;
-    M.drop_slices();
-    const size_t n = M.pin_cap;
-    void *dev = nullptr;
-    HIPCHK(hipHostGetDevicePointer(&dev, M.pin, 0));
-    M.val.map(static_cast<double *>(dev), static_cast<double *>(M.pin), n);
-    M.rval.map(static_cast<double *>(dev) + n, static_cast<double *>(M.pin) + n, n);
-    std::memset(M.pin, 0, 2 * n * sizeof(double));
-    HIPCHK(M.val.upload(c.val.data(), c.val.size()));
-    bool ok = M.take(M.jc, c.jc.size()) && M.take(M.ir, (size_t)M.nnz + 2) && M.take(M.order, std::max<size_t>(c.order.size(), 1)) &&
-              M.take(M.tv, std::max(M.unnz, 1));
-    if (ok && !c.tmap.empty()) ok = M.take(M.tmap, c.tmap.size());
-    std::vector<int4> blk = build_blocks(M.ncol, c.jc.data(), rsqp_spmv_chunk());
-    M.nblk_c = (int)blk.size();
-    ok = ok && M.take(M.blk_c, blk.size());
-    if (!ok) return 1;
-    (void)M.jc.upload(c.jc.data(), c.jc.size()); (void)M.ir.upload(c.ir.data(), c.ir.size());
-    (void)M.order.upload(c.order.data(), c.order.size());
-    if (!c.tmap.empty()) (void)M.tmap.upload(c.tmap.data(), c.tmap.size());
-    (void)M.blk_c.upload(blk.data(), blk.size());
-    M.have_csr = want_csr;
-    if (want_csr) {
-        CsrCopy r;
-        csr_from_csc(M.nrow, M.ncol, c.jc.data(), c.ir.data(), r);
-        std::vector<int> inv(std::max(M.nnz, 1), 0), ro(std::max<size_t>(c.order.size(), 1), 0);
-        for (int k = 0; k < M.nnz; k++) inv[r.perm[k]] = k;
-        for (size_t i = 0; i < c.order.size(); i++) ro[i] = inv[c.slot_of.empty() ? c.order[i] : c.slot_of[c.order[i]]];
-        std::vector<int4> blr = build_blocks(M.nrow, r.rp.data(), rsqp_spmv_chunk());
-        M.nblk_r = (int)blr.size();
-        ok = M.take(M.rp, r.rp.size()) && M.take(M.ci, (size_t)M.nnz + 2) && M.take(M.perm, std::max(M.nnz, 1)) &&
-             M.take(M.rorder, ro.size()) && M.take(M.blk_r, blr.size());
-        if (!ok) return 1;
-        (void)M.rp.upload(r.rp.data(), r.rp.size()); (void)M.ci.upload(r.ci.data(), r.ci.size());
-        (void)M.perm.upload(r.perm.data(), r.perm.size()); (void)M.rorder.upload(ro.data(), ro.size());
-        (void)M.blk_r.upload(blr.data(), blr.size());
-        M.h_rorder = ro; M.h_perm = r.perm;
-        for (int k = 0; k < M.nnz; k++) M.rval.host[k] = M.val.host[r.perm[k]];
-    }
-    if (!M.arena_mapped) HIPCHK(hipMemcpyAsync(M.arena_dev, M.arena_stage, M.arena_used, hipMemcpyHostToDevice, stream));
-    M.initialised = true;
+// the structure upload of a setter whose analysis began at t0 (rsqp_get_structure_seconds)
+int stage_structure(rsqp_solver *s, DevMatrix &M, const Compressed &cs, bool want_csr, std::chrono::steady_clock::time_point t0) {
+    s->desc_ready = false;
+    const int rc = M.set_structure(cs, want_csr, s->fits_small, s->stream);
+    if (rc != RSQP_OK) return rc;
+    if (!M.arena_dev) (void)hipStreamSynchronize(s->stream);   // this handle's stream only (the uploads are blocking copies): other handles keep running
+    M.structure_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return RSQP_OK;
 }
 
-// `cu` is the caller's layout; the device receives its canonical form (canonicalise)
-int upload_matrix(DevMatrix &M, const Compressed &cu, bool want_csr, bool zero_copy = false, hipStream_t stream = nullptr) {
-    Compressed ck;
-    std::vector<int> cptr, cidx;
-    const bool folded = canonicalise(cu, ck, cptr, cidx);
-    const Compressed &c = folded ? ck : cu;
-    M.nrow = c.nrow; M.ncol = c.ncol; M.nnz = c.nnz(); M.unnz = cu.nnz(); M.canon = !folded;
-    M.dense = (long long)M.nnz == (long long)M.nrow * M.ncol;   // (canonical: every position of every column, rows in order)
-    M.h_jc = c.jc; M.h_ir = c.ir; M.h_order = c.order; M.h_tmap = c.tmap;
-    M.uval.release(); M.cptr.release(); M.cidx.release();
-    if (folded) { M.h_ujc = cu.jc; M.h_uir = cu.ir; M.h_cptr = std::move(cptr); M.h_cidx = std::move(cidx); }
-    else { M.h_ujc.clear(); M.h_uir.clear(); M.h_cptr.clear(); M.h_cidx.clear(); }
-    M.h_uval.clear();
-    const int rc = upload_canonical(M, c, want_csr, zero_copy, stream);
-    if (rc != RSQP_OK || !folded) return rc;
-    // the caller's values: next to the host-mapped canonical ones, or on the device with the fold map
-    if (M.pin) { M.h_uval = cu.val; return RSQP_OK; }
-    HIPCHK(M.uval.alloc(std::max(M.unnz, 1), false)); HIPCHK(M.uval.upload(cu.val.data(), cu.val.size()));
-    HIPCHK(M.cptr.from(M.h_cptr)); HIPCHK(M.cidx.from(M.h_cidx));
-    return RSQP_OK;
-}
-
-int upload_canonical(DevMatrix &M, const Compressed &c, bool want_csr, bool zero_copy, hipStream_t stream) {
-    if (zero_copy && M.arena_dev && M.pin && (size_t)M.nnz + 2 <= M.pin_cap) {
-        // (an earlier copy of the staging mirror may still be on its way -- or, mapped arena, a kernel may still be reading the old
-        //  structure; nothing can be when the matrix is set for the first time)
-        if (!(M.arena_mapped && !M.initialised)) (void)hipStreamSynchronize(stream);
-        const int rc = upload_matrix_arena(M, c, want_csr, stream);
-        if (rc == RSQP_OK) return rc;
-        if (rc < 0) return rc;
-        // the arena is too small for this matrix (rc == 1): the allocating path below, and the arena is not used again
-        M.drop_slices(); M.val.release(); M.rval.release();
-        if (!M.arena_mapped) (void)hipFree(M.arena_dev);
-        M.arena_dev = nullptr; M.arena_cap = 0;
-    }
-    if (M.pin) { M.val.release(); M.rval.release(); (void)hipHostFree(M.pin); M.pin = nullptr; M.pin_cap = 0; }
-    HIPCHK(M.jc.from(c.jc));
-    HIPCHK(M.ir.alloc(M.nnz + 2, true)); HIPCHK(M.ir.upload(c.ir.data(), c.ir.size()));
-    if (zero_copy) {
-        const size_t n = (size_t)M.nnz + 2;
-        HIPCHK(hipHostMalloc(&M.pin, 2 * n * sizeof(double), hipHostMallocMapped));
-        M.pin_cap = n;
-        std::memset(M.pin, 0, 2 * n * sizeof(double));
-        void *dev = nullptr;
-        HIPCHK(hipHostGetDevicePointer(&dev, M.pin, 0));
-        M.val.map(static_cast<double *>(dev), static_cast<double *>(M.pin), n);
-        M.rval.map(static_cast<double *>(dev) + n, static_cast<double *>(M.pin) + n, n);
-        HIPCHK(M.val.upload(c.val.data(), c.val.size()));
-    } else {
-        HIPCHK(M.val.alloc(M.nnz + 2, true)); HIPCHK(M.val.upload(c.val.data(), c.val.size()));
-    }
-    HIPCHK(M.order.alloc(std::max<size_t>(c.order.size(), 1), true)); HIPCHK(M.order.upload(c.order.data(), c.order.size()));
-    if (!c.tmap.empty()) { HIPCHK(M.tmap.from(c.tmap)); }
-    HIPCHK(M.tv.alloc(std::max(M.unnz, 1), true));
-    std::vector<int4> blk = build_blocks(M.ncol, c.jc.data(), rsqp_spmv_chunk());
-    M.nblk_c = (int)blk.size();
-    HIPCHK(M.blk_c.from(blk));
-    M.have_csr = want_csr;
-    if (want_csr) {
-        CsrCopy r;
-        csr_from_csc(M.nrow, M.ncol, c.jc.data(), c.ir.data(), r);
-        HIPCHK(M.rp.from(r.rp));
-        HIPCHK(M.ci.alloc(M.nnz + 2, true)); HIPCHK(M.ci.upload(r.ci.data(), r.ci.size()));
-        HIPCHK(M.perm.alloc(std::max(M.nnz, 1), true)); HIPCHK(M.perm.upload(r.perm.data(), r.perm.size()));
-        if (!M.pin) HIPCHK(M.rval.alloc(M.nnz + 2, true));
-        {   // rorder = (CSC slot -> CSR slot) o order: where a refreshed triplet value lands in the CSR copy
-            std::vector<int> inv(std::max(M.nnz, 1), 0), ro(std::max<size_t>(c.order.size(), 1), 0);
-            for (int k = 0; k < M.nnz; k++) inv[r.perm[k]] = k;
-            for (size_t i = 0; i < c.order.size(); i++) ro[i] = inv[c.slot_of.empty() ? c.order[i] : c.slot_of[c.order[i]]];
-            HIPCHK(M.rorder.from(ro));
-            M.h_rorder = ro; M.h_perm = r.perm;
-        }
-        std::vector<int4> blr = build_blocks(M.nrow, r.rp.data(), rsqp_spmv_chunk());
-        M.nblk_r = (int)blr.size();
-        HIPCHK(M.blk_r.from(blr));
-        if (M.pin) { for (int k = 0; k < M.nnz; k++) M.rval.host[k] = M.val.host[r.perm[k]]; }
-        else if (gather_csr(M, nullptr) != hipSuccess) return fail(RSQP_ERR_DEVICE, "gather launch failed");
-    }
-    M.initialised = true;
-    return RSQP_OK;
-}
-
-// is the matrix of a CSC array (n <= 8 columns) symmetric, value by value? (eligibility of the tableau kernel of qp_tiny.hip)
-// (any layout: entries that repeat a position are summed in their order, as canonicalise sums them)
-bool small_csc_symmetric(int n, const int *jc, const int *ir, const double *val) {
-    if (n > 8) return false;
-    double d[64] = {0.0};
-    bool seen[64] = {false};
-    for (int c = 0; c < n; c++)
-        for (int k = jc[c]; k < jc[c + 1]; k++) {
-            if (ir[k] < 0 || ir[k] >= n) return false;
-            const int i = ir[k] * 8 + c;
-            d[i] = seen[i] ? d[i] + val[k] : val[k];
-            seen[i] = true;
-        }
-    for (int r = 0; r < n; r++)
-        for (int c = 0; c < r; c++)
-            if (d[r * 8 + c] != d[c * 8 + r]) return false;
-    return true;
+// the value refresh of a setter. Host-mapped values are rewritten in place, and a speculative certificate may still be reading them (no
+// other kernel of this handle is running: every solve and certificate of the single-QP boundary is waited for before its call returns)
+int refresh_values(rsqp_solver *s, DevMatrix &M, const double *val, int n, RefreshKind kind) {
+    if (M.pin && s->cert_pending) { HIPCHK(hipStreamSynchronize(s->stream)); s->cert_pending = false; }
+    return M.refresh(val, n, kind, s->stream);
 }
 
 int flush_vectors(rsqp_solver *s) {
@@ -665,6 +272,7 @@ extern "C" int rsqp_create(int nV, int nC, int device, rsqp_solver **out) {
     if (rsqp_device_count() <= 0) return fail(RSQP_ERR_DEVICE, "rsqp_create: no HIP device visible");
     if (device >= 0) HIPCHK(hipSetDevice(device));
     rsqp_solver *s = new rsqp_solver();
+    struct Guard { rsqp_solver *s; ~Guard() { delete s; } } guard{s};
     s->nV = nV; s->nC = nC;
     s->fits_small = rsqp_small_qp_fits(nV, nC) != 0;
     s->engine = s->fits_small ? 1 : 2;
@@ -707,8 +315,8 @@ extern "C" int rsqp_create(int nV, int nC, int device, rsqp_solver **out) {
         // (hs071-scale handles keep the arena in host-mapped memory: set_A / set_H then cost a store each instead of a stream wait and a
         //  copy -- 78 -> 37 us on the first QP of an SQP run, later QPs unchanged; RSQP_ARENA_MAPPED=0 / 1 forces either form)
         const bool am = s->kn.arena_mapped >= 0 ? s->kn.arena_mapped != 0 : rsqp_tiny_fits(s->kn, nV, nC) != 0;
-        if (nC > 0 && s->A.reserve(nC, nV, am) != hipSuccess) { s->A.release_arena(); (void)hipGetLastError(); }
-        if (s->H.reserve(nV, nV, am) != hipSuccess) { s->H.release_arena(); (void)hipGetLastError(); }
+        if (nC > 0 && s->A.reserve(nC, nV, am) != hipSuccess) (void)hipGetLastError();
+        if (s->H.reserve(nV, nV, am) != hipSuccess) (void)hipGetLastError();
     } else {
         for (int k = 0; k < 5; k++) HIPCHK(s->d_vec[k].alloc((k <= RSQP_VEC_UB) ? nV : nC));
         HIPCHK(s->d_x.alloc(nV)); HIPCHK(s->d_y.alloc(nV + nC)); HIPCHK(s->d_obj.alloc(1));
@@ -722,6 +330,7 @@ extern "C" int rsqp_create(int nV, int nC, int device, rsqp_solver **out) {
     HIPCHK(s->d_Ax.alloc(nC)); HIPCHK(s->d_ATy.alloc(nV)); HIPCHK(s->d_Hx.alloc(nV));
     HIPCHK(s->d_in.alloc(std::max(nV, nC))); HIPCHK(s->d_out.alloc(std::max(nV, nC)));
     s->h_x.assign(nV, 0.0); s->h_y.assign(nV + nC, 0.0); s->h_wsb.assign(nV, 0); s->h_wsc.assign(nC, 0);
+    guard.s = nullptr;
     *out = s;
     return RSQP_OK;
 }
@@ -802,41 +411,10 @@ extern "C" int rsqp_set_A_triplet(rsqp_solver *s, int nnz, const int *irow, cons
         Compressed cs;
         csc_from_entries(s->nC, s->nV, r, c, v, cs);
         M.from_triplet = true; M.n_triplet = nnz; M.n_ident_entries = nid;
-        int rc = upload_matrix(M, cs, true, s->fits_small, s->stream);
-        if (rc != RSQP_OK) return rc;
-        if (!M.arena_dev) (void)hipStreamSynchronize(s->stream);   // this handle's stream only (the uploads are blocking copies): other handles keep running
-        M.structure_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        s->desc_ready = false;
-        return RSQP_OK;
+        return stage_structure(s, M, cs, true, t0);
     }
     if (!M.from_triplet || nnz != M.n_triplet) return fail(RSQP_ERR_ARG, "rsqp_set_A_triplet: pattern changed");
-    // SpHbMat::setMatVal(rhs, I_info): only the first nnz(J) entries are rewritten
-    if (!M.canon) {   // repeated positions: the values land in the caller's layout, the canonical ones are their sums
-        if (M.pin) {
-            if (s->cert_pending) { HIPCHK(hipStreamSynchronize(s->stream)); s->cert_pending = false; }
-            for (int i = 0; i < nnz; i++) M.h_uval[M.h_order[i]] = val[i];
-            fold_host(M);
-            return RSQP_OK;
-        }
-        HIPCHK(M.tv.upload(val, nnz));
-        if (rsqp_launch_scatter(nnz, M.order.p, nullptr, M.tv.p, M.uval.p, s->stream) != hipSuccess || fold_dev(M, s->stream) != hipSuccess)
-            return fail(RSQP_ERR_DEVICE, "value refresh launch failed");
-        return RSQP_OK;
-    }
-    if (M.pin) {
-        // host-mapped values: the scatter through order_ is a host loop (no kernel of this handle is running: every solve and
-        // certificate of the single-QP boundary is waited for before its call returns)
-        if (s->cert_pending) { HIPCHK(hipStreamSynchronize(s->stream)); s->cert_pending = false; }
-        double *v = M.val.host, *rv = M.rval.host;
-        for (int i = 0; i < nnz; i++) { v[M.h_order[i]] = val[i]; rv[M.h_rorder[i]] = val[i]; }
-        return RSQP_OK;
-    }
-    HIPCHK(M.tv.upload(val, nnz));
-    // one launch: every refreshed value goes to its CSC slot and to its slot of the CSR copy (the identity entries of [J I -I]
-    // keep their values in both, SpHbMat.cpp:368-380)
-    if (rsqp_launch_scatter_csc_csr(nnz, M.order.p, M.rorder.p, M.tv.p, M.val.p, M.rval.p, s->stream) != hipSuccess)
-        return fail(RSQP_ERR_DEVICE, "value refresh launch failed");
-    return RSQP_OK;
+    return refresh_values(s, M, val, nnz, REFRESH_TRIPLET_A);
 }
 
 extern "C" int rsqp_set_H_triplet(rsqp_solver *s, int nnz, const int *irow, const int *jcol, const double *val,
@@ -862,28 +440,13 @@ extern "C" int rsqp_set_H_triplet(rsqp_solver *s, int nnz, const int *irow, cons
         cs.tmap = tmap;
         s->h_sym = is_symmetric != 0 || (s->nV <= 8 && small_csc_symmetric(s->nV, cs.jc.data(), cs.ir.data(), cs.val.data()));   // (sums repeats)
         M.from_triplet = true; M.n_triplet = nnz; M.symmetric = is_symmetric != 0;
-        int rc = upload_matrix(M, cs, false, s->fits_small, s->stream);
-        if (rc != RSQP_OK) return rc;
-        if (!M.arena_dev) (void)hipStreamSynchronize(s->stream);   // this handle's stream only (the uploads are blocking copies): other handles keep running
-        M.structure_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        s->desc_ready = false;
-        return RSQP_OK;
+        return stage_structure(s, M, cs, false, t0);
     }
     if (!M.from_triplet || nnz != M.n_triplet) return fail(RSQP_ERR_ARG, "rsqp_set_H_triplet: pattern changed");
     if (!M.symmetric) s->h_sym = false;       // (values of a general triplet matrix: re-examined below where they are at hand)
-    if (M.pin) {
-        if (s->cert_pending) { HIPCHK(hipStreamSynchronize(s->stream)); s->cert_pending = false; }
-        double *v = M.canon ? M.val.host : M.h_uval.data();     // (repeated positions: the caller's layout, then the sums)
-        for (int j = 0; j < M.unnz; j++) v[M.h_order[j]] = val[M.h_tmap.empty() ? j : M.h_tmap[j]];
-        if (!M.canon) fold_host(M);
-        if (!M.symmetric) s->h_sym = s->nV <= 8 && small_csc_symmetric(s->nV, M.h_jc.data(), M.h_ir.data(), M.val.host);
-        return RSQP_OK;
-    }
-    HIPCHK(M.tv.upload(val, nnz));
-    if (rsqp_launch_scatter(M.unnz, M.order.p, M.tmap.p, M.tv.p, M.canon ? M.val.p : M.uval.p, s->stream) != hipSuccess ||
-        (!M.canon && fold_dev(M, s->stream) != hipSuccess))
-        return fail(RSQP_ERR_DEVICE, "value refresh launch failed");
-    return RSQP_OK;
+    const int rc = refresh_values(s, M, val, nnz, REFRESH_TRIPLET_H);
+    if (rc == RSQP_OK && M.pin && !M.symmetric) s->h_sym = s->nV <= 8 && small_csc_symmetric(s->nV, M.h_jc.data(), M.h_ir.data(), M.val.host);
+    return rc;
 }
 
 namespace {
@@ -893,28 +456,12 @@ int set_csc(rsqp_solver *s, DevMatrix &M, int nrow, int ncol, const int *jc, con
     if (s->firstQPsolved && !*flag) *flag = true;
     const int nnz = jc[ncol];
     // same pattern as the caller's layout of the last call (compared entry by entry, not just by count): refresh values
-    if (M.initialised && nnz == M.unnz && !M.from_triplet && M.nrow == nrow && M.ncol == ncol &&
-        std::equal(jc, jc + ncol + 1, M.caller_jc().begin()) && std::equal(ir, ir + nnz, M.caller_ir().begin())) {
-        if (M.pin && s->cert_pending) { HIPCHK(hipStreamSynchronize(s->stream)); s->cert_pending = false; }
-        if (!M.canon) {   // rows out of order or repeated: the caller's values, then their canonical sums
-            if (M.pin) { std::copy(val, val + nnz, M.h_uval.begin()); fold_host(M); }
-            else {
-                HIPCHK(M.uval.upload(val, nnz));
-                if (fold_dev(M, s->stream) != hipSuccess) return fail(RSQP_ERR_DEVICE, "value refresh launch failed");
-            }
-            return RSQP_OK;
-        }
-        HIPCHK(M.val.upload(val, nnz));
-        if (M.pin) { if (M.have_csr) for (int k = 0; k < M.nnz; k++) M.rval.host[k] = val[M.h_perm[k]]; }
-        else if (M.have_csr && gather_csr(M, s->stream) != hipSuccess) return fail(RSQP_ERR_DEVICE, "gather launch failed");
-        return RSQP_OK;
-    }
-    if (jc[0] != 0) return fail(RSQP_ERR_ARG, "rsqp_set_*_csc: column pointers must start at 0");
-    for (int c = 0; c < ncol; c++) {
-        if (jc[c] > jc[c + 1]) return fail(RSQP_ERR_ARG, "rsqp_set_*_csc: column pointers not monotone");
-        for (int k = jc[c]; k < jc[c + 1]; k++)
-            if (ir[k] < 0 || ir[k] >= nrow) return fail(RSQP_ERR_ARG, "rsqp_set_*_csc: row index out of range");
-    }
+    if (M.initialised && nnz == M.unnz() && !M.from_triplet && M.nrow == nrow && M.ncol == ncol &&
+        std::equal(jc, jc + ncol + 1, M.caller_jc().begin()) && std::equal(ir, ir + nnz, M.caller_ir().begin()))
+        return refresh_values(s, M, val, nnz, REFRESH_CSC);
+    static const char *const why[] = {"", "rsqp_set_*_csc: column pointers must start at 0", "rsqp_set_*_csc: column pointers not monotone",
+                                      "rsqp_set_*_csc: row index out of range"};
+    if (const int f = csc_fault(nrow, ncol, jc, ir)) return fail(RSQP_ERR_ARG, why[f]);
     Compressed cs;
     cs.nrow = nrow; cs.ncol = ncol;
     cs.jc.assign(jc, jc + ncol + 1); cs.ir.assign(ir, ir + nnz); cs.val.assign(val, val + nnz);
@@ -924,13 +471,7 @@ int set_csc(rsqp_solver *s, DevMatrix &M, int nrow, int ncol, const int *jc, con
     // blocks, host mirror) is rebuilt; the dirty flag set above makes optimizeQP re-factorise
     M.from_triplet = false;
     const auto t0 = std::chrono::steady_clock::now();
-    int rc = upload_matrix(M, cs, want_csr, s->fits_small, s->stream);
-    s->desc_ready = false;
-    if (rc == RSQP_OK) {
-        if (!M.arena_dev) (void)hipStreamSynchronize(s->stream);   // this handle's stream only (the uploads are blocking copies): other handles keep running
-        M.structure_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    }
-    return rc;
+    return stage_structure(s, M, cs, want_csr, t0);
 }
 int get_csc(const DevMatrix &M, hipStream_t stream, int *jc, int *ir, double *val, int *order) {
     if (!M.initialised) return fail(RSQP_ERR_ARG, "matrix not set");
@@ -940,9 +481,7 @@ int get_csc(const DevMatrix &M, hipStream_t stream, int *jc, int *ir, double *va
     if (order) std::copy(M.h_order.begin(), M.h_order.end(), order);
     if (val) {
         HIPCHK(hipStreamSynchronize(stream));   // the value refresh kernels of this handle
-        if (M.canon) HIPCHK(M.val.download(val, M.nnz));
-        else if (M.pin) std::copy(M.h_uval.begin(), M.h_uval.end(), val);
-        else HIPCHK(M.uval.download(val, M.unnz));
+        HIPCHK(M.caller_val().download(val, M.unnz()));
     }
     return RSQP_OK;
 }
@@ -959,8 +498,8 @@ extern "C" int rsqp_set_H_csc(rsqp_solver *s, const int *jc, const int *ir, cons
     if (jc && (jc[s->nV] == 0 || (ir && val))) s->h_sym = s->nV <= 8 && small_csc_symmetric(s->nV, jc, ir, val);
     return set_csc(s, s->H, s->nV, s->nV, jc, ir, val, false, &s->upd_H);
 }
-extern "C" int rsqp_get_A_nnz(const rsqp_solver *s) { return s && s->A.initialised ? s->A.unnz : -1; }
-extern "C" int rsqp_get_H_nnz(const rsqp_solver *s) { return s && s->H.initialised ? s->H.unnz : -1; }
+extern "C" int rsqp_get_A_nnz(const rsqp_solver *s) { return s && s->A.initialised ? s->A.unnz() : -1; }
+extern "C" int rsqp_get_H_nnz(const rsqp_solver *s) { return s && s->H.initialised ? s->H.unnz() : -1; }
 extern "C" int rsqp_get_A_csc(const rsqp_solver *s, int *jc, int *ir, double *val, int *order) {
     if (!s) return fail(RSQP_ERR_ARG, "null solver");
     return get_csc(s->A, s->stream, jc, ir, val, order);
@@ -1478,11 +1017,7 @@ struct rsqp_batch {
     bool h_sym = true;                    // every H symmetric value by value (the tableau kernel of qp_tiny.hip may take the batch)
     std::vector<int> h_Hjc, h_Hir;        // host copy of the H patterns (re-examined when the values change), small batches only
     std::vector<long long> h_Huoff;       //   (the caller's layout: member q's entries start at h_Huoff[q])
-    // members given in a non-canonical layout (BatchPool): the pools hold the canonical form; the caller's values and the fold maps
-    bool A_canon = true, H_canon = true;
-    long long sumAnz_u = 0, sumHnz_u = 0;
-    DevBuf<double> Auval, Huval;
-    DevBuf<int> Acptr, Acidx, Hcptr, Hcidx;
+    ValueFold Afold, Hfold;               // members given in a non-canonical layout (PooledCsc): the pools hold the canonical form
     std::vector<QPDesc> desc;
     std::vector<int> h_csr_perm;
     hipStream_t stream = nullptr;
@@ -1509,68 +1044,6 @@ struct rsqp_batch {
 };
 
 namespace {
-// the pooled CSC matrices of a batch (member q: nrow[q] x ncol[q]; its column pointers start at 0 and index its own slice), checked
-// as set_csc checks one matrix; when some member's layout is not canonical, the canonical pools are built (canonicalise, member by
-// member) and jc / ir / val point at them, else at the caller's arrays. Canonical slot j of the pool = sum of the caller's slots
-// cidx[cptr[j] .. cptr[j+1]).
-struct BatchPool {
-    const int *jc = nullptr, *ir = nullptr;
-    const double *val = nullptr;
-    bool canon = true;
-    long long unnz = 0;                  // entries of the caller's pool
-    std::vector<long long> uoff;         // member q's entries in the caller's pool start at uoff[q]
-    std::vector<int> kjc, kir, cptr, cidx;
-    std::vector<double> kval;
-};
-int batch_pool(int nq, const int *nrow, const int *ncol, const int *jc, const int *ir, const double *val, const char *what,
-               BatchPool &P) {
-    const std::string name = std::string("rsqp_batch_create: ") + what;
-    long long ojc = 0, onz = 0;
-    P.uoff.resize(nq);
-    for (int q = 0; q < nq; q++) {
-        const int *j = jc + ojc, *r = ir + onz;
-        if (j[0] != 0) return fail(RSQP_ERR_ARG, name + " column pointers must start at 0");
-        for (int c = 0; c < ncol[q]; c++) {
-            if (j[c] > j[c + 1]) return fail(RSQP_ERR_ARG, name + " column pointers not monotone");
-            for (int k = j[c]; k < j[c + 1]; k++) {
-                if (r[k] < 0 || r[k] >= nrow[q]) return fail(RSQP_ERR_ARG, name + " row index");
-                if (k > j[c] && r[k] <= r[k - 1]) P.canon = false;
-            }
-        }
-        P.uoff[q] = onz;
-        ojc += ncol[q] + 1; onz += j[ncol[q]];
-    }
-    P.unnz = onz;
-    P.jc = jc; P.ir = ir; P.val = val;
-    if (P.canon) return RSQP_OK;
-    if (!val) return fail(RSQP_ERR_ARG, name + " values missing");
-    P.cptr.assign(1, 0);
-    ojc = 0;
-    for (int q = 0; q < nq; q++) {
-        Compressed cu, ck;
-        std::vector<int> cp, ci;
-        const int *j = jc + ojc;
-        const long long u0 = P.uoff[q];
-        cu.nrow = nrow[q]; cu.ncol = ncol[q];
-        cu.jc.assign(j, j + ncol[q] + 1); cu.ir.assign(ir + u0, ir + u0 + j[ncol[q]]); cu.val.assign(val + u0, val + u0 + j[ncol[q]]);
-        const long long cbase = (long long)P.cidx.size();
-        const bool folded = canonicalise(cu, ck, cp, ci);
-        if (folded) {
-            for (size_t t = 1; t < cp.size(); t++) P.cptr.push_back((int)(cbase + cp[t]));
-            for (int u : ci) P.cidx.push_back((int)(u0 + u));
-        } else {
-            for (int t = 0; t < cu.nnz(); t++) { P.cidx.push_back((int)(u0 + t)); P.cptr.push_back((int)(cbase + t + 1)); }
-        }
-        const Compressed &c = folded ? ck : cu;
-        P.kjc.insert(P.kjc.end(), c.jc.begin(), c.jc.end());
-        P.kir.insert(P.kir.end(), c.ir.begin(), c.ir.end());
-        P.kval.insert(P.kval.end(), c.val.begin(), c.val.end());
-        ojc += ncol[q] + 1;
-    }
-    P.jc = P.kjc.data(); P.ir = P.kir.data(); P.val = P.kval.data();
-    return RSQP_OK;
-}
-
 QPPools pools_of(rsqp_batch *b) {
     QPPools p;
     std::memset(&p, 0, sizeof(p));
@@ -1600,11 +1073,12 @@ extern "C" int rsqp_batch_create(int nq, const int *nV, const int *nC, const int
     if (device >= 0) HIPCHK(hipSetDevice(device));
     for (int q = 0; q < nq; q++)
         if (nV[q] <= 0 || nC[q] < 0) return fail(RSQP_ERR_ARG, "rsqp_batch_create: bad sizes");
-    // from here on Ajc ... Hval are the canonical pools: the caller's arrays where they are canonical (BatchPool)
-    BatchPool PA, PH;
-    int prc = batch_pool(nq, nC, nV, Ajc_in, Air_in, Aval_in, "A", PA);
-    if (prc == RSQP_OK && Hjc_in) prc = batch_pool(nq, nV, nV, Hjc_in, Hir_in, Hval_in, "H", PH);
-    if (prc != RSQP_OK) return prc;
+    // from here on Ajc ... Hval are the canonical pools: the caller's arrays where they are canonical (PooledCsc)
+    PooledCsc PA, PH;
+    static const char *const why[] = {"", " column pointers must start at 0", " column pointers not monotone", " row index", " values missing"};
+    if (const int f = pool_csc(nq, nC, nV, Ajc_in, Air_in, Aval_in, PA)) return fail(RSQP_ERR_ARG, std::string("rsqp_batch_create: A") + why[f]);
+    if (Hjc_in)
+        if (const int f = pool_csc(nq, nV, nV, Hjc_in, Hir_in, Hval_in, PH)) return fail(RSQP_ERR_ARG, std::string("rsqp_batch_create: H") + why[f]);
     const int *Ajc = PA.jc, *Air = PA.ir, *Hjc = Hjc_in ? PH.jc : nullptr, *Hir = Hjc_in ? PH.ir : nullptr;
     const double *Aval = PA.val, *Hval = Hjc_in ? PH.val : nullptr;
     rsqp_batch *b = new rsqp_batch();
@@ -1695,10 +1169,8 @@ extern "C" int rsqp_batch_create(int nq, const int *nV, const int *nC, const int
         HIPCHK(b->Hjc.upload(Hjc, offHjc)); HIPCHK(b->Hir.upload(Hir, offHnz)); HIPCHK(b->Hval.upload(Hval, offHnz));
     }
     // non-canonical layouts: the caller's values and the fold maps, for rsqp_batch_set_matrix_values
-    b->A_canon = PA.canon; b->sumAnz_u = PA.unnz;
-    if (!PA.canon) { HIPCHK(b->Auval.alloc(PA.unnz, false)); HIPCHK(b->Acptr.from(PA.cptr)); HIPCHK(b->Acidx.from(PA.cidx)); }
-    b->H_canon = PH.canon; b->sumHnz_u = b->haveH ? PH.unnz : 0;
-    if (b->haveH && !PH.canon) { HIPCHK(b->Huval.alloc(PH.unnz, false)); HIPCHK(b->Hcptr.from(PH.cptr)); HIPCHK(b->Hcidx.from(PH.cidx)); }
+    HIPCHK(PA.fold_into(b->Afold));
+    if (b->haveH) HIPCHK(PH.fold_into(b->Hfold));
     HIPCHK(b->g.alloc(offV)); HIPCHK(b->lb.alloc(offV)); HIPCHK(b->ub.alloc(offV));
     HIPCHK(b->lbA.alloc(offC)); HIPCHK(b->ubA.alloc(offC));
     HIPCHK(b->x.alloc(offV)); HIPCHK(b->y.alloc(offV + offC)); HIPCHK(b->obj.alloc(nq));
@@ -1736,22 +1208,12 @@ extern "C" int rsqp_batch_set_matrix_values(rsqp_batch *b, const double *Aval, c
     HIPCHK(hipSetDevice(b->device));
     // (the caller's layout of rsqp_batch_create; a non-canonical one is folded into the canonical pools by one launch)
     if (Aval) {
-        if (b->A_canon) HIPCHK(b->Aval.upload(Aval, b->sumAnz));
-        else {
-            HIPCHK(b->Auval.upload(Aval, b->sumAnz_u));
-            if (rsqp_launch_fold((int)b->sumAnz, b->Acptr.p, b->Acidx.p, b->Auval.p, b->Aval.p, b->stream) != hipSuccess)
-                return fail(RSQP_ERR_DEVICE, "value fold launch failed");
-        }
+        HIPCHK(b->Afold.refresh(Aval, b->Aval, (int)b->sumAnz, b->stream));
         if (rsqp_launch_gather((int)b->sumAnz, b->perm.p, b->Aval.p, b->Arv.p, b->stream) != hipSuccess)
             return fail(RSQP_ERR_DEVICE, "gather launch failed");
     }
     if (Hval && b->haveH) {
-        if (b->H_canon) HIPCHK(b->Hval.upload(Hval, b->sumHnz));
-        else {
-            HIPCHK(b->Huval.upload(Hval, b->sumHnz_u));
-            if (rsqp_launch_fold((int)b->sumHnz, b->Hcptr.p, b->Hcidx.p, b->Huval.p, b->Hval.p, b->stream) != hipSuccess)
-                return fail(RSQP_ERR_DEVICE, "value fold launch failed");
-        }
+        HIPCHK(b->Hfold.refresh(Hval, b->Hval, (int)b->sumHnz, b->stream));
         if (!b->h_Hjc.empty()) {
             b->h_sym = true;
             for (int q = 0; q < b->nq && b->h_sym; q++) {
@@ -1964,7 +1426,7 @@ int rsqp_batch_nq_internal(const rsqp_batch *b) { return b ? b->nq : 0; }
 extern "C" int rsqp_time_value_refresh_fused(rsqp_solver *s, int repeats, float *ms) {
     if (!s || repeats <= 0 || !ms || !s->A.initialised || !s->A.from_triplet || !s->A.have_csr) return fail(RSQP_ERR_ARG, "rsqp_time_value_refresh_fused");
     if (s->A.pin) return fail(RSQP_ERR_ARG, "rsqp_time_value_refresh_fused: this handle refreshes its values on the host (no kernel to time)");
-    if (!s->A.canon) return fail(RSQP_ERR_ARG, "rsqp_time_value_refresh_fused: the matrix repeats positions (its refresh folds)");
+    if (!s->A.fold.canon) return fail(RSQP_ERR_ARG, "rsqp_time_value_refresh_fused: the matrix repeats positions (its refresh folds)");
     HIPCHK(hipSetDevice(s->device));
     hipEvent_t e0, e1;
     HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
@@ -1984,7 +1446,7 @@ extern "C" int rsqp_time_value_refresh_fused(rsqp_solver *s, int repeats, float 
 extern "C" int rsqp_time_value_refresh(rsqp_solver *s, int repeats, float *ms_scatter, float *ms_gather) {
     if (!s || repeats <= 0 || !s->A.initialised || !s->A.from_triplet) return fail(RSQP_ERR_ARG, "rsqp_time_value_refresh");
     if (s->A.pin) return fail(RSQP_ERR_ARG, "rsqp_time_value_refresh: this handle refreshes its values on the host (no kernel to time)");
-    if (!s->A.canon) return fail(RSQP_ERR_ARG, "rsqp_time_value_refresh: the matrix repeats positions (its refresh folds)");
+    if (!s->A.fold.canon) return fail(RSQP_ERR_ARG, "rsqp_time_value_refresh: the matrix repeats positions (its refresh folds)");
     HIPCHK(hipSetDevice(s->device));
     hipEvent_t e0, e1;
     HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));

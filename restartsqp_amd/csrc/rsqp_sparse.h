@@ -50,7 +50,7 @@ hipError_t rsqp_launch_scatter(int n, const int *order, const int *tmap, const d
 hipError_t rsqp_launch_gather(int n, const int *perm, const double *src, double *dst, hipStream_t stream);
 // the same for a matrix that stores every entry (CSC = column-major, CSR = row-major): a tiled transpose
 hipError_t rsqp_launch_gather_dense(int nrow, int ncol, const double *src, double *dst, hipStream_t stream);
-// dst[j] = sum of src[idx[k]] for k in [ptr[j], ptr[j+1]), in that order: canonical values from the caller's layout (rsqp_api.hip)
+// dst[j] = sum of src[idx[k]] for k in [ptr[j], ptr[j+1]), in that order: canonical values from the caller's layout (rsqp_matrix.hip)
 hipError_t rsqp_launch_fold(int n, const int *ptr, const int *idx, const double *src, double *dst, hipStream_t stream);
 hipError_t rsqp_launch_scatter_csc_csr(int n, const int *order, const int *rorder, const double *tv, double *val, double *rval,
                                        hipStream_t stream);

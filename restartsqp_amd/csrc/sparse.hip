@@ -674,7 +674,7 @@ __global__ void gather_values(int n, const int *__restrict__ perm, const double 
 }
 
 // canonical values of a matrix given in a non-canonical layout (rows out of order, repeated positions): slot j is the sum of the
-// caller's slots idx[ptr[j] .. ptr[j+1]) (at least one), in the caller's order -- the host loop of rsqp_api.hip (fold_host) sums alike
+// caller's slots idx[ptr[j] .. ptr[j+1]) (at least one), in the caller's order -- the host loop of rsqp_matrix.hip (ValueFold::sum) sums alike
 __global__ void fold_values(int n, const int *__restrict__ ptr, const int *__restrict__ idx, const double *__restrict__ src,
                             double *__restrict__ dst) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
