@@ -252,10 +252,32 @@ int rsqp_batch_set_vectors(rsqp_batch *b, const double *g, const double *lb, con
                            const double *lbA, const double *ubA);
 /* refresh the matrix values (same patterns) */
 int rsqp_batch_set_matrix_values(rsqp_batch *b, const double *Aval, const double *Hval);
-/* solve all problems with one launch; data already resident on the device.
- * mode as above (WARM_REINIT not available for batches). Asynchronous on the batch's
- * stream; rsqp_batch_sync() waits. */
+/* inputs of rsqp_batch_solve(b, RSQP_MODE_WARM_REINIT, n) -- init(.., nWSR, 0, xOpt, yOpt, &guessedBounds) for every member
+ * (qpOASESInterface.cpp:204-206) --, pooled like the vectors: x0 and guess_b (-1 / 0 / +1) have sum(nV) entries, y0 the layout of
+ * y in rsqp_batch_get_results; NULL = absent for every member (all NULL: a plain init). The constraint sides come from A x0
+ * (the default of rsqp_set_reinit_guess). On the LDS- and HBM-resident kernels a member that no solve has touched yet starts
+ * cold. rsqp_batch_optimize_qp uses the same pools: what was set here is absent again after it. */
+int rsqp_batch_set_warm_start(rsqp_batch *b, const double *x0, const double *y0, const int *guess_b);
+/* Options::qp_maxiter (Options.cpp:45) of rsqp_batch_optimize_qp; default 1000, as rsqp_set_options */
+int rsqp_batch_set_options(rsqp_batch *b, int qp_maxiter);
+/* solve all problems with one launch; data already resident on the device. mode as above, the same for every member.
+ * Asynchronous on the batch's stream; rsqp_batch_sync() waits. Never touches the state of rsqp_batch_optimize_qp (as
+ * rsqp_solve does not touch a handle's). */
 int rsqp_batch_solve(rsqp_batch *b, int mode, int max_nWSR);
+/* optimizeQP (qpOASESInterface.cpp:137-224) for EVERY member, each with its own state: firstQPsolved_ (:156-158), the FIXED / VARIED
+ * dispatch of get_Matrix_change_status (:817-833; rsqp_batch_set_matrix_values is set_A / set_H, :407-409, 427-429, for the members
+ * whose first QP is solved), reset_flags (:488-496) and handle_error's QP branch (:718-757) with a fresh qp_maxiter budget. Member q
+ * ends the call with the exit flag, nWSR_used, x, y, working sets and objective a single rsqp_solver reports for the same matrices,
+ * vectors and sequence of calls (rsqp_set_reinit_guess at its default). In one call the members may run cold, hot-start on new
+ * vectors or matrices, re-initialise from their own previous solution, and be rescued; the decisions are taken on the device
+ * between the launches, and the call returns when the results are ready. nWSR_used (nq entries, may be NULL): what each member adds
+ * to Stats::qp_iter; rsqp_batch_get_results keeps reporting the nWSR of a member's LAST solve. Needs keep_state != 0 (else
+ * RSQP_ERR_ARG). rsqp_batch_get_last_kernel reports the kernel of the call's first solve. */
+int rsqp_batch_optimize_qp(rsqp_batch *b, int *nWSR_used);
+/* what the last rsqp_batch_optimize_qp did per member (nq entries each, may be NULL): mode = RSQP_MODE_* of its first solve (as
+ * rsqp_get_last_mode reports it before a rescue), rescue = 0 none, 1 handle_error re-initialised from scratch (:745-749),
+ * 2 handle_error re-initialised from the slack point x_0 (:720-743) */
+int rsqp_batch_get_dispatch(const rsqp_batch *b, int *mode, int *rescue);
 int rsqp_batch_sync(rsqp_batch *b);
 /* keep != 0 (default): every solve writes the state a hot start needs (factors, iterate, multipliers,
  * working set: what a qpOASES SQProblem object keeps between init / hotstart calls) back to HBM.

@@ -84,7 +84,11 @@ SYMBOLS = {
     "rsqp_batch_destroy": (None, [C.c_void_p]),
     "rsqp_batch_set_vectors": (C.c_int, [C.c_void_p, dp, dp, dp, dp, dp]),
     "rsqp_batch_set_matrix_values": (C.c_int, [C.c_void_p, dp, dp]),
+    "rsqp_batch_set_warm_start": (C.c_int, [C.c_void_p, dp, dp, ip]),
+    "rsqp_batch_set_options": (C.c_int, [C.c_void_p, C.c_int]),
     "rsqp_batch_solve": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "rsqp_batch_optimize_qp": (C.c_int, [C.c_void_p, ip]),
+    "rsqp_batch_get_dispatch": (C.c_int, [C.c_void_p, ip, ip]),
     "rsqp_batch_sync": (C.c_int, [C.c_void_p]),
     "rsqp_batch_set_keep_state": (C.c_int, [C.c_void_p, C.c_int]),
     "rsqp_batch_get_last_kernel": (C.c_int, [C.c_void_p]),
@@ -460,6 +464,30 @@ class Batch:
         check(lib().rsqp_batch_solve(self._h, mode, max_nWSR))
         if sync:
             check(lib().rsqp_batch_sync(self._h))
+
+    def set_warm_start(self, x0=None, y0=None, guess_b=None):
+        """inputs of solve(MODE_WARM_REINIT), pooled like the vectors (y0: the layout of y); None = absent for every member"""
+        x0, y0, guess_b = _d(x0), _d(y0), _i(guess_b)
+        sV, sC = int(self.offV[-1]), int(self.offC[-1])
+        for a, n, name in ((x0, sV, "x0"), (y0, sV + sC, "y0"), (guess_b, sV, "guess_b")):
+            if a is not None and a.size != n:
+                raise ValueError("%s has %d entries, the batch needs %d" % (name, a.size, n))
+        check(lib().rsqp_batch_set_warm_start(self._h, _dp(x0), _dp(y0), _ip(guess_b)))
+
+    def set_options(self, qp_maxiter=1000):
+        check(lib().rsqp_batch_set_options(self._h, int(qp_maxiter)))
+
+    def optimize_qp(self):
+        """optimizeQP for every member (dispatch + handle_error per member); returns nWSR_used per member"""
+        used = np.zeros(self.nq, np.int32)
+        check(lib().rsqp_batch_optimize_qp(self._h, _ip(used)))
+        return used
+
+    def dispatch(self):
+        """(mode, rescue) per member of the last optimize_qp: MODE_* of its first solve; 0 none / 1 from scratch / 2 slack point"""
+        mode = np.zeros(self.nq, np.int32); rescue = np.zeros(self.nq, np.int32)
+        check(lib().rsqp_batch_get_dispatch(self._h, _ip(mode), _ip(rescue)))
+        return mode, rescue
 
     def set_keep_state(self, keep):
         check(lib().rsqp_batch_set_keep_state(self._h, int(bool(keep))))

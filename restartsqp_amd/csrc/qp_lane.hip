@@ -815,7 +815,7 @@ int rsqp_lane_fits(const SmallKnobs &kn, const QPPools &p, int nq, int nVmax, in
     if (kn.lane == 0) return 0;
     // one shape (every member nV x nC); one sparsity pattern (member 0's arrays serve all) or patterns of their own (each lane walks its own)
     if (!(p.uniV >= 1 && p.uniV <= MV && p.uniC >= 0 && p.uniC <= 2 && nVmax <= MV && nCmax <= 2 && (p.uni_pat || p.desc))) return 0;
-    if (mode != 0 || (!p.keep_state && !p.skip_mark) || p.cert_out || p.done_flag || !p.tiny_ok || p.x0 || p.y0 || p.guess_b) return 0;
+    if (mode != 0 || p.member_mode || (!p.keep_state && !p.skip_mark) || p.cert_out || p.done_flag || !p.tiny_ok || p.x0 || p.y0 || p.guess_b) return 0;
     // (measured, tools/lane_vs_tiny_sweep.py: a launch of this kernel takes 36 us up to 16 384 problems and 43 us at 65 536 -- one
     //  round of waves either way; the 8-lane kernel holds 16 384 problems at a time: 21 us up to 8 192, 26 us at 16 384, 40 us at
     //  20 480 (second round), 47 us at 32 768, 90 us at 65 536. With the state kept, 65 536 members: 0.075 against 0.132 ms)

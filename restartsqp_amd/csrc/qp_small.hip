@@ -82,6 +82,7 @@ small_qp_kernel(QPPools P, int nq, int stride, int mode, int maxWSR) {
     const int q = L >= 64 ? (int)blockIdx.x : blockIdx.x * (64 / L) + grp;
     if (q >= nq) return;  // no workgroup barrier anywhere below: idle groups may leave
     if (P.only_bailed && P.ret[q] != RET_BAIL) return;   // second pass behind the tableau kernel (qp_small_g.h)
+    if (P.member_mode) { mode = P.member_mode[q]; if (mode < 0) return; }   // per-member call shape; < 0: not in this launch
     lchar *smem = (lchar *)smem_generic + grp * stride;
     QPDesc d = P.desc[q];
     if constexpr (SHAPE > 0) { d.nV = NVC; d.nC = NCC; }
@@ -328,7 +329,8 @@ hipError_t rsqp_launch_small_qp(const SmallKnobs &kn, const QPPools &p_in, int n
     typedef EngineG<2, 2, 8, 8> EK2;     // up to 64 variables x 64 constraints
     // (only where the null-space kernel would give a problem four waves as well: batches of SMALL problems are throughput-bound
     //  and better served by 16 / 32 lanes per problem, several problems per wave)
-    if (forcedE < 0 && eng == 1 && (nVmax > 32 || nCmax > 32) && (mode == 0 || mode == 1) && !p.done_flag) {
+    // (per-member modes: the kernel itself leaves the members whose mode it does not carry to the null-space kernel)
+    if (forcedE < 0 && eng == 1 && (nVmax > 32 || nCmax > 32) && (p.member_mode || mode == 0 || mode == 1) && !p.done_flag) {
 #define KK_LAUNCH(RV_, RC_, CV_, CC_)                                                                                            \
         do {                                                                                                                     \
             hipLaunchKernelGGL((small_qpg_kernel<RV_, RC_, CV_, CC_>), dim3(nq), dim3(256), 0, stream, p, nq, mode, maxWSR);     \

@@ -771,6 +771,7 @@ __global__ void __launch_bounds__(256, 1) small_qpg_kernel(QPPools P, int nq, in
     __shared__ __attribute__((aligned(16))) char smem_static[ENG::LDS_BYTES];
     const int q = (int)blockIdx.x;
     if (q >= nq) return;
+    if (P.member_mode) { mode = P.member_mode[q]; if (mode < 0) return; }   // per-member call shape; < 0: not in this launch
     const QPDesc d = P.desc[q];
     ENG E;
     E.carve((lchar *)smem_static, d.nV, d.nC);
@@ -782,7 +783,9 @@ __global__ void __launch_bounds__(256, 1) small_qpg_kernel(QPPools P, int nq, in
     int rcode = RET_OK, nWSR = 0;
     double obj = 0.0;
     const bool eligible = d.haveH && d.hreg == 0.0 && d.nV <= ENG::MAXV && d.nC <= ENG::MAXC;
-    if (!eligible) {
+    if (mode != 0 && mode != 1) {    // hot start on new matrices, warm re-initialisation: call shapes of the null-space kernel
+        rcode = RET_BAIL; E.bail_reason = 14;
+    } else if (!eligible) {
         rcode = RET_BAIL; E.bail_reason = 10;
     } else {
         E.stage(P.Ajc + d.offAjc, P.Air + d.offAnz, P.Aval + d.offAnz, P.Hjc + d.offHjc, P.Hir + d.offHnz, P.Hval + d.offHnz,
@@ -791,8 +794,10 @@ __global__ void __launch_bounds__(256, 1) small_qpg_kernel(QPPools P, int nq, in
         if (!(E.hscale > 0.0)) { rcode = RET_BAIL; E.bail_reason = 10; }
         else if (mode != 0 && !E.load_state(P.state + d.offState)) { rcode = RET_BAIL; E.bail_reason = 12; }   // not this kernel's state
         else if (E.bounds_inconsistent()) {
-            // (a hot start keeps the stored iterate: what the null-space kernels return in that case)
-            E.infeasible = 1; rcode = RET_INFEASIBLE;
+            // (a hot start keeps the stored iterate: what the null-space kernels return in that case; an init reports the zero
+            //  iterate with an EMPTY working set, which this formulation -- every variable starts fixed -- does not have: their call)
+            if (mode == 0) { rcode = RET_BAIL; E.bail_reason = 15; }
+            else { E.infeasible = 1; rcode = RET_INFEASIBLE; }
         } else {
             const bool hot = mode != 0;
             if (!hot) {

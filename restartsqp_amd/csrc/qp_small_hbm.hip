@@ -36,6 +36,7 @@ small_qph_kernel(QPPools P, int nq, int mode, int maxWSR) {
     const int lane = (int)threadIdx.x;
     const int q = (int)blockIdx.x;
     if (q >= nq) return;
+    if (P.member_mode) { mode = P.member_mode[q]; if (mode < 0) return; }   // per-member call shape; < 0: not in this launch
     const QPDesc d = P.desc[q];
     ENG E;
     E.lane = lane;
@@ -87,6 +88,14 @@ small_qph_kernel(QPPools P, int nq, int mode, int maxWSR) {
         SYNC();
         rcode = E.setup_aux(true, true, true, true);
         if (rcode != RET_OK) rcode = E.setup_aux(false, false, false, false);
+    } else if (mode == 3) {  // warm re-initialisation from (x0, y0, guessed bounds), as the LDS-resident kernel stages it
+        if (P.x0) for (int v = lane; v < d.nV; v += L) E.wv4[v] = P.x0[d.offV + v];
+        if (P.y0) for (int i = lane; i < d.nV + d.nC; i += L) E.dy[i] = P.y0[d.offV + d.offC + i];
+        if (P.guess_b) for (int v = lane; v < d.nV; v += L) E.wq[v] = (double)P.guess_b[d.offV + v];
+        SYNC();
+        // (no guessed constraints in this call shape, qpOASESInterface.cpp:204-206: their sides come from A x0, or from y0 on request)
+        rcode = E.setup_aux(P.x0 != nullptr, P.y0 != nullptr, P.guess_b != nullptr, false, P.reinit_from_y0 != 0);
+        if (rcode != RET_OK) rcode = E.setup_aux(false, false, false, false);
     } else {
         E.infeasible = E.unbounded = 0;
         if constexpr (ENG::K_IMAGE) {
@@ -131,7 +140,7 @@ hipError_t rsqp_launch_small_qp_hbm(const SmallKnobs &kn, const QPPools &p_in, i
     p.only_bailed = 0;
     p.k_debug_bail = -1;
     if (nq <= 0) return hipSuccess;
-    if (!rsqp_hbm_qp_fits(nVmax, nCmax) || mode < 0 || mode > 2) return hipErrorInvalidValue;
+    if (!rsqp_hbm_qp_fits(nVmax, nCmax) || mode < 0 || mode > 3) return hipErrorInvalidValue;
     // formulation as in rsqp_launch_small_qp: explicit inverses above 8 variables unless RSQP_SMALL_ENGINE says otherwise
     const int eng = kn.engine == 0 || kn.engine == 1 ? kn.engine : (nVmax > 8 ? 1 : 0);
     if (eng == 1)   // four waves per problem, dense copies of A and H in the slice

@@ -638,6 +638,8 @@ __global__ void __launch_bounds__(TB, W) tiny_qp_kernel(QPPools P, int nq, int m
     const int grp = (int)threadIdx.x >> 3;
     const int q = (int)blockIdx.x * TG + grp;
     if (q >= nq) return;        // (no workgroup barrier anywhere: idle groups may leave)
+    int mode = mode_in;
+    if (P.member_mode) { mode = P.member_mode[q]; if (mode < 0) return; }   // per-member call shape; < 0: not in this launch
     // a batch of ONE shape and ONE sparsity pattern (QPPools::uni_pat): offsets by arithmetic, pattern arrays of member 0
     QPDesc d;
     int patA, patH;
@@ -659,11 +661,11 @@ __global__ void __launch_bounds__(TB, W) tiny_qp_kernel(QPPools P, int nq, int m
 #endif
     E.stage(P, d, patA, patH);
     TSTAMP(0);
-    int mode = mode_in;
     double *sd = P.state + d.offState;
     int *si = reinterpret_cast<int *>(sd + tiny_state_doubles<MC>());
     // stored state of the previous solve (hot starts; x / y / working set as the guess of a hot start with new matrices)
-    double px = 0.0, pyv = 0.0, pyc = 0.0; int psv = -1, psc = 0;
+    // (an init -- cold or warm -- that finds the bounds inconsistent reports the zero iterate and the EMPTY working set, as qpOASES does)
+    double px = 0.0, pyv = 0.0, pyc = 0.0; int psv = 0, psc = 0;
     if (mode == 1 || mode == 2) {
         if (si[18] != TINY_MAGIC || si[16] == QPS_NOTINITIALISED) mode = 0;
         else {

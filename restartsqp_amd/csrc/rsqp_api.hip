@@ -719,25 +719,14 @@ extern "C" int rsqp_optimize_qp(rsqp_solver *s, int *nWSR_used) {
             if (!solved(s)) { if (nWSR_used) *nWSR_used = total; return RSQP_OK; }
         }
     } else {
-        // get_Matrix_change_status (:817-833)
-        const int cur = (s->upd_A || s->upd_H) ? 2 : 1;
-        if (s->old_status == 0) s->old_status = cur;
-        else {
-            if (s->new_status != 0) s->old_status = s->new_status;
-            s->new_status = cur;
-        }
-        if (s->new_status == 0)
-            rc = rsqp_solve(s, s->old_status == 1 ? RSQP_MODE_HOT_VECTORS : RSQP_MODE_HOT_MATRICES, &nWSR, nullptr,
-                            nullptr, nullptr);
-        else if (s->new_status == 1 && s->old_status == 1)
-            rc = rsqp_solve(s, RSQP_MODE_HOT_VECTORS, &nWSR, nullptr, nullptr, nullptr);
-        else if (s->new_status == 2 && s->old_status == 2)
-            rc = rsqp_solve(s, RSQP_MODE_HOT_MATRICES, &nWSR, nullptr, nullptr, nullptr);
+        // get_Matrix_change_status (:817-833) and the call shape it selects: rsqp_dispatch_mode
+        const int mode = rsqp_dispatch_mode(true, s->upd_A || s->upd_H, s->old_status, s->new_status);
+        if (mode != RSQP_MODE_WARM_REINIT)
+            rc = rsqp_solve(s, mode, &nWSR, nullptr, nullptr, nullptr);
         else {  // status flip: init(..., x_qp, y_qp, &bounds)  (:201-208)
             std::vector<double> x0 = s->h_x, y0 = s->h_y;
             std::vector<int> gb = s->h_wsb;
             rc = rsqp_solve(s, RSQP_MODE_WARM_REINIT, &nWSR, x0.data(), y0.data(), gb.data());
-            s->new_status = s->old_status = 0;
         }
         if (rc != RSQP_OK) return rc;
     }
@@ -799,23 +788,12 @@ extern "C" int rsqp_optimize_lp(rsqp_solver *s, int *nWSR_used) {
             if (!solved(s)) { if (nWSR_used) *nWSR_used = total; return RSQP_OK; }
         }
     } else {
-        const int cur = (s->upd_A || s->upd_H) ? 2 : 1;
-        if (s->old_status == 0) s->old_status = cur;
-        else {
-            if (s->new_status != 0) s->old_status = s->new_status;
-            s->new_status = cur;
-        }
-        if (s->new_status == 0)
-            rc = rsqp_solve(s, s->old_status == 1 ? RSQP_MODE_HOT_VECTORS : RSQP_MODE_HOT_MATRICES, &nWSR, nullptr,
-                            nullptr, nullptr);
-        else if (s->new_status == 1 && s->old_status == 1)
-            rc = rsqp_solve(s, RSQP_MODE_HOT_VECTORS, &nWSR, nullptr, nullptr, nullptr);
-        else if (s->new_status == 2 && s->old_status == 2)
-            rc = rsqp_solve(s, RSQP_MODE_HOT_MATRICES, &nWSR, nullptr, nullptr, nullptr);
+        const int mode = rsqp_dispatch_mode(true, s->upd_A || s->upd_H, s->old_status, s->new_status);
+        if (mode != RSQP_MODE_WARM_REINIT)
+            rc = rsqp_solve(s, mode, &nWSR, nullptr, nullptr, nullptr);
         else {   // :266-270: plain re-init on a status flip
             set_reg_for_init();
             rc = rsqp_solve(s, RSQP_MODE_COLD, &nWSR, nullptr, nullptr, nullptr);
-            s->new_status = s->old_status = 0;
         }
         if (rc != RSQP_OK) return rc;
         s->upd_A = s->upd_H = s->upd_bounds = s->upd_g = false;
@@ -1031,6 +1009,21 @@ struct rsqp_batch {
     DevBuf<int> Wb, Wc, kV, kC;
     DevBuf<double> recbuf;   // rsqp_batch_pack_records_host
     DevBuf<long long> koV, koC;
+    // warm re-initialisation inputs (RSQP_MODE_WARM_REINIT), pooled like the vectors; allocated at first use. have_*: what
+    // rsqp_batch_set_warm_start gave (rsqp_batch_solve); rsqp_batch_optimize_qp fills the same pools on the device
+    DevBuf<double> wx0, wy0;
+    DevBuf<int> wgb;
+    bool have_x0 = false, have_y0 = false, have_gb = false;
+    // optimizeQP per member (rsqp_batch_optimize_qp): nq ints each, in one block -- firstQPsolved_, old / new matrix status, mode of
+    // the call's first solve, mode of its rescue solve (-1: none), kind of rescue, count of the first solve
+    enum { OPT_FIRST = 0, OPT_OLD, OPT_NEW, OPT_MODE, OPT_RMODE, OPT_RESCUE, OPT_N1, OPT_WORDS };
+    DevBuf<int> opt;
+    // nWSR_used of the members, written by the kernels straight into host-mapped memory: ready behind the call's one wait, no copy
+    // (and no second wait) behind it
+    int *used_host = nullptr, *used_dev = nullptr;
+    int qp_maxiter = 1000;                // rsqp_batch_set_options
+    bool mats_updated = false;            // rsqp_batch_set_matrix_values since the last rsqp_batch_optimize_qp (Update_A / Update_H)
+    bool opt_started = false;             // an rsqp_batch_optimize_qp has run: members are in different states from here on
     float last_ms = 0.f;
     bool keep_state = true;
     bool timing = false;   // between timer_start and timer_stop: no per-launch events (they cost ~10 us of stream time each)
@@ -1040,6 +1033,7 @@ struct rsqp_batch {
         if (ev2) (void)hipEventDestroy(ev2);
         if (ev3) (void)hipEventDestroy(ev3);
         if (stream) (void)hipStreamDestroy(stream);
+        if (used_host) (void)hipHostFree(used_host);
     }
 };
 
@@ -1223,35 +1217,205 @@ extern "C" int rsqp_batch_set_matrix_values(rsqp_batch *b, const double *Aval, c
         }
     }
     HIPCHK(hipStreamSynchronize(b->stream));
+    // (qpOASESInterface.cpp:407-409, 427-429: counts for the members whose first QP is solved -- the plan kernel looks at that)
+    if (Aval || (Hval && b->haveH)) b->mats_updated = true;
+    return RSQP_OK;
+}
+
+namespace {
+int ensure_warm_pools(rsqp_batch *b) {
+    if (b->wx0.p) return RSQP_OK;
+    HIPCHK(b->wx0.alloc(b->sumV)); HIPCHK(b->wy0.alloc(b->sumV + b->sumC)); HIPCHK(b->wgb.alloc(b->sumV));
+    return RSQP_OK;
+}
+
+// kernel family a launch on this batch runs: 3 HBM-resident, 1 hs071-scale tableau (+ lane-per-problem), 0 LDS-resident
+int batch_family(const rsqp_batch *b, const QPPools &p) { return b->hbm ? 3 : rsqp_small_launch_is_tiny(b->kn, p, b->nVmax, b->nCmax); }
+
+// one solve launch of the whole batch (p.member_mode: of the members it names). first: the launch rsqp_batch_get_last_kernel reports
+int launch_batch(rsqp_batch *b, QPPools &p, int mode, int max_nWSR, bool first) {
+    const int fam = batch_family(b, p);
+    // the kernel families keep different layouts in the same state block: a hot start on another family's state starts cold
+    // (per-member modes: the plan kernel was told)
+    if ((mode == RSQP_MODE_HOT_VECTORS || mode == RSQP_MODE_HOT_MATRICES) && b->state_engine != fam) mode = RSQP_MODE_COLD;
+    b->state_engine = fam;
+    hipError_t e;
+    if (b->hbm) {
+        if (first) b->last_kernel = 3;
+        e = rsqp_launch_small_qp_hbm(b->kn, p, b->nq, b->nVmax, b->nCmax, mode, max_nWSR, b->stream);
+    } else {
+        // a cold-start-only batch on the tableau kernel keeps no state and leaves no mark: the handle remembers it instead
+        if (fam == 1 && !b->keep_state) { p.skip_mark = 1; b->state_engine = -1; }
+        if (first) b->last_kernel = fam == 1 ? (rsqp_lane_fits(b->kn, p, b->nq, b->nVmax, b->nCmax, mode) ? 2 : 1) : 0;
+        e = rsqp_launch_small_qp(b->kn, p, b->nq, b->nVmax, b->nCmax, b->mat_bytes_max, mode, max_nWSR, b->stream);
+    }
+    if (e != hipSuccess) return fail(RSQP_ERR_DEVICE, std::string("QP kernel launch: ") + hipGetErrorString(e));
+    return RSQP_OK;
+}
+}  // namespace
+
+extern "C" int rsqp_batch_set_warm_start(rsqp_batch *b, const double *x0, const double *y0, const int *guess_b) {
+    if (!b) return fail(RSQP_ERR_ARG, "null batch");
+    HIPCHK(hipSetDevice(b->device));
+    if (guess_b)
+        for (long long k = 0; k < b->sumV; k++)
+            if (guess_b[k] < -1 || guess_b[k] > 1) return fail(RSQP_ERR_ARG, "rsqp_batch_set_warm_start: guess_b entries are -1, 0 or +1");
+    int rc = ensure_warm_pools(b);
+    if (rc != RSQP_OK) return rc;
+    HIPCHK(hipStreamSynchronize(b->stream));
+    if (x0) HIPCHK(b->wx0.upload(x0, b->sumV));
+    if (y0) HIPCHK(b->wy0.upload(y0, b->sumV + b->sumC));
+    if (guess_b) HIPCHK(b->wgb.upload(guess_b, b->sumV));
+    b->have_x0 = x0 != nullptr; b->have_y0 = y0 != nullptr; b->have_gb = guess_b != nullptr;
+    return RSQP_OK;
+}
+
+extern "C" int rsqp_batch_set_options(rsqp_batch *b, int qp_maxiter) {
+    if (!b || qp_maxiter < 0) return fail(RSQP_ERR_ARG, "rsqp_batch_set_options");
+    b->qp_maxiter = qp_maxiter;
     return RSQP_OK;
 }
 
 extern "C" int rsqp_batch_solve(rsqp_batch *b, int mode, int max_nWSR) {
-    if (!b || mode < 0 || mode > 2 || max_nWSR < 0) return fail(RSQP_ERR_ARG, "rsqp_batch_solve");
+    if (!b || mode < 0 || mode > 3 || max_nWSR < 0) return fail(RSQP_ERR_ARG, "rsqp_batch_solve");
     HIPCHK(hipSetDevice(b->device));
     QPPools p = pools_of(b);
+    if (mode == RSQP_MODE_WARM_REINIT) {   // what rsqp_batch_set_warm_start gave; nothing given: init(.., nWSR, 0, 0, 0, 0)
+        if (b->have_x0) p.x0 = b->wx0.p;
+        if (b->have_y0) p.y0 = b->wy0.p;
+        if (b->have_gb) p.guess_b = b->wgb.p;
+    }
     if (!b->timing) HIPCHK(hipEventRecord(b->ev0, b->stream));
-    if (b->hbm) {
-        // state family 3: images in place in HBM (another layout than the LDS-resident kernels' copies)
-        if ((mode == RSQP_MODE_HOT_VECTORS || mode == RSQP_MODE_HOT_MATRICES) && b->state_engine != 3) mode = RSQP_MODE_COLD;
-        b->state_engine = 3;
-        b->last_kernel = 3;
-        hipError_t e = rsqp_launch_small_qp_hbm(b->kn, p, b->nq, b->nVmax, b->nCmax, mode, max_nWSR, b->stream);
-        if (e != hipSuccess) return fail(RSQP_ERR_DEVICE, std::string("QP kernel launch: ") + hipGetErrorString(e));
-        if (!b->timing) HIPCHK(hipEventRecord(b->ev1, b->stream));
-        return RSQP_OK;
-    }
-    {
-        const int fam = rsqp_small_launch_is_tiny(b->kn, p, b->nVmax, b->nCmax);
-        if ((mode == RSQP_MODE_HOT_VECTORS || mode == RSQP_MODE_HOT_MATRICES) && b->state_engine != fam) mode = RSQP_MODE_COLD;
-        b->state_engine = fam;
-        // a cold-start-only batch on the tableau kernel keeps no state and leaves no mark: the handle remembers it instead
-        if (fam == 1 && !b->keep_state) { p.skip_mark = 1; b->state_engine = -1; }
-        b->last_kernel = fam == 1 ? (rsqp_lane_fits(b->kn, p, b->nq, b->nVmax, b->nCmax, mode) ? 2 : 1) : 0;
-    }
-    hipError_t e = rsqp_launch_small_qp(b->kn, p, b->nq, b->nVmax, b->nCmax, b->mat_bytes_max, mode, max_nWSR, b->stream);
-    if (e != hipSuccess) return fail(RSQP_ERR_DEVICE, std::string("QP kernel launch: ") + hipGetErrorString(e));
+    const int rc = launch_batch(b, p, mode, max_nWSR, true);
+    if (rc != RSQP_OK) return rc;
     if (!b->timing) HIPCHK(hipEventRecord(b->ev1, b->stream));
+    return RSQP_OK;
+}
+
+// ---------------------------------------------------------------------------------
+// optimizeQP for every member of a batch (qpOASESInterface.cpp:137-224 + handle_error :718-757): what rsqp_optimize_qp does on one
+// handle, with the per-member decisions taken by one-thread-per-member kernels between the solve launches -- no host round trip
+// inside a call. plan -> solve -> rescue plan -> rescue solve (members that need none leave at once) -> count -> one wait.
+// ---------------------------------------------------------------------------------
+namespace {
+// before the first solve: the call shape of every member (rsqp_dispatch_mode); a FIXED <-> VARIED flip re-initialises from the
+// member's own previous x, y and bound working set (:201-208), copied into the warm-start pools
+__global__ void batch_plan_kernel(int nq, const QPDesc *__restrict__ desc, int *__restrict__ opt, int updated, int hot_ok,
+                                  const double *__restrict__ x, const double *__restrict__ y, const int *__restrict__ ws_b,
+                                  double *__restrict__ x0, double *__restrict__ y0, int *__restrict__ gb) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nq) return;
+    int old_status = opt[rsqp_batch::OPT_OLD * nq + q], new_status = opt[rsqp_batch::OPT_NEW * nq + q];
+    int mode = rsqp_dispatch_mode(opt[rsqp_batch::OPT_FIRST * nq + q] != 0, updated != 0, old_status, new_status);
+    // the stored states are another kernel family's (the host knows): a hot start runs cold, as on a single handle
+    if (!hot_ok && (mode == RSQP_MODE_HOT_VECTORS || mode == RSQP_MODE_HOT_MATRICES)) mode = RSQP_MODE_COLD;
+    opt[rsqp_batch::OPT_OLD * nq + q] = old_status; opt[rsqp_batch::OPT_NEW * nq + q] = new_status;
+    opt[rsqp_batch::OPT_MODE * nq + q] = mode;
+    if (mode == RSQP_MODE_WARM_REINIT) {
+        const QPDesc d = desc[q];
+        for (int v = 0; v < d.nV; v++) { x0[d.offV + v] = x[d.offV + v]; gb[d.offV + v] = ws_b[d.offV + v]; }
+        for (int i = 0; i < d.nV + d.nC; i++) y0[d.offV + d.offC + i] = y[d.offV + d.offC + i];
+    }
+}
+
+// behind the first solve: firstQPsolved_ (:156-158), handle_error's QP branch per member (:718-757) -- none / re-init from scratch /
+// re-init from the slack point x_0 (written to the x0 pool) --, old = new = UNDEFINED for the rescued, the count so far
+__global__ void batch_rescue_plan_kernel(int nq, const QPDesc *__restrict__ desc, int *__restrict__ opt, const int *__restrict__ status,
+                                         const int *__restrict__ nwsr, const double *__restrict__ lbA, const double *__restrict__ ubA,
+                                         double *__restrict__ x0, int *__restrict__ used) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nq) return;
+    const int sw = status[q], n1 = nwsr[q];
+    const bool solved = sw == QPS_SOLVED, infeasible = sw >= 100 && sw < 200;
+    opt[rsqp_batch::OPT_N1 * nq + q] = n1;
+    if (solved) {
+        opt[rsqp_batch::OPT_FIRST * nq + q] = 1;
+        opt[rsqp_batch::OPT_RMODE * nq + q] = -1; opt[rsqp_batch::OPT_RESCUE * nq + q] = 0; used[q] = n1;
+        return;
+    }
+    const QPDesc d = desc[q];
+    opt[rsqp_batch::OPT_OLD * nq + q] = 0; opt[rsqp_batch::OPT_NEW * nq + q] = 0;
+    if (infeasible && d.nV >= 2 * d.nC) {
+        for (int v = 0; v < d.nV; v++) x0[d.offV + v] = 0.0;
+        for (int i = 0; i < d.nC; i++) {
+            x0[d.offV + i + d.nV - 2 * d.nC] = fmax(0.0, lbA[d.offC + i]);
+            x0[d.offV + i + d.nV - d.nC] = -fmin(0.0, ubA[d.offC + i]);
+        }
+        opt[rsqp_batch::OPT_RMODE * nq + q] = RSQP_MODE_WARM_REINIT; opt[rsqp_batch::OPT_RESCUE * nq + q] = 2;
+    } else {
+        opt[rsqp_batch::OPT_RMODE * nq + q] = RSQP_MODE_COLD; opt[rsqp_batch::OPT_RESCUE * nq + q] = 1;
+    }
+}
+
+// behind the rescue solve: nWSR_used of the rescued members. A member whose FIRST init failed reports the rescue's count alone when
+// the rescue fails too (the reference throws inside handle_error, :754-756, before :211-212 add the first count)
+__global__ void batch_count_kernel(int nq, const int *__restrict__ opt, const int *__restrict__ status, const int *__restrict__ nwsr,
+                                   int *__restrict__ used) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nq || opt[rsqp_batch::OPT_RESCUE * nq + q] == 0) return;
+    const int n1 = opt[rsqp_batch::OPT_N1 * nq + q], n2 = nwsr[q];
+    const bool first_init_failed = opt[rsqp_batch::OPT_FIRST * nq + q] == 0;
+    used[q] = (first_init_failed && status[q] != QPS_SOLVED) ? n2 : n1 + n2;
+}
+}  // namespace
+
+extern "C" int rsqp_batch_optimize_qp(rsqp_batch *b, int *nWSR_used) {
+    if (!b) return fail(RSQP_ERR_ARG, "null batch");
+    if (!b->keep_state) return fail(RSQP_ERR_ARG, "rsqp_batch_optimize_qp: the batch keeps no state (rsqp_batch_set_keep_state(b, 0))");
+    HIPCHK(hipSetDevice(b->device));
+    const int nq = b->nq;
+    if (!b->opt.p) HIPCHK(b->opt.alloc((size_t)rsqp_batch::OPT_WORDS * nq));
+    if (!b->used_host) {
+        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&b->used_host), sizeof(int) * nq, hipHostMallocMapped));
+        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&b->used_dev), b->used_host, 0));
+    }
+    int rc = ensure_warm_pools(b);
+    if (rc != RSQP_OK) return rc;
+    b->have_x0 = b->have_y0 = b->have_gb = false;   // the pools are this call's from here on
+    const dim3 grid((unsigned)((nq + 255) / 256)), block(256);
+    QPPools p = pools_of(b);
+    if (!b->timing) HIPCHK(hipEventRecord(b->ev0, b->stream));
+    if (!b->opt_started) {
+        // no member has a solved first QP: init for everybody -- the uniform cold launch (lane-per-problem and mid-size tableau
+        // kernels included), no per-member modes, no warm-start pointers; the members' mode words are 0 = cold already
+        rc = launch_batch(b, p, RSQP_MODE_COLD, b->qp_maxiter, true);
+    } else {
+        hipLaunchKernelGGL(batch_plan_kernel, grid, block, 0, b->stream, nq, b->d_desc.p, b->opt.p, b->mats_updated ? 1 : 0,
+                           b->state_engine == batch_family(b, p) ? 1 : 0, b->x.p, b->y.p, b->ws_b.p, b->wx0.p, b->wy0.p, b->wgb.p);
+        HIPCHK(hipGetLastError());
+        p.member_mode = b->opt.p + (size_t)rsqp_batch::OPT_MODE * nq;
+        p.x0 = b->wx0.p; p.y0 = b->wy0.p; p.guess_b = b->wgb.p;     // the flip: all three (:204-206)
+        rc = launch_batch(b, p, RSQP_MODE_COLD, b->qp_maxiter, true);
+    }
+    if (rc != RSQP_OK) return rc;
+    b->opt_started = true;
+    b->mats_updated = false;   // reset_flags (:488-496)
+    hipLaunchKernelGGL(batch_rescue_plan_kernel, grid, block, 0, b->stream, nq, b->d_desc.p, b->opt.p, b->status.p, b->nwsr.p,
+                       b->lbA.p, b->ubA.p, b->wx0.p, b->used_dev);
+    HIPCHK(hipGetLastError());
+    // the rescue launch is unconditional: a member that needs none leaves at its first instruction, and asking the device whether
+    // anybody needs one would put a host round trip into every call
+    p = pools_of(b);
+    p.member_mode = b->opt.p + (size_t)rsqp_batch::OPT_RMODE * nq;
+    p.x0 = b->wx0.p;                                                 // handle_error: x_0 alone (:741-743)
+    rc = launch_batch(b, p, RSQP_MODE_COLD, b->qp_maxiter, false);
+    if (rc != RSQP_OK) return rc;
+    hipLaunchKernelGGL(batch_count_kernel, grid, block, 0, b->stream, nq, b->opt.p, b->status.p, b->nwsr.p, b->used_dev);
+    HIPCHK(hipGetLastError());
+    if (!b->timing) HIPCHK(hipEventRecord(b->ev1, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    if (nWSR_used) std::memcpy(nWSR_used, b->used_host, sizeof(int) * nq);
+    return RSQP_OK;
+}
+
+extern "C" int rsqp_batch_get_dispatch(const rsqp_batch *b, int *mode, int *rescue) {
+    if (!b) return fail(RSQP_ERR_ARG, "null batch");
+    if (!b->opt.p) return fail(RSQP_ERR_ARG, "rsqp_batch_get_dispatch: no rsqp_batch_optimize_qp has run");
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    const size_t nq = b->nq;
+    if (mode) HIPCHK(hipMemcpy(mode, b->opt.p + rsqp_batch::OPT_MODE * nq, sizeof(int) * nq, hipMemcpyDeviceToHost));
+    if (rescue) HIPCHK(hipMemcpy(rescue, b->opt.p + rsqp_batch::OPT_RESCUE * nq, sizeof(int) * nq, hipMemcpyDeviceToHost));
     return RSQP_OK;
 }
 

@@ -80,7 +80,30 @@ struct QPPools {
     int keep_state;   // 1: write the hot-start part of the engine image back to HBM at the end of a solve (what the
                       //    SQProblem object keeps between calls); 0: cold-start-only batches skip that write --
                       //    the image is marked "not initialised", a later hot start falls back to a cold start
+    const int *member_mode;   // non-null (rsqp_batch_optimize_qp): member q starts as member_mode[q] says (0..3 as the `mode` argument of the
+                      //    kernels, which is then ignored); a negative value = the member is not in this launch and nothing of it is
+                      //    touched. In one launch every mode-3 member has the same warm-start inputs present (x0 / y0 / guess_b are
+                      //    batch-wide pointers). The lane-per-problem kernel never sees such a launch (rsqp_lane_fits)
 };
+
+// optimizeQP's choice of the call shape (src/qpOASESInterface.cpp:150-208) from get_Matrix_change_status (:817-833), stated ONCE for
+// rsqp_optimize_qp, rsqp_optimize_lp and the plan kernel of rsqp_batch_optimize_qp. first_solved = firstQPsolved_, updated = the
+// matrices changed since the last reset_flags; old_status / new_status (0 UNDEFINED, 1 FIXED, 2 VARIED) are advanced in place.
+// Returns the RSQP_MODE_* value: 0 cold, 1 hot start on new vectors, 2 hot start on new matrices, 3 the FIXED <-> VARIED flip
+// (re-initialisation; both status words are back at UNDEFINED, :207-208).
+__host__ __device__ inline int rsqp_dispatch_mode(bool first_solved, bool updated, int &old_status, int &new_status) {
+    if (!first_solved) return 0;
+    const int cur = updated ? 2 : 1;
+    if (old_status == 0) old_status = cur;
+    else {
+        if (new_status != 0) old_status = new_status;
+        new_status = cur;
+    }
+    if (new_status == 0) return old_status == 1 ? 1 : 2;
+    if (new_status == old_status) return new_status == 1 ? 1 : 2;
+    new_status = old_status = 0;
+    return 3;
+}
 
 // number of doubles / ints of the LDS (and persistent) image of one problem
 __host__ __device__ inline int rsqp_ld(int nV) { return nV | 1; }
