@@ -258,7 +258,8 @@ int rsqp_batch_set_matrix_values(rsqp_batch *b, const double *Aval, const double
  * (the default of rsqp_set_reinit_guess). On the LDS- and HBM-resident kernels a member that no solve has touched yet starts
  * cold. rsqp_batch_optimize_qp uses the same pools: what was set here is absent again after it. */
 int rsqp_batch_set_warm_start(rsqp_batch *b, const double *x0, const double *y0, const int *guess_b);
-/* Options::qp_maxiter (Options.cpp:45) of rsqp_batch_optimize_qp; default 1000, as rsqp_set_options */
+/* Options::qp_maxiter (Options.cpp:45) of rsqp_batch_optimize_qp; default 1000, as rsqp_set_options (lp_maxiter has a setter of its
+ * own, rsqp_batch_set_lp_options) */
 int rsqp_batch_set_options(rsqp_batch *b, int qp_maxiter);
 /* solve all problems with one launch; data already resident on the device. mode as above, the same for every member.
  * Asynchronous on the batch's stream; rsqp_batch_sync() waits. Never touches the state of rsqp_batch_optimize_qp (as
@@ -274,9 +275,36 @@ int rsqp_batch_solve(rsqp_batch *b, int mode, int max_nWSR);
  * to Stats::qp_iter; rsqp_batch_get_results keeps reporting the nWSR of a member's LAST solve. Needs keep_state != 0 (else
  * RSQP_ERR_ARG). rsqp_batch_get_last_kernel reports the kernel of the call's first solve. */
 int rsqp_batch_optimize_qp(rsqp_batch *b, int *nWSR_used);
-/* what the last rsqp_batch_optimize_qp did per member (nq entries each, may be NULL): mode = RSQP_MODE_* of its first solve (as
- * rsqp_get_last_mode reports it before a rescue), rescue = 0 none, 1 handle_error re-initialised from scratch (:745-749),
- * 2 handle_error re-initialised from the slack point x_0 (:720-743) */
+/* Options::lp_maxiter (Options.cpp:54) of rsqp_batch_optimize_lp; default 100, as rsqp_set_options */
+int rsqp_batch_set_lp_options(rsqp_batch *b, int lp_maxiter);
+/* optimizeLP (qpOASESInterface.cpp:227-284) for EVERY member, each with its own state: what rsqp_optimize_lp does on one handle.
+ * Member q ends the call with the exit flag, nWSR_used, x, y, raw working sets and objective a single rsqp_solver reports from
+ * rsqp_optimize_lp for the same A, vectors and sequence of calls. Per member:
+ *   - any H of the batch is ignored: the member is solved with H = regVal*I, regVal = (|g|_2 > 0 ? |g|_2 : 1) * 1e3 * EPS, computed
+ *     from the gradient of the call at every init (first solve, FIXED <-> VARIED flip, rescue) and kept across hot starts;
+ *   - the call shape is the dispatch of rsqp_batch_optimize_qp (rsqp_batch_set_matrix_values is set_A for the members whose first
+ *     LP is solved), except that a flip is a plain init without warm-start inputs (:266-270);
+ *   - handle_error's LP branch (:688-717) with a fresh lp_maxiter budget: an infeasible member with nV >= 2 nC re-initialises from
+ *     x_0 := the x of the failed solve with its slack entries set to max(0, lbA) and -min(0, ubA), any other from scratch; a member
+ *     whose first init failed keeps firstQPsolved_ false even when the rescue succeeds;
+ *   - every member that is solved after that takes one regularisation step, a hot start on the gradient g - regVal*x with a fresh
+ *     budget, and reports the objective g'x; unsolved members take none. The gradients set by rsqp_batch_set_vectors are untouched.
+ * nWSR_used (nq entries, may be NULL) counts as rsqp_optimize_lp does: first solve + rescue + step, and the rescue's count alone
+ * when the rescue fails too; rsqp_batch_get_results keeps reporting the nWSR of a member's LAST solve. All decisions are taken on
+ * the device between the launches; the call returns when the results are ready. Needs keep_state != 0 (else RSQP_ERR_ARG).
+ * Kernels: every solve of an LP call runs on the null-space kernels -- the LDS-resident ones (rsqp_batch_get_last_kernel() == 0;
+ * Givens / TQ up to 8 variables, explicit inverses above), or the HBM-resident one (3) for batches beyond the LDS fit -- and never
+ * on the tableau kernels (1, 2, and the mid-size one), whatever H the batch has: a tableau carries H^-1 = I / regVal ~ 1e13 and
+ * loses the digits of x to it (up to 9e-4 relative, measured), and the register-resident one gives up on pivots in its rounding
+ * band, which only a single handle can hand over to the Givens kernel. rsqp_optimize_lp keeps a handle off them as well.
+ * QP and LP calls may alternate on one batch: the first call of the other kind starts every member over (firstQPsolved_ false,
+ * both status words UNDEFINED, no stored factors used), as on a single handle. rsqp_batch_test_optimality after an LP call
+ * certifies the LP (no H, no regVal term). rsqp_batch_get_last_kernel reports the kernel of the call's first solve. */
+int rsqp_batch_optimize_lp(rsqp_batch *b, int *nWSR_used);
+/* what the last rsqp_batch_optimize_qp / rsqp_batch_optimize_lp did per member (nq entries each, may be NULL): mode = RSQP_MODE_*
+ * of its first solve (as rsqp_get_last_mode reports it before a rescue), rescue = 0 none, 1 handle_error re-initialised from
+ * scratch (:745-749), 2 handle_error re-initialised from the slack point x_0 (:720-743). After an LP call mode is what the dispatch
+ * returned: 3 names a FIXED <-> VARIED flip, which an LP call runs as a plain init (RSQP_MODE_COLD without warm-start inputs). */
 int rsqp_batch_get_dispatch(const rsqp_batch *b, int *mode, int *rescue);
 int rsqp_batch_sync(rsqp_batch *b);
 /* keep != 0 (default): every solve writes the state a hot start needs (factors, iterate, multipliers,

@@ -88,6 +88,8 @@ SYMBOLS = {
     "rsqp_batch_set_options": (C.c_int, [C.c_void_p, C.c_int]),
     "rsqp_batch_solve": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "rsqp_batch_optimize_qp": (C.c_int, [C.c_void_p, ip]),
+    "rsqp_batch_set_lp_options": (C.c_int, [C.c_void_p, C.c_int]),
+    "rsqp_batch_optimize_lp": (C.c_int, [C.c_void_p, ip]),
     "rsqp_batch_get_dispatch": (C.c_int, [C.c_void_p, ip, ip]),
     "rsqp_batch_sync": (C.c_int, [C.c_void_p]),
     "rsqp_batch_set_keep_state": (C.c_int, [C.c_void_p, C.c_int]),
@@ -474,8 +476,10 @@ class Batch:
                 raise ValueError("%s has %d entries, the batch needs %d" % (name, a.size, n))
         check(lib().rsqp_batch_set_warm_start(self._h, _dp(x0), _dp(y0), _ip(guess_b)))
 
-    def set_options(self, qp_maxiter=1000):
+    def set_options(self, qp_maxiter=1000, lp_maxiter=None):
         check(lib().rsqp_batch_set_options(self._h, int(qp_maxiter)))
+        if lp_maxiter is not None:
+            check(lib().rsqp_batch_set_lp_options(self._h, int(lp_maxiter)))
 
     def optimize_qp(self):
         """optimizeQP for every member (dispatch + handle_error per member); returns nWSR_used per member"""
@@ -483,8 +487,16 @@ class Batch:
         check(lib().rsqp_batch_optimize_qp(self._h, _ip(used)))
         return used
 
+    def optimize_lp(self):
+        """optimizeLP for every member (H ignored: regVal*I, dispatch + handle_error's LP branch + one regularisation step per
+        member); returns nWSR_used per member"""
+        used = np.zeros(self.nq, np.int32)
+        check(lib().rsqp_batch_optimize_lp(self._h, _ip(used)))
+        return used
+
     def dispatch(self):
-        """(mode, rescue) per member of the last optimize_qp: MODE_* of its first solve; 0 none / 1 from scratch / 2 slack point"""
+        """(mode, rescue) per member of the last optimize_qp / optimize_lp: MODE_* of its first solve (an LP call runs a flip,
+        MODE_WARM_REINIT, as a plain init); 0 none / 1 from scratch / 2 slack point"""
         mode = np.zeros(self.nq, np.int32); rescue = np.zeros(self.nq, np.int32)
         check(lib().rsqp_batch_get_dispatch(self._h, _ip(mode), _ip(rescue)))
         return mode, rescue

@@ -330,7 +330,8 @@ hipError_t rsqp_launch_small_qp(const SmallKnobs &kn, const QPPools &p_in, int n
     // (only where the null-space kernel would give a problem four waves as well: batches of SMALL problems are throughput-bound
     //  and better served by 16 / 32 lanes per problem, several problems per wave)
     // (per-member modes: the kernel itself leaves the members whose mode it does not carry to the null-space kernel)
-    if (forcedE < 0 && eng == 1 && (nVmax > 32 || nCmax > 32) && (p.member_mode || mode == 0 || mode == 1) && !p.done_flag) {
+    // (kn.no_tiny == 2, the LP launches of a batch: every member would come back with RET_BAIL -- no H, hreg != 0)
+    if (forcedE < 0 && kn.no_tiny < 2 && eng == 1 && (nVmax > 32 || nCmax > 32) && (p.member_mode || mode == 0 || mode == 1) && !p.done_flag) {
 #define KK_LAUNCH(RV_, RC_, CV_, CC_)                                                                                            \
         do {                                                                                                                     \
             hipLaunchKernelGGL((small_qpg_kernel<RV_, RC_, CV_, CC_>), dim3(nq), dim3(256), 0, stream, p, nq, mode, maxWSR);     \

@@ -623,6 +623,11 @@ extern "C" int rsqp_solve(rsqp_solver *s, int mode, int *nWSR, const double *x0,
     if (s->engine == 2) return solve_large(s, mode, nWSR, x0, y0, guess_b);
     const int nWSR_in = *nWSR;
     QPPools p = pools_of(s);
+    // an LP (H = regVal*I with regVal ~ 1e-13) stays off the register-resident tableau kernel: the tableau carries H^-1, and its x
+    // came out up to 9e-4 (relative) off the CPU reference's on the LPs of tests/lp_batch_ref.py -- flag, count and working set were
+    // right. The Givens / TQ kernel is within 6e-12 on the same members; rsqp_batch_optimize_lp keeps its members off it as well
+    SmallKnobs kn = s->kn;
+    if (s->lp_mode) kn.no_tiny = 1;
     if (mode == RSQP_MODE_WARM_REINIT) {
         if (x0) { HIPCHK(s->d_x0.upload(x0, s->nV)); p.x0 = s->d_x0.p; }
         if (y0) { HIPCHK(s->d_y0.upload(y0, s->nV + s->nC)); p.y0 = s->d_y0.p; }
@@ -635,11 +640,11 @@ extern "C" int rsqp_solve(rsqp_solver *s, int mode, int *nWSR, const double *x0,
     if (fused_cert) { p.cert_out = s->d_kkt.p; p.cert_Wb = s->d_Wb.p; p.cert_Wc = s->d_Wc.p; }
     {   // the tableau kernel and the LDS-resident kernels keep different layouts in the same state block: a solve that changes
         // the family (H lost or regained its symmetry between two solves) starts cold instead of restoring the other's bytes
-        const int fam = rsqp_small_launch_is_tiny(s->kn, p, s->nV, s->nC);
+        const int fam = rsqp_small_launch_is_tiny(kn, p, s->nV, s->nC);
         if ((mode == RSQP_MODE_HOT_VECTORS || mode == RSQP_MODE_HOT_MATRICES) && s->state_engine != fam) { mode = RSQP_MODE_COLD; s->last_mode = mode; }
         s->state_engine = fam;
     }
-    hipError_t e = rsqp_launch_small_qp(s->kn, p, 1, s->nV, s->nC,
+    hipError_t e = rsqp_launch_small_qp(kn, p, 1, s->nV, s->nC,
                                         rsqp_mat_lds_bytes(s->nV, s->nC, s->A.initialised ? s->A.nnz : 0, s->H.initialised ? s->H.nnz : 0),
                                         mode, *nWSR, s->stream);
     if (e != hipSuccess) return fail(RSQP_ERR_DEVICE, std::string("QP kernel launch: ") + hipGetErrorString(e));
@@ -1016,8 +1021,17 @@ struct rsqp_batch {
     bool have_x0 = false, have_y0 = false, have_gb = false;
     // optimizeQP per member (rsqp_batch_optimize_qp): nq ints each, in one block -- firstQPsolved_, old / new matrix status, mode of
     // the call's first solve, mode of its rescue solve (-1: none), kind of rescue, count of the first solve
-    enum { OPT_FIRST = 0, OPT_OLD, OPT_NEW, OPT_MODE, OPT_RMODE, OPT_RESCUE, OPT_N1, OPT_WORDS };
+    // rsqp_batch_optimize_lp adds: mode the first solve is LAUNCHED with (a flip is a plain init there), mode of the proximal step
+    // (-1: the member is unsolved and takes none)
+    enum { OPT_FIRST = 0, OPT_OLD, OPT_NEW, OPT_MODE, OPT_RMODE, OPT_RESCUE, OPT_N1, OPT_LMODE, OPT_PMODE, OPT_WORDS };
     DevBuf<int> opt;
+    // optimizeLP per member (rsqp_batch_optimize_lp): the members' descriptors with H absent and hreg = regVal of the member's last
+    // init (written on the device, kept across hot starts), and the pool of the proximal step's gradients g - regVal x
+    DevBuf<QPDesc> d_desc_lp;
+    DevBuf<double> g_lp;
+    int lp_maxiter = 100;                 // rsqp_batch_set_lp_options
+    int last_kind = 0;                    // 0 no optimize call yet, 1 the last one was rsqp_batch_optimize_qp, 2 rsqp_batch_optimize_lp
+    bool cert_lp = false;                 // the results in the pools are an LP call's: rsqp_batch_test_optimality certifies the LP
     // nWSR_used of the members, written by the kernels straight into host-mapped memory: ready behind the call's one wait, no copy
     // (and no second wait) behind it
     int *used_host = nullptr, *used_dev = nullptr;
@@ -1038,10 +1052,11 @@ struct rsqp_batch {
 };
 
 namespace {
-QPPools pools_of(rsqp_batch *b) {
+// lp: a launch of rsqp_batch_optimize_lp -- the LP descriptors (no H, per-member hreg), read by every kernel it runs on
+QPPools pools_of(rsqp_batch *b, bool lp = false) {
     QPPools p;
     std::memset(&p, 0, sizeof(p));
-    p.desc = b->d_desc.p;
+    p.desc = lp ? b->d_desc_lp.p : b->d_desc.p;
     p.Ajc = b->Ajc.p; p.Air = b->Air.p; p.Aval = b->Aval.p;
     p.Arp = b->Arp.p; p.Aci = b->Aci.p; p.Arv = b->Arv.p;
     p.Hjc = b->Hjc.p; p.Hir = b->Hir.p; p.Hval = b->Hval.p;
@@ -1052,10 +1067,18 @@ QPPools pools_of(rsqp_batch *b) {
     p.uniV = b->uniV; p.uniC = b->uniC;
     p.keep_state = b->keep_state ? 1 : 0;
     p.done_flag = nullptr; p.done_val = 0;
-    p.tiny_ok = (b->h_sym || !b->haveH) ? 1 : 0;
-    p.uni_pat = b->uni_pat ? 1 : 0;
-    p.uni_annz = b->uni_annz; p.uni_hnnz = b->uni_hnnz; p.uni_haveH = b->haveH ? 1 : 0; p.uni_state = b->uni_state;
+    p.tiny_ok = (b->h_sym || !b->haveH || lp) ? 1 : 0;   // (as pools_of(rsqp_solver *): an unsymmetric H does not move the LPs)
+    // the batch-wide uni_hreg / uni_haveH cannot say what an LP member needs: LP launches read the descriptors
+    p.uni_pat = (b->uni_pat && !lp) ? 1 : 0;
+    p.uni_annz = b->uni_annz; p.uni_hnnz = lp ? 0 : b->uni_hnnz; p.uni_haveH = (b->haveH && !lp) ? 1 : 0; p.uni_state = b->uni_state;
     return p;
+}
+// the knobs of a launch: LP launches stay off the register-resident tableau kernels, which answer RET_SETUP_FAILED on a pivot in
+// their rounding band and have no hand-over inside a batch (a single handle re-solves on the Givens kernel, rsqp_solve)
+SmallKnobs knobs_of(const rsqp_batch *b, bool lp) {
+    SmallKnobs k = b->kn;
+    if (lp) k.no_tiny = 2;   // (nor the mid-size tableau kernel, which would hand every LP member back: no H, hreg != 0)
+    return k;
 }
 }  // namespace
 
@@ -1230,11 +1253,14 @@ int ensure_warm_pools(rsqp_batch *b) {
 }
 
 // kernel family a launch on this batch runs: 3 HBM-resident, 1 hs071-scale tableau (+ lane-per-problem), 0 LDS-resident
-int batch_family(const rsqp_batch *b, const QPPools &p) { return b->hbm ? 3 : rsqp_small_launch_is_tiny(b->kn, p, b->nVmax, b->nCmax); }
+int batch_family(const rsqp_batch *b, const QPPools &p, bool lp = false) {
+    return b->hbm ? 3 : rsqp_small_launch_is_tiny(knobs_of(b, lp), p, b->nVmax, b->nCmax);
+}
 
 // one solve launch of the whole batch (p.member_mode: of the members it names). first: the launch rsqp_batch_get_last_kernel reports
-int launch_batch(rsqp_batch *b, QPPools &p, int mode, int max_nWSR, bool first) {
-    const int fam = batch_family(b, p);
+int launch_batch(rsqp_batch *b, QPPools &p, int mode, int max_nWSR, bool first, bool lp = false) {
+    const SmallKnobs kn = knobs_of(b, lp);
+    const int fam = batch_family(b, p, lp);
     // the kernel families keep different layouts in the same state block: a hot start on another family's state starts cold
     // (per-member modes: the plan kernel was told)
     if ((mode == RSQP_MODE_HOT_VECTORS || mode == RSQP_MODE_HOT_MATRICES) && b->state_engine != fam) mode = RSQP_MODE_COLD;
@@ -1242,12 +1268,12 @@ int launch_batch(rsqp_batch *b, QPPools &p, int mode, int max_nWSR, bool first) 
     hipError_t e;
     if (b->hbm) {
         if (first) b->last_kernel = 3;
-        e = rsqp_launch_small_qp_hbm(b->kn, p, b->nq, b->nVmax, b->nCmax, mode, max_nWSR, b->stream);
+        e = rsqp_launch_small_qp_hbm(kn, p, b->nq, b->nVmax, b->nCmax, mode, max_nWSR, b->stream);
     } else {
         // a cold-start-only batch on the tableau kernel keeps no state and leaves no mark: the handle remembers it instead
         if (fam == 1 && !b->keep_state) { p.skip_mark = 1; b->state_engine = -1; }
-        if (first) b->last_kernel = fam == 1 ? (rsqp_lane_fits(b->kn, p, b->nq, b->nVmax, b->nCmax, mode) ? 2 : 1) : 0;
-        e = rsqp_launch_small_qp(b->kn, p, b->nq, b->nVmax, b->nCmax, b->mat_bytes_max, mode, max_nWSR, b->stream);
+        if (first) b->last_kernel = fam == 1 ? (rsqp_lane_fits(kn, p, b->nq, b->nVmax, b->nCmax, mode) ? 2 : 1) : 0;
+        e = rsqp_launch_small_qp(kn, p, b->nq, b->nVmax, b->nCmax, b->mat_bytes_max, mode, max_nWSR, b->stream);
     }
     if (e != hipSuccess) return fail(RSQP_ERR_DEVICE, std::string("QP kernel launch: ") + hipGetErrorString(e));
     return RSQP_OK;
@@ -1288,6 +1314,7 @@ extern "C" int rsqp_batch_solve(rsqp_batch *b, int mode, int max_nWSR) {
     if (!b->timing) HIPCHK(hipEventRecord(b->ev0, b->stream));
     const int rc = launch_batch(b, p, mode, max_nWSR, true);
     if (rc != RSQP_OK) return rc;
+    b->cert_lp = false;
     if (!b->timing) HIPCHK(hipEventRecord(b->ev1, b->stream));
     return RSQP_OK;
 }
@@ -1357,6 +1384,149 @@ __global__ void batch_count_kernel(int nq, const int *__restrict__ opt, const in
     const bool first_init_failed = opt[rsqp_batch::OPT_FIRST * nq + q] == 0;
     used[q] = (first_init_failed && status[q] != QPS_SOLVED) ? n2 : n1 + n2;
 }
+
+// what both optimize entry points need before their first launch. kind: 1 rsqp_batch_optimize_qp, 2 rsqp_batch_optimize_lp. The first
+// call of the other kind starts every member over -- firstQPsolved_ false, both status words UNDEFINED, hence a cold start that
+// reads no stored factors -- as a single handle does (rsqp_optimize_qp / rsqp_optimize_lp; the reference keeps separate LP and QP
+// objects, Algorithm.cpp:561-562)
+int ensure_optimize_pools(rsqp_batch *b, int kind) {
+    const int nq = b->nq;
+    if (!b->opt.p) HIPCHK(b->opt.alloc((size_t)rsqp_batch::OPT_WORDS * nq));
+    if (!b->used_host) {
+        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&b->used_host), sizeof(int) * nq, hipHostMallocMapped));
+        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&b->used_dev), b->used_host, 0));
+    }
+    const int rc = ensure_warm_pools(b);
+    if (rc != RSQP_OK) return rc;
+    b->have_x0 = b->have_y0 = b->have_gb = false;   // the pools are this call's from here on
+    if (kind == 2 && !b->d_desc_lp.p) {
+        std::vector<QPDesc> lp = b->desc;
+        for (QPDesc &d : lp) { d.haveH = 0; d.hnnz = 0; d.hreg = 0.0; }
+        HIPCHK(b->d_desc_lp.from(lp));
+        HIPCHK(b->g_lp.alloc(b->sumV));
+    }
+    if (b->last_kind != 0 && b->last_kind != kind) {
+        HIPCHK(hipMemsetAsync(b->opt.p, 0, sizeof(int) * (size_t)rsqp_batch::OPT_WORDS * nq, b->stream));
+        b->opt_started = false;
+    }
+    b->last_kind = kind;
+    return RSQP_OK;
+}
+
+// ---------------------------------------------------------------------------------
+// optimizeLP for every member of a batch (qpOASESInterface.cpp:227-284 + handle_error's LP branch :688-717): what rsqp_optimize_lp
+// does on one handle. plan -> solve -> rescue plan -> rescue solve -> proximal plan -> proximal step -> finish -> one wait. The plan
+// kernels run one wavefront per member: the gradient norm, g - regVal x and g'x are reductions over up to RSQP_BATCH_MAX_V entries.
+// ---------------------------------------------------------------------------------
+__device__ inline double lp_wave_sum(double v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+// regVal of an init: (|g|_2 > 0 ? |g|_2 : 1) * 1e3 * EPS (the same value in every lane)
+__device__ inline double lp_reg_val(const QPDesc &d, const double *__restrict__ g) {
+    double s = 0.0;
+    for (int v = (int)threadIdx.x; v < d.nV; v += 64) s += g[d.offV + v] * g[d.offV + v];
+    const double ng = sqrt(lp_wave_sum(s));
+    return (ng > 0.0 ? ng : 1.0) * 1.0e3 * RSQP_EPS;
+}
+
+// before the first solve: the call shape of every member (rsqp_dispatch_mode). A FIXED <-> VARIED flip is a plain init here
+// (:266-270): OPT_MODE keeps what the dispatch said (3), OPT_LMODE what is launched (0). Every init fixes the member's regVal from
+// the gradient of this call; a hot start keeps the one its factors were built with
+__global__ void __launch_bounds__(64)
+batch_lp_plan_kernel(int nq, QPDesc *__restrict__ desc, int *__restrict__ opt, int updated, int hot_ok, const double *__restrict__ g) {
+    const int q = (int)blockIdx.x;
+    if (q >= nq) return;
+    const QPDesc d = desc[q];
+    int old_status = opt[rsqp_batch::OPT_OLD * nq + q], new_status = opt[rsqp_batch::OPT_NEW * nq + q];
+    int mode = rsqp_dispatch_mode(opt[rsqp_batch::OPT_FIRST * nq + q] != 0, updated != 0, old_status, new_status);
+    const bool init = mode == RSQP_MODE_COLD || mode == RSQP_MODE_WARM_REINIT;
+    const double reg = init ? lp_reg_val(d, g) : d.hreg;
+    // (stored states of another kernel family: the hot start runs cold on the regVal it has, as rsqp_solve does on a handle)
+    if (!hot_ok && !init) mode = RSQP_MODE_COLD;
+    __syncthreads();   // every lane has read the member's words
+    if (threadIdx.x == 0) {
+        opt[rsqp_batch::OPT_OLD * nq + q] = old_status; opt[rsqp_batch::OPT_NEW * nq + q] = new_status;
+        opt[rsqp_batch::OPT_MODE * nq + q] = mode;
+        opt[rsqp_batch::OPT_LMODE * nq + q] = init ? RSQP_MODE_COLD : mode;
+        desc[q].hreg = reg;
+    }
+}
+
+// behind the first solve: firstQPsolved_ (:248-250), handle_error's LP branch per member (:688-717) -- none / re-init from scratch /
+// re-init from x_0 := the x of the failed solve with its slack entries overwritten (:693-699; written to the x0 pool) --, a fresh
+// regVal for the re-init, old = new = UNDEFINED for the rescued
+__global__ void __launch_bounds__(64)
+batch_lp_rescue_plan_kernel(int nq, QPDesc *__restrict__ desc, int *__restrict__ opt, const int *__restrict__ status,
+                            const int *__restrict__ nwsr, const double *__restrict__ g, const double *__restrict__ x,
+                            const double *__restrict__ lbA, const double *__restrict__ ubA, double *__restrict__ x0) {
+    const int q = (int)blockIdx.x, lane = (int)threadIdx.x;
+    if (q >= nq) return;
+    const int sw = status[q];
+    const bool solved = sw == QPS_SOLVED, infeasible = sw >= 100 && sw < 200;
+    if (solved) {
+        if (lane == 0) {
+            opt[rsqp_batch::OPT_N1 * nq + q] = nwsr[q];
+            opt[rsqp_batch::OPT_FIRST * nq + q] = 1;
+            opt[rsqp_batch::OPT_RMODE * nq + q] = -1; opt[rsqp_batch::OPT_RESCUE * nq + q] = 0;
+        }
+        return;
+    }
+    const QPDesc d = desc[q];
+    const double reg = lp_reg_val(d, g);
+    const bool slack = infeasible && d.nV >= 2 * d.nC;
+    if (slack) {
+        for (int v = lane; v < d.nV; v += 64) x0[d.offV + v] = x[d.offV + v];
+        __syncthreads();
+        for (int i = lane; i < d.nC; i += 64) {
+            x0[d.offV + i + d.nV - 2 * d.nC] = fmax(0.0, lbA[d.offC + i]);
+            x0[d.offV + i + d.nV - d.nC] = -fmin(0.0, ubA[d.offC + i]);
+        }
+    }
+    if (lane == 0) {
+        opt[rsqp_batch::OPT_N1 * nq + q] = nwsr[q];
+        opt[rsqp_batch::OPT_OLD * nq + q] = 0; opt[rsqp_batch::OPT_NEW * nq + q] = 0;
+        opt[rsqp_batch::OPT_RMODE * nq + q] = slack ? RSQP_MODE_WARM_REINIT : RSQP_MODE_COLD;
+        opt[rsqp_batch::OPT_RESCUE * nq + q] = slack ? 2 : 1;
+        desc[q].hreg = reg;
+    }
+}
+
+// behind the rescue solve: the count so far (a member whose rescue failed too reports the rescue's count alone, on both branches:
+// the reference throws inside handle_error, :714-716, before :278-279 add the other), and the proximal step of every member that is
+// solved now (:280-283): a hot start on the gradient g - regVal x, written to the scratch pool -- the batch's g keeps the caller's
+__global__ void __launch_bounds__(64)
+batch_lp_prox_plan_kernel(int nq, const QPDesc *__restrict__ desc, int *__restrict__ opt, const int *__restrict__ status,
+                          const int *__restrict__ nwsr, const double *__restrict__ g, const double *__restrict__ x,
+                          double *__restrict__ g_lp) {
+    const int q = (int)blockIdx.x, lane = (int)threadIdx.x;
+    if (q >= nq) return;
+    const bool solved = status[q] == QPS_SOLVED, rescued = opt[rsqp_batch::OPT_RESCUE * nq + q] != 0;
+    const int n1 = opt[rsqp_batch::OPT_N1 * nq + q], n2 = nwsr[q];
+    __syncthreads();
+    if (lane == 0) {
+        opt[rsqp_batch::OPT_N1 * nq + q] = rescued ? (solved ? n1 + n2 : n2) : n1;
+        opt[rsqp_batch::OPT_PMODE * nq + q] = solved ? RSQP_MODE_HOT_VECTORS : -1;
+    }
+    if (!solved) return;
+    const QPDesc d = desc[q];
+    for (int v = lane; v < d.nV; v += 64) g_lp[d.offV + v] = g[d.offV + v] - d.hreg * x[d.offV + v];
+}
+
+// behind the proximal step: nWSR_used, and the objective g'x with the caller's gradient (:283) for the members that took the step
+__global__ void __launch_bounds__(64)
+batch_lp_finish_kernel(int nq, const QPDesc *__restrict__ desc, const int *__restrict__ opt, const int *__restrict__ nwsr,
+                       const double *__restrict__ g, const double *__restrict__ x, double *__restrict__ obj, int *__restrict__ used) {
+    const int q = (int)blockIdx.x, lane = (int)threadIdx.x;
+    if (q >= nq) return;
+    const int total = opt[rsqp_batch::OPT_N1 * nq + q];
+    if (opt[rsqp_batch::OPT_PMODE * nq + q] < 0) { if (lane == 0) used[q] = total; return; }
+    const QPDesc d = desc[q];
+    double s = 0.0;
+    for (int v = lane; v < d.nV; v += 64) s += g[d.offV + v] * x[d.offV + v];
+    s = lp_wave_sum(s);
+    if (lane == 0) { obj[q] = s; used[q] = total + nwsr[q]; }
+}
 }  // namespace
 
 extern "C" int rsqp_batch_optimize_qp(rsqp_batch *b, int *nWSR_used) {
@@ -1364,14 +1534,8 @@ extern "C" int rsqp_batch_optimize_qp(rsqp_batch *b, int *nWSR_used) {
     if (!b->keep_state) return fail(RSQP_ERR_ARG, "rsqp_batch_optimize_qp: the batch keeps no state (rsqp_batch_set_keep_state(b, 0))");
     HIPCHK(hipSetDevice(b->device));
     const int nq = b->nq;
-    if (!b->opt.p) HIPCHK(b->opt.alloc((size_t)rsqp_batch::OPT_WORDS * nq));
-    if (!b->used_host) {
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&b->used_host), sizeof(int) * nq, hipHostMallocMapped));
-        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&b->used_dev), b->used_host, 0));
-    }
-    int rc = ensure_warm_pools(b);
+    int rc = ensure_optimize_pools(b, 1);
     if (rc != RSQP_OK) return rc;
-    b->have_x0 = b->have_y0 = b->have_gb = false;   // the pools are this call's from here on
     const dim3 grid((unsigned)((nq + 255) / 256)), block(256);
     QPPools p = pools_of(b);
     if (!b->timing) HIPCHK(hipEventRecord(b->ev0, b->stream));
@@ -1389,6 +1553,7 @@ extern "C" int rsqp_batch_optimize_qp(rsqp_batch *b, int *nWSR_used) {
     }
     if (rc != RSQP_OK) return rc;
     b->opt_started = true;
+    b->cert_lp = false;
     b->mats_updated = false;   // reset_flags (:488-496)
     hipLaunchKernelGGL(batch_rescue_plan_kernel, grid, block, 0, b->stream, nq, b->d_desc.p, b->opt.p, b->status.p, b->nwsr.p,
                        b->lbA.p, b->ubA.p, b->wx0.p, b->used_dev);
@@ -1408,9 +1573,58 @@ extern "C" int rsqp_batch_optimize_qp(rsqp_batch *b, int *nWSR_used) {
     return RSQP_OK;
 }
 
+extern "C" int rsqp_batch_set_lp_options(rsqp_batch *b, int lp_maxiter) {
+    if (!b || lp_maxiter < 0) return fail(RSQP_ERR_ARG, "rsqp_batch_set_lp_options");
+    b->lp_maxiter = lp_maxiter;
+    return RSQP_OK;
+}
+
+extern "C" int rsqp_batch_optimize_lp(rsqp_batch *b, int *nWSR_used) {
+    if (!b) return fail(RSQP_ERR_ARG, "null batch");
+    if (!b->keep_state) return fail(RSQP_ERR_ARG, "rsqp_batch_optimize_lp: the batch keeps no state (rsqp_batch_set_keep_state(b, 0))");
+    HIPCHK(hipSetDevice(b->device));
+    const int nq = b->nq;
+    int rc = ensure_optimize_pools(b, 2);
+    if (rc != RSQP_OK) return rc;
+    const dim3 grid((unsigned)nq), block(64);
+    int *const opt = b->opt.p;
+    // every launch carries per-member modes and reads the LP descriptors: H absent, hreg = the member's regVal
+    QPPools p = pools_of(b, true);
+    if (!b->timing) HIPCHK(hipEventRecord(b->ev0, b->stream));
+    hipLaunchKernelGGL(batch_lp_plan_kernel, grid, block, 0, b->stream, nq, b->d_desc_lp.p, opt, b->mats_updated ? 1 : 0,
+                       b->state_engine == batch_family(b, p, true) ? 1 : 0, b->g.p);
+    HIPCHK(hipGetLastError());
+    p.member_mode = opt + (size_t)rsqp_batch::OPT_LMODE * nq;
+    if ((rc = launch_batch(b, p, RSQP_MODE_COLD, b->lp_maxiter, true, true)) != RSQP_OK) return rc;
+    b->opt_started = true;
+    b->cert_lp = true;
+    b->mats_updated = false;   // reset_flags (:488-496)
+    hipLaunchKernelGGL(batch_lp_rescue_plan_kernel, grid, block, 0, b->stream, nq, b->d_desc_lp.p, opt, b->status.p, b->nwsr.p, b->g.p,
+                       b->x.p, b->lbA.p, b->ubA.p, b->wx0.p);
+    HIPCHK(hipGetLastError());
+    // (unconditional, as in rsqp_batch_optimize_qp: a member that needs no rescue leaves at its first instruction)
+    p.member_mode = opt + (size_t)rsqp_batch::OPT_RMODE * nq;
+    p.x0 = b->wx0.p;                                                 // handle_error: x_0 alone (:700-702)
+    if ((rc = launch_batch(b, p, RSQP_MODE_COLD, b->lp_maxiter, false, true)) != RSQP_OK) return rc;
+    hipLaunchKernelGGL(batch_lp_prox_plan_kernel, grid, block, 0, b->stream, nq, b->d_desc_lp.p, opt, b->status.p, b->nwsr.p, b->g.p,
+                       b->x.p, b->g_lp.p);
+    HIPCHK(hipGetLastError());
+    p.member_mode = opt + (size_t)rsqp_batch::OPT_PMODE * nq;
+    p.x0 = nullptr;
+    p.g = b->g_lp.p;
+    if ((rc = launch_batch(b, p, RSQP_MODE_HOT_VECTORS, b->lp_maxiter, false, true)) != RSQP_OK) return rc;
+    hipLaunchKernelGGL(batch_lp_finish_kernel, grid, block, 0, b->stream, nq, b->d_desc_lp.p, opt, b->nwsr.p, b->g.p, b->x.p, b->obj.p,
+                       b->used_dev);
+    HIPCHK(hipGetLastError());
+    if (!b->timing) HIPCHK(hipEventRecord(b->ev1, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    if (nWSR_used) std::memcpy(nWSR_used, b->used_host, sizeof(int) * nq);
+    return RSQP_OK;
+}
+
 extern "C" int rsqp_batch_get_dispatch(const rsqp_batch *b, int *mode, int *rescue) {
     if (!b) return fail(RSQP_ERR_ARG, "null batch");
-    if (!b->opt.p) return fail(RSQP_ERR_ARG, "rsqp_batch_get_dispatch: no rsqp_batch_optimize_qp has run");
+    if (!b->opt.p) return fail(RSQP_ERR_ARG, "rsqp_batch_get_dispatch: no rsqp_batch_optimize_qp / rsqp_batch_optimize_lp has run");
     HIPCHK(hipSetDevice(b->device));
     HIPCHK(hipStreamSynchronize(b->stream));
     const size_t nq = b->nq;
@@ -1491,7 +1705,7 @@ extern "C" int rsqp_batch_test_optimality(rsqp_batch *b, rsqp_optimality_status 
         }
         HIPCHK(b->kV.from(kv)); HIPCHK(b->kC.from(kc)); HIPCHK(b->koV.from(ov)); HIPCHK(b->koC.from(oc));
     }
-    QPPools p = pools_of(b);
+    QPPools p = pools_of(b, b->cert_lp);   // behind an LP call: H absent (and no regVal term: the certificate reads no hreg)
     RsqpKktArgs a;
     std::memset(&a, 0, sizeof(a));
     a.nV = b->kV.p; a.nC = b->kC.p; a.offV = b->koV.p; a.offC = b->koC.p;

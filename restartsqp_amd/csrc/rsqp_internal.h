@@ -41,7 +41,7 @@ struct SmallKnobs {
     int k_debug_bail = -1;    // RSQP_K_DEBUG_BAIL      test hook: the mid-size tableau kernel bails out of a hot start before its n-th change
     int lanes = -1;           // RSQP_SMALL_LANES       lanes per problem (8 / 16 / 32 / 64)
     int waves = -1;           // RSQP_SMALL_WAVES       waves per SIMD the build is compiled for
-    int no_tiny = 0;          // (set by the single-QP rescue, rsqp_api.hip) no hs071-scale tableau kernel
+    int no_tiny = 0;          // (set by the single-QP rescue, rsqp_api.hip) 1: no hs071-scale tableau kernel; 2 (the LP launches of a batch): nor the mid-size one
     int lane = -1;            // RSQP_LANE              0: never the lane-per-problem kernel (qp_lane.hip); n > 0: from n members on (default 16 385)
     int arena_mapped = -1;    // RSQP_ARENA_MAPPED      single-QP handles: patterns / plans in host-mapped memory, no upload at set_A / set_H (-1: hs071 scale only)
     int no_spin = 0;          // RSQP_NO_SPIN           single-QP waits block in hipStreamSynchronize instead of spinning on a mapped word
