@@ -1,0 +1,829 @@
+// rsqp_batch.hip -- the batch of independent QPs of include/rsqp_hip.h (rsqp_batch_*), host side and the one-thread- or
+// one-wavefront-per-member kernels that take optimizeQP's / optimizeLP's decisions between the solve launches.
+//
+// Host logic restated from the reference adapter src/qpOASESInterface.cpp as rsqp_api.hip restates it for one handle: the
+// FIXED/VARIED warm-start dispatch (:137-224, :227-284, :817-833), handle_error (:686-758), status mapping (:332-357).
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "rsqp_host.h"
+#include "rsqp_matrix.h"
+#include "rsqp_sparse.h"
+
+// =====================================================================================
+// batch of independent QPs
+// =====================================================================================
+static_assert(RSQP_BATCH_MAX_V == RSQP_HBM_MAX_V && RSQP_BATCH_MAX_C == RSQP_HBM_MAX_C, "batch size limits of rsqp_hip.h and rsqp_internal.h");
+struct rsqp_batch {
+    int nq = 0, device = 0, nVmax = 0, nCmax = 0, uniV = -1, uniC = -1;
+    bool uni_pat = false; int uni_annz = 0, uni_hnnz = 0; long long uni_state = 0;     // (QPPools::uni_pat)
+    long long sumV = 0, sumC = 0, sumAnz = 0, sumHnz = 0, mat_bytes_max = 0;
+    bool haveH = false;
+    SmallKnobs kn = rsqp_small_knobs_from_env();
+    int state_engine = -1;                // kernel family that wrote the members' hot-start states (see rsqp_solver::state_engine)
+    int last_kernel = -1;                 // rsqp_batch_get_last_kernel
+    bool hbm = false;                     // images beyond the LDS of a CU: every member on the HBM-resident kernel (qp_small_hbm.hip)
+    bool h_sym = true;                    // every H symmetric value by value (the tableau kernel of qp_tiny.hip may take the batch)
+    std::vector<int> h_Hjc, h_Hir;        // host copy of the H patterns (re-examined when the values change), small batches only
+    std::vector<long long> h_Huoff;       //   (the caller's layout: member q's entries start at h_Huoff[q])
+    ValueFold Afold, Hfold;               // members given in a non-canonical layout (PooledCsc): the pools hold the canonical form
+    std::vector<QPDesc> desc;
+    std::vector<int> h_csr_perm;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
+    DevBuf<QPDesc> d_desc;
+    DevBuf<int> Ajc, Air, Arp, Aci, perm, Hjc, Hir;
+    DevBuf<double> Aval, Arv, Hval;
+    DevBuf<double> g, lb, ub, lbA, ubA, x, y, obj, state;
+    DevBuf<int> ws_b, ws_c, status, ret, nwsr, nflips;
+    DevBuf<double> Ax, ATy, Hx, kkt;
+    DevBuf<int> Wb, Wc, kV, kC;
+    DevBuf<double> recbuf;   // rsqp_batch_pack_records_host
+    DevBuf<long long> koV, koC;
+    // warm re-initialisation inputs (RSQP_MODE_WARM_REINIT), pooled like the vectors; allocated at first use. have_*: what
+    // rsqp_batch_set_warm_start gave (rsqp_batch_solve); rsqp_batch_optimize_qp fills the same pools on the device
+    DevBuf<double> wx0, wy0;
+    DevBuf<int> wgb;
+    bool have_x0 = false, have_y0 = false, have_gb = false;
+    // optimizeQP per member (rsqp_batch_optimize_qp): nq ints each, in one block -- firstQPsolved_, old / new matrix status, mode of
+    // the call's first solve, mode of its rescue solve (-1: none), kind of rescue, count of the first solve
+    // rsqp_batch_optimize_lp adds: mode the first solve is LAUNCHED with (a flip is a plain init there), mode of the proximal step
+    // (-1: the member is unsolved and takes none)
+    enum { OPT_FIRST = 0, OPT_OLD, OPT_NEW, OPT_MODE, OPT_RMODE, OPT_RESCUE, OPT_N1, OPT_LMODE, OPT_PMODE, OPT_WORDS };
+    DevBuf<int> opt;
+    // optimizeLP per member (rsqp_batch_optimize_lp): the members' descriptors with H absent and hreg = regVal of the member's last
+    // init (written on the device, kept across hot starts), and the pool of the proximal step's gradients g - regVal x
+    DevBuf<QPDesc> d_desc_lp;
+    DevBuf<double> g_lp;
+    int lp_maxiter = 100;                 // rsqp_batch_set_lp_options
+    int last_kind = 0;                    // 0 no optimize call yet, 1 the last one was rsqp_batch_optimize_qp, 2 rsqp_batch_optimize_lp
+    bool cert_lp = false;                 // the results in the pools are an LP call's: rsqp_batch_test_optimality certifies the LP
+    // nWSR_used of the members, written by the kernels straight into host-mapped memory: ready behind the call's one wait, no copy
+    // (and no second wait) behind it
+    int *used_host = nullptr, *used_dev = nullptr;
+    int qp_maxiter = 1000;                // rsqp_batch_set_options
+    bool mats_updated = false;            // rsqp_batch_set_matrix_values since the last rsqp_batch_optimize_qp (Update_A / Update_H)
+    bool opt_started = false;             // an rsqp_batch_optimize_qp has run: members are in different states from here on
+    float last_ms = 0.f;
+    bool keep_state = true;
+    bool timing = false;   // between timer_start and timer_stop: no per-launch events (they cost ~10 us of stream time each)
+    ~rsqp_batch() {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        if (ev2) (void)hipEventDestroy(ev2);
+        if (ev3) (void)hipEventDestroy(ev3);
+        if (stream) (void)hipStreamDestroy(stream);
+        if (used_host) (void)hipHostFree(used_host);
+    }
+};
+
+namespace {
+// lp: a launch of rsqp_batch_optimize_lp -- the LP descriptors (no H, per-member hreg), read by every kernel it runs on
+QPPools pools_of(rsqp_batch *b, bool lp) {
+    QPPools p;
+    std::memset(&p, 0, sizeof(p));
+    p.desc = lp ? b->d_desc_lp.p : b->d_desc.p;
+    p.Ajc = b->Ajc.p; p.Air = b->Air.p; p.Aval = b->Aval.p;
+    p.Arp = b->Arp.p; p.Aci = b->Aci.p; p.Arv = b->Arv.p;
+    p.Hjc = b->Hjc.p; p.Hir = b->Hir.p; p.Hval = b->Hval.p;
+    p.g = b->g.p; p.lb = b->lb.p; p.ub = b->ub.p; p.lbA = b->lbA.p; p.ubA = b->ubA.p;
+    p.x = b->x.p; p.y = b->y.p; p.ws_b = b->ws_b.p; p.ws_c = b->ws_c.p;
+    p.status = b->status.p; p.ret = b->ret.p; p.nwsr = b->nwsr.p; p.nflips = b->nflips.p;
+    p.obj = b->obj.p; p.state = b->state.p;
+    p.uniV = b->uniV; p.uniC = b->uniC;
+    p.keep_state = b->keep_state ? 1 : 0;
+    p.done_flag = nullptr; p.done_val = 0;
+    p.tiny_ok = (b->h_sym || !b->haveH || lp) ? 1 : 0;   // (as pools_of(rsqp_solver *): an unsymmetric H does not move the LPs)
+    // the batch-wide uni_hreg / uni_haveH cannot say what an LP member needs: LP launches read the descriptors
+    p.uni_pat = (b->uni_pat && !lp) ? 1 : 0;
+    p.uni_annz = b->uni_annz; p.uni_hnnz = lp ? 0 : b->uni_hnnz; p.uni_haveH = (b->haveH && !lp) ? 1 : 0; p.uni_state = b->uni_state;
+    return p;
+}
+// the knobs of a launch: LP launches stay off the register-resident tableau kernels, which answer RET_SETUP_FAILED on a pivot in
+// their rounding band and have no hand-over inside a batch (a single handle re-solves on the Givens kernel, rsqp_solve)
+SmallKnobs knobs_of(const rsqp_batch *b, bool lp) {
+    SmallKnobs k = b->kn;
+    if (lp) k.no_tiny = 2;   // (nor the mid-size tableau kernel, which would hand every LP member back: no H, hreg != 0)
+    return k;
+}
+}  // namespace
+
+extern "C" int rsqp_batch_create(int nq, const int *nV, const int *nC, const int *Ajc_in, const int *Air_in,
+                                 const double *Aval_in, const int *Hjc_in, const int *Hir_in, const double *Hval_in,
+                                 int device, rsqp_batch **out) {
+    if (!out || nq <= 0 || !nV || !nC || !Ajc_in) return fail(RSQP_ERR_ARG, "rsqp_batch_create");
+    if (rsqp_device_count() <= 0) return fail(RSQP_ERR_DEVICE, "rsqp_batch_create: no HIP device visible");
+    if (device >= 0) HIPCHK(hipSetDevice(device));
+    for (int q = 0; q < nq; q++)
+        if (nV[q] <= 0 || nC[q] < 0) return fail(RSQP_ERR_ARG, "rsqp_batch_create: bad sizes");
+    // from here on Ajc ... Hval are the canonical pools: the caller's arrays where they are canonical (PooledCsc)
+    PooledCsc PA, PH;
+    static const char *const why[] = {"", " column pointers must start at 0", " column pointers not monotone", " row index", " values missing"};
+    if (const int f = pool_csc(nq, nC, nV, Ajc_in, Air_in, Aval_in, PA)) return fail(RSQP_ERR_ARG, std::string("rsqp_batch_create: A") + why[f]);
+    if (Hjc_in)
+        if (const int f = pool_csc(nq, nV, nV, Hjc_in, Hir_in, Hval_in, PH)) return fail(RSQP_ERR_ARG, std::string("rsqp_batch_create: H") + why[f]);
+    const int *Ajc = PA.jc, *Air = PA.ir, *Hjc = Hjc_in ? PH.jc : nullptr, *Hir = Hjc_in ? PH.ir : nullptr;
+    const double *Aval = PA.val, *Hval = Hjc_in ? PH.val : nullptr;
+    rsqp_batch *b = new rsqp_batch();
+    struct Guard { rsqp_batch *b; ~Guard() { delete b; } } guard{b};
+    b->nq = nq;
+    HIPCHK(hipGetDevice(&b->device));
+    b->haveH = Hjc != nullptr;
+    b->desc.resize(nq);
+    std::vector<int> h_Arp, h_Aci, h_perm;
+    long long offV = 0, offC = 0, offAjc = 0, offAnz = 0, offArp = 0, offHjc = 0, offHnz = 0, offState = 0;
+    for (int q = 0; q < nq; q++) {
+        QPDesc &d = b->desc[q];
+        d.nV = nV[q]; d.nC = nC[q];
+        d.offV = (int)offV; d.offC = (int)offC; d.offAjc = (int)offAjc; d.offAnz = (int)offAnz;
+        d.offArp = (int)offArp; d.offHjc = (int)offHjc; d.offHnz = (int)offHnz; d.haveH = b->haveH;
+        d.offState = offState;
+        const int *jc = Ajc + offAjc;
+        const int annz = jc[d.nV];
+        d.annz = annz; d.hnnz = b->haveH ? Hjc[offHjc + d.nV] : 0;
+        CsrCopy r;
+        csr_from_csc(d.nC, d.nV, jc, Air + offAnz, r);
+        h_Arp.insert(h_Arp.end(), r.rp.begin(), r.rp.end());
+        h_Aci.insert(h_Aci.end(), r.ci.begin(), r.ci.end());
+        for (int v : r.perm) h_perm.push_back((int)offAnz + v);
+        b->nVmax = std::max(b->nVmax, d.nV); b->nCmax = std::max(b->nCmax, d.nC);
+        if (q == 0) { b->uniV = d.nV; b->uniC = d.nC; }
+        else { if (b->uniV != d.nV) b->uniV = -1; if (b->uniC != d.nC) b->uniC = -1; }
+        offV += d.nV; offC += d.nC; offAjc += d.nV + 1; offAnz += annz; offArp += d.nC + 1;
+        b->mat_bytes_max = std::max(b->mat_bytes_max, rsqp_mat_lds_bytes(d.nV, d.nC, annz, b->haveH ? Hjc[offHjc + d.nV] : 0));
+        if (b->haveH) {
+            const int hnnz = Hjc[offHjc + d.nV];
+            offHjc += d.nV + 1; offHnz += hnnz;
+        }
+        offState += rsqp_state_bytes(d.nV, d.nC) / 8;
+    }
+    if (!rsqp_small_qp_fits(b->nVmax, b->nCmax)) {
+        // the whole batch runs the HBM-resident kernel: its state slices are the images used in place (plus the dense
+        // matrices), with no extension for the KKT-tableau kernel
+        if (!rsqp_hbm_qp_fits(b->nVmax, b->nCmax))
+            return fail(RSQP_ERR_TOO_LARGE, "rsqp_batch_create: a problem exceeds the batch limit of " + std::to_string(RSQP_HBM_MAX_V) +
+                                                " variables and " + std::to_string(RSQP_HBM_MAX_C) + " constraints");
+        b->hbm = true;
+        offState = 0;
+        for (int q = 0; q < nq; q++) {
+            b->desc[q].offState = offState;
+            offState += rsqp_hbm_state_bytes(b->desc[q].nV, b->desc[q].nC) / 8;
+        }
+    }
+    if (b->haveH && b->nVmax <= 8) {
+        // (rsqp_batch_set_matrix_values gets the caller's layout: its pattern is kept)
+        b->h_Hjc.assign(Hjc_in, Hjc_in + offHjc); b->h_Hir.assign(Hir_in, Hir_in + PH.unnz); b->h_Huoff = PH.uoff;
+        for (int q = 0; q < nq && b->h_sym; q++) {
+            const QPDesc &d = b->desc[q];
+            b->h_sym = small_csc_symmetric(d.nV, Hjc + d.offHjc, Hir + d.offHnz, Hval + d.offHnz);
+        }
+    } else if (b->haveH) b->h_sym = false;
+    b->sumV = offV; b->sumC = offC; b->sumAnz = offAnz; b->sumHnz = offHnz;
+    // uniform batch: every member has the sizes and the patterns of member 0 (QPPools::uni_pat)
+    b->uni_pat = b->uniV > 0 && b->uniC >= 0;
+    if (b->uni_pat) {
+        const QPDesc &d0 = b->desc[0];
+        b->uni_annz = d0.annz; b->uni_hnnz = d0.hnnz;
+        b->uni_state = (b->hbm ? rsqp_hbm_state_bytes(d0.nV, d0.nC) : rsqp_state_bytes(d0.nV, d0.nC)) / 8;
+        for (int q = 1; q < nq && b->uni_pat; q++) {
+            const QPDesc &d = b->desc[q];
+            b->uni_pat = d.annz == d0.annz && d.hnnz == d0.hnnz &&
+                         std::memcmp(Ajc + d.offAjc, Ajc, sizeof(int) * (d0.nV + 1)) == 0 &&
+                         std::memcmp(Air + d.offAnz, Air, sizeof(int) * d0.annz) == 0 &&
+                         (!b->haveH || (std::memcmp(Hjc + d.offHjc, Hjc, sizeof(int) * (d0.nV + 1)) == 0 &&
+                                        std::memcmp(Hir + d.offHnz, Hir, sizeof(int) * d0.hnnz) == 0));
+        }
+    }
+    HIPCHK(hipStreamCreate(&b->stream));
+    HIPCHK(hipEventCreate(&b->ev0)); HIPCHK(hipEventCreate(&b->ev1));
+    HIPCHK(hipEventCreate(&b->ev2)); HIPCHK(hipEventCreate(&b->ev3));
+    HIPCHK(b->d_desc.from(b->desc));
+    HIPCHK(b->Ajc.alloc(offAjc)); HIPCHK(b->Ajc.upload(Ajc, offAjc));
+    HIPCHK(b->Air.alloc(offAnz)); HIPCHK(b->Air.upload(Air, offAnz));
+    HIPCHK(b->Aval.alloc(offAnz)); HIPCHK(b->Aval.upload(Aval, offAnz));
+    HIPCHK(b->Arp.alloc(offArp)); HIPCHK(b->Arp.upload(h_Arp.data(), h_Arp.size()));
+    HIPCHK(b->Aci.alloc(offAnz)); HIPCHK(b->Aci.upload(h_Aci.data(), h_Aci.size()));
+    HIPCHK(b->perm.alloc(offAnz)); HIPCHK(b->perm.upload(h_perm.data(), h_perm.size()));
+    HIPCHK(b->Arv.alloc(offAnz));
+    if (rsqp_launch_gather((int)offAnz, b->perm.p, b->Aval.p, b->Arv.p, b->stream) != hipSuccess)
+        return fail(RSQP_ERR_DEVICE, "gather launch failed");
+    HIPCHK(b->Hjc.alloc(b->haveH ? offHjc : 2)); HIPCHK(b->Hir.alloc(offHnz)); HIPCHK(b->Hval.alloc(offHnz));
+    if (b->haveH) {
+        HIPCHK(b->Hjc.upload(Hjc, offHjc)); HIPCHK(b->Hir.upload(Hir, offHnz)); HIPCHK(b->Hval.upload(Hval, offHnz));
+    }
+    // non-canonical layouts: the caller's values and the fold maps, for rsqp_batch_set_matrix_values
+    HIPCHK(PA.fold_into(b->Afold));
+    if (b->haveH) HIPCHK(PH.fold_into(b->Hfold));
+    HIPCHK(b->g.alloc(offV)); HIPCHK(b->lb.alloc(offV)); HIPCHK(b->ub.alloc(offV));
+    HIPCHK(b->lbA.alloc(offC)); HIPCHK(b->ubA.alloc(offC));
+    HIPCHK(b->x.alloc(offV)); HIPCHK(b->y.alloc(offV + offC)); HIPCHK(b->obj.alloc(nq));
+    HIPCHK(b->ws_b.alloc(offV)); HIPCHK(b->ws_c.alloc(offC));
+    HIPCHK(b->status.alloc(nq)); HIPCHK(b->ret.alloc(nq)); HIPCHK(b->nwsr.alloc(nq)); HIPCHK(b->nflips.alloc(nq));
+    if (b->hbm) {
+        const hipError_t e = b->state.alloc((size_t)offState);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(RSQP_ERR_TOO_LARGE, "rsqp_batch_create: the state block of the batch (" + std::to_string(8 * offState) +
+                                                " bytes) cannot be allocated: " + hipGetErrorString(e));
+        }
+    } else {
+        HIPCHK(b->state.alloc((size_t)offState));
+    }
+    HIPCHK(hipStreamSynchronize(b->stream));
+    guard.b = nullptr;
+    *out = b;
+    return RSQP_OK;
+}
+
+extern "C" void rsqp_batch_destroy(rsqp_batch *b) { delete b; }
+
+extern "C" int rsqp_batch_set_vectors(rsqp_batch *b, const double *g, const double *lb, const double *ub,
+                                      const double *lbA, const double *ubA) {
+    if (!b || !g || !lb || !ub || (b->sumC > 0 && (!lbA || !ubA))) return fail(RSQP_ERR_ARG, "rsqp_batch_set_vectors");
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(b->g.upload(g, b->sumV)); HIPCHK(b->lb.upload(lb, b->sumV)); HIPCHK(b->ub.upload(ub, b->sumV));
+    HIPCHK(b->lbA.upload(lbA, b->sumC)); HIPCHK(b->ubA.upload(ubA, b->sumC));
+    return RSQP_OK;
+}
+
+extern "C" int rsqp_batch_set_matrix_values(rsqp_batch *b, const double *Aval, const double *Hval) {
+    if (!b) return fail(RSQP_ERR_ARG, "null batch");
+    HIPCHK(hipSetDevice(b->device));
+    // (the caller's layout of rsqp_batch_create; a non-canonical one is folded into the canonical pools by one launch)
+    if (Aval) {
+        HIPCHK(b->Afold.refresh(Aval, b->Aval, (int)b->sumAnz, b->stream));
+        if (rsqp_launch_gather((int)b->sumAnz, b->perm.p, b->Aval.p, b->Arv.p, b->stream) != hipSuccess)
+            return fail(RSQP_ERR_DEVICE, "gather launch failed");
+    }
+    if (Hval && b->haveH) {
+        HIPCHK(b->Hfold.refresh(Hval, b->Hval, (int)b->sumHnz, b->stream));
+        if (!b->h_Hjc.empty()) {
+            b->h_sym = true;
+            for (int q = 0; q < b->nq && b->h_sym; q++) {
+                const QPDesc &d = b->desc[q];
+                b->h_sym = small_csc_symmetric(d.nV, b->h_Hjc.data() + d.offHjc, b->h_Hir.data() + b->h_Huoff[q], Hval + b->h_Huoff[q]);
+            }
+        }
+    }
+    HIPCHK(hipStreamSynchronize(b->stream));
+    // (qpOASESInterface.cpp:407-409, 427-429: counts for the members whose first QP is solved -- the plan kernel looks at that)
+    if (Aval || (Hval && b->haveH)) b->mats_updated = true;
+    return RSQP_OK;
+}
+
+namespace {
+int ensure_warm_pools(rsqp_batch *b) {
+    if (b->wx0.p) return RSQP_OK;
+    HIPCHK(b->wx0.alloc(b->sumV)); HIPCHK(b->wy0.alloc(b->sumV + b->sumC)); HIPCHK(b->wgb.alloc(b->sumV));
+    return RSQP_OK;
+}
+
+// kernel family a launch on this batch runs: 3 HBM-resident, 1 hs071-scale tableau (+ lane-per-problem), 0 LDS-resident
+int batch_family(const rsqp_batch *b, const QPPools &p, bool lp) {
+    return b->hbm ? 3 : rsqp_small_launch_is_tiny(knobs_of(b, lp), p, b->nVmax, b->nCmax);
+}
+
+// one solve launch of the whole batch (p.member_mode: of the members it names). first: the launch rsqp_batch_get_last_kernel reports;
+// lp: a launch of rsqp_batch_optimize_lp (pools_of, knobs_of)
+int launch_batch(rsqp_batch *b, QPPools &p, int mode, int max_nWSR, bool first, bool lp) {
+    const SmallKnobs kn = knobs_of(b, lp);
+    const int fam = batch_family(b, p, lp);
+    // the kernel families keep different layouts in the same state block: a hot start on another family's state starts cold
+    // (per-member modes: the plan kernel was told)
+    if ((mode == RSQP_MODE_HOT_VECTORS || mode == RSQP_MODE_HOT_MATRICES) && b->state_engine != fam) mode = RSQP_MODE_COLD;
+    b->state_engine = fam;
+    hipError_t e;
+    if (b->hbm) {
+        if (first) b->last_kernel = 3;
+        e = rsqp_launch_small_qp_hbm(kn, p, b->nq, b->nVmax, b->nCmax, mode, max_nWSR, b->stream);
+    } else {
+        // a cold-start-only batch on the tableau kernel keeps no state and leaves no mark: the handle remembers it instead
+        if (fam == 1 && !b->keep_state) { p.skip_mark = 1; b->state_engine = -1; }
+        if (first) b->last_kernel = fam == 1 ? (rsqp_lane_fits(kn, p, b->nq, b->nVmax, b->nCmax, mode) ? 2 : 1) : 0;
+        e = rsqp_launch_small_qp(kn, p, b->nq, b->nVmax, b->nCmax, b->mat_bytes_max, mode, max_nWSR, b->stream);
+    }
+    if (e != hipSuccess) return fail(RSQP_ERR_DEVICE, std::string("QP kernel launch: ") + hipGetErrorString(e));
+    return RSQP_OK;
+}
+}  // namespace
+
+extern "C" int rsqp_batch_set_warm_start(rsqp_batch *b, const double *x0, const double *y0, const int *guess_b) {
+    if (!b) return fail(RSQP_ERR_ARG, "null batch");
+    HIPCHK(hipSetDevice(b->device));
+    if (guess_b)
+        for (long long k = 0; k < b->sumV; k++)
+            if (guess_b[k] < -1 || guess_b[k] > 1) return fail(RSQP_ERR_ARG, "rsqp_batch_set_warm_start: guess_b entries are -1, 0 or +1");
+    int rc = ensure_warm_pools(b);
+    if (rc != RSQP_OK) return rc;
+    HIPCHK(hipStreamSynchronize(b->stream));
+    if (x0) HIPCHK(b->wx0.upload(x0, b->sumV));
+    if (y0) HIPCHK(b->wy0.upload(y0, b->sumV + b->sumC));
+    if (guess_b) HIPCHK(b->wgb.upload(guess_b, b->sumV));
+    b->have_x0 = x0 != nullptr; b->have_y0 = y0 != nullptr; b->have_gb = guess_b != nullptr;
+    return RSQP_OK;
+}
+
+extern "C" int rsqp_batch_set_options(rsqp_batch *b, int qp_maxiter) {
+    if (!b || qp_maxiter < 0) return fail(RSQP_ERR_ARG, "rsqp_batch_set_options");
+    b->qp_maxiter = qp_maxiter;
+    return RSQP_OK;
+}
+
+extern "C" int rsqp_batch_solve(rsqp_batch *b, int mode, int max_nWSR) {
+    if (!b || mode < 0 || mode > 3 || max_nWSR < 0) return fail(RSQP_ERR_ARG, "rsqp_batch_solve");
+    HIPCHK(hipSetDevice(b->device));
+    QPPools p = pools_of(b, false);
+    if (mode == RSQP_MODE_WARM_REINIT) {   // what rsqp_batch_set_warm_start gave; nothing given: init(.., nWSR, 0, 0, 0, 0)
+        if (b->have_x0) p.x0 = b->wx0.p;
+        if (b->have_y0) p.y0 = b->wy0.p;
+        if (b->have_gb) p.guess_b = b->wgb.p;
+    }
+    if (!b->timing) HIPCHK(hipEventRecord(b->ev0, b->stream));
+    const int rc = launch_batch(b, p, mode, max_nWSR, true, false);
+    if (rc != RSQP_OK) return rc;
+    b->cert_lp = false;
+    if (!b->timing) HIPCHK(hipEventRecord(b->ev1, b->stream));
+    return RSQP_OK;
+}
+
+// ---------------------------------------------------------------------------------
+// optimizeQP for every member of a batch (qpOASESInterface.cpp:137-224 + handle_error :718-757): what rsqp_optimize_qp does on one
+// handle, with the per-member decisions taken by one-thread-per-member kernels between the solve launches -- no host round trip
+// inside a call. plan -> solve -> rescue plan -> rescue solve (members that need none leave at once) -> count -> one wait.
+// ---------------------------------------------------------------------------------
+namespace {
+// before the first solve: the call shape of every member (rsqp_dispatch_mode); a FIXED <-> VARIED flip re-initialises from the
+// member's own previous x, y and bound working set (:201-208), copied into the warm-start pools
+__global__ void batch_plan_kernel(int nq, const QPDesc *__restrict__ desc, int *__restrict__ opt, int updated, int hot_ok,
+                                  const double *__restrict__ x, const double *__restrict__ y, const int *__restrict__ ws_b,
+                                  double *__restrict__ x0, double *__restrict__ y0, int *__restrict__ gb) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nq) return;
+    int old_status = opt[rsqp_batch::OPT_OLD * nq + q], new_status = opt[rsqp_batch::OPT_NEW * nq + q];
+    int mode = rsqp_dispatch_mode(opt[rsqp_batch::OPT_FIRST * nq + q] != 0, updated != 0, old_status, new_status);
+    // the stored states are another kernel family's (the host knows): a hot start runs cold, as on a single handle
+    if (!hot_ok && (mode == RSQP_MODE_HOT_VECTORS || mode == RSQP_MODE_HOT_MATRICES)) mode = RSQP_MODE_COLD;
+    opt[rsqp_batch::OPT_OLD * nq + q] = old_status; opt[rsqp_batch::OPT_NEW * nq + q] = new_status;
+    opt[rsqp_batch::OPT_MODE * nq + q] = mode;
+    if (mode == RSQP_MODE_WARM_REINIT) {
+        const QPDesc d = desc[q];
+        for (int v = 0; v < d.nV; v++) { x0[d.offV + v] = x[d.offV + v]; gb[d.offV + v] = ws_b[d.offV + v]; }
+        for (int i = 0; i < d.nV + d.nC; i++) y0[d.offV + d.offC + i] = y[d.offV + d.offC + i];
+    }
+}
+
+// behind the first solve: firstQPsolved_ (:156-158), handle_error's QP branch per member (:718-757) -- none / re-init from scratch /
+// re-init from the slack point x_0 (written to the x0 pool) --, old = new = UNDEFINED for the rescued, the count so far
+__global__ void batch_rescue_plan_kernel(int nq, const QPDesc *__restrict__ desc, int *__restrict__ opt, const int *__restrict__ status,
+                                         const int *__restrict__ nwsr, const double *__restrict__ lbA, const double *__restrict__ ubA,
+                                         double *__restrict__ x0, int *__restrict__ used) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nq) return;
+    const int sw = status[q], n1 = nwsr[q];
+    const bool solved = sw == QPS_SOLVED, infeasible = sw >= 100 && sw < 200;
+    opt[rsqp_batch::OPT_N1 * nq + q] = n1;
+    if (solved) {
+        opt[rsqp_batch::OPT_FIRST * nq + q] = 1;
+        opt[rsqp_batch::OPT_RMODE * nq + q] = -1; opt[rsqp_batch::OPT_RESCUE * nq + q] = 0; used[q] = n1;
+        return;
+    }
+    const QPDesc d = desc[q];
+    opt[rsqp_batch::OPT_OLD * nq + q] = 0; opt[rsqp_batch::OPT_NEW * nq + q] = 0;
+    if (infeasible && d.nV >= 2 * d.nC) {
+        for (int v = 0; v < d.nV; v++) x0[d.offV + v] = 0.0;
+        for (int i = 0; i < d.nC; i++) {
+            x0[d.offV + i + d.nV - 2 * d.nC] = fmax(0.0, lbA[d.offC + i]);
+            x0[d.offV + i + d.nV - d.nC] = -fmin(0.0, ubA[d.offC + i]);
+        }
+        opt[rsqp_batch::OPT_RMODE * nq + q] = RSQP_MODE_WARM_REINIT; opt[rsqp_batch::OPT_RESCUE * nq + q] = 2;
+    } else {
+        opt[rsqp_batch::OPT_RMODE * nq + q] = RSQP_MODE_COLD; opt[rsqp_batch::OPT_RESCUE * nq + q] = 1;
+    }
+}
+
+// behind the rescue solve: nWSR_used of the rescued members. A member whose FIRST init failed reports the rescue's count alone when
+// the rescue fails too (the reference throws inside handle_error, :754-756, before :211-212 add the first count)
+__global__ void batch_count_kernel(int nq, const int *__restrict__ opt, const int *__restrict__ status, const int *__restrict__ nwsr,
+                                   int *__restrict__ used) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nq || opt[rsqp_batch::OPT_RESCUE * nq + q] == 0) return;
+    const int n1 = opt[rsqp_batch::OPT_N1 * nq + q], n2 = nwsr[q];
+    const bool first_init_failed = opt[rsqp_batch::OPT_FIRST * nq + q] == 0;
+    used[q] = (first_init_failed && status[q] != QPS_SOLVED) ? n2 : n1 + n2;
+}
+
+// what both optimize entry points do before their first launch: the checks, the pools, the first event. kind: 1
+// rsqp_batch_optimize_qp, 2 rsqp_batch_optimize_lp. The first call of the other kind starts every member over -- firstQPsolved_
+// false, both status words UNDEFINED, hence a cold start that reads no stored factors -- as a single handle does (rsqp_optimize_qp /
+// rsqp_optimize_lp; the reference keeps separate LP and QP objects, Algorithm.cpp:561-562)
+int begin_optimize(rsqp_batch *b, int kind) {
+    if (!b) return fail(RSQP_ERR_ARG, "null batch");
+    if (!b->keep_state)
+        return fail(RSQP_ERR_ARG, std::string(kind == 1 ? "rsqp_batch_optimize_qp" : "rsqp_batch_optimize_lp") +
+                                      ": the batch keeps no state (rsqp_batch_set_keep_state(b, 0))");
+    HIPCHK(hipSetDevice(b->device));
+    const int nq = b->nq;
+    if (!b->opt.p) HIPCHK(b->opt.alloc((size_t)rsqp_batch::OPT_WORDS * nq));
+    if (!b->used_host) {
+        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&b->used_host), sizeof(int) * nq, hipHostMallocMapped));
+        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&b->used_dev), b->used_host, 0));
+    }
+    const int rc = ensure_warm_pools(b);
+    if (rc != RSQP_OK) return rc;
+    b->have_x0 = b->have_y0 = b->have_gb = false;   // the pools are this call's from here on
+    if (kind == 2 && !b->d_desc_lp.p) {
+        std::vector<QPDesc> lp = b->desc;
+        for (QPDesc &d : lp) { d.haveH = 0; d.hnnz = 0; d.hreg = 0.0; }
+        HIPCHK(b->d_desc_lp.from(lp));
+        HIPCHK(b->g_lp.alloc(b->sumV));
+    }
+    if (b->last_kind != 0 && b->last_kind != kind) {
+        HIPCHK(hipMemsetAsync(b->opt.p, 0, sizeof(int) * (size_t)rsqp_batch::OPT_WORDS * nq, b->stream));
+        b->opt_started = false;
+    }
+    b->last_kind = kind;
+    if (!b->timing) HIPCHK(hipEventRecord(b->ev0, b->stream));
+    return RSQP_OK;
+}
+
+// the solve launch behind a plan kernel: every member starts as word `word` of its opt block says (QPPools::member_mode)
+int launch_members(rsqp_batch *b, QPPools &p, int word, int mode, int max_nWSR, bool first, bool lp) {
+    p.member_mode = b->opt.p + (size_t)word * b->nq;
+    return launch_batch(b, p, mode, max_nWSR, first, lp);
+}
+
+// what both optimize entry points do behind their last launch: the second event, the call's one wait, the members' counts
+int finish_optimize(rsqp_batch *b, int *nWSR_used) {
+    if (!b->timing) HIPCHK(hipEventRecord(b->ev1, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    if (nWSR_used) std::memcpy(nWSR_used, b->used_host, sizeof(int) * b->nq);
+    return RSQP_OK;
+}
+
+// ---------------------------------------------------------------------------------
+// optimizeLP for every member of a batch (qpOASESInterface.cpp:227-284 + handle_error's LP branch :688-717): what rsqp_optimize_lp
+// does on one handle. plan -> solve -> rescue plan -> rescue solve -> proximal plan -> proximal step -> finish -> one wait. The plan
+// kernels run one wavefront per member: the gradient norm, g - regVal x and g'x are reductions over up to RSQP_BATCH_MAX_V entries.
+// ---------------------------------------------------------------------------------
+__device__ inline double lp_wave_sum(double v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+// regVal of an init: (|g|_2 > 0 ? |g|_2 : 1) * 1e3 * EPS (the same value in every lane)
+__device__ inline double lp_reg_val(const QPDesc &d, const double *__restrict__ g) {
+    double s = 0.0;
+    for (int v = (int)threadIdx.x; v < d.nV; v += 64) s += g[d.offV + v] * g[d.offV + v];
+    const double ng = sqrt(lp_wave_sum(s));
+    return (ng > 0.0 ? ng : 1.0) * 1.0e3 * RSQP_EPS;
+}
+
+// before the first solve: the call shape of every member (rsqp_dispatch_mode). A FIXED <-> VARIED flip is a plain init here
+// (:266-270): OPT_MODE keeps what the dispatch said (3), OPT_LMODE what is launched (0). Every init fixes the member's regVal from
+// the gradient of this call; a hot start keeps the one its factors were built with
+__global__ void __launch_bounds__(64)
+batch_lp_plan_kernel(int nq, QPDesc *__restrict__ desc, int *__restrict__ opt, int updated, int hot_ok, const double *__restrict__ g) {
+    const int q = (int)blockIdx.x;
+    if (q >= nq) return;
+    const QPDesc d = desc[q];
+    int old_status = opt[rsqp_batch::OPT_OLD * nq + q], new_status = opt[rsqp_batch::OPT_NEW * nq + q];
+    int mode = rsqp_dispatch_mode(opt[rsqp_batch::OPT_FIRST * nq + q] != 0, updated != 0, old_status, new_status);
+    const bool init = mode == RSQP_MODE_COLD || mode == RSQP_MODE_WARM_REINIT;
+    const double reg = init ? lp_reg_val(d, g) : d.hreg;
+    // (stored states of another kernel family: the hot start runs cold on the regVal it has, as rsqp_solve does on a handle)
+    if (!hot_ok && !init) mode = RSQP_MODE_COLD;
+    __syncthreads();   // every lane has read the member's words
+    if (threadIdx.x == 0) {
+        opt[rsqp_batch::OPT_OLD * nq + q] = old_status; opt[rsqp_batch::OPT_NEW * nq + q] = new_status;
+        opt[rsqp_batch::OPT_MODE * nq + q] = mode;
+        opt[rsqp_batch::OPT_LMODE * nq + q] = init ? RSQP_MODE_COLD : mode;
+        desc[q].hreg = reg;
+    }
+}
+
+// behind the first solve: firstQPsolved_ (:248-250), handle_error's LP branch per member (:688-717) -- none / re-init from scratch /
+// re-init from x_0 := the x of the failed solve with its slack entries overwritten (:693-699; written to the x0 pool) --, a fresh
+// regVal for the re-init, old = new = UNDEFINED for the rescued
+__global__ void __launch_bounds__(64)
+batch_lp_rescue_plan_kernel(int nq, QPDesc *__restrict__ desc, int *__restrict__ opt, const int *__restrict__ status,
+                            const int *__restrict__ nwsr, const double *__restrict__ g, const double *__restrict__ x,
+                            const double *__restrict__ lbA, const double *__restrict__ ubA, double *__restrict__ x0) {
+    const int q = (int)blockIdx.x, lane = (int)threadIdx.x;
+    if (q >= nq) return;
+    const int sw = status[q];
+    const bool solved = sw == QPS_SOLVED, infeasible = sw >= 100 && sw < 200;
+    if (solved) {
+        if (lane == 0) {
+            opt[rsqp_batch::OPT_N1 * nq + q] = nwsr[q];
+            opt[rsqp_batch::OPT_FIRST * nq + q] = 1;
+            opt[rsqp_batch::OPT_RMODE * nq + q] = -1; opt[rsqp_batch::OPT_RESCUE * nq + q] = 0;
+        }
+        return;
+    }
+    const QPDesc d = desc[q];
+    const double reg = lp_reg_val(d, g);
+    const bool slack = infeasible && d.nV >= 2 * d.nC;
+    if (slack) {
+        for (int v = lane; v < d.nV; v += 64) x0[d.offV + v] = x[d.offV + v];
+        __syncthreads();
+        for (int i = lane; i < d.nC; i += 64) {
+            x0[d.offV + i + d.nV - 2 * d.nC] = fmax(0.0, lbA[d.offC + i]);
+            x0[d.offV + i + d.nV - d.nC] = -fmin(0.0, ubA[d.offC + i]);
+        }
+    }
+    if (lane == 0) {
+        opt[rsqp_batch::OPT_N1 * nq + q] = nwsr[q];
+        opt[rsqp_batch::OPT_OLD * nq + q] = 0; opt[rsqp_batch::OPT_NEW * nq + q] = 0;
+        opt[rsqp_batch::OPT_RMODE * nq + q] = slack ? RSQP_MODE_WARM_REINIT : RSQP_MODE_COLD;
+        opt[rsqp_batch::OPT_RESCUE * nq + q] = slack ? 2 : 1;
+        desc[q].hreg = reg;
+    }
+}
+
+// behind the rescue solve: the count so far (a member whose rescue failed too reports the rescue's count alone, on both branches:
+// the reference throws inside handle_error, :714-716, before :278-279 add the other), and the proximal step of every member that is
+// solved now (:280-283): a hot start on the gradient g - regVal x, written to the scratch pool -- the batch's g keeps the caller's
+__global__ void __launch_bounds__(64)
+batch_lp_prox_plan_kernel(int nq, const QPDesc *__restrict__ desc, int *__restrict__ opt, const int *__restrict__ status,
+                          const int *__restrict__ nwsr, const double *__restrict__ g, const double *__restrict__ x,
+                          double *__restrict__ g_lp) {
+    const int q = (int)blockIdx.x, lane = (int)threadIdx.x;
+    if (q >= nq) return;
+    const bool solved = status[q] == QPS_SOLVED, rescued = opt[rsqp_batch::OPT_RESCUE * nq + q] != 0;
+    const int n1 = opt[rsqp_batch::OPT_N1 * nq + q], n2 = nwsr[q];
+    __syncthreads();
+    if (lane == 0) {
+        opt[rsqp_batch::OPT_N1 * nq + q] = rescued ? (solved ? n1 + n2 : n2) : n1;
+        opt[rsqp_batch::OPT_PMODE * nq + q] = solved ? RSQP_MODE_HOT_VECTORS : -1;
+    }
+    if (!solved) return;
+    const QPDesc d = desc[q];
+    for (int v = lane; v < d.nV; v += 64) g_lp[d.offV + v] = g[d.offV + v] - d.hreg * x[d.offV + v];
+}
+
+// behind the proximal step: nWSR_used, and the objective g'x with the caller's gradient (:283) for the members that took the step
+__global__ void __launch_bounds__(64)
+batch_lp_finish_kernel(int nq, const QPDesc *__restrict__ desc, const int *__restrict__ opt, const int *__restrict__ nwsr,
+                       const double *__restrict__ g, const double *__restrict__ x, double *__restrict__ obj, int *__restrict__ used) {
+    const int q = (int)blockIdx.x, lane = (int)threadIdx.x;
+    if (q >= nq) return;
+    const int total = opt[rsqp_batch::OPT_N1 * nq + q];
+    if (opt[rsqp_batch::OPT_PMODE * nq + q] < 0) { if (lane == 0) used[q] = total; return; }
+    const QPDesc d = desc[q];
+    double s = 0.0;
+    for (int v = lane; v < d.nV; v += 64) s += g[d.offV + v] * x[d.offV + v];
+    s = lp_wave_sum(s);
+    if (lane == 0) { obj[q] = s; used[q] = total + nwsr[q]; }
+}
+}  // namespace
+
+extern "C" int rsqp_batch_optimize_qp(rsqp_batch *b, int *nWSR_used) {
+    int rc = begin_optimize(b, 1);
+    if (rc != RSQP_OK) return rc;
+    const int nq = b->nq;
+    const dim3 grid((unsigned)((nq + 255) / 256)), block(256);
+    QPPools p = pools_of(b, false);
+    if (!b->opt_started) {
+        // no member has a solved first QP: init for everybody -- the uniform cold launch (lane-per-problem and mid-size tableau
+        // kernels included), no per-member modes, no warm-start pointers; the members' mode words are 0 = cold already
+        rc = launch_batch(b, p, RSQP_MODE_COLD, b->qp_maxiter, true, false);
+    } else {
+        hipLaunchKernelGGL(batch_plan_kernel, grid, block, 0, b->stream, nq, b->d_desc.p, b->opt.p, b->mats_updated ? 1 : 0,
+                           b->state_engine == batch_family(b, p, false) ? 1 : 0, b->x.p, b->y.p, b->ws_b.p, b->wx0.p, b->wy0.p, b->wgb.p);
+        HIPCHK(hipGetLastError());
+        p.x0 = b->wx0.p; p.y0 = b->wy0.p; p.guess_b = b->wgb.p;     // the flip: all three (:204-206)
+        rc = launch_members(b, p, rsqp_batch::OPT_MODE, RSQP_MODE_COLD, b->qp_maxiter, true, false);
+    }
+    if (rc != RSQP_OK) return rc;
+    b->opt_started = true;
+    b->cert_lp = false;
+    b->mats_updated = false;   // reset_flags (:488-496)
+    hipLaunchKernelGGL(batch_rescue_plan_kernel, grid, block, 0, b->stream, nq, b->d_desc.p, b->opt.p, b->status.p, b->nwsr.p,
+                       b->lbA.p, b->ubA.p, b->wx0.p, b->used_dev);
+    HIPCHK(hipGetLastError());
+    // the rescue launch is unconditional: a member that needs none leaves at its first instruction, and asking the device whether
+    // anybody needs one would put a host round trip into every call
+    p = pools_of(b, false);
+    p.x0 = b->wx0.p;                                                 // handle_error: x_0 alone (:741-743)
+    rc = launch_members(b, p, rsqp_batch::OPT_RMODE, RSQP_MODE_COLD, b->qp_maxiter, false, false);
+    if (rc != RSQP_OK) return rc;
+    hipLaunchKernelGGL(batch_count_kernel, grid, block, 0, b->stream, nq, b->opt.p, b->status.p, b->nwsr.p, b->used_dev);
+    HIPCHK(hipGetLastError());
+    return finish_optimize(b, nWSR_used);
+}
+
+extern "C" int rsqp_batch_set_lp_options(rsqp_batch *b, int lp_maxiter) {
+    if (!b || lp_maxiter < 0) return fail(RSQP_ERR_ARG, "rsqp_batch_set_lp_options");
+    b->lp_maxiter = lp_maxiter;
+    return RSQP_OK;
+}
+
+extern "C" int rsqp_batch_optimize_lp(rsqp_batch *b, int *nWSR_used) {
+    int rc = begin_optimize(b, 2);
+    if (rc != RSQP_OK) return rc;
+    const int nq = b->nq;
+    const dim3 grid((unsigned)nq), block(64);
+    int *const opt = b->opt.p;
+    // every launch carries per-member modes and reads the LP descriptors: H absent, hreg = the member's regVal
+    QPPools p = pools_of(b, true);
+    hipLaunchKernelGGL(batch_lp_plan_kernel, grid, block, 0, b->stream, nq, b->d_desc_lp.p, opt, b->mats_updated ? 1 : 0,
+                       b->state_engine == batch_family(b, p, true) ? 1 : 0, b->g.p);
+    HIPCHK(hipGetLastError());
+    if ((rc = launch_members(b, p, rsqp_batch::OPT_LMODE, RSQP_MODE_COLD, b->lp_maxiter, true, true)) != RSQP_OK) return rc;
+    b->opt_started = true;
+    b->cert_lp = true;
+    b->mats_updated = false;   // reset_flags (:488-496)
+    hipLaunchKernelGGL(batch_lp_rescue_plan_kernel, grid, block, 0, b->stream, nq, b->d_desc_lp.p, opt, b->status.p, b->nwsr.p, b->g.p,
+                       b->x.p, b->lbA.p, b->ubA.p, b->wx0.p);
+    HIPCHK(hipGetLastError());
+    // (unconditional, as in rsqp_batch_optimize_qp: a member that needs no rescue leaves at its first instruction)
+    p.x0 = b->wx0.p;                                                 // handle_error: x_0 alone (:700-702)
+    if ((rc = launch_members(b, p, rsqp_batch::OPT_RMODE, RSQP_MODE_COLD, b->lp_maxiter, false, true)) != RSQP_OK) return rc;
+    hipLaunchKernelGGL(batch_lp_prox_plan_kernel, grid, block, 0, b->stream, nq, b->d_desc_lp.p, opt, b->status.p, b->nwsr.p, b->g.p,
+                       b->x.p, b->g_lp.p);
+    HIPCHK(hipGetLastError());
+    p.x0 = nullptr;
+    p.g = b->g_lp.p;
+    if ((rc = launch_members(b, p, rsqp_batch::OPT_PMODE, RSQP_MODE_HOT_VECTORS, b->lp_maxiter, false, true)) != RSQP_OK) return rc;
+    hipLaunchKernelGGL(batch_lp_finish_kernel, grid, block, 0, b->stream, nq, b->d_desc_lp.p, opt, b->nwsr.p, b->g.p, b->x.p, b->obj.p,
+                       b->used_dev);
+    HIPCHK(hipGetLastError());
+    return finish_optimize(b, nWSR_used);
+}
+
+extern "C" int rsqp_batch_get_dispatch(const rsqp_batch *b, int *mode, int *rescue) {
+    if (!b) return fail(RSQP_ERR_ARG, "null batch");
+    if (!b->opt.p) return fail(RSQP_ERR_ARG, "rsqp_batch_get_dispatch: no rsqp_batch_optimize_qp / rsqp_batch_optimize_lp has run");
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    const size_t nq = b->nq;
+    if (mode) HIPCHK(hipMemcpy(mode, b->opt.p + rsqp_batch::OPT_MODE * nq, sizeof(int) * nq, hipMemcpyDeviceToHost));
+    if (rescue) HIPCHK(hipMemcpy(rescue, b->opt.p + rsqp_batch::OPT_RESCUE * nq, sizeof(int) * nq, hipMemcpyDeviceToHost));
+    return RSQP_OK;
+}
+
+extern "C" int rsqp_batch_get_last_kernel(const rsqp_batch *b) { return b ? b->last_kernel : -1; }
+
+extern "C" int rsqp_batch_set_keep_state(rsqp_batch *b, int keep) {
+    if (!b) return fail(RSQP_ERR_ARG, "null batch");
+    b->keep_state = keep != 0;
+    return RSQP_OK;
+}
+
+extern "C" int rsqp_batch_sync(rsqp_batch *b) {
+    if (!b) return fail(RSQP_ERR_ARG, "null batch");
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return RSQP_OK;
+}
+
+extern "C" float rsqp_batch_last_solve_ms(rsqp_batch *b) {
+    if (!b) return -1.f;
+    if (hipEventSynchronize(b->ev1) != hipSuccess) return -1.f;
+    float ms = -1.f;
+    if (hipEventElapsedTime(&ms, b->ev0, b->ev1) != hipSuccess) return -1.f;
+    b->last_ms = ms;
+    return ms;
+}
+
+extern "C" int rsqp_batch_timer_start(rsqp_batch *b) {
+    if (!b) return fail(RSQP_ERR_ARG, "null batch");
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipEventRecord(b->ev2, b->stream));
+    b->timing = true;
+    return RSQP_OK;
+}
+extern "C" float rsqp_batch_timer_stop_ms(rsqp_batch *b) {
+    if (!b) return -1.f;
+    float ms = -1.f;
+    b->timing = false;
+    if (hipEventRecord(b->ev3, b->stream) != hipSuccess) return -1.f;
+    if (hipEventSynchronize(b->ev3) != hipSuccess) return -1.f;
+    if (hipEventElapsedTime(&ms, b->ev2, b->ev3) != hipSuccess) return -1.f;
+    return ms;
+}
+
+extern "C" int rsqp_batch_get_results(rsqp_batch *b, double *x, double *y, int *ws_b, int *ws_c, int *status,
+                                      int *nWSR, double *obj) {
+    if (!b) return fail(RSQP_ERR_ARG, "null batch");
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    if (x) HIPCHK(b->x.download(x, b->sumV));
+    if (y) HIPCHK(b->y.download(y, b->sumV + b->sumC));
+    if (ws_b) HIPCHK(b->ws_b.download(ws_b, b->sumV));
+    if (ws_c) HIPCHK(b->ws_c.download(ws_c, b->sumC));
+    if (status) {
+        std::vector<int> sw(b->nq), rt(b->nq);
+        HIPCHK(b->status.download(sw.data(), b->nq)); HIPCHK(b->ret.download(rt.data(), b->nq));
+        for (int q = 0; q < b->nq; q++) status[q] = exitflag_of(sw[q], rt[q]);
+    }
+    if (nWSR) HIPCHK(b->nwsr.download(nWSR, b->nq));
+    if (obj) HIPCHK(b->obj.download(obj, b->nq));
+    return RSQP_OK;
+}
+
+extern "C" int rsqp_batch_test_optimality(rsqp_batch *b, rsqp_optimality_status *out, int *ok) {
+    if (!b) return fail(RSQP_ERR_ARG, "null batch");
+    HIPCHK(hipSetDevice(b->device));
+    if (!b->Ax.p) {
+        HIPCHK(b->Ax.alloc(b->sumC)); HIPCHK(b->ATy.alloc(b->sumV)); HIPCHK(b->Hx.alloc(b->sumV));
+        HIPCHK(b->kkt.alloc(6 * (size_t)b->nq)); HIPCHK(b->Wb.alloc(b->sumV)); HIPCHK(b->Wc.alloc(b->sumC));
+        std::vector<int> kv(b->nq), kc(b->nq);
+        std::vector<long long> ov(b->nq), oc(b->nq);
+        for (int q = 0; q < b->nq; q++) {
+            kv[q] = b->desc[q].nV; kc[q] = b->desc[q].nC; ov[q] = b->desc[q].offV; oc[q] = b->desc[q].offC;
+        }
+        HIPCHK(b->kV.from(kv)); HIPCHK(b->kC.from(kc)); HIPCHK(b->koV.from(ov)); HIPCHK(b->koC.from(oc));
+    }
+    QPPools p = pools_of(b, b->cert_lp);   // behind an LP call: H absent (and no regVal term: the certificate reads no hreg)
+    RsqpKktArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.nV = b->kV.p; a.nC = b->kC.p; a.offV = b->koV.p; a.offC = b->koC.p;
+    a.x = b->x.p; a.y = b->y.p; a.g = b->g.p; a.lb = b->lb.p; a.ub = b->ub.p; a.lbA = b->lbA.p; a.ubA = b->ubA.p;
+    a.Ax = b->Ax.p; a.ATy = b->ATy.p; a.Hx = b->Hx.p; a.ws_b = b->ws_b.p; a.ws_c = b->ws_c.p;
+    a.W_b = b->Wb.p; a.W_c = b->Wc.p; a.out = b->kkt.p;
+    if (rsqp_launch_small_certificate(p, a, b->nq, b->Ax.p, b->ATy.p, b->Hx.p, b->stream) != hipSuccess)
+        return fail(RSQP_ERR_DEVICE, "certificate launch failed");
+    HIPCHK(hipStreamSynchronize(b->stream));
+    std::vector<double> o(6 * (size_t)b->nq);
+    HIPCHK(b->kkt.download(o.data(), o.size()));
+    for (int q = 0; q < b->nq; q++) {
+        if (out) {
+            out[q].primal_violation = o[6 * q]; out[q].dual_violation = o[6 * q + 1];
+            out[q].compl_violation = o[6 * q + 2]; out[q].stationarity_violation = o[6 * q + 3];
+            out[q].KKT_error = o[6 * q + 4];
+        }
+        if (ok) ok[q] = o[6 * q + 5] != 0.0 ? RSQP_ERR_WORKING_SET : (o[6 * q + 4] > 1.0e-6 ? 0 : 1);
+    }
+    return RSQP_OK;
+}
+
+// ---------------------------------------------------------------------------------
+// fixed-stride result records on the device: what a rank contributes to the gather of a sharded batch
+// (SURVEY 8(e)). Layout = restartsqp_amd/parallel.py pack_records:
+//   {exitflag, nWSR, objective, KKT_error, x[nVmax], y_bounds[nVmax], y_constr[nCmax], ws_b[nVmax], ws_c[nCmax]}
+// One thread per record entry; unused tail entries of a smaller problem are zero.
+// ---------------------------------------------------------------------------------
+namespace {
+__global__ void pack_records_kernel(int nq, int nVmax, int nCmax, const QPDesc *__restrict__ desc,
+                                    const double *__restrict__ x, const double *__restrict__ y,
+                                    const int *__restrict__ ws_b, const int *__restrict__ ws_c,
+                                    const int *__restrict__ status, const int *__restrict__ nwsr,
+                                    const double *__restrict__ obj, const double *__restrict__ kkt,
+                                    double *__restrict__ rec) {
+    const int stride = 4 + 3 * nVmax + 2 * nCmax;
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long long)nq * stride) return;
+    const int q = (int)(t / stride), e = (int)(t % stride);
+    const QPDesc d = desc[q];
+    double v = 0.0;
+    if (e < 4) {
+        if (e == 0) {   // exitflag_of() of rsqp_host.h: qpOASESInterface::get_status (src/qpOASESInterface.cpp:332-357)
+            const int sw = status[q];
+            v = sw >= 200 ? RSQP_QPERROR_UNBOUNDED : (sw >= 100 ? RSQP_QPERROR_INFEASIBLE : (sw == QPS_SOLVED ? RSQP_QP_OPTIMAL : RSQP_QPERROR_NOTINITIALISED + sw));
+        } else if (e == 1) v = nwsr[q];
+        else if (e == 2) v = obj[q];
+        else v = kkt ? kkt[6 * q + 4] : 0.0;
+    } else {
+        int o = e - 4;
+        if (o < nVmax) { if (o < d.nV) v = x[d.offV + o]; }
+        else if ((o -= nVmax) < nVmax) { if (o < d.nV) v = y[d.offV + d.offC + o]; }
+        else if ((o -= nVmax) < nCmax) { if (o < d.nC) v = y[d.offV + d.offC + d.nV + o]; }
+        else if ((o -= nCmax) < nVmax) { if (o < d.nV) v = ws_b[d.offV + o]; }
+        else { o -= nVmax; if (o < d.nC) v = ws_c[d.offC + o]; }
+    }
+    rec[t] = v;
+}
+}  // namespace
+
+extern "C" int rsqp_batch_record_stride(const rsqp_batch *b) {
+    return b ? 4 + 3 * b->nVmax + 2 * b->nCmax : -1;
+}
+
+extern "C" int rsqp_batch_pack_records_dev(rsqp_batch *b, double *rec_dev) {
+    if (!b || !rec_dev) return fail(RSQP_ERR_ARG, "rsqp_batch_pack_records_dev");
+    HIPCHK(hipSetDevice(b->device));
+    const long long tot = (long long)b->nq * rsqp_batch_record_stride(b);
+    hipLaunchKernelGGL(pack_records_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, b->stream, b->nq, b->nVmax,
+                       b->nCmax, b->d_desc.p, b->x.p, b->y.p, b->ws_b.p, b->ws_c.p, b->status.p, b->nwsr.p, b->obj.p,
+                       b->kkt.p /* null until the certificate has run */, rec_dev);
+    HIPCHK(hipGetLastError());
+    return RSQP_OK;
+}
+
+extern "C" int rsqp_batch_pack_records_host(rsqp_batch *b, double *rec_host) {
+    if (!b || !rec_host) return fail(RSQP_ERR_ARG, "rsqp_batch_pack_records_host");
+    HIPCHK(hipSetDevice(b->device));
+    const size_t tot = (size_t)b->nq * rsqp_batch_record_stride(b);
+    if (b->recbuf.n < tot) HIPCHK(b->recbuf.alloc(tot, false));
+    int rc = rsqp_batch_pack_records_dev(b, b->recbuf.p);
+    if (rc != RSQP_OK) return rc;
+    HIPCHK(hipStreamSynchronize(b->stream));
+    HIPCHK(b->recbuf.download(rec_host, tot));
+    return RSQP_OK;
+}
+
+// (rsqp_host.h: the native RCCL call sites of rsqp_rccl.cpp reach the batch through these)
+hipStream_t rsqp_batch_stream_internal(rsqp_batch *b) { return b->stream; }
+int rsqp_batch_device_internal(const rsqp_batch *b) { return b->device; }
+int rsqp_batch_nq_internal(const rsqp_batch *b) { return b ? b->nq : 0; }

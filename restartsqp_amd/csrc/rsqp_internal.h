@@ -41,7 +41,7 @@ struct SmallKnobs {
     int k_debug_bail = -1;    // RSQP_K_DEBUG_BAIL      test hook: the mid-size tableau kernel bails out of a hot start before its n-th change
     int lanes = -1;           // RSQP_SMALL_LANES       lanes per problem (8 / 16 / 32 / 64)
     int waves = -1;           // RSQP_SMALL_WAVES       waves per SIMD the build is compiled for
-    int no_tiny = 0;          // (set by the single-QP rescue, rsqp_api.hip) 1: no hs071-scale tableau kernel; 2 (the LP launches of a batch): nor the mid-size one
+    int no_tiny = 0;          // (set by the single-QP rescue, rsqp_api.hip, and by knobs_of, rsqp_batch.hip) 1: no hs071-scale tableau kernel; 2 (the LP launches of a batch): nor the mid-size one
     int lane = -1;            // RSQP_LANE              0: never the lane-per-problem kernel (qp_lane.hip); n > 0: from n members on (default 16 385)
     int arena_mapped = -1;    // RSQP_ARENA_MAPPED      single-QP handles: patterns / plans in host-mapped memory, no upload at set_A / set_H (-1: hs071 scale only)
     int no_spin = 0;          // RSQP_NO_SPIN           single-QP waits block in hipStreamSynchronize instead of spinning on a mapped word
@@ -132,7 +132,7 @@ __host__ __device__ inline long long rsqp_state_bytes(int nV, int nC) {
 // batches whose images exceed the LDS of a CU (qp_small_hbm.hip): limits of the members' sizes, and the state slice of one
 // member -- the image used in place, 8 x 256 bytes of cross-wave partial sums, dense copies of A and H. No KKT-tableau
 // extension: the mid-size tableau kernel never sees these batches.
-#define RSQP_HBM_MAX_V 512   // = RSQP_BATCH_MAX_V / _C of rsqp_hip.h (checked in rsqp_api.hip)
+#define RSQP_HBM_MAX_V 512   // = RSQP_BATCH_MAX_V / _C of rsqp_hip.h (checked in rsqp_batch.hip)
 #define RSQP_HBM_MAX_C 512
 __host__ __device__ inline long long rsqp_hbm_state_bytes(int nV, int nC) {
     return rsqp_image_bytes(nV, nC) + 8LL * 256 + 8LL * ((long long)nV * nV + (long long)nC * nV);

@@ -3,23 +3,15 @@
 // The one decision of this module: the device holds the CANONICAL CSC of a matrix (rows strictly ascending within each column, one
 // entry per position), a CSR copy of it where products by rows are wanted, and -- where the caller's layout is not canonical -- the
 // caller's values with a fold map from each canonical slot to the caller's slots. SpHbMat::setStructure is DevMatrix::set_structure,
-// SpHbMat::setMatVal is DevMatrix::refresh. The C ABI (rsqp_api.hip) reads the device arrays; it does not know how they are filled.
+// SpHbMat::setMatVal is DevMatrix::refresh. The C ABI (rsqp_api.hip, rsqp_batch.hip) reads the device arrays; it does not know how they are filled.
 #pragma once
 #include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
 
-#include "../../include/rsqp_hip.h"
+#include "rsqp_host.h"
 #include "rsqp_sparse.h"
-
-int rsqp_fail_msg(int code, const char *msg);   // rsqp_api.hip: sets rsqp_last_error()
-#define HIPCHK(call)                                                                                              \
-    do {                                                                                                          \
-        hipError_t e_ = (call);                                                                                   \
-        if (e_ != hipSuccess)                                                                                     \
-            return rsqp_fail_msg(RSQP_ERR_DEVICE, (std::string(#call) + ": " + hipGetErrorString(e_)).c_str());   \
-    } while (0)
 
 template <class T>
 struct DevBuf {

@@ -35,12 +35,7 @@ const char *ncclGetErrorString(ncclResult_t);
 #include <mutex>
 #include <string>
 
-#include "../../include/rsqp_hip.h"
-
-int rsqp_fail_msg(int code, const char *msg);                  // rsqp_api.hip: sets rsqp_last_error()
-hipStream_t rsqp_batch_stream_internal(rsqp_batch *b);         // rsqp_api.hip
-int rsqp_batch_device_internal(const rsqp_batch *b);
-int rsqp_batch_nq_internal(const rsqp_batch *b);
+#include "rsqp_host.h"
 
 namespace {
 struct Rccl {

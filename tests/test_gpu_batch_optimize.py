@@ -1,4 +1,4 @@
-"""optimizeQP per member of a batch (rsqp_batch_optimize_qp): the warm-start dispatch of reference
+"""optimizeQP per member of a batch (rsqp_batch_optimize_qp, restartsqp_amd/csrc/rsqp_batch.hip): the warm-start dispatch of reference
 src/qpOASESInterface.cpp:137-224 and handle_error's QP branch (:718-757) for every member of an rsqp_batch, each in its own state.
 
 Reference of every comparison: the CPU oracle, driven by `Ref` below -- a restatement of rsqp_optimize_qp (dispatch + rescue) over
@@ -25,7 +25,7 @@ RESCUES = {None: 0, "rescue_cold": 1, "rescue_slack": 2}
 
 
 class Ref:
-    """rsqp_optimize_qp (restartsqp_amd/csrc/rsqp_api.hip) over oracle.OracleQP; s.log = what the last optimize ran"""
+    """rsqp_optimize_qp (restartsqp_amd/csrc/rsqp_api.hip, the single handle) over oracle.OracleQP; s.log = what the last optimize ran"""
 
     def __init__(s, O, q, maxit):
         s.qp = O.OracleQP(q.nV, q.nC); s.maxit = maxit

@@ -28,6 +28,15 @@ def test_library_exports_every_declared_symbol(capi):
     assert b"gfx950" in L.rsqp_version()
 
 
+def test_build_sources_are_the_translation_units_of_csrc():
+    """build._sources() skips a name that does not exist and a shared library links with undefined symbols: a mistyped or
+    forgotten unit would only fail at symbol lookup."""
+    from restartsqp_amd import build
+    units = set(f for f in os.listdir(build.CSRC) if f.endswith((".hip", ".cpp")) and os.path.isfile(os.path.join(build.CSRC, f)))
+    assert len(build.SOURCES) == len(set(build.SOURCES))
+    assert set(build.SOURCES) == units - {build.STAMP}, set(build.SOURCES) ^ (units - {build.STAMP})
+
+
 def test_no_silent_cpu_fallback(capi):
     """Without a GPU every entry point that computes must fail loudly."""
     if capi.device_count() > 0:

@@ -6,8 +6,11 @@ Each .hip source of restartsqp_amd/csrc is compiled with the library's flags plu
 sides. The assembly is split per function (from `.type <sym>,@function` to `.Lfunc_end`, with the `.amdhsa_kernel`
 descriptor block of a kernel appended), comments are dropped and local labels are renumbered per function (removing
 one kernel shifts the numbers of the ones after it), and the functions are compared by symbol. Prints, per TU, the
-functions only on one side and every function present on both sides whose code or descriptor differs; exit status 1
-if any differ or are new. A refactor that deletes dead kernels shows only removals."""
+functions only on one side and every function present on both sides whose code or descriptor differs. A symbol removed
+from exactly one TU and added to exactly one other has moved: the two texts are compared and it is reported as "moved,
+identical" or "moved, CHANGED". The TUs are never merged into one table (qp_small.hip and qp_small_hbm.hip define
+equally named, different functions in their anonymous namespaces). Exit status 1 if any function is new, changed or
+moved with a change. A refactor that deletes dead kernels shows only removals."""
 import os
 import re
 import subprocess
@@ -82,19 +85,36 @@ def main():
                     jobs.append((tree, tu, os.path.join(tmp, "%s.%s.s" % (tu, side))))
         with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
             list(ex.map(lambda j: emit(*j), jobs))
-        bad = False
+        old_f, new_f = {}, {}
         for tu in tus:
             po, pn = (os.path.join(tmp, "%s.%s.s" % (tu, s)) for s in ("old", "new"))
-            fo = functions(po) if os.path.exists(po) else {}
-            fn = functions(pn) if os.path.exists(pn) else {}
-            gone = sorted(set(fo) - set(fn))
-            added = sorted(set(fn) - set(fo))
-            changed = sorted(s for s in set(fo) & set(fn) if fo[s] != fn[s])
-            print("%-16s %4d functions, %d identical, %d removed, %d added, %d changed" %
-                  (tu, len(fo), len(set(fo) & set(fn)) - len(changed), len(gone), len(added), len(changed)))
+            old_f[tu] = functions(po) if os.path.exists(po) else {}
+            new_f[tu] = functions(pn) if os.path.exists(pn) else {}
+        # a symbol that left exactly one TU and arrived in exactly one other: {symbol: (from, to)}
+        left, came = {}, {}
+        for tu in tus:
+            for sym in set(old_f[tu]) - set(new_f[tu]):
+                left.setdefault(sym, []).append(tu)
+            for sym in set(new_f[tu]) - set(old_f[tu]):
+                came.setdefault(sym, []).append(tu)
+        moved = {sym: (left[sym][0], came[sym][0]) for sym in left if len(left[sym]) == 1 and len(came.get(sym, [])) == 1}
+        bad = False
+        for tu in tus:
+            fo, fn = old_f[tu], new_f[tu]
+            gone = sorted(sym for sym in set(fo) - set(fn) if sym not in moved)
+            added = sorted(sym for sym in set(fn) - set(fo) if sym not in moved)
+            changed = sorted(sym for sym in set(fo) & set(fn) if fo[sym] != fn[sym])
+            out = sorted(sym for sym in fo if sym in moved and moved[sym][0] == tu)
+            into = sorted(sym for sym in fn if sym in moved and moved[sym][1] == tu)
+            print("%-16s %4d functions, %d identical, %d removed, %d added, %d changed, %d moved out, %d moved in" %
+                  (tu, len(fo), len(set(fo) & set(fn)) - len(changed), len(gone), len(added), len(changed), len(out), len(into)))
             for tag, syms in (("removed", gone), ("added", added), ("CHANGED", changed)):
-                for s in syms:
-                    print("    %s %s" % (tag, s))
+                for sym in syms:
+                    print("    %s %s" % (tag, sym))
+            for sym in into:
+                same = old_f[moved[sym][0]][sym] == fn[sym]
+                print("    moved, %s %s (from %s)" % ("identical" if same else "CHANGED", sym, moved[sym][0]))
+                bad |= not same
             bad |= bool(added or changed)
     sys.exit(1 if bad else 0)
 
