@@ -306,6 +306,40 @@ int rsqp_batch_optimize_lp(rsqp_batch *b, int *nWSR_used);
  * scratch (:745-749), 2 handle_error re-initialised from the slack point x_0 (:720-743). After an LP call mode is what the dispatch
  * returned: 3 names a FIXED <-> VARIED flip, which an LP call runs as a plain init (RSQP_MODE_COLD without warm-start inputs). */
 int rsqp_batch_get_dispatch(const rsqp_batch *b, int *mode, int *rescue);
+/* Members of a batch on their own: many SQP runs advanced together on one batch do not stay in step. The rule of the three calls
+ * below: member q behaves as a single rsqp_solver that received only the calls q was named in or took part in.
+ *
+ * rsqp_batch_set_members: who takes part in the following rsqp_batch_optimize_qp / _lp calls: take_part[q] != 0 (nq entries); NULL =
+ * everybody (the default). Sticky until the next call of this function. A member that sits out a call: nothing of it is read for a
+ * decision and nothing of it is written -- it keeps its results (x, y, working sets, status, nWSR of its last solve, objective), its
+ * stored factors and the regVal of its last LP init, firstQPsolved_, both status words and a pending update mark; nWSR_used[q] = 0,
+ * and rsqp_batch_get_dispatch reports mode = -1, rescue = 0 for it. A member that sits out with an unsolved or infeasible last answer
+ * is not rescued. A mask that names nobody is legal: the optimize call returns RSQP_OK with nWSR_used all 0.
+ *   - Update_A / Update_H are per member: rsqp_batch_set_matrix_values raises them for everybody, rsqp_batch_set_matrix_values_of
+ *     for the named members alone (qpOASESInterface.cpp:407-409, 427-429: for those whose first QP is solved). A member's mark is
+ *     cleared (reset_flags, :488-496) by the next optimize call that member takes part in, and by no other: a member named while it
+ *     sits out finds the mark waiting.
+ *   - which kernel family wrote a stored state is known per member: a call that some members sit out may run on another family than
+ *     the one before (an H of a batch of at most 8 variables that turns unsymmetric moves the batch off the tableau kernel). A member
+ *     whose stored state is another family's starts cold at its next hot start and is reported as mode 0, as the whole batch is.
+ *   - the first optimize call of a batch is the uniform cold launch only when everybody takes part; otherwise the members that take
+ *     part come out cold through the per-member dispatch (never on the lane-per-problem kernel, which carries no per-member modes).
+ * Unchanged on purpose: rsqp_batch_solve, rsqp_batch_test_optimality, rsqp_batch_get_results and the record packers ignore the mask
+ * (rsqp_batch_solve runs and rewrites the state of every member); the first optimize call of the other kind (QP <-> LP) still starts
+ * every member over, those that sit out included -- a lock-step driver keeps an LP batch beside its QP batch, as the reference
+ * keeps two handler objects (src/Algorithm.cpp:561-562). With take_part == NULL or all ones, and without the _of setters, every entry
+ * point launches what it launched before these calls existed. */
+int rsqp_batch_set_members(rsqp_batch *b, const int *take_part);
+/* rsqp_batch_set_matrix_values for the members with members[q] != 0 only (nq entries; pools in the layout of rsqp_batch_create, the
+ * entries of the other members are ignored and may hold anything); raises Update_A / Update_H (:407-409, 427-429) for the named
+ * members alone. For batches of at most 8 variables the symmetry of H is re-examined for the named members, from the values given.
+ * members == NULL: exactly rsqp_batch_set_matrix_values. Naming nobody does nothing. Returns when the values are in place. */
+int rsqp_batch_set_matrix_values_of(rsqp_batch *b, const int *members, const double *Aval, const double *Hval);
+/* rsqp_batch_set_vectors for the named members only; the pools of the others keep their values (their entries in the arrays given
+ * are ignored). members == NULL: exactly rsqp_batch_set_vectors. g, lb, ub (and lbA, ubA when the batch has constraints) are
+ * required: RSQP_ERR_ARG before any device call otherwise, as for a null batch. */
+int rsqp_batch_set_vectors_of(rsqp_batch *b, const int *members, const double *g, const double *lb, const double *ub,
+                              const double *lbA, const double *ubA);
 int rsqp_batch_sync(rsqp_batch *b);
 /* keep != 0 (default): every solve writes the state a hot start needs (factors, iterate, multipliers,
  * working set: what a qpOASES SQProblem object keeps between init / hotstart calls) back to HBM.

@@ -91,6 +91,9 @@ SYMBOLS = {
     "rsqp_batch_set_lp_options": (C.c_int, [C.c_void_p, C.c_int]),
     "rsqp_batch_optimize_lp": (C.c_int, [C.c_void_p, ip]),
     "rsqp_batch_get_dispatch": (C.c_int, [C.c_void_p, ip, ip]),
+    "rsqp_batch_set_members": (C.c_int, [C.c_void_p, ip]),
+    "rsqp_batch_set_matrix_values_of": (C.c_int, [C.c_void_p, ip, dp, dp]),
+    "rsqp_batch_set_vectors_of": (C.c_int, [C.c_void_p, ip, dp, dp, dp, dp, dp]),
     "rsqp_batch_sync": (C.c_int, [C.c_void_p]),
     "rsqp_batch_set_keep_state": (C.c_int, [C.c_void_p, C.c_int]),
     "rsqp_batch_get_last_kernel": (C.c_int, [C.c_void_p]),
@@ -450,17 +453,42 @@ class Batch:
 
     __del__ = close
 
-    def set_vectors(self, g, lb, ub, lbA, ubA):
+    def _mask(self, mask):
+        """a per-member mask as nq ints (None stays None: everybody)"""
+        if mask is None:
+            return None
+        m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.int32)
+        if m.ndim != 1 or m.size != self.nq:
+            raise ValueError("the mask has %d entries, the batch has %d members" % (m.size, self.nq))
+        return m
+
+    def set_members(self, mask=None):
+        """who takes part in the following optimize_qp / optimize_lp calls (mask[q] != 0); None = everybody. A member that sits out
+        keeps everything it has; its nWSR_used is 0 and dispatch() reports mode -1 for it"""
+        m = self._mask(mask)
+        check(lib().rsqp_batch_set_members(self._h, _ip(m)))
+
+    def set_vectors(self, g, lb, ub, lbA, ubA, members=None):
+        """members: a mask -- only the named members' entries are written (the others' may be anything of the right size)"""
         g, lb, ub, lbA, ubA = _d(g), _d(lb), _d(ub), _d(lbA), _d(ubA)
-        check(lib().rsqp_batch_set_vectors(self._h, _dp(g), _dp(lb), _dp(ub), _dp(lbA), _dp(ubA)))
+        if members is None:
+            check(lib().rsqp_batch_set_vectors(self._h, _dp(g), _dp(lb), _dp(ub), _dp(lbA), _dp(ubA)))
+        else:
+            m = self._mask(members)
+            check(lib().rsqp_batch_set_vectors_of(self._h, _ip(m), _dp(g), _dp(lb), _dp(ub), _dp(lbA), _dp(ubA)))
 
-    def set_vectors_from(self, problems):
+    def set_vectors_from(self, problems, members=None):
         cat = lambda name: np.concatenate([getattr(p, name) for p in problems] + [np.zeros(0)])
-        self.set_vectors(cat("g"), cat("lb"), cat("ub"), cat("lbA"), cat("ubA"))
+        self.set_vectors(cat("g"), cat("lb"), cat("ub"), cat("lbA"), cat("ubA"), members=members)
 
-    def set_matrix_values(self, Aval=None, Hval=None):
+    def set_matrix_values(self, Aval=None, Hval=None, members=None):
+        """members: a mask -- only the named members' values are written, and only they count as updated (Update_A / Update_H)"""
         Aval, Hval = _d(Aval), _d(Hval)
-        check(lib().rsqp_batch_set_matrix_values(self._h, _dp(Aval), _dp(Hval)))
+        if members is None:
+            check(lib().rsqp_batch_set_matrix_values(self._h, _dp(Aval), _dp(Hval)))
+        else:
+            m = self._mask(members)
+            check(lib().rsqp_batch_set_matrix_values_of(self._h, _ip(m), _dp(Aval), _dp(Hval)))
 
     def solve(self, mode=MODE_COLD, max_nWSR=1000, sync=True):
         check(lib().rsqp_batch_solve(self._h, mode, max_nWSR))
@@ -496,7 +524,7 @@ class Batch:
 
     def dispatch(self):
         """(mode, rescue) per member of the last optimize_qp / optimize_lp: MODE_* of its first solve (an LP call runs a flip,
-        MODE_WARM_REINIT, as a plain init); 0 none / 1 from scratch / 2 slack point"""
+        MODE_WARM_REINIT, as a plain init; -1: the member sat out, set_members); 0 none / 1 from scratch / 2 slack point"""
         mode = np.zeros(self.nq, np.int32); rescue = np.zeros(self.nq, np.int32)
         check(lib().rsqp_batch_get_dispatch(self._h, _ip(mode), _ip(rescue)))
         return mode, rescue

@@ -22,12 +22,15 @@ struct rsqp_batch {
     long long sumV = 0, sumC = 0, sumAnz = 0, sumHnz = 0, mat_bytes_max = 0;
     bool haveH = false;
     SmallKnobs kn = rsqp_small_knobs_from_env();
-    int state_engine = -1;                // kernel family that wrote the members' hot-start states (see rsqp_solver::state_engine)
+    // kernel family that wrote the members' hot-start states (see rsqp_solver::state_engine): >= 0 every member's, -1 nobody has one,
+    // -2 the members differ -- word OPT_FAM of each says (a call some members sat out ran on another family)
+    int state_engine = -1;
     int last_kernel = -1;                 // rsqp_batch_get_last_kernel
     bool hbm = false;                     // images beyond the LDS of a CU: every member on the HBM-resident kernel (qp_small_hbm.hip)
     bool h_sym = true;                    // every H symmetric value by value (the tableau kernel of qp_tiny.hip may take the batch)
     std::vector<int> h_Hjc, h_Hir;        // host copy of the H patterns (re-examined when the values change), small batches only
     std::vector<long long> h_Huoff;       //   (the caller's layout: member q's entries start at h_Huoff[q])
+    std::vector<char> h_symq;             //   member q's H is symmetric; h_sym = all of them (rsqp_batch_set_matrix_values_of)
     ValueFold Afold, Hfold;               // members given in a non-canonical layout (PooledCsc): the pools hold the canonical form
     std::vector<QPDesc> desc;
     std::vector<int> h_csr_perm;
@@ -51,8 +54,20 @@ struct rsqp_batch {
     // the call's first solve, mode of its rescue solve (-1: none), kind of rescue, count of the first solve
     // rsqp_batch_optimize_lp adds: mode the first solve is LAUNCHED with (a flip is a plain init there), mode of the proximal step
     // (-1: the member is unsolved and takes none)
-    enum { OPT_FIRST = 0, OPT_OLD, OPT_NEW, OPT_MODE, OPT_RMODE, OPT_RESCUE, OPT_N1, OPT_LMODE, OPT_PMODE, OPT_WORDS };
+    // per member across calls as well: OPT_UPD the update mark (Update_A / Update_H of rsqp_batch_set_matrix_values_of, and of
+    // rsqp_batch_set_matrix_values for a member that sat out the call that took the batch-wide mats_updated), OPT_FAM 1 + the kernel
+    // family that wrote the member's stored state (0 none; read while state_engine == -2)
+    enum { OPT_FIRST = 0, OPT_OLD, OPT_NEW, OPT_MODE, OPT_RMODE, OPT_RESCUE, OPT_N1, OPT_LMODE, OPT_PMODE, OPT_UPD, OPT_FAM, OPT_WORDS };
     DevBuf<int> opt;
+    // rsqp_batch_set_members: who takes part in the optimize calls. The kernels get the mask only while somebody sits out; with the
+    // default and with an all-ones mask the calls issue what they issued before there was a mask
+    DevBuf<int> take;
+    bool sitters = false;                 // somebody sits out
+    // rsqp_batch_set_vectors_of / rsqp_batch_set_matrix_values_of: the caller's arrays and mask on the device, allocated at first use,
+    // and where member q's entries start in a non-canonical caller layout (Afold / Hfold)
+    DevBuf<double> stage;
+    DevBuf<int> named;
+    DevBuf<long long> Auoff, Huoff;
     // optimizeLP per member (rsqp_batch_optimize_lp): the members' descriptors with H absent and hreg = regVal of the member's last
     // init (written on the device, kept across hot starts), and the pool of the proximal step's gradients g - regVal x
     DevBuf<QPDesc> d_desc_lp;
@@ -64,7 +79,7 @@ struct rsqp_batch {
     // (and no second wait) behind it
     int *used_host = nullptr, *used_dev = nullptr;
     int qp_maxiter = 1000;                // rsqp_batch_set_options
-    bool mats_updated = false;            // rsqp_batch_set_matrix_values since the last rsqp_batch_optimize_qp (Update_A / Update_H)
+    bool mats_updated = false;            // rsqp_batch_set_matrix_values since the last optimize call (Update_A / Update_H of everybody)
     bool opt_started = false;             // an rsqp_batch_optimize_qp has run: members are in different states from here on
     float last_ms = 0.f;
     bool keep_state = true;
@@ -175,9 +190,11 @@ extern "C" int rsqp_batch_create(int nq, const int *nV, const int *nC, const int
     if (b->haveH && b->nVmax <= 8) {
         // (rsqp_batch_set_matrix_values gets the caller's layout: its pattern is kept)
         b->h_Hjc.assign(Hjc_in, Hjc_in + offHjc); b->h_Hir.assign(Hir_in, Hir_in + PH.unnz); b->h_Huoff = PH.uoff;
-        for (int q = 0; q < nq && b->h_sym; q++) {
+        b->h_symq.assign(nq, 1);
+        for (int q = 0; q < nq; q++) {
             const QPDesc &d = b->desc[q];
-            b->h_sym = small_csc_symmetric(d.nV, Hjc + d.offHjc, Hir + d.offHnz, Hval + d.offHnz);
+            b->h_symq[q] = small_csc_symmetric(d.nV, Hjc + d.offHjc, Hir + d.offHnz, Hval + d.offHnz);
+            b->h_sym = b->h_sym && b->h_symq[q];
         }
     } else if (b->haveH) b->h_sym = false;
     b->sumV = offV; b->sumC = offC; b->sumAnz = offAnz; b->sumHnz = offHnz;
@@ -214,8 +231,13 @@ extern "C" int rsqp_batch_create(int nq, const int *nV, const int *nC, const int
         HIPCHK(b->Hjc.upload(Hjc, offHjc)); HIPCHK(b->Hir.upload(Hir, offHnz)); HIPCHK(b->Hval.upload(Hval, offHnz));
     }
     // non-canonical layouts: the caller's values and the fold maps, for rsqp_batch_set_matrix_values
+    // (with the caller's first values: rsqp_batch_set_matrix_values_of rewrites the named members' alone)
     HIPCHK(PA.fold_into(b->Afold));
-    if (b->haveH) HIPCHK(PH.fold_into(b->Hfold));
+    if (!b->Afold.canon) { HIPCHK(b->Afold.uval.upload(Aval_in, b->Afold.unnz)); HIPCHK(b->Auoff.from(PA.uoff)); }
+    if (b->haveH) {
+        HIPCHK(PH.fold_into(b->Hfold));
+        if (!b->Hfold.canon) { HIPCHK(b->Hfold.uval.upload(Hval_in, b->Hfold.unnz)); HIPCHK(b->Huoff.from(PH.uoff)); }
+    }
     HIPCHK(b->g.alloc(offV)); HIPCHK(b->lb.alloc(offV)); HIPCHK(b->ub.alloc(offV));
     HIPCHK(b->lbA.alloc(offC)); HIPCHK(b->ubA.alloc(offC));
     HIPCHK(b->x.alloc(offV)); HIPCHK(b->y.alloc(offV + offC)); HIPCHK(b->obj.alloc(nq));
@@ -261,15 +283,189 @@ extern "C" int rsqp_batch_set_matrix_values(rsqp_batch *b, const double *Aval, c
         HIPCHK(b->Hfold.refresh(Hval, b->Hval, (int)b->sumHnz, b->stream));
         if (!b->h_Hjc.empty()) {
             b->h_sym = true;
-            for (int q = 0; q < b->nq && b->h_sym; q++) {
+            for (int q = 0; q < b->nq; q++) {
                 const QPDesc &d = b->desc[q];
-                b->h_sym = small_csc_symmetric(d.nV, b->h_Hjc.data() + d.offHjc, b->h_Hir.data() + b->h_Huoff[q], Hval + b->h_Huoff[q]);
+                b->h_symq[q] = small_csc_symmetric(d.nV, b->h_Hjc.data() + d.offHjc, b->h_Hir.data() + b->h_Huoff[q], Hval + b->h_Huoff[q]);
+                b->h_sym = b->h_sym && b->h_symq[q];
             }
         }
     }
     HIPCHK(hipStreamSynchronize(b->stream));
     // (qpOASESInterface.cpp:407-409, 427-429: counts for the members whose first QP is solved -- the plan kernel looks at that)
     if (Aval || (Hval && b->haveH)) b->mats_updated = true;
+    return RSQP_OK;
+}
+
+// ---------------------------------------------------------------------------------
+// members of a batch on their own: who takes part in the optimize calls, and setters that write the named members only
+// ---------------------------------------------------------------------------------
+namespace {
+int ensure_opt(rsqp_batch *b) {
+    if (!b->opt.p) HIPCHK(b->opt.alloc((size_t)rsqp_batch::OPT_WORDS * b->nq));
+    return RSQP_OK;
+}
+
+// up to five pooled arrays in one launch: entry e of the concatenation belongs to array s (end[s-1] <= e < end[s]) and there to the
+// member its position says; it is copied iff that member is named. uni[s] > 0: every member has uni[s] entries in array s; else the
+// member is searched in the offsets `kind[s]` names -- of the descriptors (0 offV, 1 offC, 2 offAnz, 3 offHnz), or uoff[s] (4: a
+// caller's layout that is not the canonical one). mark != null: the update mark of every named member whose first QP is solved
+// (qpOASESInterface.cpp:407-409, 427-429). Consecutive lanes read and write consecutive entries.
+struct MaskedCopy {
+    int nseg, nq;
+    long long end[5];
+    int uni[5], kind[5];
+    const double *src[5];
+    double *dst[5];
+    const long long *uoff[5];
+    const QPDesc *desc;
+    const int *named;
+    int *mark;            // the OPT_UPD words of the opt block
+    const int *first;     // the OPT_FIRST words
+};
+__device__ inline long long member_start(const MaskedCopy &a, int s, int q) {
+    switch (a.kind[s]) {
+    case 0: return a.desc[q].offV;
+    case 1: return a.desc[q].offC;
+    case 2: return a.desc[q].offAnz;
+    case 3: return a.desc[q].offHnz;
+    default: return a.uoff[s][q];
+    }
+}
+__global__ void __launch_bounds__(256) batch_masked_copy_kernel(MaskedCopy a) {
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (a.mark && e < a.nq && a.named[e] != 0 && a.first[e] != 0) a.mark[e] = 1;
+    if (a.nseg <= 0 || e >= a.end[a.nseg - 1]) return;
+    int s = 0;
+    while (e >= a.end[s]) s++;                        // (s < nseg: e is below the last end)
+    const long long k = e - (s > 0 ? a.end[s - 1] : 0);
+    int q;
+    if (a.uni[s] > 0) q = (int)(k / a.uni[s]);
+    else {                                            // the last member that starts at or before k (members without entries own none)
+        int lo = 0, hi = a.nq - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (member_start(a, s, mid) <= k) lo = mid; else hi = mid - 1;
+        }
+        q = lo;
+    }
+    if (a.named[q] != 0) a.dst[s][k] = a.src[s][k];
+}
+
+// the mask on the device; *count = members named
+int upload_mask(rsqp_batch *b, DevBuf<int> &dst, const int *mask, int *count) {
+    std::vector<int> m(b->nq);
+    int n = 0;
+    for (int q = 0; q < b->nq; q++) n += (m[q] = mask[q] != 0 ? 1 : 0);
+    *count = n;
+    if (!dst.p) HIPCHK(dst.alloc(b->nq));
+    HIPCHK(dst.upload(m.data(), b->nq));
+    return RSQP_OK;
+}
+int ensure_stage(rsqp_batch *b) {
+    const size_t need = (size_t)std::max<long long>(3 * b->sumV + 2 * b->sumC, b->Afold.unnz + (b->haveH ? b->Hfold.unnz : 0));
+    if (!b->stage.p) HIPCHK(b->stage.alloc(need, false));
+    return RSQP_OK;
+}
+void add_segment(MaskedCopy &a, long long n, int uni, int kind, const double *src, double *dst, const long long *uoff) {
+    const int s = a.nseg++;
+    a.end[s] = (s > 0 ? a.end[s - 1] : 0) + n;
+    a.uni[s] = uni; a.kind[s] = kind; a.src[s] = src; a.dst[s] = dst; a.uoff[s] = uoff;
+}
+int launch_masked_copy(rsqp_batch *b, MaskedCopy &a) {
+    a.nq = b->nq; a.desc = b->d_desc.p; a.named = b->named.p;
+    const long long n = std::max<long long>(a.nseg > 0 ? a.end[a.nseg - 1] : 0, a.mark ? b->nq : 0);
+    if (n <= 0) return RSQP_OK;
+    hipLaunchKernelGGL(batch_masked_copy_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, b->stream, a);
+    HIPCHK(hipGetLastError());
+    return RSQP_OK;
+}
+}  // namespace
+
+extern "C" int rsqp_batch_set_members(rsqp_batch *b, const int *take_part) {
+    if (!b) return fail(RSQP_ERR_ARG, "null batch");
+    int n = b->nq;
+    if (take_part) {   // (everybody named: the calls run as they do without a mask)
+        HIPCHK(hipSetDevice(b->device));
+        const int rc = upload_mask(b, b->take, take_part, &n);
+        if (rc != RSQP_OK) return rc;
+    }
+    b->sitters = n < b->nq;
+    return RSQP_OK;
+}
+
+extern "C" int rsqp_batch_set_vectors_of(rsqp_batch *b, const int *members, const double *g, const double *lb, const double *ub,
+                                         const double *lbA, const double *ubA) {
+    if (!b || !g || !lb || !ub || (b->sumC > 0 && (!lbA || !ubA))) return fail(RSQP_ERR_ARG, "rsqp_batch_set_vectors_of");
+    if (!members) return rsqp_batch_set_vectors(b, g, lb, ub, lbA, ubA);
+    HIPCHK(hipSetDevice(b->device));
+    int rc, n = 0;
+    if ((rc = upload_mask(b, b->named, members, &n)) != RSQP_OK || n == 0) return rc;
+    if ((rc = ensure_stage(b)) != RSQP_OK) return rc;
+    const long long sV = b->sumV, sC = b->sumC;
+    double *const st = b->stage.p;
+    HIPCHK(hipMemcpy(st, g, sizeof(double) * sV, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(st + sV, lb, sizeof(double) * sV, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(st + 2 * sV, ub, sizeof(double) * sV, hipMemcpyHostToDevice));
+    if (sC > 0) {
+        HIPCHK(hipMemcpy(st + 3 * sV, lbA, sizeof(double) * sC, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(st + 3 * sV + sC, ubA, sizeof(double) * sC, hipMemcpyHostToDevice));
+    }
+    MaskedCopy a;
+    std::memset(&a, 0, sizeof(a));
+    const int uV = b->uniV > 0 ? b->uniV : 0, uC = b->uniC > 0 ? b->uniC : 0;
+    add_segment(a, sV, uV, 0, st, b->g.p, nullptr);
+    add_segment(a, sV, uV, 0, st + sV, b->lb.p, nullptr);
+    add_segment(a, sV, uV, 0, st + 2 * sV, b->ub.p, nullptr);
+    add_segment(a, sC, uC, 1, st + 3 * sV, b->lbA.p, nullptr);
+    add_segment(a, sC, uC, 1, st + 3 * sV + sC, b->ubA.p, nullptr);
+    if ((rc = launch_masked_copy(b, a)) != RSQP_OK) return rc;
+    HIPCHK(hipStreamSynchronize(b->stream));   // (the staging pool is free again)
+    return RSQP_OK;
+}
+
+extern "C" int rsqp_batch_set_matrix_values_of(rsqp_batch *b, const int *members, const double *Aval, const double *Hval) {
+    if (!b) return fail(RSQP_ERR_ARG, "null batch");
+    if (!members) return rsqp_batch_set_matrix_values(b, Aval, Hval);
+    if (!b->haveH) Hval = nullptr;
+    HIPCHK(hipSetDevice(b->device));
+    int rc, n = 0;
+    if ((rc = upload_mask(b, b->named, members, &n)) != RSQP_OK || n == 0 || (!Aval && !Hval)) return rc;
+    if ((rc = ensure_stage(b)) != RSQP_OK || (rc = ensure_opt(b)) != RSQP_OK) return rc;
+    const long long uA = b->Afold.unnz, uH = b->Hfold.unnz;
+    double *const st = b->stage.p;
+    MaskedCopy a;
+    std::memset(&a, 0, sizeof(a));
+    // (a canonical layout: straight into the pools; else into the caller's values, which are folded behind the copy)
+    if (Aval) {
+        HIPCHK(hipMemcpy(st, Aval, sizeof(double) * uA, hipMemcpyHostToDevice));
+        if (b->Afold.canon) add_segment(a, uA, b->uni_pat ? b->uni_annz : 0, 2, st, b->Aval.p, nullptr);
+        else add_segment(a, uA, 0, 4, st, b->Afold.uval.p, b->Auoff.p);
+    }
+    if (Hval) {
+        HIPCHK(hipMemcpy(st + uA, Hval, sizeof(double) * uH, hipMemcpyHostToDevice));
+        if (b->Hfold.canon) add_segment(a, uH, b->uni_pat ? b->uni_hnnz : 0, 3, st + uA, b->Hval.p, nullptr);
+        else add_segment(a, uH, 0, 4, st + uA, b->Hfold.uval.p, b->Huoff.p);
+    }
+    a.mark = b->opt.p + (size_t)rsqp_batch::OPT_UPD * b->nq; a.first = b->opt.p + (size_t)rsqp_batch::OPT_FIRST * b->nq;
+    if ((rc = launch_masked_copy(b, a)) != RSQP_OK) return rc;
+    if (Aval) {
+        if (!b->Afold.canon) HIPCHK(b->Afold.sum(b->Aval, (int)b->sumAnz, b->stream));
+        if (rsqp_launch_gather((int)b->sumAnz, b->perm.p, b->Aval.p, b->Arv.p, b->stream) != hipSuccess)
+            return fail(RSQP_ERR_DEVICE, "gather launch failed");
+    }
+    if (Hval) {
+        if (!b->Hfold.canon) HIPCHK(b->Hfold.sum(b->Hval, (int)b->sumHnz, b->stream));
+        if (!b->h_Hjc.empty()) {   // the named members' symmetry anew, from the values given
+            b->h_sym = true;
+            for (int q = 0; q < b->nq; q++) {
+                const QPDesc &d = b->desc[q];
+                if (members[q] != 0)
+                    b->h_symq[q] = small_csc_symmetric(d.nV, b->h_Hjc.data() + d.offHjc, b->h_Hir.data() + b->h_Huoff[q], Hval + b->h_Huoff[q]);
+                b->h_sym = b->h_sym && b->h_symq[q];
+            }
+        }
+    }
+    HIPCHK(hipStreamSynchronize(b->stream));
     return RSQP_OK;
 }
 
@@ -291,9 +487,10 @@ int launch_batch(rsqp_batch *b, QPPools &p, int mode, int max_nWSR, bool first, 
     const SmallKnobs kn = knobs_of(b, lp);
     const int fam = batch_family(b, p, lp);
     // the kernel families keep different layouts in the same state block: a hot start on another family's state starts cold
-    // (per-member modes: the plan kernel was told)
-    if ((mode == RSQP_MODE_HOT_VECTORS || mode == RSQP_MODE_HOT_MATRICES) && b->state_engine != fam) mode = RSQP_MODE_COLD;
-    b->state_engine = fam;
+    // (per-member modes: the plan kernel was told, and `mode` is not read)
+    if (!p.member_mode && (mode == RSQP_MODE_HOT_VECTORS || mode == RSQP_MODE_HOT_MATRICES) && b->state_engine != fam) mode = RSQP_MODE_COLD;
+    // every member of the launch has a state of this family now; one that sits out keeps what it had
+    b->state_engine = (p.member_mode && b->sitters && b->state_engine != fam) ? -2 : fam;
     hipError_t e;
     if (b->hbm) {
         if (first) b->last_kernel = 3;
@@ -354,19 +551,42 @@ extern "C" int rsqp_batch_solve(rsqp_batch *b, int mode, int max_nWSR) {
 // inside a call. plan -> solve -> rescue plan -> rescue solve (members that need none leave at once) -> count -> one wait.
 // ---------------------------------------------------------------------------------
 namespace {
+// a member that sits out a call (rsqp_batch_set_members; take == null: nobody does). The plan, rescue-plan and count kernels of a QP
+// call and the plan, rescue-plan, prox-plan and finish kernels of an LP call ask this first, before any look at the member's status or
+// counts: a stale "infeasible" of a member that sits out is not rescued (the solve launches skip it by its mode word, -1)
+__device__ inline bool sits_out(const int *__restrict__ take, int q) { return take && take[q] == 0; }
+// what the first kernel of a call leaves for such a member: no launch of the call runs it (every mode word -1, which is also what
+// rsqp_batch_get_dispatch reports); what the call takes from the host for EVERYBODY is put down in its own words -- the batch-wide
+// update mark, which the host clears behind the call, and the batch-wide family of the stored states, when the call is about to move
+// the others to another one (fam_all1 = 1 + family, 0 nobody has a state, -1 the words hold already). Its nWSR_used = 0 comes from
+// the kernel that writes everybody's (strided 4-byte stores of a second kernel into the host-mapped array cost 60 us at 65 536 members)
+__device__ inline void plan_sitter(int nq, int q, int *__restrict__ opt, int updated, int fam_all1) {
+    opt[rsqp_batch::OPT_MODE * nq + q] = -1; opt[rsqp_batch::OPT_LMODE * nq + q] = -1;
+    opt[rsqp_batch::OPT_RMODE * nq + q] = -1; opt[rsqp_batch::OPT_PMODE * nq + q] = -1;
+    opt[rsqp_batch::OPT_RESCUE * nq + q] = 0;
+    if (updated && opt[rsqp_batch::OPT_FIRST * nq + q] != 0) opt[rsqp_batch::OPT_UPD * nq + q] = 1;   // (:407, :427: firstQPsolved_ &&)
+    if (fam_all1 >= 0) opt[rsqp_batch::OPT_FAM * nq + q] = fam_all1;
+}
+
 // before the first solve: the call shape of every member (rsqp_dispatch_mode); a FIXED <-> VARIED flip re-initialises from the
-// member's own previous x, y and bound working set (:201-208), copied into the warm-start pools
-__global__ void batch_plan_kernel(int nq, const QPDesc *__restrict__ desc, int *__restrict__ opt, int updated, int hot_ok,
-                                  const double *__restrict__ x, const double *__restrict__ y, const int *__restrict__ ws_b,
-                                  double *__restrict__ x0, double *__restrict__ y0, int *__restrict__ gb) {
+// member's own previous x, y and bound working set (:201-208), copied into the warm-start pools. updated: Update_A / Update_H of
+// everybody (rsqp_batch_set_matrix_values), beside the member's own mark, which this call consumes (reset_flags, :488-496).
+// fam1 = 1 + the kernel family of this call's launches, fam_all1 as in plan_sitter
+__global__ void batch_plan_kernel(int nq, const QPDesc *__restrict__ desc, int *__restrict__ opt, const int *__restrict__ take,
+                                  int updated, int fam_all1, int fam1, const double *__restrict__ x, const double *__restrict__ y,
+                                  const int *__restrict__ ws_b, double *__restrict__ x0, double *__restrict__ y0, int *__restrict__ gb) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= nq) return;
+    if (sits_out(take, q)) { plan_sitter(nq, q, opt, updated, fam_all1); return; }
     int old_status = opt[rsqp_batch::OPT_OLD * nq + q], new_status = opt[rsqp_batch::OPT_NEW * nq + q];
-    int mode = rsqp_dispatch_mode(opt[rsqp_batch::OPT_FIRST * nq + q] != 0, updated != 0, old_status, new_status);
-    // the stored states are another kernel family's (the host knows): a hot start runs cold, as on a single handle
+    const bool upd = updated != 0 || opt[rsqp_batch::OPT_UPD * nq + q] != 0;
+    int mode = rsqp_dispatch_mode(opt[rsqp_batch::OPT_FIRST * nq + q] != 0, upd, old_status, new_status);
+    // the member's stored state is another kernel family's: a hot start runs cold, as on a single handle
+    const bool hot_ok = (fam_all1 >= 0 ? fam_all1 : opt[rsqp_batch::OPT_FAM * nq + q]) == fam1;
     if (!hot_ok && (mode == RSQP_MODE_HOT_VECTORS || mode == RSQP_MODE_HOT_MATRICES)) mode = RSQP_MODE_COLD;
     opt[rsqp_batch::OPT_OLD * nq + q] = old_status; opt[rsqp_batch::OPT_NEW * nq + q] = new_status;
     opt[rsqp_batch::OPT_MODE * nq + q] = mode;
+    opt[rsqp_batch::OPT_UPD * nq + q] = 0; opt[rsqp_batch::OPT_FAM * nq + q] = fam1;
     if (mode == RSQP_MODE_WARM_REINIT) {
         const QPDesc d = desc[q];
         for (int v = 0; v < d.nV; v++) { x0[d.offV + v] = x[d.offV + v]; gb[d.offV + v] = ws_b[d.offV + v]; }
@@ -377,10 +597,11 @@ __global__ void batch_plan_kernel(int nq, const QPDesc *__restrict__ desc, int *
 // behind the first solve: firstQPsolved_ (:156-158), handle_error's QP branch per member (:718-757) -- none / re-init from scratch /
 // re-init from the slack point x_0 (written to the x0 pool) --, old = new = UNDEFINED for the rescued, the count so far
 __global__ void batch_rescue_plan_kernel(int nq, const QPDesc *__restrict__ desc, int *__restrict__ opt, const int *__restrict__ status,
-                                         const int *__restrict__ nwsr, const double *__restrict__ lbA, const double *__restrict__ ubA,
-                                         double *__restrict__ x0, int *__restrict__ used) {
+                                         const int *__restrict__ take, const int *__restrict__ nwsr, const double *__restrict__ lbA,
+                                         const double *__restrict__ ubA, double *__restrict__ x0, int *__restrict__ used) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= nq) return;
+    if (sits_out(take, q)) { used[q] = 0; return; }   // (the plan kernel has written its words)
     const int sw = status[q], n1 = nwsr[q];
     const bool solved = sw == QPS_SOLVED, infeasible = sw >= 100 && sw < 200;
     opt[rsqp_batch::OPT_N1 * nq + q] = n1;
@@ -405,10 +626,10 @@ __global__ void batch_rescue_plan_kernel(int nq, const QPDesc *__restrict__ desc
 
 // behind the rescue solve: nWSR_used of the rescued members. A member whose FIRST init failed reports the rescue's count alone when
 // the rescue fails too (the reference throws inside handle_error, :754-756, before :211-212 add the first count)
-__global__ void batch_count_kernel(int nq, const int *__restrict__ opt, const int *__restrict__ status, const int *__restrict__ nwsr,
-                                   int *__restrict__ used) {
+__global__ void batch_count_kernel(int nq, const int *__restrict__ opt, const int *__restrict__ take, const int *__restrict__ status,
+                                   const int *__restrict__ nwsr, int *__restrict__ used) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= nq || opt[rsqp_batch::OPT_RESCUE * nq + q] == 0) return;
+    if (q >= nq || sits_out(take, q) || opt[rsqp_batch::OPT_RESCUE * nq + q] == 0) return;
     const int n1 = opt[rsqp_batch::OPT_N1 * nq + q], n2 = nwsr[q];
     const bool first_init_failed = opt[rsqp_batch::OPT_FIRST * nq + q] == 0;
     used[q] = (first_init_failed && status[q] != QPS_SOLVED) ? n2 : n1 + n2;
@@ -425,13 +646,13 @@ int begin_optimize(rsqp_batch *b, int kind) {
                                       ": the batch keeps no state (rsqp_batch_set_keep_state(b, 0))");
     HIPCHK(hipSetDevice(b->device));
     const int nq = b->nq;
-    if (!b->opt.p) HIPCHK(b->opt.alloc((size_t)rsqp_batch::OPT_WORDS * nq));
+    int rc = ensure_opt(b);
+    if (rc != RSQP_OK) return rc;
     if (!b->used_host) {
         HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&b->used_host), sizeof(int) * nq, hipHostMallocMapped));
         HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&b->used_dev), b->used_host, 0));
     }
-    const int rc = ensure_warm_pools(b);
-    if (rc != RSQP_OK) return rc;
+    if ((rc = ensure_warm_pools(b)) != RSQP_OK) return rc;
     b->have_x0 = b->have_y0 = b->have_gb = false;   // the pools are this call's from here on
     if (kind == 2 && !b->d_desc_lp.p) {
         std::vector<QPDesc> lp = b->desc;
@@ -483,20 +704,28 @@ __device__ inline double lp_reg_val(const QPDesc &d, const double *__restrict__ 
 // (:266-270): OPT_MODE keeps what the dispatch said (3), OPT_LMODE what is launched (0). Every init fixes the member's regVal from
 // the gradient of this call; a hot start keeps the one its factors were built with
 __global__ void __launch_bounds__(64)
-batch_lp_plan_kernel(int nq, QPDesc *__restrict__ desc, int *__restrict__ opt, int updated, int hot_ok, const double *__restrict__ g) {
+batch_lp_plan_kernel(int nq, QPDesc *__restrict__ desc, int *__restrict__ opt, const int *__restrict__ take, int updated, int fam_all1,
+                     int fam1, const double *__restrict__ g) {
     const int q = (int)blockIdx.x;
     if (q >= nq) return;
+    if (sits_out(take, q)) {   // (its descriptor keeps the regVal of its own last init)
+        if (threadIdx.x == 0) plan_sitter(nq, q, opt, updated, fam_all1);
+        return;
+    }
     const QPDesc d = desc[q];
     int old_status = opt[rsqp_batch::OPT_OLD * nq + q], new_status = opt[rsqp_batch::OPT_NEW * nq + q];
-    int mode = rsqp_dispatch_mode(opt[rsqp_batch::OPT_FIRST * nq + q] != 0, updated != 0, old_status, new_status);
+    const bool upd = updated != 0 || opt[rsqp_batch::OPT_UPD * nq + q] != 0;
+    int mode = rsqp_dispatch_mode(opt[rsqp_batch::OPT_FIRST * nq + q] != 0, upd, old_status, new_status);
     const bool init = mode == RSQP_MODE_COLD || mode == RSQP_MODE_WARM_REINIT;
     const double reg = init ? lp_reg_val(d, g) : d.hreg;
-    // (stored states of another kernel family: the hot start runs cold on the regVal it has, as rsqp_solve does on a handle)
+    // (a stored state of another kernel family: the hot start runs cold on the regVal it has, as rsqp_solve does on a handle)
+    const bool hot_ok = (fam_all1 >= 0 ? fam_all1 : opt[rsqp_batch::OPT_FAM * nq + q]) == fam1;
     if (!hot_ok && !init) mode = RSQP_MODE_COLD;
     __syncthreads();   // every lane has read the member's words
     if (threadIdx.x == 0) {
         opt[rsqp_batch::OPT_OLD * nq + q] = old_status; opt[rsqp_batch::OPT_NEW * nq + q] = new_status;
         opt[rsqp_batch::OPT_MODE * nq + q] = mode;
+        opt[rsqp_batch::OPT_UPD * nq + q] = 0; opt[rsqp_batch::OPT_FAM * nq + q] = fam1;
         opt[rsqp_batch::OPT_LMODE * nq + q] = init ? RSQP_MODE_COLD : mode;
         desc[q].hreg = reg;
     }
@@ -506,11 +735,12 @@ batch_lp_plan_kernel(int nq, QPDesc *__restrict__ desc, int *__restrict__ opt, i
 // re-init from x_0 := the x of the failed solve with its slack entries overwritten (:693-699; written to the x0 pool) --, a fresh
 // regVal for the re-init, old = new = UNDEFINED for the rescued
 __global__ void __launch_bounds__(64)
-batch_lp_rescue_plan_kernel(int nq, QPDesc *__restrict__ desc, int *__restrict__ opt, const int *__restrict__ status,
-                            const int *__restrict__ nwsr, const double *__restrict__ g, const double *__restrict__ x,
-                            const double *__restrict__ lbA, const double *__restrict__ ubA, double *__restrict__ x0) {
+batch_lp_rescue_plan_kernel(int nq, QPDesc *__restrict__ desc, int *__restrict__ opt, const int *__restrict__ take,
+                            const int *__restrict__ status, const int *__restrict__ nwsr, const double *__restrict__ g,
+                            const double *__restrict__ x, const double *__restrict__ lbA, const double *__restrict__ ubA,
+                            double *__restrict__ x0) {
     const int q = (int)blockIdx.x, lane = (int)threadIdx.x;
-    if (q >= nq) return;
+    if (q >= nq || sits_out(take, q)) return;
     const int sw = status[q];
     const bool solved = sw == QPS_SOLVED, infeasible = sw >= 100 && sw < 200;
     if (solved) {
@@ -545,11 +775,11 @@ batch_lp_rescue_plan_kernel(int nq, QPDesc *__restrict__ desc, int *__restrict__
 // the reference throws inside handle_error, :714-716, before :278-279 add the other), and the proximal step of every member that is
 // solved now (:280-283): a hot start on the gradient g - regVal x, written to the scratch pool -- the batch's g keeps the caller's
 __global__ void __launch_bounds__(64)
-batch_lp_prox_plan_kernel(int nq, const QPDesc *__restrict__ desc, int *__restrict__ opt, const int *__restrict__ status,
-                          const int *__restrict__ nwsr, const double *__restrict__ g, const double *__restrict__ x,
-                          double *__restrict__ g_lp) {
+batch_lp_prox_plan_kernel(int nq, const QPDesc *__restrict__ desc, int *__restrict__ opt, const int *__restrict__ take,
+                          const int *__restrict__ status, const int *__restrict__ nwsr, const double *__restrict__ g,
+                          const double *__restrict__ x, double *__restrict__ g_lp) {
     const int q = (int)blockIdx.x, lane = (int)threadIdx.x;
-    if (q >= nq) return;
+    if (q >= nq || sits_out(take, q)) return;   // (OPT_PMODE is -1 since the plan kernel)
     const bool solved = status[q] == QPS_SOLVED, rescued = opt[rsqp_batch::OPT_RESCUE * nq + q] != 0;
     const int n1 = opt[rsqp_batch::OPT_N1 * nq + q], n2 = nwsr[q];
     __syncthreads();
@@ -564,10 +794,12 @@ batch_lp_prox_plan_kernel(int nq, const QPDesc *__restrict__ desc, int *__restri
 
 // behind the proximal step: nWSR_used, and the objective g'x with the caller's gradient (:283) for the members that took the step
 __global__ void __launch_bounds__(64)
-batch_lp_finish_kernel(int nq, const QPDesc *__restrict__ desc, const int *__restrict__ opt, const int *__restrict__ nwsr,
-                       const double *__restrict__ g, const double *__restrict__ x, double *__restrict__ obj, int *__restrict__ used) {
+batch_lp_finish_kernel(int nq, const QPDesc *__restrict__ desc, const int *__restrict__ opt, const int *__restrict__ take,
+                       const int *__restrict__ nwsr, const double *__restrict__ g, const double *__restrict__ x, double *__restrict__ obj,
+                       int *__restrict__ used) {
     const int q = (int)blockIdx.x, lane = (int)threadIdx.x;
     if (q >= nq) return;
+    if (sits_out(take, q)) { if (lane == 0) used[q] = 0; return; }
     const int total = opt[rsqp_batch::OPT_N1 * nq + q];
     if (opt[rsqp_batch::OPT_PMODE * nq + q] < 0) { if (lane == 0) used[q] = total; return; }
     const QPDesc d = desc[q];
@@ -584,22 +816,26 @@ extern "C" int rsqp_batch_optimize_qp(rsqp_batch *b, int *nWSR_used) {
     const int nq = b->nq;
     const dim3 grid((unsigned)((nq + 255) / 256)), block(256);
     QPPools p = pools_of(b, false);
-    if (!b->opt_started) {
+    const int *const take = b->sitters ? b->take.p : nullptr;   // (null: everybody takes part)
+    if (!b->opt_started && !take) {
         // no member has a solved first QP: init for everybody -- the uniform cold launch (lane-per-problem and mid-size tableau
         // kernels included), no per-member modes, no warm-start pointers; the members' mode words are 0 = cold already
         rc = launch_batch(b, p, RSQP_MODE_COLD, b->qp_maxiter, true, false);
     } else {
-        hipLaunchKernelGGL(batch_plan_kernel, grid, block, 0, b->stream, nq, b->d_desc.p, b->opt.p, b->mats_updated ? 1 : 0,
-                           b->state_engine == batch_family(b, p, false) ? 1 : 0, b->x.p, b->y.p, b->ws_b.p, b->wx0.p, b->wy0.p, b->wgb.p);
+        // (a first call that somebody sits out comes here as well: a member without a solved first QP comes out cold)
+        hipLaunchKernelGGL(batch_plan_kernel, grid, block, 0, b->stream, nq, b->d_desc.p, b->opt.p, take, b->mats_updated ? 1 : 0,
+                           b->state_engine + 1, batch_family(b, p, false) + 1, b->x.p, b->y.p, b->ws_b.p, b->wx0.p, b->wy0.p, b->wgb.p);
         HIPCHK(hipGetLastError());
         p.x0 = b->wx0.p; p.y0 = b->wy0.p; p.guess_b = b->wgb.p;     // the flip: all three (:204-206)
         rc = launch_members(b, p, rsqp_batch::OPT_MODE, RSQP_MODE_COLD, b->qp_maxiter, true, false);
     }
     if (rc != RSQP_OK) return rc;
+    // (also behind a call nobody took part in: its plan kernel has written -1 into the mode words, which the uniform cold launch
+    //  relies on being 0; the next call goes through the plan kernel, where members without a solved first QP come out cold)
     b->opt_started = true;
     b->cert_lp = false;
-    b->mats_updated = false;   // reset_flags (:488-496)
-    hipLaunchKernelGGL(batch_rescue_plan_kernel, grid, block, 0, b->stream, nq, b->d_desc.p, b->opt.p, b->status.p, b->nwsr.p,
+    b->mats_updated = false;   // reset_flags (:488-496); a member that sat out has the mark in its own word now
+    hipLaunchKernelGGL(batch_rescue_plan_kernel, grid, block, 0, b->stream, nq, b->d_desc.p, b->opt.p, b->status.p, take, b->nwsr.p,
                        b->lbA.p, b->ubA.p, b->wx0.p, b->used_dev);
     HIPCHK(hipGetLastError());
     // the rescue launch is unconditional: a member that needs none leaves at its first instruction, and asking the device whether
@@ -608,7 +844,7 @@ extern "C" int rsqp_batch_optimize_qp(rsqp_batch *b, int *nWSR_used) {
     p.x0 = b->wx0.p;                                                 // handle_error: x_0 alone (:741-743)
     rc = launch_members(b, p, rsqp_batch::OPT_RMODE, RSQP_MODE_COLD, b->qp_maxiter, false, false);
     if (rc != RSQP_OK) return rc;
-    hipLaunchKernelGGL(batch_count_kernel, grid, block, 0, b->stream, nq, b->opt.p, b->status.p, b->nwsr.p, b->used_dev);
+    hipLaunchKernelGGL(batch_count_kernel, grid, block, 0, b->stream, nq, b->opt.p, take, b->status.p, b->nwsr.p, b->used_dev);
     HIPCHK(hipGetLastError());
     return finish_optimize(b, nWSR_used);
 }
@@ -625,29 +861,30 @@ extern "C" int rsqp_batch_optimize_lp(rsqp_batch *b, int *nWSR_used) {
     const int nq = b->nq;
     const dim3 grid((unsigned)nq), block(64);
     int *const opt = b->opt.p;
+    const int *const take = b->sitters ? b->take.p : nullptr;   // (null: everybody takes part)
     // every launch carries per-member modes and reads the LP descriptors: H absent, hreg = the member's regVal
     QPPools p = pools_of(b, true);
-    hipLaunchKernelGGL(batch_lp_plan_kernel, grid, block, 0, b->stream, nq, b->d_desc_lp.p, opt, b->mats_updated ? 1 : 0,
-                       b->state_engine == batch_family(b, p, true) ? 1 : 0, b->g.p);
+    hipLaunchKernelGGL(batch_lp_plan_kernel, grid, block, 0, b->stream, nq, b->d_desc_lp.p, opt, take, b->mats_updated ? 1 : 0,
+                       b->state_engine + 1, batch_family(b, p, true) + 1, b->g.p);
     HIPCHK(hipGetLastError());
     if ((rc = launch_members(b, p, rsqp_batch::OPT_LMODE, RSQP_MODE_COLD, b->lp_maxiter, true, true)) != RSQP_OK) return rc;
     b->opt_started = true;
     b->cert_lp = true;
-    b->mats_updated = false;   // reset_flags (:488-496)
-    hipLaunchKernelGGL(batch_lp_rescue_plan_kernel, grid, block, 0, b->stream, nq, b->d_desc_lp.p, opt, b->status.p, b->nwsr.p, b->g.p,
-                       b->x.p, b->lbA.p, b->ubA.p, b->wx0.p);
+    b->mats_updated = false;   // reset_flags (:488-496); a member that sat out has the mark in its own word now
+    hipLaunchKernelGGL(batch_lp_rescue_plan_kernel, grid, block, 0, b->stream, nq, b->d_desc_lp.p, opt, take, b->status.p, b->nwsr.p,
+                       b->g.p, b->x.p, b->lbA.p, b->ubA.p, b->wx0.p);
     HIPCHK(hipGetLastError());
     // (unconditional, as in rsqp_batch_optimize_qp: a member that needs no rescue leaves at its first instruction)
     p.x0 = b->wx0.p;                                                 // handle_error: x_0 alone (:700-702)
     if ((rc = launch_members(b, p, rsqp_batch::OPT_RMODE, RSQP_MODE_COLD, b->lp_maxiter, false, true)) != RSQP_OK) return rc;
-    hipLaunchKernelGGL(batch_lp_prox_plan_kernel, grid, block, 0, b->stream, nq, b->d_desc_lp.p, opt, b->status.p, b->nwsr.p, b->g.p,
-                       b->x.p, b->g_lp.p);
+    hipLaunchKernelGGL(batch_lp_prox_plan_kernel, grid, block, 0, b->stream, nq, b->d_desc_lp.p, opt, take, b->status.p, b->nwsr.p,
+                       b->g.p, b->x.p, b->g_lp.p);
     HIPCHK(hipGetLastError());
     p.x0 = nullptr;
     p.g = b->g_lp.p;
     if ((rc = launch_members(b, p, rsqp_batch::OPT_PMODE, RSQP_MODE_HOT_VECTORS, b->lp_maxiter, false, true)) != RSQP_OK) return rc;
-    hipLaunchKernelGGL(batch_lp_finish_kernel, grid, block, 0, b->stream, nq, b->d_desc_lp.p, opt, b->nwsr.p, b->g.p, b->x.p, b->obj.p,
-                       b->used_dev);
+    hipLaunchKernelGGL(batch_lp_finish_kernel, grid, block, 0, b->stream, nq, b->d_desc_lp.p, opt, take, b->nwsr.p, b->g.p, b->x.p,
+                       b->obj.p, b->used_dev);
     HIPCHK(hipGetLastError());
     return finish_optimize(b, nWSR_used);
 }

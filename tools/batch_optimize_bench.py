@@ -4,7 +4,8 @@
 
 m1_*:  steady FIXED state (every member hot-starts on new vectors, nobody is rescued): wall time of one rsqp_batch_optimize_qp
        against rsqp_batch_solve(HOT_VECTORS) + rsqp_batch_sync on the same batch and vectors -- 65 536 hs071-scale members
-       (m1_tiny), the 512-member hs0xx batch (m1_hs512).
+       (m1_tiny), the 512-member hs0xx batch (m1_hs512); and the same call with every second member sitting out
+       (rsqp_batch_set_members), where the library has it.
 m2:    the seven-step sequence of tests/test_gpu_batch_optimize.py on hs_batch(512): one batch against 512 single handles.
 trace: three calls per batch and nothing else, to run under `rocprofv3 --kernel-trace --stats`.
 TREE=<checkout> imports restartsqp_amd from another checkout (one that lacks the entry point measures its rsqp_batch_solve and
@@ -65,6 +66,17 @@ def m1(label, base):
         out["optimize_qp_without_nWSR_used"] = stats(ts)
         r2 = b2.results()
         out["same_as_solve"] = bool(all(np.array_equal(a["x"], c["x"]) and a["nWSR"] == c["nWSR"] for a, c in zip(res, r2)))
+        if "rsqp_batch_set_members" in capi.SYMBOLS:       # every second member sits out (rsqp_batch_set_members): against the full call above
+            half = (np.arange(len(base)) % 2 == 0).astype(np.int32)
+            b2.set_members(half)
+            ts = []
+            for r in range(reps + 5):
+                b2.set_vectors(*sets[r % 2])
+                t0 = time.perf_counter(); used = b2.optimize_qp(); t1 = time.perf_counter()
+                if r >= 5: ts.append(t1 - t0)
+            mode, rescue = b2.dispatch()
+            assert np.all(mode[half == 1] == 1) and np.all(mode[half == 0] == -1) and np.all(used[half == 0] == 0)
+            out["optimize_qp_every_second_member_sits_out"] = stats(ts)
         b2.close()
     b.close()
     print(json.dumps(dict(measurement="M1", side=side, batch=label, nq=len(base), **out)), flush=True)
