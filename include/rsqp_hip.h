@@ -340,6 +340,52 @@ int rsqp_batch_set_matrix_values_of(rsqp_batch *b, const int *members, const dou
  * required: RSQP_ERR_ARG before any device call otherwise, as for a null batch. */
 int rsqp_batch_set_vectors_of(rsqp_batch *b, const int *members, const double *g, const double *lb, const double *ub,
                               const double *lbA, const double *ubA);
+/* The QPhandler of every member, on the device: the caller side of a lock-step SQP loop (src/QPhandler.cpp) without a round trip
+ * of the QP vectors through the host. The layer reads the shape QPhandler builds (src/QPhandler.cpp:39-51, NEW_FORMULATION=false,
+ * qpOASES branch): member q has m_q = nC[q] constraints and n_q = nV[q] - 2 nC[q] NLP variables, its QP variables are (p, u, v) --
+ * the reading handle_error makes of the slack positions. "NLP layout": pooled over the batch, member q owns n_q entries starting at
+ * offV[q] - 2 offC[q] (offV, offC: where its entries start in g and in lbA). "Constraint layout": the layout of lbA.
+ *
+ * rsqp_batch_handler_set_problem: the NLP bounds of every member, fixed for a run; host pointers, copied once. x_l, x_u: NLP layout;
+ * c_l, c_u: constraint layout (may be NULL when the batch has no constraints). +-inf allowed. RSQP_ERR_ARG when a member has
+ * nV < 2 nC + 1 (no NLP variable left beside the slacks). */
+int rsqp_batch_handler_set_problem(rsqp_batch *b, const double *x_l, const double *x_u, const double *c_l, const double *c_u);
+enum { RSQP_HU_SET = 1, RSQP_HU_BOUNDS = 2, RSQP_HU_DELTA = 4, RSQP_HU_PENALTY = 8, RSQP_HU_GRAD = 16, RSQP_HU_UBA = 32 };
+typedef struct {
+    const int *what;            /* nq: RSQP_HU_* bits per member; 0 = this member is not touched            */
+    const double *delta, *rho;  /* nq                                                                        */
+    const double *x_k, *grad;   /* NLP layout; grad may be NULL (the LP handler, QPhandler::set_g(rho), :657-660) */
+    const double *c_k;          /* constraint layout                                                         */
+} rsqp_handler_iterate;
+/* rsqp_batch_handler_update: member q gets what a single QPhandler writes through its per-element setters, chosen by W = what[q]
+ * with the precedence of Algorithm::setupQP (src/Algorithm.cpp:645-697); n = n_q, INF = 1e18 (Utils.hpp:35):
+ *   W & SET        set_bounds + set_g (:167-201, 272-297): lbA = c_l - c_k, ubA = c_u - c_k; lb[i<n] = max(x_l - x_k, -delta),
+ *                  ub[i<n] = min(x_u - x_k, delta); lb[n..) = 0, ub[n..) = INF; g[i<n] = grad (0 when grad == NULL), g[n..) = rho.
+ *                  SET includes everything: the other bits are ignored.
+ *   else W & BOUNDS  update_bounds (:342-368): lbA, lb[i<n], ub[i<n] -- and ubA ONLY with RSQP_HU_UBA: the reference's qpOASES
+ *                  branch leaves ubA stale (:358-360), which turns its own run infeasible after the first accepted step when a
+ *                  constraint is an equality; a driver that wants the correct value says UBA (handler.py update_bounds(refresh_ubA=)).
+ *   else W & DELTA   update_delta (:533-567): lb[i<n], ub[i<n].
+ *   W & PENALTY    update_penalty (:430-441): g[n..) = rho.
+ *   W & GRAD       update_grad (:450-463): g[i<n] = grad; ignored when grad == NULL.
+ * The formulas are one subtraction and one max / min per entry: the pools hold the host's values bit for bit. Nothing else of a
+ * member is written and a member with W == 0 keeps every byte; the mask of rsqp_batch_set_members plays no role, the word is the
+ * mask. on_device == 0: host pointers (staged at first use); != 0: every pointer of *it is DEVICE memory of the batch's device, and
+ * the caller guarantees that its contents are complete before the call. what, delta, rho, x_k (and c_k when the batch has
+ * constraints) are required, and rsqp_batch_handler_set_problem must have been called: RSQP_ERR_ARG before any device call
+ * otherwise. The update marks, firstQPsolved_ and the stored factors are untouched: vectors never raise Update_A / Update_H.
+ * Matrices stay with rsqp_batch_set_matrix_values_of (A keeps the [J I -I] layout the batch was created with, H = blkdiag(H_k, 0)
+ * has the entries of H_k). Returns when the pools are written. */
+int rsqp_batch_handler_update(rsqp_batch *b, const rsqp_handler_iterate *it, int on_device);
+/* what Algorithm takes from a solved QP (src/Algorithm.cpp:84, 609-622, 889), from the result pools of the last solve, whichever
+ * call wrote them: p = x[0..n), lam_x = y[0..n) (NLP layout), lam_c = y[nV..nV+m) (constraint layout), norm_p = max |p_i|,
+ * infea_model = sum over i >= n of |x_i| (get_infea_measure_model, src/QPhandler.cpp:592-594; a tree sum: it differs from the
+ * index-order sum by rounding) (nq entries each). Every output may be NULL; on_device as above (outputs in DEVICE memory). For a
+ * member no solve has touched the values are unspecified. Needs rsqp_batch_handler_set_problem (the size check), else RSQP_ERR_ARG. */
+int rsqp_batch_handler_get_step(rsqp_batch *b, double *p, double *lam_c, double *lam_x, double *infea_model,
+                                double *norm_p, int on_device);
+/* the vector pools as they are on the device (mirror of rsqp_get_vector), in the layout of rsqp_batch_set_vectors; any may be NULL */
+int rsqp_batch_get_vectors(rsqp_batch *b, double *g, double *lb, double *ub, double *lbA, double *ubA);
 int rsqp_batch_sync(rsqp_batch *b);
 /* keep != 0 (default): every solve writes the state a hot start needs (factors, iterate, multipliers,
  * working set: what a qpOASES SQProblem object keeps between init / hotstart calls) back to HBM.

@@ -6,6 +6,7 @@ and every call that needs a GPU returns ``RSQP_ERR_DEVICE`` -> ``RsqpError`` wit
 """
 import ctypes as C
 import os
+import sys
 
 import numpy as np
 
@@ -15,6 +16,7 @@ LIB_PATH = os.environ.get("RSQP_LIB") or os.path.join(_HERE, "lib", "librsqp_hip
 OK = 0
 ERR_ARG, ERR_DEVICE, ERR_TOO_LARGE, ERR_WORKING_SET = -1, -2, -3, -4
 VEC_G, VEC_LB, VEC_UB, VEC_LBA, VEC_UBA = range(5)
+HU_SET, HU_BOUNDS, HU_DELTA, HU_PENALTY, HU_GRAD, HU_UBA = 1, 2, 4, 8, 16, 32   # RSQP_HU_*: the words of Batch.handler_update
 MODE_COLD, MODE_HOT_VECTORS, MODE_HOT_MATRICES, MODE_WARM_REINIT = range(4)
 QP_OPTIMAL, QPERROR_INFEASIBLE, QPERROR_UNBOUNDED = 20, 22, 23
 ACTIVE_ABOVE, ACTIVE_BELOW, ACTIVE_BOTH_SIDE, INACTIVE = 1, -1, -99, 0
@@ -94,6 +96,10 @@ SYMBOLS = {
     "rsqp_batch_set_members": (C.c_int, [C.c_void_p, ip]),
     "rsqp_batch_set_matrix_values_of": (C.c_int, [C.c_void_p, ip, dp, dp]),
     "rsqp_batch_set_vectors_of": (C.c_int, [C.c_void_p, ip, dp, dp, dp, dp, dp]),
+    "rsqp_batch_handler_set_problem": (C.c_int, [C.c_void_p, dp, dp, dp, dp]),
+    "rsqp_batch_handler_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "rsqp_batch_handler_get_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "rsqp_batch_get_vectors": (C.c_int, [C.c_void_p, dp, dp, dp, dp, dp]),
     "rsqp_batch_sync": (C.c_int, [C.c_void_p]),
     "rsqp_batch_set_keep_state": (C.c_int, [C.c_void_p, C.c_int]),
     "rsqp_batch_get_last_kernel": (C.c_int, [C.c_void_p]),
@@ -130,6 +136,12 @@ class OptimalityStatus(C.Structure):
                 ("KKT_error", C.c_double)]
 
 
+class HandlerIterate(C.Structure):
+    """rsqp_handler_iterate: host or device addresses, as handler_update's on_device says"""
+    _fields_ = [("what", C.c_void_p), ("delta", C.c_void_p), ("rho", C.c_void_p), ("x_k", C.c_void_p), ("grad", C.c_void_p),
+                ("c_k", C.c_void_p)]
+
+
 class RsqpError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("rsqp error %d: %s" % (code, msg))
@@ -137,14 +149,16 @@ class RsqpError(RuntimeError):
 
 
 _LIB = None
+_TORCH_FIRST = False    # torch was imported before the library was loaded: its copy of the HIP runtime serves both (device_torch)
 
 
 def lib():
     """Load librsqp_hip.so; raises if it is missing (there is no fallback path)."""
-    global _LIB
+    global _LIB, _TORCH_FIRST
     if _LIB is None:
         if not os.path.exists(LIB_PATH):
             raise ImportError("%s not built: run `python -c 'import __graft_entry__ as g; g.build()'`" % LIB_PATH)
+        _TORCH_FIRST = "torch" in sys.modules
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in SYMBOLS.items():
             f = getattr(L, name)
@@ -152,6 +166,17 @@ def lib():
             f.argtypes = args
         _LIB = L
     return _LIB
+
+
+def device_torch():
+    """torch, for the calls that take or make device tensors. torch ships its own copy of the HIP runtime, with the soname the
+    library asks for: imported BEFORE the library is loaded, that copy serves both and a tensor's data_ptr() is memory of the
+    runtime the batch runs on. The other order leaves two runtimes in the process, and torch finds no GPU."""
+    lib()
+    if not _TORCH_FIRST:
+        raise RuntimeError("device tensors need `import torch` before restartsqp_amd.capi loads librsqp_hip.so (one HIP runtime)")
+    import torch
+    return torch
 
 
 def check(rc):
@@ -442,6 +467,7 @@ class Batch:
         check(lib().rsqp_batch_create(self.nq, _ip(self.nV), _ip(self.nC), _ip(Ajc), _ip(Air), _dp(Aval), _ip(Hjc),
                                       _ip(Hir), _dp(Hval), device, C.byref(h)))
         self._h = h
+        self.device = device
         self.offV = np.concatenate([[0], np.cumsum(self.nV)]).astype(np.int64)
         self.offC = np.concatenate([[0], np.cumsum(self.nC)]).astype(np.int64)
         self.set_vectors_from(problems)
@@ -489,6 +515,85 @@ class Batch:
         else:
             m = self._mask(members)
             check(lib().rsqp_batch_set_matrix_values_of(self._h, _ip(m), _dp(Aval), _dp(Hval)))
+
+    # ---- the QPhandler of every member (rsqp_batch_handler_*): NLP layout = member q owns nV[q] - 2 nC[q] entries, pooled ----
+    def _handler_sizes(self):
+        sV, sC = int(np.sum(self.nV)), int(np.sum(self.nC))
+        return sV - 2 * sC, sC
+
+    @staticmethod
+    def _sized(a, n, name, dtype=np.float64):
+        """a host array of exactly n entries (None stays None)"""
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=dtype)
+        if a.ndim != 1 or a.size != n:
+            raise ValueError("%s has %d entries, the batch needs %d" % (name, a.size, n))
+        return a
+
+    @staticmethod
+    def _dev_addr(t, n, name, dtype="float64"):
+        """the address of a device tensor (torch, or anything with data_ptr / numel / dtype / is_contiguous) of n entries"""
+        if t is None:
+            return None
+        if int(t.numel()) != n:
+            raise ValueError("%s has %d entries, the batch needs %d" % (name, int(t.numel()), n))
+        if not str(t.dtype).endswith(dtype) or not t.is_contiguous() or not getattr(t, "is_cuda", True):
+            raise ValueError("%s must be a contiguous %s tensor on the batch's device" % (name, dtype))
+        return int(t.data_ptr())
+
+    def handler_set_problem(self, x_l, x_u, c_l=None, c_u=None):
+        """the NLP bounds of every member, fixed for a run: x_l, x_u in the NLP layout, c_l, c_u in the layout of lbA"""
+        sN, sC = self._handler_sizes()
+        x_l, x_u = self._sized(x_l, sN, "x_l"), self._sized(x_u, sN, "x_u")
+        c_l, c_u = self._sized(c_l, sC, "c_l"), self._sized(c_u, sC, "c_u")
+        if x_l is None or x_u is None or (sC > 0 and (c_l is None or c_u is None)):
+            raise ValueError("x_l, x_u (and c_l, c_u when the batch has constraints) are required")
+        check(lib().rsqp_batch_handler_set_problem(self._h, _dp(x_l), _dp(x_u), _dp(c_l), _dp(c_u)))
+
+    def handler_update(self, what, delta, rho, x_k, c_k, grad=None, on_device=False):
+        """QPhandler's setters for every member on the device: what[q] = HU_* bits (0: member q is not touched); delta, rho: nq;
+        x_k, grad: NLP layout (grad None: the LP handler's set_g(rho)); c_k: the layout of lbA. on_device: every argument is a
+        tensor on the batch's device (what: int32, the others float64), complete before the call"""
+        sN, sC = self._handler_sizes()
+        spec = (("what", what, self.nq), ("delta", delta, self.nq), ("rho", rho, self.nq), ("x_k", x_k, sN), ("grad", grad, sN),
+                ("c_k", c_k, sC))
+        if on_device:
+            addr = [self._dev_addr(a, n, name, "int32" if name == "what" else "float64") for name, a, n in spec]
+            keep = None
+        else:
+            keep = [self._sized(a, n, name, np.int32 if name == "what" else np.float64) for name, a, n in spec]
+            addr = [None if a is None else a.ctypes.data for a in keep]
+        for (name, _, n), a in zip(spec, addr):
+            if a is None and name != "grad" and n > 0:
+                raise ValueError("%s is required" % name)
+        it = HandlerIterate(*addr)
+        check(lib().rsqp_batch_handler_update(self._h, C.addressof(it), int(bool(on_device))))
+        del keep
+
+    def handler_step(self, on_device=False, out=None):
+        """what Algorithm reads from the last solve, as a dict: p, lam_x (NLP layout), lam_c (layout of lbA), infea_model, norm_p
+        (nq). on_device: written into float64 tensors on the batch's device -- those of `out` (same keys), else new torch tensors"""
+        sN, sC = self._handler_sizes()
+        sizes = (("p", sN), ("lam_c", sC), ("lam_x", sN), ("infea_model", self.nq), ("norm_p", self.nq))
+        if on_device:
+            if out is None:
+                torch = device_torch()
+                dev = "cuda" if getattr(self, "device", -1) < 0 else "cuda:%d" % self.device
+                out = {k: torch.empty(n, dtype=torch.float64, device=dev) for k, n in sizes}
+            addr = [self._dev_addr(out[k], n, k) for k, n in sizes]
+        else:
+            out = {k: np.zeros(n) for k, n in sizes}
+            addr = [out[k].ctypes.data for k, n in sizes]
+        check(lib().rsqp_batch_handler_get_step(self._h, *addr, int(bool(on_device))))
+        return out
+
+    def get_vectors(self):
+        """(g, lb, ub, lbA, ubA) as the pools hold them on the device, in the layout of set_vectors"""
+        sV, sC = int(np.sum(self.nV)), int(np.sum(self.nC))
+        v = [np.zeros(sV), np.zeros(sV), np.zeros(sV), np.zeros(sC), np.zeros(sC)]
+        check(lib().rsqp_batch_get_vectors(self._h, *[_dp(a) for a in v]))
+        return tuple(v)
 
     def solve(self, mode=MODE_COLD, max_nWSR=1000, sync=True):
         check(lib().rsqp_batch_solve(self._h, mode, max_nWSR))

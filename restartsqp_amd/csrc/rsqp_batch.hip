@@ -68,6 +68,13 @@ struct rsqp_batch {
     DevBuf<double> stage;
     DevBuf<int> named;
     DevBuf<long long> Auoff, Huoff;
+    // the QPhandler layer (rsqp_batch_handler_*): the NLP bounds of the members (x_l, x_u in the NLP layout, c_l, c_u in the
+    // constraint layout), and the staging of host-pointer calls, allocated at first use -- the caller's arrays are packed into one
+    // pinned block and cross in one copy each way (the stage of the named setters is too small for nq-sized words)
+    DevBuf<double> h_xl, h_xu, h_cl, h_cu, h_in, h_out;
+    double *h_pin = nullptr;              // pinned, max(words of an update, words of a step)
+    long long sumN = 0;                   // NLP variables of the batch: sumV - 2 sumC
+    bool have_problem = false;            // rsqp_batch_handler_set_problem has run
     // optimizeLP per member (rsqp_batch_optimize_lp): the members' descriptors with H absent and hreg = regVal of the member's last
     // init (written on the device, kept across hot starts), and the pool of the proximal step's gradients g - regVal x
     DevBuf<QPDesc> d_desc_lp;
@@ -91,6 +98,7 @@ struct rsqp_batch {
         if (ev3) (void)hipEventDestroy(ev3);
         if (stream) (void)hipStreamDestroy(stream);
         if (used_host) (void)hipHostFree(used_host);
+        if (h_pin) (void)hipHostFree(h_pin);
     }
 };
 
@@ -466,6 +474,212 @@ extern "C" int rsqp_batch_set_matrix_values_of(rsqp_batch *b, const int *members
         }
     }
     HIPCHK(hipStreamSynchronize(b->stream));
+    return RSQP_OK;
+}
+
+// ---------------------------------------------------------------------------------
+// the QPhandler of every member on the device (src/QPhandler.cpp; rsqp_batch_handler_* of rsqp_hip.h): the five QP vectors from an
+// NLP iterate, and what Algorithm reads back from a solved QP. Member q: m = nC constraints, n = nV - 2 nC NLP variables, QP
+// variables (p, u, v) (:39-51); its NLP entries start at offV - 2 offC
+// ---------------------------------------------------------------------------------
+namespace {
+constexpr double HANDLER_INF = 1.0e18;   // INF of the reference (Utils.hpp:35)
+
+// one thread per entry of the concatenation g | lb | ub | lbA | ubA; the member of an entry as in batch_masked_copy_kernel: a
+// division in a one-shape batch (uniV > 0), else the last member whose offset is at or before the entry. Every formula is one
+// subtraction and one fmax / fmin, as the host states them (QPhandler.cpp:167-201, 272-297, 342-368, 430-463, 533-567)
+struct HandlerUpdate {
+    int nq, uniV, uniC;   // uniV > 0: every member is uniV x uniC
+    int sumV, sumC;
+    const QPDesc *desc;
+    const int *what;
+    const double *delta, *rho, *x_k, *grad, *c_k;   // the iterate (rsqp_handler_iterate)
+    const double *x_l, *x_u, *c_l, *c_u;            // rsqp_batch_handler_set_problem
+    double *g, *lb, *ub, *lbA, *ubA;
+};
+__global__ void __launch_bounds__(256) batch_handler_update_kernel(HandlerUpdate a) {
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= 3LL * a.sumV + 2LL * a.sumC) return;
+    const bool isV = e < 3LL * a.sumV;
+    int s, k;
+    if (isV) { s = (e >= a.sumV) + (e >= 2LL * a.sumV); k = (int)(e - (long long)s * a.sumV); }
+    else { k = (int)(e - 3LL * a.sumV); s = 3 + (k >= a.sumC); if (s == 4) k -= a.sumC; }
+    int q, nV, nC, offV, offC;
+    if (a.uniV > 0) {
+        nV = a.uniV; nC = a.uniC;
+        q = isV ? k / nV : k / nC;       // (a constraint entry exists: nC > 0)
+        offV = q * nV; offC = q * nC;
+    } else {
+        int lo = 0, hi = a.nq - 1;       // (members without constraints own no entry of lbA / ubA)
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if ((isV ? a.desc[mid].offV : a.desc[mid].offC) <= k) lo = mid; else hi = mid - 1;
+        }
+        q = lo;
+        nV = a.desc[q].nV; nC = a.desc[q].nC; offV = a.desc[q].offV; offC = a.desc[q].offC;
+    }
+    const int W = a.what[q];
+    if (W == 0) return;
+    const bool set = (W & RSQP_HU_SET) != 0;
+    if (!isV) {
+        if (s == 3) { if (set || (W & RSQP_HU_BOUNDS)) a.lbA[k] = a.c_l[k] - a.c_k[k]; }
+        else if (set || ((W & RSQP_HU_BOUNDS) && (W & RSQP_HU_UBA))) a.ubA[k] = a.c_u[k] - a.c_k[k];
+        return;
+    }
+    const int i = k - offV, n = nV - 2 * nC, j = offV - 2 * offC + i;   // j: the entry in the NLP layout (i < n)
+    if (i >= n) {            // a slack variable
+        if (s == 0) { if (set || (W & RSQP_HU_PENALTY)) a.g[k] = a.rho[q]; }
+        else if (set) { if (s == 1) a.lb[k] = 0.0; else a.ub[k] = HANDLER_INF; }
+        return;
+    }
+    if (s == 0) {
+        if (set) a.g[k] = a.grad ? a.grad[j] : 0.0;
+        else if ((W & RSQP_HU_GRAD) && a.grad) a.g[k] = a.grad[j];
+    } else if (set || (W & (RSQP_HU_BOUNDS | RSQP_HU_DELTA))) {
+        if (s == 1) a.lb[k] = fmax(a.x_l[j] - a.x_k[j], -a.delta[q]);
+        else a.ub[k] = fmin(a.x_u[j] - a.x_k[j], a.delta[q]);
+    }
+}
+
+// G lanes per member (8 for hs071-scale batches, else a wavefront): the copies walk the member's entries G at a time, norm_p is a
+// maximum over the sub-group (exact in any order), infea_model a sum over it. Lanes past the last member skip the loops and stay
+// in the shuffles. Any output may be null
+template <int G>
+__global__ void __launch_bounds__(256)
+batch_handler_step_kernel(int nq, const QPDesc *__restrict__ desc, const double *__restrict__ x, const double *__restrict__ y,
+                          double *__restrict__ p, double *__restrict__ lam_c, double *__restrict__ lam_x,
+                          double *__restrict__ infea, double *__restrict__ norm_p) {
+    const int q = (int)(((long long)blockIdx.x * blockDim.x + threadIdx.x) / G), lane = (int)threadIdx.x % G;
+    double mx = 0.0, sm = 0.0;
+    if (q < nq) {
+        const int nV = desc[q].nV, nC = desc[q].nC, offV = desc[q].offV, offC = desc[q].offC;
+        const int n = nV - 2 * nC, offN = offV - 2 * offC, offY = offV + offC;
+        for (int i = lane; i < n; i += G) {
+            const double v = x[offV + i];
+            if (p) p[offN + i] = v;
+            if (lam_x) lam_x[offN + i] = y[offY + i];
+            mx = fmax(mx, fabs(v));
+        }
+        if (lam_c)
+            for (int i = lane; i < nC; i += G) lam_c[offC + i] = y[offY + nV + i];
+        for (int i = n + lane; i < nV; i += G) sm += fabs(x[offV + i]);
+    }
+    for (int o = G / 2; o > 0; o >>= 1) {
+        mx = fmax(mx, __shfl_xor(mx, o, G));
+        sm += __shfl_xor(sm, o, G);
+    }
+    if (q < nq && lane == 0) {
+        if (norm_p) norm_p[q] = mx;
+        if (infea) infea[q] = sm;
+    }
+}
+
+// words (doubles) of the packed block of a host-pointer update: delta | rho | x_k | grad | c_k | what (ints); a step's is smaller
+long long handler_in_words(const rsqp_batch *b) { return 2LL * b->nq + 2 * b->sumN + b->sumC + (b->nq + 1) / 2; }
+int ensure_handler_stage(rsqp_batch *b) {
+    if (b->h_pin) return RSQP_OK;
+    const size_t w = (size_t)handler_in_words(b);
+    HIPCHK(b->h_in.alloc(w, false)); HIPCHK(b->h_out.alloc(w, false));
+    HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&b->h_pin), sizeof(double) * w, hipHostMallocDefault));
+    return RSQP_OK;
+}
+}  // namespace
+
+extern "C" int rsqp_batch_handler_set_problem(rsqp_batch *b, const double *x_l, const double *x_u, const double *c_l, const double *c_u) {
+    if (!b || !x_l || !x_u || (b->sumC > 0 && (!c_l || !c_u))) return fail(RSQP_ERR_ARG, "rsqp_batch_handler_set_problem");
+    for (int q = 0; q < b->nq; q++)
+        if (b->desc[q].nV < 2 * b->desc[q].nC + 1)
+            return fail(RSQP_ERR_ARG, "rsqp_batch_handler_set_problem: member " + std::to_string(q) + " has nV < 2 nC + 1: not the (p, u, v) shape of QPhandler");
+    HIPCHK(hipSetDevice(b->device));
+    b->sumN = b->sumV - 2 * b->sumC;
+    HIPCHK(b->h_xl.alloc(b->sumN, false)); HIPCHK(b->h_xu.alloc(b->sumN, false));
+    HIPCHK(b->h_cl.alloc(b->sumC, false)); HIPCHK(b->h_cu.alloc(b->sumC, false));
+    HIPCHK(b->h_xl.upload(x_l, b->sumN)); HIPCHK(b->h_xu.upload(x_u, b->sumN));
+    HIPCHK(b->h_cl.upload(c_l, b->sumC)); HIPCHK(b->h_cu.upload(c_u, b->sumC));
+    b->have_problem = true;
+    return RSQP_OK;
+}
+
+extern "C" int rsqp_batch_handler_update(rsqp_batch *b, const rsqp_handler_iterate *it, int on_device) {
+    if (!b || !it || !it->what || !it->delta || !it->rho || !it->x_k || (b->sumC > 0 && !it->c_k))
+        return fail(RSQP_ERR_ARG, "rsqp_batch_handler_update: what, delta, rho, x_k (and c_k) are required");
+    if (!b->have_problem) return fail(RSQP_ERR_ARG, "rsqp_batch_handler_update: rsqp_batch_handler_set_problem has not been called");
+    HIPCHK(hipSetDevice(b->device));
+    HandlerUpdate a;
+    std::memset(&a, 0, sizeof(a));
+    if (on_device) {
+        a.what = it->what; a.delta = it->delta; a.rho = it->rho; a.x_k = it->x_k; a.grad = it->grad; a.c_k = it->c_k;
+    } else {
+        const int rc = ensure_handler_stage(b);
+        if (rc != RSQP_OK) return rc;
+        const size_t nq = (size_t)b->nq, sN = (size_t)b->sumN, sC = (size_t)b->sumC;
+        const size_t o_rho = nq, o_x = 2 * nq, o_g = o_x + sN, o_c = o_g + sN, o_w = o_c + sC;
+        // (the pinned block is free: every call that uses it waits for its copy)
+        std::memcpy(b->h_pin, it->delta, sizeof(double) * nq); std::memcpy(b->h_pin + o_rho, it->rho, sizeof(double) * nq);
+        std::memcpy(b->h_pin + o_x, it->x_k, sizeof(double) * sN);
+        if (it->grad) std::memcpy(b->h_pin + o_g, it->grad, sizeof(double) * sN);
+        if (sC > 0) std::memcpy(b->h_pin + o_c, it->c_k, sizeof(double) * sC);
+        std::memcpy(b->h_pin + o_w, it->what, sizeof(int) * nq);
+        HIPCHK(hipMemcpyAsync(b->h_in.p, b->h_pin, sizeof(double) * (size_t)handler_in_words(b), hipMemcpyHostToDevice, b->stream));
+        double *const d = b->h_in.p;
+        a.delta = d; a.rho = d + o_rho; a.x_k = d + o_x; a.grad = it->grad ? d + o_g : nullptr; a.c_k = d + o_c;
+        a.what = reinterpret_cast<const int *>(d + o_w);
+    }
+    a.nq = b->nq; a.sumV = (int)b->sumV; a.sumC = (int)b->sumC; a.desc = b->d_desc.p;
+    a.uniV = (b->uniV > 0 && b->uniC >= 0) ? b->uniV : 0; a.uniC = a.uniV > 0 ? b->uniC : 0;
+    a.x_l = b->h_xl.p; a.x_u = b->h_xu.p; a.c_l = b->h_cl.p; a.c_u = b->h_cu.p;
+    a.g = b->g.p; a.lb = b->lb.p; a.ub = b->ub.p; a.lbA = b->lbA.p; a.ubA = b->ubA.p;
+    const long long n = 3 * b->sumV + 2 * b->sumC;
+    hipLaunchKernelGGL(batch_handler_update_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, b->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return RSQP_OK;
+}
+
+extern "C" int rsqp_batch_handler_get_step(rsqp_batch *b, double *p, double *lam_c, double *lam_x, double *infea_model,
+                                           double *norm_p, int on_device) {
+    if (!b) return fail(RSQP_ERR_ARG, "null batch");
+    if (!b->have_problem) return fail(RSQP_ERR_ARG, "rsqp_batch_handler_get_step: rsqp_batch_handler_set_problem has not been called");
+    HIPCHK(hipSetDevice(b->device));
+    const size_t nq = (size_t)b->nq, sN = (size_t)b->sumN, sC = (size_t)b->sumC;
+    const size_t o_lx = sN, o_lc = 2 * sN, o_in = o_lc + sC, o_np = o_in + nq, words = o_np + nq;
+    double *dp = p, *dlc = lam_c, *dlx = lam_x, *din = infea_model, *dnp = norm_p;
+    if (!on_device) {
+        const int rc = ensure_handler_stage(b);
+        if (rc != RSQP_OK) return rc;
+        double *const d = b->h_out.p;
+        dp = p ? d : nullptr; dlx = lam_x ? d + o_lx : nullptr; dlc = lam_c ? d + o_lc : nullptr;
+        din = infea_model ? d + o_in : nullptr; dnp = norm_p ? d + o_np : nullptr;
+    }
+    // hs071-scale members: 8 lanes each, eight members per wavefront
+    const int G = (b->nVmax + b->nCmax <= 16) ? 8 : 64;
+    const dim3 grid((unsigned)(((long long)b->nq * G + 255) / 256)), block(256);
+    if (G == 8)
+        hipLaunchKernelGGL(batch_handler_step_kernel<8>, grid, block, 0, b->stream, b->nq, b->d_desc.p, b->x.p, b->y.p, dp, dlc, dlx, din, dnp);
+    else
+        hipLaunchKernelGGL(batch_handler_step_kernel<64>, grid, block, 0, b->stream, b->nq, b->d_desc.p, b->x.p, b->y.p, dp, dlc, dlx, din, dnp);
+    HIPCHK(hipGetLastError());
+    if (!on_device) HIPCHK(hipMemcpyAsync(b->h_pin, b->h_out.p, sizeof(double) * words, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    if (!on_device) {
+        if (p) std::memcpy(p, b->h_pin, sizeof(double) * sN);
+        if (lam_x) std::memcpy(lam_x, b->h_pin + o_lx, sizeof(double) * sN);
+        if (lam_c) std::memcpy(lam_c, b->h_pin + o_lc, sizeof(double) * sC);
+        if (infea_model) std::memcpy(infea_model, b->h_pin + o_in, sizeof(double) * nq);
+        if (norm_p) std::memcpy(norm_p, b->h_pin + o_np, sizeof(double) * nq);
+    }
+    return RSQP_OK;
+}
+
+extern "C" int rsqp_batch_get_vectors(rsqp_batch *b, double *g, double *lb, double *ub, double *lbA, double *ubA) {
+    if (!b) return fail(RSQP_ERR_ARG, "null batch");
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    if (g) HIPCHK(b->g.download(g, b->sumV));
+    if (lb) HIPCHK(b->lb.download(lb, b->sumV));
+    if (ub) HIPCHK(b->ub.download(ub, b->sumV));
+    if (lbA) HIPCHK(b->lbA.download(lbA, b->sumC));
+    if (ubA) HIPCHK(b->ubA.download(ubA, b->sumC));
     return RSQP_OK;
 }
 

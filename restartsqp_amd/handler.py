@@ -8,6 +8,7 @@ certificate. NEW_FORMULATION=false, non-QORE branch.
 """
 import numpy as np
 
+from . import capi
 from .interface import HipQPInterface
 from .sqptypes import INF, QP, QP_NOT_OPTIMAL, IdentityInfo, NLPInfo, Options
 
@@ -109,3 +110,169 @@ class QPhandler:
     def get_infea_measure_model(self):  # :592-594, oneNorm of the slack part
         x = self.solverInterface_.get_optimal_solution()
         return float(np.abs(x[self.nlp_info_.nVar:]).sum())
+
+
+# ------------------------------------------------------------------------------------
+# the handler of every member of a batch (rsqp_batch_handler_* of include/rsqp_hip.h)
+# ------------------------------------------------------------------------------------
+def batch_handler_reference(state, what, delta, rho, x_k, c_k, grad, n, m, x_l, x_u, c_l, c_u):
+    """The update rule of rsqp_batch_handler_update restated in numpy: the expected value of every test.
+
+    state: (g, lb, ub, lbA, ubA) pooled as Batch.set_vectors takes them; a new tuple is returned. n[q], m[q]: NLP variables and
+    constraints of member q (its QP has n + 2 m variables). x_k, grad, x_l, x_u: NLP layout; c_k, c_l, c_u: constraint layout;
+    what, delta, rho: one entry per member. Precedence as Algorithm::setupQP (src/Algorithm.cpp:645-697): SET (set_bounds + set_g,
+    src/QPhandler.cpp:167-201, 272-297) includes everything; else BOUNDS (update_bounds, :342-368; ubA only with UBA) before DELTA
+    (update_delta, :533-567); PENALTY (:430-441) and GRAD (:450-463; ignored without grad) beside them."""
+    g, lb, ub, lbA, ubA = (np.array(a, dtype=np.float64) for a in state)
+    oN = oC = oV = 0
+    for q in range(len(n)):
+        nq_, mq, W = int(n[q]), int(m[q]), int(what[q])
+        N, Cc, V, S = slice(oN, oN + nq_), slice(oC, oC + mq), slice(oV, oV + nq_), slice(oV + nq_, oV + nq_ + 2 * mq)
+        oN, oC, oV = oN + nq_, oC + mq, oV + nq_ + 2 * mq
+        if W & capi.HU_SET:
+            lbA[Cc] = c_l[Cc] - c_k[Cc]; ubA[Cc] = c_u[Cc] - c_k[Cc]
+            lb[V] = np.maximum(x_l[N] - x_k[N], -delta[q]); ub[V] = np.minimum(x_u[N] - x_k[N], delta[q])
+            lb[S] = 0.0; ub[S] = INF
+            g[V] = 0.0 if grad is None else grad[N]
+            g[S] = rho[q]
+            continue
+        if W & capi.HU_BOUNDS:
+            lbA[Cc] = c_l[Cc] - c_k[Cc]
+            if W & capi.HU_UBA:
+                ubA[Cc] = c_u[Cc] - c_k[Cc]
+        if W & (capi.HU_BOUNDS | capi.HU_DELTA):
+            lb[V] = np.maximum(x_l[N] - x_k[N], -delta[q]); ub[V] = np.minimum(x_u[N] - x_k[N], delta[q])
+        if W & capi.HU_PENALTY:
+            g[S] = rho[q]
+        if W & capi.HU_GRAD and grad is not None:
+            g[V] = grad[N]
+    return g, lb, ub, lbA, ubA
+
+
+class BatchQPhandler:
+    """QPhandler for every member of a ``capi.Batch`` whose members have the (p, u, v) shape: the reference's method names, each with
+    a member mask first. A call notes its arguments for the named members and ORs bits into a pending word per member;
+    ``solveQP`` / ``solveLP`` flush all words with ONE ``Batch.handler_update`` and solve for the members given.
+
+    Arrays are pooled over the batch (x_k, grad: NLP layout; c_k: the layout of lbA); only the named members' entries are read.
+    delta and rho are scalars or one entry per member. on_device: x_k, c_k and grad are torch tensors on the batch's device, the
+    words and the iterate stay there, and ``step(on_device=True)`` leaves the step data there as well."""
+
+    def __init__(self, batch, x_l, x_u, c_l=None, c_u=None, on_device=False):
+        self.batch, self.on_device = batch, bool(on_device)
+        batch.handler_set_problem(x_l, x_u, c_l, c_u)
+        self.m = np.asarray(batch.nC, dtype=np.int64)
+        self.n = np.asarray(batch.nV, dtype=np.int64) - 2 * self.m
+        nq = batch.nq
+        self.what = np.zeros(nq, np.int32)
+        self._halves = np.zeros(nq, np.int32)          # 1 set_bounds seen, 2 set_g seen: SET is both (setupQP :645-660)
+        self.delta, self.rho = np.zeros(nq), np.zeros(nq)
+        self.have_grad = False
+        memN, memC = np.repeat(np.arange(nq), self.n), np.repeat(np.arange(nq), self.m)
+        sN, sC = int(self.n.sum()), int(self.m.sum())
+        if self.on_device:
+            torch = capi.device_torch()
+            self._xp = torch
+            dev = "cuda" if getattr(batch, "device", -1) < 0 else "cuda:%d" % batch.device
+            self._memN, self._memC = torch.as_tensor(memN, device=dev), torch.as_tensor(memC, device=dev)
+            z = lambda k: torch.zeros(k, dtype=torch.float64, device=dev)
+            self._dev = dev
+        else:
+            self._xp = np
+            self._memN, self._memC = memN, memC
+            z = np.zeros
+        self.x_k, self.grad, self.c_k = z(sN), z(sN), z(sC)
+
+    # -- bookkeeping --
+    def _mask(self, members):
+        m = np.ones(self.batch.nq, bool) if members is None else np.asarray(members) != 0
+        if m.shape != (self.batch.nq,):
+            raise ValueError("the mask has %d entries, the batch has %d members" % (m.size, self.batch.nq))
+        return m
+
+    def _take(self, name, src, mask, mem):
+        """the named members' entries of a pooled array into the handler's copy"""
+        if self.on_device:
+            sel = self._xp.as_tensor(mask, device=self._dev)[mem]
+            setattr(self, name, self._xp.where(sel, src, getattr(self, name)))
+        else:
+            setattr(self, name, np.where(mask[mem], np.asarray(src, dtype=np.float64), getattr(self, name)))
+
+    def _bounds(self, mask, delta, x_k, c_k=None):
+        self.delta = np.where(mask, delta, self.delta)
+        self._take("x_k", x_k, mask, self._memN)
+        if c_k is not None:
+            self._take("c_k", c_k, mask, self._memC)
+
+    # -- the reference's setters --
+    def set_bounds(self, members, delta, x_k, c_k):                                   # QPhandler.cpp:167-201
+        mask = self._mask(members)
+        self._bounds(mask, delta, x_k, c_k)
+        self._halves[mask] |= 1
+
+    def set_g(self, members, grad, rho):                                              # :272-297; grad None: set_g(rho), :657-660
+        mask = self._mask(members)
+        self.rho = np.where(mask, rho, self.rho)
+        if grad is not None:
+            self._take("grad", grad, mask, self._memN)
+            self.have_grad = True
+        self._halves[mask] |= 2
+
+    def update_bounds(self, members, delta, x_k, c_k, refresh_ubA=False):             # :342-368 (ubA stays stale: QPhandler above)
+        mask = self._mask(members)
+        self._bounds(mask, delta, x_k, c_k)
+        self.what[mask] |= capi.HU_BOUNDS | (capi.HU_UBA if refresh_ubA else 0)
+
+    def update_delta(self, members, delta, x_k):                                      # :533-567
+        mask = self._mask(members)
+        self._bounds(mask, delta, x_k)
+        self.what[mask] |= capi.HU_DELTA
+
+    def update_penalty(self, members, rho):                                           # :430-441
+        mask = self._mask(members)
+        self.rho = np.where(mask, rho, self.rho)
+        self.what[mask] |= capi.HU_PENALTY
+
+    def update_grad(self, members, grad):                                             # :450-463
+        mask = self._mask(members)
+        self._take("grad", grad, mask, self._memN)
+        self.have_grad = True
+        self.what[mask] |= capi.HU_GRAD
+
+    # -- flush and solve --
+    def flush(self):
+        """one handler_update for everything pending; returns the words it sent"""
+        if np.any((self._halves != 0) & (self._halves != 3)):
+            raise ValueError("set_bounds and set_g go together (Algorithm::setupQP, src/Algorithm.cpp:645-660)")
+        what = np.where(self._halves == 3, capi.HU_SET, self.what).astype(np.int32)
+        self.what[:] = 0; self._halves[:] = 0
+        if not what.any():
+            return what
+        grad = self.grad if self.have_grad else None
+        if self.on_device:
+            t = self._xp
+            args = (t.as_tensor(what, device=self._dev), t.as_tensor(self.delta, device=self._dev),
+                    t.as_tensor(self.rho, device=self._dev), self.x_k, self.c_k, grad)
+            t.cuda.synchronize()                       # the inputs are complete before the call (torch fills them on its own stream)
+            self.batch.handler_update(*args, on_device=True)
+        else:
+            self.batch.handler_update(what, self.delta, self.rho, self.x_k, self.c_k, grad)
+        return what
+
+    def _solve(self, members, run):
+        self.flush()
+        self.batch.set_members(None if members is None else self._mask(members))
+        used = run()
+        ok, kkt = self.batch.test_optimality()
+        return used, ok, kkt
+
+    def solveQP(self, members=None):                                                  # :470-499 + the certificate (:580-587)
+        """flush, then optimize_qp for the members given (None: everybody) and the certificate: (nWSR_used, ok, KKT_error)"""
+        return self._solve(members, self.batch.optimize_qp)
+
+    def solveLP(self, members=None):                                                  # include/sqphot/QPhandler.hpp:66-68
+        return self._solve(members, self.batch.optimize_lp)
+
+    def step(self, on_device=None, out=None):
+        """p, lam_c, lam_x, infea_model (get_infea_measure_model, :592-594) and norm_p of the last solve (Batch.handler_step)"""
+        return self.batch.handler_step(self.on_device if on_device is None else on_device, out=out)

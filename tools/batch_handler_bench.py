@@ -1,0 +1,130 @@
+"""What one lock-step SQP iteration costs around the solve, on 65 536 hs071-shaped members (n = 4, m = 2): from a new iterate to
+the five QP vectors in the pools, the solve, and the step data (p, multipliers, norm_p, infea_model) back.
+
+    python tools/batch_handler_bench.py [--nq 65536] [--iters 30] [--parent-tree DIR]
+
+Routes, each in a process of its own under `timeout` (the driver stops at the first that fails or runs out of time):
+  a      the route before rsqp_batch_handler_*: QPhandler's formulas in numpy, rsqp_batch_set_vectors_of (all members named),
+         rsqp_batch_optimize_qp, rsqp_batch_get_results for all of x and y, the reductions in numpy. Needs nothing new, so
+         --parent-tree DIR runs it on another checkout as well (built there), in the same job.
+  b_host rsqp_batch_handler_update + rsqp_batch_optimize_qp + rsqp_batch_handler_get_step with host pointers.
+  b_dev  the same with the iterate and the step data in torch tensors on the device (torch imported before the library is loaded,
+         capi.device_torch); norm_p and infea_model, what the acceptance test of the host loop reads, are copied to the host.
+Iteration 0 is SET for everybody (a cold start), the others BOUNDS|UBA|GRAD (hot starts on new vectors); 3 warm-up iterations,
+then the median over --iters of the whole iteration and of its parts. One JSON line per route."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+WARMUP = 3
+
+
+def iterates(np, nq, count, seed=11):
+    """hs071's first iterate, perturbed per member and iteration: (delta, rho, x_k [nq,4], c_k [nq,2], grad [nq,4])"""
+    rng = np.random.default_rng(seed)
+    x0, c0, g0 = np.array([1.0, 5.0, 5.0, 1.0]), np.array([25.0, 52.0]), np.array([12.0, 1.0, 2.0, 11.0])
+    out = []
+    for _ in range(count):
+        x = np.clip(x0 * (1.0 + 0.02 * rng.normal(size=(nq, 4))), 1.0, 5.0)
+        out.append((np.ones(nq), np.ones(nq), x, c0 * (1.0 + 0.02 * rng.normal(size=(nq, 2))), g0 * (1.0 + 0.02 * rng.normal(size=(nq, 4)))))
+    return out
+
+
+def run_route(route, tree, nq, iters):
+    if route == "b_dev":
+        import torch
+    sys.path.insert(0, tree)
+    import numpy as np
+    from restartsqp_amd import capi, problems
+    base = problems.hs071_first_qp()
+    nlp = problems.hs071_nlp()
+    b = capi.Batch([base] * nq)
+    n, m, INF = 4, 2, 1.0e18
+    x_l, x_u, c_l, c_u = nlp["x_l"], nlp["x_u"], nlp["c_l"], nlp["c_u"]
+    if route != "a":
+        b.handler_set_problem(np.tile(x_l, nq), np.tile(x_u, nq), np.tile(c_l, nq), np.tile(c_u, nq))
+    its = iterates(np, nq, WARMUP + iters)
+    ones = np.ones(nq, np.int32)
+    first = np.full(nq, capi.HU_SET if route != "a" else 1, np.int32)
+    later = np.full(nq, (capi.HU_BOUNDS | capi.HU_UBA | capi.HU_GRAD) if route != "a" else 0, np.int32)
+    parts = {k: [] for k in ("vectors", "solve", "step", "total")}
+    extra = {k: [] for k in ("formulas", "upload", "download", "reduce")}
+    L = capi.lib()
+    sV, sC = nq * (n + 2 * m), nq * m
+    xbuf, ybuf = np.zeros(sV), np.zeros(sV + sC)
+    check = 0.0
+    for k, (delta, rho, x_k, c_k, grad) in enumerate(its):
+        if route == "b_dev":
+            dev = [torch.as_tensor(a.reshape(-1), device="cuda") for a in (first if k == 0 else later, delta, rho, x_k, c_k, grad)]
+            torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if route == "a":
+            g = np.empty((nq, n + 2 * m)); lb = np.zeros((nq, n + 2 * m)); ub = np.full((nq, n + 2 * m), INF)
+            g[:, :n] = grad; g[:, n:] = rho[:, None]
+            lb[:, :n] = np.maximum(x_l - x_k, -delta[:, None]); ub[:, :n] = np.minimum(x_u - x_k, delta[:, None])
+            lbA = c_l - c_k; ubA = c_u - c_k
+            t_f = time.perf_counter()
+            b.set_vectors(g.reshape(-1), lb.reshape(-1), ub.reshape(-1), lbA.reshape(-1), ubA.reshape(-1), members=ones)
+            extra["formulas"].append(t_f - t0); extra["upload"].append(time.perf_counter() - t_f)
+        elif route == "b_host":
+            b.handler_update(first if k == 0 else later, delta, rho, x_k.reshape(-1), c_k.reshape(-1), grad.reshape(-1))
+        else:
+            b.handler_update(dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], on_device=True)
+        t1 = time.perf_counter()
+        b.optimize_qp()
+        t2 = time.perf_counter()
+        if route == "a":
+            capi.check(L.rsqp_batch_get_results(b._h, xbuf.ctypes.data_as(capi.dp), ybuf.ctypes.data_as(capi.dp), None, None, None, None, None))
+            t_d = time.perf_counter()
+            X, Y = xbuf.reshape(nq, n + 2 * m), ybuf.reshape(nq, n + 3 * m)
+            p, lam_x, lam_c = X[:, :n], Y[:, :n], Y[:, n + 2 * m:]
+            norm_p, infea = np.abs(p).max(axis=1), np.abs(X[:, n:]).sum(axis=1)
+            extra["download"].append(t_d - t2); extra["reduce"].append(time.perf_counter() - t_d)
+        elif route == "b_host":
+            st = b.handler_step()
+            norm_p, infea = st["norm_p"], st["infea_model"]
+        else:
+            st = b.handler_step(on_device=True)
+            norm_p, infea = st["norm_p"].cpu().numpy(), st["infea_model"].cpu().numpy()
+        t3 = time.perf_counter()
+        check += float(norm_p.sum() + infea.sum())
+        if k >= WARMUP:
+            for name, v in (("vectors", t1 - t0), ("solve", t2 - t1), ("step", t3 - t2), ("total", t3 - t0)):
+                parts[name].append(v)
+        else:
+            for v in extra.values():
+                del v[:]
+    solved = sum(1 for s in b.results()[:256] if s["status"] == 20)
+    med = lambda v: round(1e3 * float(np.median(v)), 4)
+    out = dict(route=route, tree=os.path.relpath(tree, HERE), nq=nq, iters=iters, kernel=b.last_kernel(), solved_of_first_256=solved,
+               checksum=check, ms_median={k: med(v) for k, v in parts.items()})
+    out["ms_median"].update({k: med(v) for k, v in extra.items() if v})
+    b.close()
+    print(json.dumps(out), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--nq", type=int, default=65536)
+    ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--parent-tree", default=None)
+    ap.add_argument("--route", default=None, help="run one route in this process (what the driver starts)")
+    ap.add_argument("--tree", default=HERE)
+    ap.add_argument("--timeout", type=int, default=240, help="seconds per route")
+    a = ap.parse_args()
+    if a.route:
+        return run_route(a.route, os.path.abspath(a.tree), a.nq, a.iters)
+    jobs = ([("a", os.path.abspath(a.parent_tree))] if a.parent_tree else []) + [("a", HERE), ("b_host", HERE), ("b_dev", HERE)]
+    for route, tree in jobs:
+        rc = subprocess.call(["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--route", route, "--tree", tree,
+                              "--nq", str(a.nq), "--iters", str(a.iters)])
+        if rc != 0:
+            sys.exit("route %s on %s ended with status %d: nothing more is started" % (route, tree, rc))
+
+
+if __name__ == "__main__":
+    main()
