@@ -374,8 +374,8 @@ typedef struct {
  * the caller guarantees that its contents are complete before the call. what, delta, rho, x_k (and c_k when the batch has
  * constraints) are required, and rsqp_batch_handler_set_problem must have been called: RSQP_ERR_ARG before any device call
  * otherwise. The update marks, firstQPsolved_ and the stored factors are untouched: vectors never raise Update_A / Update_H.
- * Matrices stay with rsqp_batch_set_matrix_values_of (A keeps the [J I -I] layout the batch was created with, H = blkdiag(H_k, 0)
- * has the entries of H_k). Returns when the pools are written. */
+ * Matrices go through rsqp_batch_handler_set_matrices, or with host values through rsqp_batch_set_matrix_values_of (A keeps the
+ * [J I -I] layout the batch was created with, H = blkdiag(H_k, 0) has the entries of H_k). Returns when the pools are written. */
 int rsqp_batch_handler_update(rsqp_batch *b, const rsqp_handler_iterate *it, int on_device);
 /* what Algorithm takes from a solved QP (src/Algorithm.cpp:84, 609-622, 889), from the result pools of the last solve, whichever
  * call wrote them: p = x[0..n), lam_x = y[0..n) (NLP layout), lam_c = y[nV..nV+m) (constraint layout), norm_p = max |p_i|,
@@ -386,6 +386,36 @@ int rsqp_batch_handler_get_step(rsqp_batch *b, double *p, double *lam_c, double 
                                 double *norm_p, int on_device);
 /* the vector pools as they are on the device (mirror of rsqp_get_vector), in the layout of rsqp_batch_set_vectors; any may be NULL */
 int rsqp_batch_get_vectors(rsqp_batch *b, double *g, double *lb, double *ub, double *lbA, double *ubA);
+/* rsqp_batch_handler_set_matrices: the matrix half of Algorithm::setupQP (src/Algorithm.cpp:645-697) -- set_A / set_H at iteration 0
+ * (src/QPhandler.cpp:310-334), update_A / update_H after an accepted step (:508-530) -- for every member, without a round trip of the
+ * values through the host and without the identity entries of A = [J I -I], which never change. W = what[q] (nq entries):
+ *   W & RSQP_HM_JAC   the member's J entries are taken from jac. "Jacobian layout": pooled over the batch, member q owns the entries
+ *                     of columns [0, n_q) of its A in the order given to rsqp_batch_create -- Ajc_q[n_q] of them, a prefix of the
+ *                     member's entries (of its canonical entries as well). The entries of the slack columns are never written,
+ *                     whether they are one +-1 each or stored densely with explicit zeros.
+ *   W & RSQP_HM_HESS  the member's H entries are taken from hess, which has the layout of Hval of rsqp_batch_create (H =
+ *                     blkdiag(H_k, 0) has the entries of H_k). Ignored when the batch has no H, as rsqp_batch_set_matrix_values_of
+ *                     ignores its Hval there.
+ *   W == 0            every byte of the member stays as it is, its update mark included.
+ * A member with a bit set whose first QP is solved gets Update_A / Update_H raised (qpOASESInterface.cpp:407-409, 427-429), exactly
+ * as rsqp_batch_set_matrix_values_of raises it; the mask of rsqp_batch_set_members plays no role. One launch writes both forms of a
+ * J value -- its slot in the CSC pool and its slot in the CSR copy -- so no batch-wide refresh of the CSR copy follows; a batch
+ * created in a layout that is not canonical (rows out of order, repeated positions) takes the values into its caller-layout copies
+ * and folds them, as rsqp_batch_set_matrix_values_of does. For batches of at most 8 variables the symmetry of H of every member that
+ * carries HESS is decided on the device, with the verdict rsqp_batch_set_matrix_values_of reaches on the same values, and the host's
+ * record of it follows before the call returns: every later call, the host setters included, takes the kernel family it would have
+ * taken after the host route.
+ * on_device == 0: host pointers, packed into the pinned block of the handler layer and copied up once. what is required; jac is
+ * required when some word has JAC, hess when some word has HESS and the batch has an H. on_device != 0: what, jac and hess are DEVICE
+ * memory of the batch's device, complete before the call (the contract of rsqp_batch_handler_update). The library cannot read the
+ * words without a copy and does not: a NULL jac (hess) is the caller's promise that no word carries JAC (HESS) -- such a bit is
+ * ignored. rsqp_batch_handler_set_problem must have been called (the shape check). RSQP_ERR_ARG before any device call otherwise.
+ * Returns when the pools are written. */
+enum { RSQP_HM_JAC = 1, RSQP_HM_HESS = 2 };
+int rsqp_batch_handler_set_matrices(rsqp_batch *b, const int *what, const double *jac, const double *hess, int on_device);
+/* the value pools as they are on the device (mirror of rsqp_batch_get_vectors), in the layout of rsqp_batch_create -- for a batch
+ * created in a layout that is not canonical, the caller-layout copies. Either may be NULL; Hval is not written when the batch has no H */
+int rsqp_batch_get_matrix_values(rsqp_batch *b, double *Aval, double *Hval);
 int rsqp_batch_sync(rsqp_batch *b);
 /* keep != 0 (default): every solve writes the state a hot start needs (factors, iterate, multipliers,
  * working set: what a qpOASES SQProblem object keeps between init / hotstart calls) back to HBM.

@@ -17,6 +17,7 @@ OK = 0
 ERR_ARG, ERR_DEVICE, ERR_TOO_LARGE, ERR_WORKING_SET = -1, -2, -3, -4
 VEC_G, VEC_LB, VEC_UB, VEC_LBA, VEC_UBA = range(5)
 HU_SET, HU_BOUNDS, HU_DELTA, HU_PENALTY, HU_GRAD, HU_UBA = 1, 2, 4, 8, 16, 32   # RSQP_HU_*: the words of Batch.handler_update
+HM_JAC, HM_HESS = 1, 2                                                          # RSQP_HM_*: the words of Batch.handler_set_matrices
 MODE_COLD, MODE_HOT_VECTORS, MODE_HOT_MATRICES, MODE_WARM_REINIT = range(4)
 QP_OPTIMAL, QPERROR_INFEASIBLE, QPERROR_UNBOUNDED = 20, 22, 23
 ACTIVE_ABOVE, ACTIVE_BELOW, ACTIVE_BOTH_SIDE, INACTIVE = 1, -1, -99, 0
@@ -100,6 +101,8 @@ SYMBOLS = {
     "rsqp_batch_handler_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "rsqp_batch_handler_get_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "rsqp_batch_get_vectors": (C.c_int, [C.c_void_p, dp, dp, dp, dp, dp]),
+    "rsqp_batch_handler_set_matrices": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "rsqp_batch_get_matrix_values": (C.c_int, [C.c_void_p, dp, dp]),
     "rsqp_batch_sync": (C.c_int, [C.c_void_p]),
     "rsqp_batch_set_keep_state": (C.c_int, [C.c_void_p, C.c_int]),
     "rsqp_batch_get_last_kernel": (C.c_int, [C.c_void_p]),
@@ -470,6 +473,10 @@ class Batch:
         self.device = device
         self.offV = np.concatenate([[0], np.cumsum(self.nV)]).astype(np.int64)
         self.offC = np.concatenate([[0], np.cumsum(self.nC)]).astype(np.int64)
+        # entries per member in the caller's layout: of J (columns [0, nV - 2 nC) of A: handler_set_matrices), of A and of H
+        self.jnz = np.array([int(p.A_jc[max(p.nV - 2 * p.nC, 0)]) for p in problems], np.int64)
+        self.annz = np.array([int(p.A_jc[p.nV]) for p in problems], np.int64)
+        self.hnnz = np.array([int(p.H_jc[p.nV]) for p in problems], np.int64) if haveH else None
         self.set_vectors_from(problems)
 
     def close(self):
@@ -594,6 +601,39 @@ class Batch:
         v = [np.zeros(sV), np.zeros(sV), np.zeros(sV), np.zeros(sC), np.zeros(sC)]
         check(lib().rsqp_batch_get_vectors(self._h, *[_dp(a) for a in v]))
         return tuple(v)
+
+    def _matrix_sizes(self):
+        """(entries of jac, of the A value pool, of the H value pool -- None without H) in the layout the batch was created with"""
+        return int(np.sum(self.jnz)), int(np.sum(self.annz)), None if self.hnnz is None else int(np.sum(self.hnnz))
+
+    def handler_set_matrices(self, what, jac=None, hess=None, on_device=False):
+        """QPhandler's set_A / set_H, update_A / update_H for every member on the device: what[q] = HM_* bits (0: member q is not
+        touched). jac: pooled, member q owns the entries of its J -- columns [0, n_q) of its A, in the order of its A_val; the
+        identity entries are never written. hess: the layout of the H values the batch was created with (ignored when the batch has
+        no H). on_device: what (int32), jac and hess (float64) are tensors on the batch's device, complete before the call; a
+        missing jac / hess then promises that no word carries its bit"""
+        nJ, nA, nH = self._matrix_sizes()
+        spec = (("what", what, self.nq), ("jac", jac, nJ), ("hess", None if nH is None else hess, nH))
+        if what is None:
+            raise ValueError("what is required")
+        if on_device:
+            addr = [self._dev_addr(a, n, name, "int32" if name == "what" else "float64") for name, a, n in spec]
+            keep = None
+        else:
+            keep = [self._sized(a, n, name, np.int32 if name == "what" else np.float64) for name, a, n in spec]
+            addr = [None if a is None else a.ctypes.data for a in keep]
+            seen = int(np.bitwise_or.reduce(keep[0])) if self.nq else 0
+            if (seen & HM_JAC and keep[1] is None) or (seen & HM_HESS and nH is not None and keep[2] is None):
+                raise ValueError("a word names a matrix that is not given")
+        check(lib().rsqp_batch_handler_set_matrices(self._h, *addr, int(bool(on_device))))
+        del keep
+
+    def get_matrix_values(self):
+        """(Aval, Hval) as the pools hold them on the device, in the layout the batch was created with; Hval None without H"""
+        nJ, nA, nH = self._matrix_sizes()
+        A, H = np.zeros(nA), (None if nH is None else np.zeros(nH))
+        check(lib().rsqp_batch_get_matrix_values(self._h, _dp(A), _dp(H)))
+        return A, H
 
     def solve(self, mode=MODE_COLD, max_nWSR=1000, sync=True):
         check(lib().rsqp_batch_solve(self._h, mode, max_nWSR))

@@ -54,7 +54,7 @@ struct rsqp_batch {
     // the call's first solve, mode of its rescue solve (-1: none), kind of rescue, count of the first solve
     // rsqp_batch_optimize_lp adds: mode the first solve is LAUNCHED with (a flip is a plain init there), mode of the proximal step
     // (-1: the member is unsolved and takes none)
-    // per member across calls as well: OPT_UPD the update mark (Update_A / Update_H of rsqp_batch_set_matrix_values_of, and of
+    // per member across calls as well: OPT_UPD the update mark (Update_A / Update_H of rsqp_batch_set_matrix_values_of and rsqp_batch_handler_set_matrices, and of
     // rsqp_batch_set_matrix_values for a member that sat out the call that took the batch-wide mats_updated), OPT_FAM 1 + the kernel
     // family that wrote the member's stored state (0 none; read while state_engine == -2)
     enum { OPT_FIRST = 0, OPT_OLD, OPT_NEW, OPT_MODE, OPT_RMODE, OPT_RESCUE, OPT_N1, OPT_LMODE, OPT_PMODE, OPT_UPD, OPT_FAM, OPT_WORDS };
@@ -72,9 +72,25 @@ struct rsqp_batch {
     // constraint layout), and the staging of host-pointer calls, allocated at first use -- the caller's arrays are packed into one
     // pinned block and cross in one copy each way (the stage of the named setters is too small for nq-sized words)
     DevBuf<double> h_xl, h_xu, h_cl, h_cu, h_in, h_out;
-    double *h_pin = nullptr;              // pinned, max(words of an update, words of a step)
+    double *h_pin = nullptr;              // pinned, max(words of an update, words of a step, words of a matrix call)
+    size_t h_pin_words = 0;
     long long sumN = 0;                   // NLP variables of the batch: sumV - 2 sumC
     bool have_problem = false;            // rsqp_batch_handler_set_problem has run
+    // rsqp_batch_handler_set_matrices: h_jn[q] = entries of columns [0, n_q) of member q's A in the caller's layout (from
+    // rsqp_batch_create; sumJ of them in all). At the first call: where member q's entries start in jac (hm_joff, nq + 1), the
+    // inverse of perm (hm_inv: CSC slot -> CSR slot) and the staging of host-pointer calls (hm_in: jac | hess | what)
+    std::vector<int> h_jn;
+    long long sumJ = 0;
+    bool uni_jn = false;                  // a one-pattern batch in a canonical layout: every member has h_jn[0] entries in jac
+    bool hm_ready = false;
+    DevBuf<long long> hm_joff;
+    DevBuf<int> hm_inv;
+    DevBuf<double> hm_in;
+    // the symmetry of every member's H on the device (batches of at most 8 variables): the device's copy of h_symq, stale after a
+    // host setter has re-examined members, and the host-mapped word a verdict that differs from the copy is flagged through
+    DevBuf<char> d_symq;
+    bool symq_stale = true;
+    int *sym_host = nullptr, *sym_dev = nullptr;
     // optimizeLP per member (rsqp_batch_optimize_lp): the members' descriptors with H absent and hreg = regVal of the member's last
     // init (written on the device, kept across hot starts), and the pool of the proximal step's gradients g - regVal x
     DevBuf<QPDesc> d_desc_lp;
@@ -99,6 +115,7 @@ struct rsqp_batch {
         if (stream) (void)hipStreamDestroy(stream);
         if (used_host) (void)hipHostFree(used_host);
         if (h_pin) (void)hipHostFree(h_pin);
+        if (sym_host) (void)hipHostFree(sym_host);
     }
 };
 
@@ -166,6 +183,9 @@ extern "C" int rsqp_batch_create(int nq, const int *nV, const int *nC, const int
         const int *jc = Ajc + offAjc;
         const int annz = jc[d.nV];
         d.annz = annz; d.hnnz = b->haveH ? Hjc[offHjc + d.nV] : 0;
+        // (the J block of a member of the QPhandler shape, in the caller's layout: rsqp_batch_handler_set_matrices)
+        b->h_jn.push_back(d.nV > 2 * d.nC ? Ajc_in[offAjc + d.nV - 2 * d.nC] : 0);
+        b->sumJ += b->h_jn.back();
         CsrCopy r;
         csr_from_csc(d.nC, d.nV, jc, Air + offAnz, r);
         h_Arp.insert(h_Arp.end(), r.rp.begin(), r.rp.end());
@@ -221,6 +241,7 @@ extern "C" int rsqp_batch_create(int nq, const int *nV, const int *nC, const int
                                         std::memcmp(Hir + d.offHnz, Hir, sizeof(int) * d0.hnnz) == 0));
         }
     }
+    b->uni_jn = b->uni_pat && PA.canon;   // (one canonical pattern: one J count; a folded layout may repeat positions per member)
     HIPCHK(hipStreamCreate(&b->stream));
     HIPCHK(hipEventCreate(&b->ev0)); HIPCHK(hipEventCreate(&b->ev1));
     HIPCHK(hipEventCreate(&b->ev2)); HIPCHK(hipEventCreate(&b->ev3));
@@ -290,7 +311,7 @@ extern "C" int rsqp_batch_set_matrix_values(rsqp_batch *b, const double *Aval, c
     if (Hval && b->haveH) {
         HIPCHK(b->Hfold.refresh(Hval, b->Hval, (int)b->sumHnz, b->stream));
         if (!b->h_Hjc.empty()) {
-            b->h_sym = true;
+            b->h_sym = true; b->symq_stale = true;
             for (int q = 0; q < b->nq; q++) {
                 const QPDesc &d = b->desc[q];
                 b->h_symq[q] = small_csc_symmetric(d.nV, b->h_Hjc.data() + d.offHjc, b->h_Hir.data() + b->h_Huoff[q], Hval + b->h_Huoff[q]);
@@ -464,7 +485,7 @@ extern "C" int rsqp_batch_set_matrix_values_of(rsqp_batch *b, const int *members
     if (Hval) {
         if (!b->Hfold.canon) HIPCHK(b->Hfold.sum(b->Hval, (int)b->sumHnz, b->stream));
         if (!b->h_Hjc.empty()) {   // the named members' symmetry anew, from the values given
-            b->h_sym = true;
+            b->h_sym = true; b->symq_stale = true;
             for (int q = 0; q < b->nq; q++) {
                 const QPDesc &d = b->desc[q];
                 if (members[q] != 0)
@@ -576,12 +597,19 @@ batch_handler_step_kernel(int nq, const QPDesc *__restrict__ desc, const double 
 
 // words (doubles) of the packed block of a host-pointer update: delta | rho | x_k | grad | c_k | what (ints); a step's is smaller
 long long handler_in_words(const rsqp_batch *b) { return 2LL * b->nq + 2 * b->sumN + b->sumC + (b->nq + 1) / 2; }
-int ensure_handler_stage(rsqp_batch *b) {
-    if (b->h_pin) return RSQP_OK;
-    const size_t w = (size_t)handler_in_words(b);
-    HIPCHK(b->h_in.alloc(w, false)); HIPCHK(b->h_out.alloc(w, false));
-    HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&b->h_pin), sizeof(double) * w, hipHostMallocDefault));
+// the pinned block holds `words` doubles (it is free: every call that uses it waits for its copy)
+int ensure_pinned(rsqp_batch *b, size_t words) {
+    if (b->h_pin_words >= words) return RSQP_OK;
+    if (b->h_pin) HIPCHK(hipHostFree(b->h_pin));
+    b->h_pin = nullptr; b->h_pin_words = 0;
+    HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&b->h_pin), sizeof(double) * std::max<size_t>(words, 1), hipHostMallocDefault));
+    b->h_pin_words = words;
     return RSQP_OK;
+}
+int ensure_handler_stage(rsqp_batch *b) {
+    const size_t w = (size_t)handler_in_words(b);
+    if (!b->h_in.p) { HIPCHK(b->h_in.alloc(w, false)); HIPCHK(b->h_out.alloc(w, false)); }
+    return ensure_pinned(b, w);
 }
 }  // namespace
 
@@ -680,6 +708,200 @@ extern "C" int rsqp_batch_get_vectors(rsqp_batch *b, double *g, double *lb, doub
     if (ub) HIPCHK(b->ub.download(ub, b->sumV));
     if (lbA) HIPCHK(b->lbA.download(lbA, b->sumC));
     if (ubA) HIPCHK(b->ubA.download(ubA, b->sumC));
+    return RSQP_OK;
+}
+
+// ---------------------------------------------------------------------------------
+// the matrices of the QPhandler on the device (rsqp_batch_handler_set_matrices): set_A / set_H, update_A / update_H of
+// src/QPhandler.cpp:310-334, 508-530 for every member, J without the identity entries of [J I -I]
+// ---------------------------------------------------------------------------------
+namespace {
+// one thread per entry of the concatenation jac | hess; the member of an entry as in batch_masked_copy_kernel: a division where every
+// member has as many entries (uniJ / uniH > 0), else the last member whose start is at or before the entry -- joff for jac, the
+// descriptors' offHnz or the caller-layout starts Huoff for hess. A J value of a canonical batch is written twice, into its slot of
+// the CSC pool and, through the inverse of perm, into its slot of the CSR copy (as scatter_values_csc_csr of sparse.hip writes both
+// forms on a single handle); of a folded batch into the caller-layout copy, which is folded behind this launch. The first nq
+// threads raise the update marks (qpOASESInterface.cpp:407-409, 427-429). bits: the RSQP_HM_* bits that count in this launch.
+struct HandlerMatrices {
+    int nq, bits;
+    long long nJ, nH;                 // entries of jac and of hess (0: not given)
+    int uniJ, uniA, uniH;             // uniA: entries of A per member where uniJ > 0
+    const QPDesc *desc;
+    const int *what;
+    const double *jac, *hess;
+    const long long *joff, *Auoff, *Huoff;   // Auoff / Huoff: null for a canonical layout
+    const int *inv;                   // CSC slot -> CSR slot
+    double *Aval, *Arv, *Auval, *Hdst;
+    int *mark;
+    const int *first;
+};
+__global__ void __launch_bounds__(256) batch_handler_matrices_kernel(HandlerMatrices a) {
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < a.nq && (a.what[e] & a.bits) != 0 && a.first[e] != 0) a.mark[e] = 1;
+    if (e >= a.nJ + a.nH) return;
+    const bool isJ = e < a.nJ;
+    const long long k = isJ ? e : e - a.nJ;
+    const int uni = isJ ? a.uniJ : a.uniH;
+    int q;
+    if (uni > 0) q = (int)(k / uni);
+    else {                                            // (members without entries own none)
+        int lo = 0, hi = a.nq - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            const long long start = isJ ? a.joff[mid] : (a.Huoff ? a.Huoff[mid] : (long long)a.desc[mid].offHnz);
+            if (start <= k) lo = mid; else hi = mid - 1;
+        }
+        q = lo;
+    }
+    const int W = a.what[q] & a.bits;
+    if (!isJ) {
+        if (W & RSQP_HM_HESS) a.Hdst[k] = a.hess[k];
+        return;
+    }
+    if (!(W & RSQP_HM_JAC)) return;
+    const double v = a.jac[k];
+    const long long i = k - (uni > 0 ? (long long)q * uni : a.joff[q]);     // the entry within the member's J block
+    if (a.Auoff) { a.Auval[a.Auoff[q] + i] = v; return; }
+    const long long slot = (uni > 0 ? (long long)q * a.uniA : (long long)a.desc[q].offAnz) + i;
+    a.Aval[slot] = v;
+    a.Arv[a.inv[slot]] = v;
+}
+
+__global__ void __launch_bounds__(256) invert_perm_kernel(int n, const int *__restrict__ perm, int *__restrict__ inv) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < n) inv[perm[p]] = p;
+}
+
+// one thread per member that carries HESS: small_csc_symmetric (rsqp_matrix.hip) on the canonical pools, where no position repeats
+// (a folded layout has been summed in the caller's order, as small_csc_symmetric sums it). The dense comparison of that function,
+// d[r][c] != d[c][r] for every pair with absent entries 0, is: every off-diagonal entry equals its transposed entry, or 0 where
+// that is absent -- NaN differs from everything in both. A verdict that is not the one on record is flagged for the host
+__global__ void __launch_bounds__(256)
+batch_hess_symmetry_kernel(int nq, const QPDesc *__restrict__ desc, const int *__restrict__ what, const int *__restrict__ Hjc,
+                           const int *__restrict__ Hir, const double *__restrict__ Hval, char *__restrict__ symq, int *__restrict__ changed) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nq || (what[q] & RSQP_HM_HESS) == 0) return;
+    const int nV = desc[q].nV;
+    const int *const jc = Hjc + desc[q].offHjc, *const ir = Hir + desc[q].offHnz;
+    const double *const val = Hval + desc[q].offHnz;
+    bool sym = true;
+    for (int c = 0; c < nV; c++)
+        for (int k = jc[c]; k < jc[c + 1]; k++) {
+            const int r = ir[k];
+            if (r == c) continue;
+            double other = 0.0;
+            for (int t = jc[r]; t < jc[r + 1]; t++)
+                if (ir[t] == c) other = val[t];
+            if (val[k] != other) sym = false;
+        }
+    const char s = sym ? 1 : 0;
+    if (symq[q] != s) { symq[q] = s; *changed = 1; }
+}
+
+// what the first call builds: where the members' entries start in jac, and the inverse of perm
+int ensure_handler_matrices(rsqp_batch *b) {
+    if (b->hm_ready) return RSQP_OK;
+    std::vector<long long> joff((size_t)b->nq + 1, 0);
+    for (int q = 0; q < b->nq; q++) joff[q + 1] = joff[q] + b->h_jn[q];
+    HIPCHK(b->hm_joff.from(joff));
+    HIPCHK(b->hm_inv.alloc((size_t)b->sumAnz, false));
+    if (b->sumAnz > 0) {
+        hipLaunchKernelGGL(invert_perm_kernel, dim3((unsigned)((b->sumAnz + 255) / 256)), dim3(256), 0, b->stream, (int)b->sumAnz,
+                           b->perm.p, b->hm_inv.p);
+        HIPCHK(hipGetLastError());
+    }
+    b->hm_ready = true;
+    return RSQP_OK;
+}
+}  // namespace
+
+extern "C" int rsqp_batch_handler_set_matrices(rsqp_batch *b, const int *what, const double *jac, const double *hess, int on_device) {
+    if (!b || !what) return fail(RSQP_ERR_ARG, "rsqp_batch_handler_set_matrices: the batch and what are required");
+    if (!b->have_problem) return fail(RSQP_ERR_ARG, "rsqp_batch_handler_set_matrices: rsqp_batch_handler_set_problem has not been called");
+    if (!b->haveH) hess = nullptr;
+    if (!on_device) {
+        int seen = 0;
+        for (int q = 0; q < b->nq; q++) seen |= what[q];
+        if (!b->haveH) seen &= ~RSQP_HM_HESS;
+        if ((seen & RSQP_HM_JAC) && !jac) return fail(RSQP_ERR_ARG, "rsqp_batch_handler_set_matrices: a word has JAC and jac is NULL");
+        if ((seen & RSQP_HM_HESS) && !hess) return fail(RSQP_ERR_ARG, "rsqp_batch_handler_set_matrices: a word has HESS and hess is NULL");
+        if (!(seen & RSQP_HM_JAC)) jac = nullptr;
+        if (!(seen & RSQP_HM_HESS)) hess = nullptr;
+    }
+    if (!jac && !hess) return RSQP_OK;   // nobody is named
+    HIPCHK(hipSetDevice(b->device));
+    int rc;
+    if ((rc = ensure_opt(b)) != RSQP_OK || (rc = ensure_handler_matrices(b)) != RSQP_OK) return rc;
+    const size_t nq = (size_t)b->nq;
+    const long long nJ = jac ? b->sumJ : 0, nH = hess ? b->Hfold.unnz : 0;
+    const bool judge = hess && !b->h_Hjc.empty();   // batches of at most 8 variables: the symmetry of the members that carry HESS
+    if (judge) {
+        if (!b->sym_host) {
+            HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&b->sym_host), sizeof(int), hipHostMallocMapped));
+            HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&b->sym_dev), b->sym_host, 0));
+            HIPCHK(b->d_symq.alloc(nq, false));
+        }
+        if (b->symq_stale) {
+            HIPCHK(hipMemcpyAsync(b->d_symq.p, b->h_symq.data(), nq, hipMemcpyHostToDevice, b->stream));
+            HIPCHK(hipStreamSynchronize(b->stream));   // (pageable memory: the copy has read it)
+            b->symq_stale = false;
+        }
+        *b->sym_host = 0;
+    }
+    HandlerMatrices a;
+    std::memset(&a, 0, sizeof(a));
+    if (on_device) {
+        a.what = what; a.jac = jac; a.hess = hess;
+    } else {
+        // what | jac | hess, the arrays that are given alone: one copy up
+        const size_t o_j = (nq + 1) / 2, o_h = o_j + (size_t)nJ, words = o_h + (size_t)nH;
+        if ((rc = ensure_pinned(b, words)) != RSQP_OK) return rc;
+        if (b->hm_in.n < words) HIPCHK(b->hm_in.alloc(words, false));
+        std::memcpy(b->h_pin, what, sizeof(int) * nq);
+        if (jac) std::memcpy(b->h_pin + o_j, jac, sizeof(double) * (size_t)nJ);
+        if (hess) std::memcpy(b->h_pin + o_h, hess, sizeof(double) * (size_t)nH);
+        HIPCHK(hipMemcpyAsync(b->hm_in.p, b->h_pin, sizeof(double) * words, hipMemcpyHostToDevice, b->stream));
+        a.what = reinterpret_cast<const int *>(b->hm_in.p); a.jac = b->hm_in.p + o_j; a.hess = b->hm_in.p + o_h;
+    }
+    a.nq = b->nq; a.bits = (jac ? RSQP_HM_JAC : 0) | (hess ? RSQP_HM_HESS : 0);
+    a.nJ = nJ; a.nH = nH;
+    a.uniJ = b->uni_jn ? b->h_jn[0] : 0; a.uniA = b->uni_annz;
+    a.uniH = (b->uni_pat && b->Hfold.canon) ? b->uni_hnnz : 0;
+    a.desc = b->d_desc.p; a.joff = b->hm_joff.p; a.inv = b->hm_inv.p;
+    a.Aval = b->Aval.p; a.Arv = b->Arv.p;
+    if (!b->Afold.canon) { a.Auoff = b->Auoff.p; a.Auval = b->Afold.uval.p; }
+    a.Hdst = b->Hval.p;
+    if (hess && !b->Hfold.canon) { a.Huoff = b->Huoff.p; a.Hdst = b->Hfold.uval.p; }
+    a.mark = b->opt.p + (size_t)rsqp_batch::OPT_UPD * nq; a.first = b->opt.p + (size_t)rsqp_batch::OPT_FIRST * nq;
+    const long long n = std::max<long long>(nJ + nH, b->nq);
+    hipLaunchKernelGGL(batch_handler_matrices_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, b->stream, a);
+    HIPCHK(hipGetLastError());
+    if (jac && !b->Afold.canon) {   // the folded layout: sum the caller's values, then the CSR copy from the sums
+        HIPCHK(b->Afold.sum(b->Aval, (int)b->sumAnz, b->stream));
+        if (rsqp_launch_gather((int)b->sumAnz, b->perm.p, b->Aval.p, b->Arv.p, b->stream) != hipSuccess)
+            return fail(RSQP_ERR_DEVICE, "gather launch failed");
+    }
+    if (hess && !b->Hfold.canon) HIPCHK(b->Hfold.sum(b->Hval, (int)b->sumHnz, b->stream));
+    if (judge) {
+        hipLaunchKernelGGL(batch_hess_symmetry_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, b->stream, b->nq, b->d_desc.p,
+                           a.what, b->Hjc.p, b->Hir.p, b->Hval.p, b->d_symq.p, b->sym_dev);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(b->stream));
+    if (judge && *b->sym_host != 0) {   // a verdict changed: the host's record follows (nq bytes)
+        HIPCHK(hipMemcpy(b->h_symq.data(), b->d_symq.p, nq, hipMemcpyDeviceToHost));
+        b->h_sym = true;
+        for (int q = 0; q < b->nq; q++) b->h_sym = b->h_sym && b->h_symq[q];
+    }
+    return RSQP_OK;
+}
+
+extern "C" int rsqp_batch_get_matrix_values(rsqp_batch *b, double *Aval, double *Hval) {
+    if (!b) return fail(RSQP_ERR_ARG, "null batch");
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    if (Aval) HIPCHK((b->Afold.canon ? b->Aval : b->Afold.uval).download(Aval, (size_t)b->Afold.unnz));
+    if (Hval && b->haveH) HIPCHK((b->Hfold.canon ? b->Hval : b->Hfold.uval).download(Hval, (size_t)b->Hfold.unnz));
     return RSQP_OK;
 }
 

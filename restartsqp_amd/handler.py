@@ -149,10 +149,38 @@ def batch_handler_reference(state, what, delta, rho, x_k, c_k, grad, n, m, x_l, 
     return g, lb, ub, lbA, ubA
 
 
+def batch_matrices_reference(Aval, Hval, what, jac, hess, nV, nC, Ajc_per_member, Hjc_per_member=None):
+    """The rule of rsqp_batch_handler_set_matrices restated in numpy: the expected value of every test.
+
+    Aval, Hval: the value pools in the layout of the batch's creation (Hval None: a batch without H); new arrays are returned.
+    Member q has m = nC[q] constraints and n = nV[q] - 2 m NLP variables; Ajc_per_member[q] are the column pointers of its A (and
+    Hjc_per_member[q] of its H, needed with Hval). With HM_JAC its entries of columns [0, n) -- the first Ajc[n] of the member, the J
+    of A = [J I -I] (src/QPhandler.cpp:326-334, 520-530) -- are the member's next Ajc[n] entries of jac; the entries of the slack
+    columns are never written. With HM_HESS its H entries are those of hess, which has the layout of Hval (:310-318, 508-517). A
+    member with word 0 keeps everything; every member owns its share of jac and hess whatever its word says."""
+    A = np.array(Aval, dtype=np.float64)
+    H = None if Hval is None else np.array(Hval, dtype=np.float64)
+    oA = oJ = oH = 0
+    for q in range(len(nV)):
+        jc = np.asarray(Ajc_per_member[q])
+        n, W = int(nV[q]) - 2 * int(nC[q]), int(what[q])
+        nj, na = int(jc[n]), int(jc[int(nV[q])])
+        if W & capi.HM_JAC:
+            A[oA:oA + nj] = np.asarray(jac, dtype=np.float64)[oJ:oJ + nj]
+        oA, oJ = oA + na, oJ + nj
+        if H is not None:
+            nh = int(np.asarray(Hjc_per_member[q])[int(nV[q])])
+            if W & capi.HM_HESS:
+                H[oH:oH + nh] = np.asarray(hess, dtype=np.float64)[oH:oH + nh]
+            oH += nh
+    return A, H
+
+
 class BatchQPhandler:
     """QPhandler for every member of a ``capi.Batch`` whose members have the (p, u, v) shape: the reference's method names, each with
     a member mask first. A call notes its arguments for the named members and ORs bits into a pending word per member;
-    ``solveQP`` / ``solveLP`` flush all words with ONE ``Batch.handler_update`` and solve for the members given.
+    ``solveQP`` / ``solveLP`` flush all words -- ONE ``Batch.handler_set_matrices`` when set_A / set_H / update_A / update_H were
+    called, then ONE ``Batch.handler_update`` -- and solve for the members given.
 
     Arrays are pooled over the batch (x_k, grad: NLP layout; c_k: the layout of lbA); only the named members' entries are read.
     delta and rho are scalars or one entry per member. on_device: x_k, c_k and grad are torch tensors on the batch's device, the
@@ -182,6 +210,16 @@ class BatchQPhandler:
             self._memN, self._memC = memN, memC
             z = np.zeros
         self.x_k, self.grad, self.c_k = z(sN), z(sN), z(sC)
+        # the matrices: pending HM_* words, the members' J and H entries (Batch.handler_set_matrices), the words of the last flush
+        self.mwhat = np.zeros(nq, np.int32)
+        self.matrix_words = np.zeros(nq, np.int32)
+        memJ = np.repeat(np.arange(nq), batch.jnz)
+        memH = np.repeat(np.arange(nq), batch.hnnz) if batch.hnnz is not None else np.zeros(0, np.int64)
+        if self.on_device:
+            self._memJ, self._memH = torch.as_tensor(memJ, device=dev), torch.as_tensor(memH, device=dev)
+        else:
+            self._memJ, self._memH = memJ, memH
+        self.jac, self.hess = z(memJ.size), z(memH.size)
 
     # -- bookkeeping --
     def _mask(self, members):
@@ -239,11 +277,45 @@ class BatchQPhandler:
         self.have_grad = True
         self.what[mask] |= capi.HU_GRAD
 
+    def set_A(self, members, jac):                                                    # :326-334; jac: Batch.handler_set_matrices
+        mask = self._mask(members)
+        self._take("jac", jac, mask, self._memJ)
+        self.mwhat[mask] |= capi.HM_JAC
+
+    update_A = set_A                                                                  # :520-530
+
+    def set_H(self, members, hess):                                                   # :310-318
+        mask = self._mask(members)
+        self._take("hess", hess, mask, self._memH)
+        self.mwhat[mask] |= capi.HM_HESS
+
+    update_H = set_H                                                                  # :508-517
+
     # -- flush and solve --
+    def _flush_matrices(self):
+        """one handler_set_matrices for the pending matrix words, which are kept in matrix_words"""
+        self.matrix_words = self.mwhat.copy()
+        self.mwhat[:] = 0
+        w = self.matrix_words
+        if not w.any():
+            return
+        jac = self.jac if (w & capi.HM_JAC).any() else None
+        hess = self.hess if (w & capi.HM_HESS).any() else None
+        if self.on_device:
+            t = self._xp
+            dw = t.as_tensor(w, device=self._dev)
+            t.cuda.synchronize()                       # the inputs are complete before the call, as in flush()
+            self.batch.handler_set_matrices(dw, jac, hess, on_device=True)
+        else:
+            self.batch.handler_set_matrices(w, jac, hess)
+
     def flush(self):
-        """one handler_update for everything pending; returns the words it sent"""
+        """the matrices first, then the vectors, as Algorithm::setupQP orders them (src/Algorithm.cpp:645-697): one
+        handler_set_matrices for the pending matrix words (none without any; they stay readable as matrix_words), one handler_update
+        for everything else pending; returns the vector words it sent"""
         if np.any((self._halves != 0) & (self._halves != 3)):
             raise ValueError("set_bounds and set_g go together (Algorithm::setupQP, src/Algorithm.cpp:645-660)")
+        self._flush_matrices()
         what = np.where(self._halves == 3, capi.HU_SET, self.what).astype(np.int32)
         self.what[:] = 0; self._halves[:] = 0
         if not what.any():

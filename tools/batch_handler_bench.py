@@ -1,7 +1,7 @@
 """What one lock-step SQP iteration costs around the solve, on 65 536 hs071-shaped members (n = 4, m = 2): from a new iterate to
 the five QP vectors in the pools, the solve, and the step data (p, multipliers, norm_p, infea_model) back.
 
-    python tools/batch_handler_bench.py [--nq 65536] [--iters 30] [--parent-tree DIR]
+    python tools/batch_handler_bench.py [--nq 65536] [--iters 30] [--parent-tree DIR] [--matrices none|all|half]
 
 Routes, each in a process of its own under `timeout` (the driver stops at the first that fails or runs out of time):
   a      the route before rsqp_batch_handler_*: QPhandler's formulas in numpy, rsqp_batch_set_vectors_of (all members named),
@@ -11,7 +11,14 @@ Routes, each in a process of its own under `timeout` (the driver stops at the fi
   b_dev  the same with the iterate and the step data in torch tensors on the device (torch imported before the library is loaded,
          capi.device_torch); norm_p and infea_model, what the acceptance test of the host loop reads, are copied to the host.
 Iteration 0 is SET for everybody (a cold start), the others BOUNDS|UBA|GRAD (hot starts on new vectors); 3 warm-up iterations,
-then the median over --iters of the whole iteration and of its parts. One JSON line per route."""
+then the median over --iters of the whole iteration and of its parts. One JSON line per route.
+
+--matrices all | half: every iteration also brings a new J_k and H_k for every member, or for every second one (those members run
+RSQP_MODE_HOT_MATRICES from iteration 1 on). The values are float64 tensors on the device, where a driver that evaluates its NLPs
+on the GPU has them, complete before the clock starts; every route imports torch first. The part "matrices" is then
+  a      the tensors to the host, [J I -I] assembled in numpy, rsqp_batch_set_matrix_values_of (host pointers, the whole A pool);
+  b_host the tensors to the host, rsqp_batch_handler_set_matrices with host pointers (J and H entries alone);
+  b_dev  rsqp_batch_handler_set_matrices with the tensors' device pointers."""
 import argparse
 import json
 import os
@@ -34,8 +41,16 @@ def iterates(np, nq, count, seed=11):
     return out
 
 
-def run_route(route, tree, nq, iters):
-    if route == "b_dev":
+def matrix_values(np, base, nq, count, seed=13):
+    """per iteration: J of every member (the 8 entries of hs071's 2 x 4 Jacobian, each moved by about 2 %) and the entries of H_k
+    scaled per member (symmetric as before: the batch stays on the hs071-scale tableau kernel)"""
+    rng = np.random.default_rng(seed)
+    J0, H0 = base.A_val[:base.A_jc[4]], base.H_val
+    return [(J0 * (1.0 + 0.02 * rng.normal(size=(nq, J0.size))), H0 * (1.0 + 0.02 * rng.uniform(-1.0, 1.0, (nq, 1)))) for _ in range(count)]
+
+
+def run_route(route, tree, nq, iters, matrices="none"):
+    if route == "b_dev" or matrices != "none":
         import torch
     sys.path.insert(0, tree)
     import numpy as np
@@ -48,10 +63,13 @@ def run_route(route, tree, nq, iters):
     if route != "a":
         b.handler_set_problem(np.tile(x_l, nq), np.tile(x_u, nq), np.tile(c_l, nq), np.tile(c_u, nq))
     its = iterates(np, nq, WARMUP + iters)
+    mats = matrix_values(np, base, nq, WARMUP + iters) if matrices != "none" else None
+    named = np.ones(nq, bool) if matrices == "all" else np.arange(nq) % 2 == 0
+    ident = base.A_val[base.A_jc[4]:]                  # the entries of [I -I]: they never change
     ones = np.ones(nq, np.int32)
     first = np.full(nq, capi.HU_SET if route != "a" else 1, np.int32)
     later = np.full(nq, (capi.HU_BOUNDS | capi.HU_UBA | capi.HU_GRAD) if route != "a" else 0, np.int32)
-    parts = {k: [] for k in ("vectors", "solve", "step", "total")}
+    parts = {k: [] for k in ("matrices", "vectors", "solve", "step", "total")}
     extra = {k: [] for k in ("formulas", "upload", "download", "reduce")}
     L = capi.lib()
     sV, sC = nq * (n + 2 * m), nq * m
@@ -61,6 +79,22 @@ def run_route(route, tree, nq, iters):
         if route == "b_dev":
             dev = [torch.as_tensor(a.reshape(-1), device="cuda") for a in (first if k == 0 else later, delta, rho, x_k, c_k, grad)]
             torch.cuda.synchronize()
+        if mats is not None:
+            tJ, tH = (torch.as_tensor(a.reshape(-1), device="cuda") for a in mats[k])
+            if route == "b_dev":
+                tW = torch.as_tensor(np.where(named, capi.HM_JAC | capi.HM_HESS, 0).astype(np.int32), device="cuda")
+            torch.cuda.synchronize()
+        tm = time.perf_counter()
+        if mats is None:
+            pass
+        elif route == "a":
+            Jh, Hh = tJ.cpu().numpy().reshape(nq, -1), tH.cpu().numpy()
+            A = np.empty((nq, Jh.shape[1] + ident.size)); A[:, :Jh.shape[1]] = Jh; A[:, Jh.shape[1]:] = ident
+            b.set_matrix_values(A.reshape(-1), Hh, members=named)
+        elif route == "b_host":
+            b.handler_set_matrices(np.where(named, capi.HM_JAC | capi.HM_HESS, 0), tJ.cpu().numpy(), tH.cpu().numpy())
+        else:
+            b.handler_set_matrices(tW, tJ, tH, on_device=True)
         t0 = time.perf_counter()
         if route == "a":
             g = np.empty((nq, n + 2 * m)); lb = np.zeros((nq, n + 2 * m)); ub = np.full((nq, n + 2 * m), INF)
@@ -93,15 +127,17 @@ def run_route(route, tree, nq, iters):
         t3 = time.perf_counter()
         check += float(norm_p.sum() + infea.sum())
         if k >= WARMUP:
-            for name, v in (("vectors", t1 - t0), ("solve", t2 - t1), ("step", t3 - t2), ("total", t3 - t0)):
+            for name, v in (("matrices", t0 - tm), ("vectors", t1 - t0), ("solve", t2 - t1), ("step", t3 - t2), ("total", t3 - tm)):
                 parts[name].append(v)
         else:
             for v in extra.values():
                 del v[:]
     solved = sum(1 for s in b.results()[:256] if s["status"] == 20)
     med = lambda v: round(1e3 * float(np.median(v)), 4)
-    out = dict(route=route, tree=os.path.relpath(tree, HERE), nq=nq, iters=iters, kernel=b.last_kernel(), solved_of_first_256=solved,
-               checksum=check, ms_median={k: med(v) for k, v in parts.items()})
+    out = dict(route=route, tree=os.path.relpath(tree, HERE), nq=nq, iters=iters, matrices=matrices, kernel=b.last_kernel(),
+               solved_of_first_256=solved, checksum=check, ms_median={k: med(v) for k, v in parts.items()})
+    if mats is not None:                               # what the last iteration dispatched: members per RSQP_MODE_*
+        out["modes_last"] = np.bincount(b.dispatch()[0], minlength=4).tolist()
     out["ms_median"].update({k: med(v) for k, v in extra.items() if v})
     b.close()
     print(json.dumps(out), flush=True)
@@ -112,16 +148,17 @@ def main():
     ap.add_argument("--nq", type=int, default=65536)
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--parent-tree", default=None)
+    ap.add_argument("--matrices", default="none", choices=("none", "all", "half"), help="new J and H per iteration: for nobody, everybody, every second member")
     ap.add_argument("--route", default=None, help="run one route in this process (what the driver starts)")
     ap.add_argument("--tree", default=HERE)
     ap.add_argument("--timeout", type=int, default=240, help="seconds per route")
     a = ap.parse_args()
     if a.route:
-        return run_route(a.route, os.path.abspath(a.tree), a.nq, a.iters)
+        return run_route(a.route, os.path.abspath(a.tree), a.nq, a.iters, a.matrices)
     jobs = ([("a", os.path.abspath(a.parent_tree))] if a.parent_tree else []) + [("a", HERE), ("b_host", HERE), ("b_dev", HERE)]
     for route, tree in jobs:
         rc = subprocess.call(["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--route", route, "--tree", tree,
-                              "--nq", str(a.nq), "--iters", str(a.iters)])
+                              "--nq", str(a.nq), "--iters", str(a.iters), "--matrices", a.matrices])
         if rc != 0:
             sys.exit("route %s on %s ended with status %d: nothing more is started" % (route, tree, rc))
 
