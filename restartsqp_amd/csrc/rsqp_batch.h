@@ -1,0 +1,159 @@
+// rsqp_batch.h -- struct rsqp_batch and what more than one of its translation units uses. Private to them: rsqp_batch.hip (the batch
+// itself: create, whole-batch setters, solve, results, certificate, records), rsqp_batch_optimize.hip (optimizeQP / optimizeLP per
+// member and their plan kernels) and rsqp_batch_handler.hip (everything that writes the pools member by member). Device code does not
+// cross a unit: the __device__ helpers here are inline. Everything but the struct itself (the opaque type of the C ABI) is in namespace
+// rsqp_batch_units, which the three units open.
+#pragma once
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "rsqp_host.h"
+#include "rsqp_matrix.h"
+
+namespace rsqp_batch_units {
+// pinned host memory, with its device view where it is mapped; freed with its owner
+template <class T>
+struct HostBuf {
+    T *p = nullptr, *dev = nullptr;
+    size_t n = 0;
+    HostBuf() = default;
+    HostBuf(const HostBuf &) = delete;
+    HostBuf &operator=(const HostBuf &) = delete;
+    ~HostBuf() { if (p) (void)hipHostFree(p); }
+    hipError_t alloc(size_t count, bool mapped) {
+        if (p) (void)hipHostFree(p);
+        p = dev = nullptr; n = 0;
+        hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&p), sizeof(T) * std::max<size_t>(count, 1), mapped ? hipHostMallocMapped : hipHostMallocDefault);
+        if (e == hipSuccess && mapped) e = hipHostGetDevicePointer(reinterpret_cast<void **>(&dev), p, 0);
+        if (e == hipSuccess) n = count;
+        return e;
+    }
+};
+
+// optimizeQP per member (rsqp_batch_optimize_qp): nq ints each, in one block (rsqp_batch::opt) -- firstQPsolved_, old / new matrix
+// status, mode of the call's first solve, mode of its rescue solve (-1: none), kind of rescue, count of the first solve
+// rsqp_batch_optimize_lp adds: mode the first solve is LAUNCHED with (a flip is a plain init there), mode of the proximal step
+// (-1: the member is unsolved and takes none)
+// per member across calls as well: OPT_UPD the update mark (Update_A / Update_H of rsqp_batch_set_matrix_values_of and
+// rsqp_batch_handler_set_matrices, and of rsqp_batch_set_matrix_values for a member that sat out the call that took the batch-wide
+// mats_updated), OPT_FAM 1 + the kernel family that wrote the member's stored state (0 none; read while state_engine == -2)
+enum { OPT_FIRST = 0, OPT_OLD, OPT_NEW, OPT_MODE, OPT_RMODE, OPT_RESCUE, OPT_N1, OPT_LMODE, OPT_PMODE, OPT_UPD, OPT_FAM, OPT_WORDS };
+// word `word` of member q
+__device__ inline int &opt_word(int *opt, int nq, int word, int q) { return opt[word * nq + q]; }
+__device__ inline const int &opt_word(const int *opt, int nq, int word, int q) { return opt[word * nq + q]; }
+}  // namespace rsqp_batch_units
+using namespace rsqp_batch_units;
+
+struct rsqp_batch {
+    int nq = 0, device = 0, nVmax = 0, nCmax = 0, uniV = -1, uniC = -1;
+    bool uni_pat = false; int uni_annz = 0, uni_hnnz = 0; long long uni_state = 0;     // (QPPools::uni_pat)
+    long long sumV = 0, sumC = 0, sumAnz = 0, sumHnz = 0, mat_bytes_max = 0;
+    bool haveH = false;
+    SmallKnobs kn = rsqp_small_knobs_from_env();
+    // kernel family that wrote the members' hot-start states (see rsqp_solver::state_engine): >= 0 every member's, -1 nobody has one,
+    // -2 the members differ -- word OPT_FAM of each says (a call some members sat out ran on another family)
+    int state_engine = -1;
+    int last_kernel = -1;                 // rsqp_batch_get_last_kernel
+    bool hbm = false;                     // images beyond the LDS of a CU: every member on the HBM-resident kernel (qp_small_hbm.hip)
+    // the host's record of H's symmetry (judge_h_sym): h_sym = every H symmetric value by value (the tableau kernel of qp_tiny.hip
+    // may take the batch); h_symq[q] = member q's is. Kept for batches of at most 8 variables, with the H patterns in the caller's
+    // layout (member q's entries start at h_Huoff[q]), which are re-examined when the values change
+    bool h_sym = true;
+    std::vector<int> h_Hjc, h_Hir;
+    std::vector<long long> h_Huoff;
+    std::vector<char> h_symq;
+    ValueFold Afold, Hfold;               // members given in a non-canonical layout (PooledCsc): the pools hold the canonical form
+    std::vector<QPDesc> desc;
+    std::vector<int> h_csr_perm;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
+    DevBuf<QPDesc> d_desc;
+    DevBuf<int> Ajc, Air, Arp, Aci, perm, Hjc, Hir;
+    DevBuf<double> Aval, Arv, Hval;
+    DevBuf<double> g, lb, ub, lbA, ubA, x, y, obj, state;
+    DevBuf<int> ws_b, ws_c, status, ret, nwsr, nflips;
+    DevBuf<double> Ax, ATy, Hx, kkt;
+    DevBuf<int> Wb, Wc, kV, kC;
+    DevBuf<long long> koV, koC;
+    // the one device scratch block (ensure_scratch; grows, never shrinks) and the pinned block host-pointer calls pack their arrays
+    // into (ensure_staging of rsqp_batch_handler.hip). Every call that uses either waits for the stream before it returns, so both
+    // are free at every entry and each user lays out its own offsets from 0: the named setters (the caller's arrays), the
+    // host-pointer handler calls (one packed block up or down), rsqp_batch_pack_records_host (the records; it waits before its
+    // download). rsqp_batch_solve and rsqp_batch_pack_records_dev return without waiting and use neither
+    DevBuf<double> scratch;
+    HostBuf<double> pin;
+    // warm re-initialisation inputs (RSQP_MODE_WARM_REINIT), pooled like the vectors; allocated at first use. have_*: what
+    // rsqp_batch_set_warm_start gave (rsqp_batch_solve); rsqp_batch_optimize_qp fills the same pools on the device
+    DevBuf<double> wx0, wy0;
+    DevBuf<int> wgb;
+    bool have_x0 = false, have_y0 = false, have_gb = false;
+    DevBuf<int> opt;                      // the OPT_* words, OPT_WORDS * nq (ensure_opt)
+    // rsqp_batch_set_members: who takes part in the optimize calls. The kernels get the mask only while somebody sits out; with the
+    // default and with an all-ones mask the calls issue what they issued before there was a mask
+    DevBuf<int> take;
+    bool sitters = false;                 // somebody sits out
+    // rsqp_batch_set_vectors_of / rsqp_batch_set_matrix_values_of: the caller's mask on the device, allocated at first use, and where
+    // member q's entries start in a non-canonical caller layout (Afold / Hfold)
+    DevBuf<int> named;
+    DevBuf<long long> Auoff, Huoff;
+    // the QPhandler layer (rsqp_batch_handler_*): the NLP bounds of the members (x_l, x_u in the NLP layout, c_l, c_u in the
+    // constraint layout)
+    DevBuf<double> h_xl, h_xu, h_cl, h_cu;
+    long long sumN = 0;                   // NLP variables of the batch: sumV - 2 sumC
+    bool have_problem = false;            // rsqp_batch_handler_set_problem has run
+    // rsqp_batch_handler_set_matrices: h_jn[q] = entries of columns [0, n_q) of member q's A in the caller's layout (from
+    // rsqp_batch_create; sumJ of them in all). At the first call: where member q's entries start in jac (hm_joff, nq + 1) and the
+    // inverse of perm (hm_inv: CSC slot -> CSR slot)
+    std::vector<int> h_jn;
+    long long sumJ = 0;
+    bool uni_jn = false;                  // a one-pattern batch in a canonical layout: every member has h_jn[0] entries in jac
+    bool hm_ready = false;
+    DevBuf<long long> hm_joff;
+    DevBuf<int> hm_inv;
+    // the symmetry of every member's H on the device (batches of at most 8 variables): the device's copy of h_symq, stale after a
+    // host setter has re-examined members, and the host-mapped word a verdict that differs from the copy is flagged through
+    DevBuf<char> d_symq;
+    bool symq_stale = true;
+    HostBuf<int> sym;
+    // optimizeLP per member (rsqp_batch_optimize_lp): the members' descriptors with H absent and hreg = regVal of the member's last
+    // init (written on the device, kept across hot starts), and the pool of the proximal step's gradients g - regVal x
+    DevBuf<QPDesc> d_desc_lp;
+    DevBuf<double> g_lp;
+    int lp_maxiter = 100;                 // rsqp_batch_set_lp_options
+    int last_kind = 0;                    // 0 no optimize call yet, 1 the last one was rsqp_batch_optimize_qp, 2 rsqp_batch_optimize_lp
+    bool cert_lp = false;                 // the results in the pools are an LP call's: rsqp_batch_test_optimality certifies the LP
+    // nWSR_used of the members, written by the kernels straight into host-mapped memory: ready behind the call's one wait, no copy
+    // (and no second wait) behind it
+    HostBuf<int> used;
+    int qp_maxiter = 1000;                // rsqp_batch_set_options
+    bool mats_updated = false;            // rsqp_batch_set_matrix_values since the last optimize call (Update_A / Update_H of everybody)
+    bool opt_started = false;             // an rsqp_batch_optimize_qp has run: members are in different states from here on
+    float last_ms = 0.f;
+    bool keep_state = true;
+    bool timing = false;   // between timer_start and timer_stop: no per-launch events (they cost ~10 us of stream time each)
+    ~rsqp_batch() {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        if (ev2) (void)hipEventDestroy(ev2);
+        if (ev3) (void)hipEventDestroy(ev3);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+namespace rsqp_batch_units {
+// rsqp_batch.hip
+QPPools pools_of(rsqp_batch *b, bool lp);
+int batch_family(const rsqp_batch *b, const QPPools &p, bool lp);
+int launch_batch(rsqp_batch *b, QPPools &p, int mode, int max_nWSR, bool first, bool lp);
+int ensure_opt(rsqp_batch *b);
+int ensure_warm_pools(rsqp_batch *b);
+int ensure_scratch(rsqp_batch *b, size_t words);
+// members == null: everybody's h_symq anew from Hval, else the named members' (values in the caller's layout); then h_sym, and the
+// device's copy is stale. Hval == null: h_symq is on record already (read back from the device) and h_sym alone follows it
+void judge_h_sym(rsqp_batch *b, const int *members, const double *Hval);
+// after values have been written: the sums of a folded layout into the canonical pool, and (A) the CSR copy from that pool
+int settle_A(rsqp_batch *b);
+int settle_H(rsqp_batch *b);
+}  // namespace rsqp_batch_units

@@ -1,5 +1,5 @@
 // rsqp_host.h -- what every host translation unit of the C ABI shares: how an entry point reports an error, the status mapping, and
-// the accessors through which rsqp_rccl.cpp reaches a batch (struct rsqp_batch is private to rsqp_batch.hip).
+// the accessors through which rsqp_rccl.cpp reaches a batch (struct rsqp_batch is private to the batch units: rsqp_batch.h).
 #pragma once
 #include <string>
 

@@ -114,8 +114,6 @@ struct ValueFold {
     hipError_t set_folded(std::vector<int> &&cptr_, std::vector<int> &&cidx_, long long unnz_, const double *val0, bool on_host);
     // dst[j] = sum of the caller's values of canonical slot j, in the caller's order (host loop and fold_values of sparse.hip add alike)
     hipError_t sum(DevBuf<double> &dst, int nnz, hipStream_t stream);
-    // all values anew, in the caller's layout: a copy when canonical, else a copy and the sums
-    hipError_t refresh(const double *val, DevBuf<double> &dst, int nnz, hipStream_t stream);
 };
 
 // the pooled CSC matrices of a batch (member q: nrow[q] x ncol[q]; its column pointers start at 0 and index its own slice). When some

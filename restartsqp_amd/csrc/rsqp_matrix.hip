@@ -144,12 +144,6 @@ hipError_t ValueFold::sum(DevBuf<double> &dst, int nnz, hipStream_t stream) {
     return hipSuccess;
 }
 
-hipError_t ValueFold::refresh(const double *val, DevBuf<double> &dst, int nnz, hipStream_t stream) {
-    if (canon) return dst.upload(val, nnz);
-    const hipError_t e = uval.upload(val, unnz);
-    return e == hipSuccess ? sum(dst, nnz, stream) : e;
-}
-
 int pool_csc(int nq, const int *nrow, const int *ncol, const int *jc, const int *ir, const double *val, PooledCsc &P) {
     long long ojc = 0, onz = 0;
     P.uoff.resize(nq);

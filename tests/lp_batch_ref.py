@@ -1,5 +1,5 @@
 """Shared by tests/test_gpu_batch_optimize_lp.py and tests/test_batch_optimize_lp_args.py: the reference of optimizeLP per member of
-a batch (rsqp_batch_optimize_lp, restartsqp_amd/csrc/rsqp_batch.hip) and the inputs of its tests.
+a batch (rsqp_batch_optimize_lp, restartsqp_amd/csrc/rsqp_batch_optimize.hip) and the inputs of its tests.
 
 `LPRef` restates rsqp_optimize_lp (restartsqp_amd/csrc/rsqp_api.hip; reference src/qpOASESInterface.cpp:227-284 and the LP branch of
 handle_error, :688-717) over oracle.OracleQP, the way `Ref` of tests/test_gpu_batch_optimize.py restates rsqp_optimize_qp. The six-step

@@ -1,5 +1,5 @@
 """The QPhandler of every member of a batch on the device (rsqp_batch_handler_set_problem / _update / _get_step, rsqp_batch_get_vectors;
-restartsqp_amd/csrc/rsqp_batch.hip). Expected vectors come from handler.batch_handler_reference and problems.handler_qp (checked
+restartsqp_amd/csrc/rsqp_batch_handler.hip). Expected vectors come from handler.batch_handler_reference and problems.handler_qp (checked
 against each other and against QPhandler's setters on the CPU, tests/test_batch_handler_args.py), never from the library; the
 step data are compared with the results() of the same solve."""
 import numpy as np

@@ -1,5 +1,5 @@
 """The matrices of the QPhandler of every member of a batch on the device (rsqp_batch_handler_set_matrices,
-rsqp_batch_get_matrix_values; restartsqp_amd/csrc/rsqp_batch.hip). Expected pools come from handler.batch_matrices_reference (checked
+rsqp_batch_get_matrix_values; restartsqp_amd/csrc/rsqp_batch_handler.hip). Expected pools come from handler.batch_matrices_reference (checked
 against problems.handler_qp on the CPU, tests/test_batch_handler_matrices_args.py), never from the library. What the pools do not
 show -- the CSR copy of A, the update marks, the kernel family -- is checked on twins: two batches of the same members, one driven
 through the host setter rsqp_batch_set_matrix_values_of and one through the new call, must dispatch, run and answer alike, byte for

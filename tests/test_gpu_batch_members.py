@@ -1,6 +1,6 @@
 """Members of a batch on their own (rsqp_batch_set_members, rsqp_batch_set_matrix_values_of, rsqp_batch_set_vectors_of;
-restartsqp_amd/csrc/rsqp_batch.hip): a member sits out optimize calls, takes new matrices alone, and behaves as a single rsqp_solver
-that received only the calls it was named in or took part in.
+restartsqp_amd/csrc/rsqp_batch_optimize.hip, rsqp_batch_handler.hip): a member sits out optimize calls, takes new matrices alone,
+and behaves as a single rsqp_solver that received only the calls it was named in or took part in.
 
 The sequences, references and tolerances are those of tests/test_gpu_batch_optimize.py (`T`) and tests/lp_batch_ref.py (`R`); what is
 new is a SCHEDULE from one seeded generator: per step and member `takes_part` (p = 0.7, the first step included), and per step that

@@ -1,4 +1,4 @@
-"""optimizeQP per member of a batch (rsqp_batch_optimize_qp, restartsqp_amd/csrc/rsqp_batch.hip): the warm-start dispatch of reference
+"""optimizeQP per member of a batch (rsqp_batch_optimize_qp, restartsqp_amd/csrc/rsqp_batch_optimize.hip): the warm-start dispatch of reference
 src/qpOASESInterface.cpp:137-224 and handle_error's QP branch (:718-757) for every member of an rsqp_batch, each in its own state.
 
 Reference of every comparison: the CPU oracle, driven by `Ref` below -- a restatement of rsqp_optimize_qp (dispatch + rescue) over
