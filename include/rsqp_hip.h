@@ -428,6 +428,11 @@ int rsqp_batch_set_keep_state(rsqp_batch *b, int keep);
  * with more than 16 384 members; RSQP_LANE), 3 = the HBM-resident null-space kernel (one workgroup per problem, its image in
  * the batch state block: batches whose largest member does not fit the LDS-resident kernels); -1 before the first solve */
 int rsqp_batch_get_last_kernel(const rsqp_batch *b);
+/* the build of the lane-per-problem kernel the same launch took: 4 = H kept as its leading 4 x 4 block (a batch of one sparsity
+ * pattern whose H has no entry outside it, as in the QPhandler formulation, where the slack variables have no curvature), 8 = the
+ * full triangle of H (RSQP_LANE_HBLOCK=0 forces it); 0 when that launch was not the lane-per-problem kernel's. Both builds give
+ * the same bits. */
+int rsqp_batch_get_lane_hblock(const rsqp_batch *b);
 /* device time of the last rsqp_batch_solve in milliseconds (HIP events on its stream) */
 float rsqp_batch_last_solve_ms(rsqp_batch *b);
 /* HIP-event stopwatch on the batch's stream: start records an event, stop records a

@@ -106,6 +106,7 @@ SYMBOLS = {
     "rsqp_batch_sync": (C.c_int, [C.c_void_p]),
     "rsqp_batch_set_keep_state": (C.c_int, [C.c_void_p, C.c_int]),
     "rsqp_batch_get_last_kernel": (C.c_int, [C.c_void_p]),
+    "rsqp_batch_get_lane_hblock": (C.c_int, [C.c_void_p]),
     "rsqp_batch_last_solve_ms": (C.c_float, [C.c_void_p]),
     "rsqp_batch_timer_start": (C.c_int, [C.c_void_p]),
     "rsqp_batch_timer_stop_ms": (C.c_float, [C.c_void_p]),
@@ -681,6 +682,11 @@ class Batch:
         """0 LDS null-space kernels, 1 tableau kernel with 8 lanes per problem, 2 lane-per-problem kernel, 3 HBM-resident
         null-space kernel (batches beyond the LDS fit) (rsqp_batch_get_last_kernel)"""
         return lib().rsqp_batch_get_last_kernel(self._h)
+
+    def lane_hblock(self):
+        """the lane-per-problem kernel's build of the last launch: 4 = H as its leading 4 x 4 block, 8 = the full triangle
+        (RSQP_LANE_HBLOCK=0 forces it), 0 = another kernel ran (rsqp_batch_get_lane_hblock)"""
+        return lib().rsqp_batch_get_lane_hblock(self._h)
 
     def last_solve_ms(self):
         return lib().rsqp_batch_last_solve_ms(self._h)

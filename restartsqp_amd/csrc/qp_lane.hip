@@ -77,11 +77,16 @@ __device__ __forceinline__ double recip(double x) {      // v_rcp_f64 + two Newt
     return y;
 }
 
-template <int MC>
+// HB: H has entries only in its leading HB x HB block (4, or 8 = anywhere) and no regularisation is added to it -- the host's
+// word for the whole batch (QPPools::lane_hblock). In the QPhandler formulation [x u v] the slacks have no curvature, so the
+// headline's H (11 entries on 4 variables) takes 10 register pairs instead of 36; everything beyond the block is the +0 the full
+// build holds there, and the products with it are left out: fma(+0, x, h) is h for finite x (h starts at +0), bit for bit
+template <int MC, int HB>
 struct LaneT {
-    static constexpr int N = MV + MC, NT = N * (N + 1) / 2, NH = MV * (MV + 1) / 2, NA = MC * MV, REFRESH = 8;
+    static_assert(HB == 4 || HB == MV, "leading block of H");
+    static constexpr int N = MV + MC, NT = N * (N + 1) / 2, NH = HB * (HB + 1) / 2, NA = MC * MV, REFRESH = 8;
     ldouble *G, *K;                      // my problem's tableau / the dense A of the data: entry e at [e * WL]
-    double Hr[NH];                       // the upper triangle of H: registers (compile-time positions only; staged through LDS)
+    double Hr[NH];                       // the upper triangle of H's block: registers (compile-time positions only; staged through LDS)
     double xv[MV], lo[MV], up[MV], loN[MV], upN[MV], yv[MV], g[MV], gN[MV], gy[MV];
     double ax[MC], loA[MC], upA[MC], cloN[MC], cupN[MC], yc[MC];
     int sv[MV], sc[MC];
@@ -89,7 +94,7 @@ struct LaneT {
     double hscale, hreg;
     long long tlast;                     // (-DRSQP_STAMPS builds)
 
-    __device__ __forceinline__ double Hs(int i, int k) const { return Hr[tri(i, k)]; }                     // static i, k < MV
+    __device__ __forceinline__ double Hs(int i, int k) const { return Hr[tri(i, k)]; }                     // static i, k < HB
     __device__ __forceinline__ double As(int i, int k) const { return K[(i * MV + k) * WL]; }             // i may vary by lane
     __device__ __forceinline__ int nFR() const { return __popc(fmask); }
     __device__ __forceinline__ int nAC() const { return __popc(amask); }
@@ -113,7 +118,7 @@ struct LaneT {
         double h[MV], aty[MV], a[MC];
         SFOR(k, MV, h[k] = 0.0; aty[k] = 0.0;);
         SFOR(i, MC, a[i] = 0.0;);
-        SFOR(k, MV, SFOR(j, (k) + 1, const double w = Hs(j, k);
+        SFOR(k, HB, SFOR(j, (k) + 1, const double w = Hs(j, k);
                 h[j] = fma(w, xv[k], h[j]);
                 if (j != k) h[k] = fma(w, xv[j], h[k]);););
         // (h[k] above: the terms j < k arrive in its own pass, the diagonal last of that pass, the terms beyond in later passes)
@@ -325,7 +330,9 @@ struct LaneT {
         SFOR1(j, MV, const int ja = P.Ajc[j <= nV ? j : nV], jh = hfast ? P.Hjc[j <= nV ? j : nV] : 0;
               const int jj = forH ? jh : ja; pcol += (j <= nV && pe >= jj) ? 1 : 0;);
         LSTAMP(10);
-        if (lane < 2 * HC) tab[lane] = pe < pn ? (forH ? (prow <= pcol ? ((pcol * (pcol + 1)) >> 1) + prow : -1) : NT + prow * MV + pcol) : -1;
+        // (an entry of H outside the block cannot come: the host checked the pattern; it would be skipped, not written out of place)
+        const bool hin = prow <= pcol && (HB == MV || pcol < HB);
+        if (lane < 2 * HC) tab[lane] = pe < pn ? (forH ? (hin ? ((pcol * (pcol + 1)) >> 1) + prow : -1) : NT + prow * MV + pcol) : -1;
         }
         SFOR(e, NA, K[e * WL] = 0.0;);
         wave_sync();
@@ -351,7 +358,7 @@ struct LaneT {
         if constexpr (!UNI) own_entries<false>(P.Ajc + qown * (nV + 1), P.Air, P.Aval, P.desc[qown].offAnz);
         wave_sync();           // (every lane has read its slots: the space is the tableau's / H's from here on)
         LSTAMP(12);
-        // ---- H: the upper triangle is collected in slots 0 .. NH - 1 (H arrives with both triangles: the table skips the lower one).
+        // ---- H: the upper triangle of its block is collected in slots 0 .. NH - 1 (H arrives with both triangles: the table skips the lower one).
         // Up to 16 entries per problem (the headline's H has 11) come through the table like A; a fuller H is gathered by its owner
         // (a round of 16 load instructions covers ALL entries of 1024 / hnnz problems, not 16 entries of each)
         SFOR(e, NH, G[e * WL] = 0.0;);
@@ -362,6 +369,8 @@ struct LaneT {
             if (lane >= nqw) {
                 SFOR(e, NH, G[e * WL] = S[e * WL];);
             }
+        } else if constexpr (HB < MV) {
+            // (a block of 4 x 4 has at most 16 entries: they came through the table, or there are none)
         } else if (!UNI) {
             if (P.uni_haveH) own_entries<true>(P.Hjc + qown * (nV + 1), P.Hir, P.Hval, P.desc[qown].offHnz);
         } else if (hnnz > HC) {
@@ -379,9 +388,9 @@ struct LaneT {
                      });
             }
         }
-        // (H + hreg I: the LP regularisation; hscale = the largest diagonal entry)
+        // (H + hreg I: the LP regularisation; hscale = the largest diagonal entry -- beyond the block the diagonal is 0 and moves nothing)
         hscale = 0.0;
-        SFOR(k, MV, SFOR(j, k + 1, double w = G[tri(j, k) * WL];
+        SFOR(k, HB, SFOR(j, k + 1, double w = G[tri(j, k) * WL];
                          if (j == k) { w = (k < nV) ? w + hreg : w; hscale = fmax(hscale, k < nV ? fabs(w) : 0.0); }
                          Hr[tri(j, k)] = w;););
         LSTAMP(13);
@@ -391,7 +400,7 @@ struct LaneT {
              cloN[i] = c ? clampinf(la_[i]) : -RSQP_INFTY; cupN[i] = c ? clampinf(ua_[i]) : RSQP_INFTY;);
     }
     __device__ __forceinline__ void g_from_K() {     // S empty: G = -K
-        SFOR(k, MV, SFOR(j, k + 1, G[tri(j, k) * WL] = -Hs(j, k);););
+        SFOR(k, MV, SFOR(j, k + 1, if constexpr (k < HB) G[tri(j, k) * WL] = -Hs(j, k); else G[tri(j, k) * WL] = -0.0;););
         SFOR(i, MC, SFOR(k, MV, G[tri(k, MV + i) * WL] = -As(i, k);); SFOR(j, i + 1, G[tri(MV + j, MV + i) * WL] = 0.0;););
     }
     __device__ __forceinline__ bool bounds_inconsistent() const {
@@ -724,9 +733,10 @@ struct LaneT {
 // with one wave per SIMD to hide the round trips, 100-144 KB of code, 340-960 registers spilled to scratch. Removed.)
 constexpr int LANE_TINY_MAGIC = 0x7a11e;
 
-template <int MC, bool KEEP, bool UNI>
+template <int MC, bool KEEP, bool UNI, int HB>
 __global__ void __launch_bounds__(WL) lane_qp_kernel(QPPools P, int nq, int maxWSR) {
-    typedef LaneT<MC> ENG;
+    static_assert(UNI || HB == MV, "the block build serves one-pattern batches");
+    typedef LaneT<MC, HB> ENG;
     constexpr int N = ENG::N;
     __shared__ __attribute__((aligned(16))) double lds[(ENG::NT + ENG::NA) * WL + 16];      // (+ the staging table: 32 ints)
     ldouble *T = (ldouble *)lds;
@@ -821,15 +831,21 @@ int rsqp_lane_fits(const SmallKnobs &kn, const QPPools &p, int nq, int nVmax, in
     //  20 480 (second round), 47 us at 32 768, 90 us at 65 536. With the state kept, 65 536 members: 0.075 against 0.132 ms)
     return nq >= (kn.lane > 0 ? kn.lane : 16385) ? 1 : 0;
 }
+// the build a launch of the lane-per-problem kernel takes: 4 = H kept as its leading 4 x 4 block, 8 = the full triangle. The block
+// build needs what only a one-pattern launch without regularisation can promise (QPPools::lane_hblock: the host's word on the pattern)
+int rsqp_lane_hblock(const QPPools &p) { return (p.uni_pat && p.lane_hblock == 4 && p.uni_hreg == 0.0) ? 4 : 8; }
 hipError_t rsqp_launch_lane_qp(const QPPools &p, int nq, int maxWSR, hipStream_t stream) {
     if (nq <= 0) return hipSuccess;
     const dim3 grid((unsigned)((nq + WL - 1) / WL)), block(WL);
-    if (p.uni_pat) {
-        if (p.keep_state) hipLaunchKernelGGL((lane_qp_kernel<2, true, true>), grid, block, 0, stream, p, nq, maxWSR);
-        else hipLaunchKernelGGL((lane_qp_kernel<2, false, true>), grid, block, 0, stream, p, nq, maxWSR);
+    if (rsqp_lane_hblock(p) == 4) {
+        if (p.keep_state) hipLaunchKernelGGL((lane_qp_kernel<2, true, true, 4>), grid, block, 0, stream, p, nq, maxWSR);
+        else hipLaunchKernelGGL((lane_qp_kernel<2, false, true, 4>), grid, block, 0, stream, p, nq, maxWSR);
+    } else if (p.uni_pat) {
+        if (p.keep_state) hipLaunchKernelGGL((lane_qp_kernel<2, true, true, 8>), grid, block, 0, stream, p, nq, maxWSR);
+        else hipLaunchKernelGGL((lane_qp_kernel<2, false, true, 8>), grid, block, 0, stream, p, nq, maxWSR);
     } else {
-        if (p.keep_state) hipLaunchKernelGGL((lane_qp_kernel<2, true, false>), grid, block, 0, stream, p, nq, maxWSR);
-        else hipLaunchKernelGGL((lane_qp_kernel<2, false, false>), grid, block, 0, stream, p, nq, maxWSR);
+        if (p.keep_state) hipLaunchKernelGGL((lane_qp_kernel<2, true, false, 8>), grid, block, 0, stream, p, nq, maxWSR);
+        else hipLaunchKernelGGL((lane_qp_kernel<2, false, false, 8>), grid, block, 0, stream, p, nq, maxWSR);
     }
     return hipGetLastError();
 }

@@ -41,6 +41,7 @@ QPPools pools_of(rsqp_batch *b, bool lp) {
     // the batch-wide uni_hreg / uni_haveH cannot say what an LP member needs: LP launches read the descriptors
     p.uni_pat = (b->uni_pat && !lp) ? 1 : 0;
     p.uni_annz = b->uni_annz; p.uni_hnnz = lp ? 0 : b->uni_hnnz; p.uni_haveH = (b->haveH && !lp) ? 1 : 0; p.uni_state = b->uni_state;
+    p.lane_hblock = (p.uni_pat && b->kn.lane_hblock != 0) ? b->lane_hblock : 8;   // (uni_hreg stays 0 in a batch)
     return p;
 }
 
@@ -165,6 +166,14 @@ extern "C" int rsqp_batch_create(int nq, const int *nV, const int *nC, const int
                                         std::memcmp(Hir + d.offHnz, Hir, sizeof(int) * d0.hnnz) == 0));
         }
     }
+    // (the lane-per-problem kernel keeps H as its leading 4 x 4 block when the one pattern has nothing outside it: the slacks of
+    //  the QPhandler formulation have no curvature)
+    if (b->uni_pat) {
+        bool inside = true;
+        for (int c = 0; b->haveH && c < b->uniV; c++)
+            for (int e = Hjc[c]; e < Hjc[c + 1]; e++) inside = inside && c < 4 && Hir[e] < 4;
+        b->lane_hblock = inside ? 4 : 8;
+    }
     b->uni_jn = b->uni_pat && PA.canon;   // (one canonical pattern: one J count; a folded layout may repeat positions per member)
     HIPCHK(hipStreamCreate(&b->stream));
     HIPCHK(hipEventCreate(&b->ev0)); HIPCHK(hipEventCreate(&b->ev1));
@@ -268,12 +277,13 @@ int launch_batch(rsqp_batch *b, QPPools &p, int mode, int max_nWSR, bool first, 
     b->state_engine = (p.member_mode && b->sitters && b->state_engine != fam) ? -2 : fam;
     hipError_t e;
     if (b->hbm) {
-        if (first) b->last_kernel = 3;
+        if (first) { b->last_kernel = 3; b->last_hblock = 0; }
         e = rsqp_launch_small_qp_hbm(kn, p, b->nq, b->nVmax, b->nCmax, mode, max_nWSR, b->stream);
     } else {
         // a cold-start-only batch on the tableau kernel keeps no state and leaves no mark: the handle remembers it instead
         if (fam == 1 && !b->keep_state) { p.skip_mark = 1; b->state_engine = -1; }
         if (first) b->last_kernel = fam == 1 ? (rsqp_lane_fits(kn, p, b->nq, b->nVmax, b->nCmax, mode) ? 2 : 1) : 0;
+        if (first) b->last_hblock = b->last_kernel == 2 ? rsqp_lane_hblock(p) : 0;
         e = rsqp_launch_small_qp(kn, p, b->nq, b->nVmax, b->nCmax, b->mat_bytes_max, mode, max_nWSR, b->stream);
     }
     if (e != hipSuccess) return fail(RSQP_ERR_DEVICE, std::string("QP kernel launch: ") + hipGetErrorString(e));
@@ -321,6 +331,7 @@ extern "C" int rsqp_batch_solve(rsqp_batch *b, int mode, int max_nWSR) {
 }
 
 extern "C" int rsqp_batch_get_last_kernel(const rsqp_batch *b) { return b ? b->last_kernel : -1; }
+extern "C" int rsqp_batch_get_lane_hblock(const rsqp_batch *b) { return b ? b->last_hblock : 0; }
 
 extern "C" int rsqp_batch_set_keep_state(rsqp_batch *b, int keep) {
     if (!b) return fail(RSQP_ERR_ARG, "null batch");

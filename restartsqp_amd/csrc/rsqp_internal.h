@@ -43,6 +43,7 @@ struct SmallKnobs {
     int waves = -1;           // RSQP_SMALL_WAVES       waves per SIMD the build is compiled for
     int no_tiny = 0;          // (set by the single-QP rescue, rsqp_api.hip, and by knobs_of, rsqp_batch.hip) 1: no hs071-scale tableau kernel; 2 (the LP launches of a batch): nor the mid-size one
     int lane = -1;            // RSQP_LANE              0: never the lane-per-problem kernel (qp_lane.hip); n > 0: from n members on (default 16 385)
+    int lane_hblock = -1;     // RSQP_LANE_HBLOCK       0: the lane-per-problem kernel always keeps the full triangle of H (never its leading-block build)
     int arena_mapped = -1;    // RSQP_ARENA_MAPPED      single-QP handles: patterns / plans in host-mapped memory, no upload at set_A / set_H (-1: hs071 scale only)
     int no_spin = 0;          // RSQP_NO_SPIN           single-QP waits block in hipStreamSynchronize instead of spinning on a mapped word
 };
@@ -77,6 +78,8 @@ struct QPPools {
     int skip_mark;    // 1 (batches with keep_state = 0 on the hs071-scale tableau kernel): the HOST remembers that no state was kept
                       //    (rsqp_batch::state_engine = -1: the next hot start runs cold), so the kernel does not touch the state block at
                       //    all -- the "not initialised" mark was one scattered 64-byte line per QP
+    int lane_hblock;  // 4: one pattern (uni_pat) whose H has every entry in its leading 4 x 4 block (or no entry): the lane-per-problem
+                      //    kernel keeps that block alone (rsqp_lane_hblock, qp_lane.hip); anything else: the full triangle
     int keep_state;   // 1: write the hot-start part of the engine image back to HBM at the end of a solve (what the
                       //    SQProblem object keeps between calls); 0: cold-start-only batches skip that write --
                       //    the image is marked "not initialised", a later hot start falls back to a cold start
@@ -159,6 +162,7 @@ int rsqp_small_qp_fits(int nVmax, int nCmax);
 int rsqp_tiny_fits(const SmallKnobs &kn, int nVmax, int nCmax);
 // qp_lane.hip: one lane per problem, for cold starts of large one-shape batches of at most 8 x 2
 int rsqp_lane_fits(const SmallKnobs &kn, const QPPools &p, int nq, int nVmax, int nCmax, int mode);
+int rsqp_lane_hblock(const QPPools &p);      // the build rsqp_launch_lane_qp takes for p: 4 (leading block of H) or 8 (full H)
 hipError_t rsqp_launch_lane_qp(const QPPools &p, int nq, int maxWSR, hipStream_t stream);
 // 1 when rsqp_launch_small_qp hands this launch to the register-resident tableau kernel (qp_tiny.hip), whose hot-start state has
 // another layout than the LDS-resident kernels': the caller forces a cold start when the answer changes between two solves of a

@@ -5,6 +5,7 @@ set -e
 cd "$(dirname "$0")/.."
 OBJ=restartsqp_amd/lib/obj
 /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -std=c++17 -fPIC -x hip "$@" -c restartsqp_amd/csrc/qp_lane.hip -o $OBJ/qp_lane_exp.o
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o restartsqp_amd/lib/librsqp_exp.so \
-    $OBJ/qp_lane_exp.o $OBJ/qp_tiny.o $OBJ/qp_small.o $OBJ/rsqp_api.o $OBJ/qp_large.o $OBJ/sparse.o $OBJ/dense_la.o $OBJ/qp_dump.o $OBJ/rsqp_rccl.o $OBJ/build_stamp.o
+# (every other object of the product build, whatever translation units it has: run the product build first)
+OTHERS=$(ls $OBJ/*.o | grep -v -e '/qp_lane\.o$' -e '/qp_lane_exp\.o$')
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o restartsqp_amd/lib/librsqp_exp.so $OBJ/qp_lane_exp.o $OTHERS
 echo built restartsqp_amd/lib/librsqp_exp.so
