@@ -433,6 +433,21 @@ int rsqp_batch_get_last_kernel(const rsqp_batch *b);
  * full triangle of H (RSQP_LANE_HBLOCK=0 forces it); 0 when that launch was not the lane-per-problem kernel's. Both builds give
  * the same bits. */
 int rsqp_batch_get_lane_hblock(const rsqp_batch *b);
+/* the launch plan of a batch or single-QP solve, without a GPU (host only; what rsqp_batch_get_last_kernel and
+ * rsqp_batch_get_lane_hblock report is read from the same plan). in[RSQP_PLAN_IN_WORDS], in this order: the switches RSQP_SMALL_ENGINE,
+ * RSQP_SMALL_LANES, RSQP_SMALL_WAVES (-1 = unset), no_tiny (0; 1 the single-QP rescue and LP handles, 2 the LP launches of a batch),
+ * RSQP_LANE (-1 = unset); nq, nVmax, nCmax, mat_bytes_max (LDS bytes of the largest member's staged matrices, -1 = never staged), mode
+ * (RSQP_MODE_*), hbm (the batch is beyond the LDS fit), state_engine (family that wrote the stored states: 0 / 1 / 3, < 0 none); then
+ * what the launch knows of its members, 0 / 1 unless noted: tiny_ok (every H symmetric), uniV, uniC (the one shape, else -1), uni_pat,
+ * desc, keep_state, skip_mark (the caller remembers a launch that keeps no state: batches), member_mode, done_flag, cert_out, x0, y0,
+ * guess_b (present), lane_hblock (4 / 8), uni_hreg (nonzero). out[RSQP_PLAN_OUT_WORDS]: invalid, empty, family (as
+ * rsqp_batch_get_last_kernel), engine (0 Givens / TQ, 1 explicit inverses), L, mat_lds, W, shape (NV * 256 + NC of a compile-time
+ * shape, else 0), mc, keep, uni, hb (the tableau and lane-per-problem builds), first (the mid-size tableau kernel goes first: 1 the
+ * 72 x 32 build, 2 the 64 x 64 build), grid, block, dynamic LDS bytes, stride, mode (after the rule that a hot start on another
+ * family's state starts cold), state_family, skip_mark. Returns RSQP_ERR_ARG on a null pointer or other counts. */
+#define RSQP_PLAN_IN_WORDS 27
+#define RSQP_PLAN_OUT_WORDS 20
+int rsqp_describe_small_launch(const int *in, int n_in, int *out, int n_out);
 /* device time of the last rsqp_batch_solve in milliseconds (HIP events on its stream) */
 float rsqp_batch_last_solve_ms(rsqp_batch *b);
 /* HIP-event stopwatch on the batch's stream: start records an event, stop records a

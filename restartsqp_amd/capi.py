@@ -107,6 +107,7 @@ SYMBOLS = {
     "rsqp_batch_set_keep_state": (C.c_int, [C.c_void_p, C.c_int]),
     "rsqp_batch_get_last_kernel": (C.c_int, [C.c_void_p]),
     "rsqp_batch_get_lane_hblock": (C.c_int, [C.c_void_p]),
+    "rsqp_describe_small_launch": (C.c_int, [ip, C.c_int, ip, C.c_int]),
     "rsqp_batch_last_solve_ms": (C.c_float, [C.c_void_p]),
     "rsqp_batch_timer_start": (C.c_int, [C.c_void_p]),
     "rsqp_batch_timer_stop_ms": (C.c_float, [C.c_void_p]),
@@ -170,6 +171,24 @@ def lib():
             f.argtypes = args
         _LIB = L
     return _LIB
+
+
+# the words of rsqp_describe_small_launch, in the order of include/rsqp_hip.h
+SMALL_LAUNCH_IN = ("engine", "lanes", "waves", "no_tiny", "lane", "nq", "nVmax", "nCmax", "mat_bytes_max", "mode", "hbm", "state_engine",
+                   "tiny_ok", "uniV", "uniC", "uni_pat", "desc", "keep_state", "skip_mark", "member_mode", "done_flag", "cert_out", "x0", "y0",
+                   "guess_b", "lane_hblock", "uni_hreg")
+SMALL_LAUNCH_OUT = ("invalid", "empty", "family", "engine", "L", "mat_lds", "W", "shape", "mc", "keep", "uni", "hb", "first", "grid", "block",
+                    "lds", "stride", "mode", "state_family", "skip_mark")
+
+
+def describe_small_launch(**words):
+    """the launch plan for the given words of SMALL_LAUNCH_IN (all of them, by name) as a dict over SMALL_LAUNCH_OUT; needs no GPU
+    (rsqp_describe_small_launch)"""
+    a = np.array([words[k] for k in SMALL_LAUNCH_IN], np.int32)
+    assert len(words) == len(SMALL_LAUNCH_IN)
+    out = np.zeros(len(SMALL_LAUNCH_OUT), np.int32)
+    check(lib().rsqp_describe_small_launch(_ip(a), len(a), _ip(out), len(out)))
+    return dict(zip(SMALL_LAUNCH_OUT, out.tolist()))
 
 
 def device_torch():

@@ -22,7 +22,7 @@
 // 65 536 problems in flight on the 256 CUs.
 #include <type_traits>
 
-#include "rsqp_internal.h"
+#include "rsqp_small_plan.h"
 
 #define LDS __attribute__((address_space(3)))
 typedef LDS double ldouble;
@@ -69,13 +69,7 @@ template <int I, int E, class F> __device__ __forceinline__ void sfor_(F &&f) {
 __device__ __forceinline__ int opq(int v) { asm volatile("" : "+v"(v)); return v; }
 __host__ __device__ constexpr int tri(int j, int k) { return j <= k ? k * (k + 1) / 2 + j : j * (j + 1) / 2 + k; }
 
-__device__ __forceinline__ double clampinf(double v) { return v > RSQP_INFTY ? RSQP_INFTY : (v < -RSQP_INFTY ? -RSQP_INFTY : v); }
-__device__ __forceinline__ double recip(double x) {      // v_rcp_f64 + two Newton steps (as qp_tiny.hip)
-    double y = __builtin_amdgcn_rcp(x);
-    double e = fma(-x, y, 1.0); y = fma(y, e, y);
-    e = fma(-x, y, 1.0); y = fma(y, e, y);
-    return y;
-}
+#include "qp_leaf.h"
 
 // HB: H has entries only in its leading HB x HB block (4, or 8 = anywhere) and no regularisation is added to it -- the host's
 // word for the whole batch (QPPools::lane_hblock). In the QPhandler formulation [x u v] the slacks have no curvature, so the
@@ -817,35 +811,18 @@ __global__ void __launch_bounds__(WL) lane_qp_kernel(QPPools P, int nq, int maxW
 
 }  // namespace
 
-// 1 if this launch is served by the lane-per-problem kernel: a cold start of a one-shape batch of at most 8 x 2 with more members
-// (16 384) than 8 lanes per problem hold at a time; no certificate / doorbell of a single-QP handle, no warm re-initialisation
-// inputs. A batch that keeps its state gets it written in the 8-lane kernel's layout; one that does not leaves no mark either
-// (the handle remembers: QPPools::skip_mark)
-int rsqp_lane_fits(const SmallKnobs &kn, const QPPools &p, int nq, int nVmax, int nCmax, int mode) {
-    if (kn.lane == 0) return 0;
-    // one shape (every member nV x nC); one sparsity pattern (member 0's arrays serve all) or patterns of their own (each lane walks its own)
-    if (!(p.uniV >= 1 && p.uniV <= MV && p.uniC >= 0 && p.uniC <= 2 && nVmax <= MV && nCmax <= 2 && (p.uni_pat || p.desc))) return 0;
-    if (mode != 0 || p.member_mode || (!p.keep_state && !p.skip_mark) || p.cert_out || p.done_flag || !p.tiny_ok || p.x0 || p.y0 || p.guess_b) return 0;
-    // (measured, tools/lane_vs_tiny_sweep.py: a launch of this kernel takes 36 us up to 16 384 problems and 43 us at 65 536 -- one
-    //  round of waves either way; the 8-lane kernel holds 16 384 problems at a time: 21 us up to 8 192, 26 us at 16 384, 40 us at
-    //  20 480 (second round), 47 us at 32 768, 90 us at 65 536. With the state kept, 65 536 members: 0.075 against 0.132 ms)
-    return nq >= (kn.lane > 0 ? kn.lane : 16385) ? 1 : 0;
-}
-// the build a launch of the lane-per-problem kernel takes: 4 = H kept as its leading 4 x 4 block, 8 = the full triangle. The block
-// build needs what only a one-pattern launch without regularisation can promise (QPPools::lane_hblock: the host's word on the pattern)
-int rsqp_lane_hblock(const QPPools &p) { return (p.uni_pat && p.lane_hblock == 4 && p.uni_hreg == 0.0) ? 4 : 8; }
-hipError_t rsqp_launch_lane_qp(const QPPools &p, int nq, int maxWSR, hipStream_t stream) {
-    if (nq <= 0) return hipSuccess;
-    const dim3 grid((unsigned)((nq + WL - 1) / WL)), block(WL);
-    if (rsqp_lane_hblock(p) == 4) {
-        if (p.keep_state) hipLaunchKernelGGL((lane_qp_kernel<2, true, true, 4>), grid, block, 0, stream, p, nq, maxWSR);
-        else hipLaunchKernelGGL((lane_qp_kernel<2, false, true, 4>), grid, block, 0, stream, p, nq, maxWSR);
-    } else if (p.uni_pat) {
-        if (p.keep_state) hipLaunchKernelGGL((lane_qp_kernel<2, true, true, 8>), grid, block, 0, stream, p, nq, maxWSR);
-        else hipLaunchKernelGGL((lane_qp_kernel<2, false, true, 8>), grid, block, 0, stream, p, nq, maxWSR);
-    } else {
-        if (p.keep_state) hipLaunchKernelGGL((lane_qp_kernel<2, true, false, 8>), grid, block, 0, stream, p, nq, maxWSR);
-        else hipLaunchKernelGGL((lane_qp_kernel<2, false, false, 8>), grid, block, 0, stream, p, nq, maxWSR);
+// the plan's build (rsqp_small_plan.h): state kept or not; one pattern or patterns of their own; H as its leading 4 x 4 block or in full
+hipError_t rsqp_launch_lane_qp(const SmallPlan &pl, const QPPools &p, int nq, int maxWSR, hipStream_t stream) {
+    static_assert(MV == 8 && WL == kLaneBlock, "rsqp_plan_lane_fits");
+    const dim3 grid(pl.grid), block(pl.block);
+    switch (pl.mc * 1000 + pl.keep * 100 + pl.uni * 10 + pl.hb) {
+    case 2114: hipLaunchKernelGGL((lane_qp_kernel<2, true, true, 4>), grid, block, 0, stream, p, nq, maxWSR); break;
+    case 2014: hipLaunchKernelGGL((lane_qp_kernel<2, false, true, 4>), grid, block, 0, stream, p, nq, maxWSR); break;
+    case 2118: hipLaunchKernelGGL((lane_qp_kernel<2, true, true, 8>), grid, block, 0, stream, p, nq, maxWSR); break;
+    case 2018: hipLaunchKernelGGL((lane_qp_kernel<2, false, true, 8>), grid, block, 0, stream, p, nq, maxWSR); break;
+    case 2108: hipLaunchKernelGGL((lane_qp_kernel<2, true, false, 8>), grid, block, 0, stream, p, nq, maxWSR); break;
+    case 2008: hipLaunchKernelGGL((lane_qp_kernel<2, false, false, 8>), grid, block, 0, stream, p, nq, maxWSR); break;
+    default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }

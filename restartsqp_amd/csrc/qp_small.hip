@@ -29,7 +29,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "rsqp_internal.h"
+#include "rsqp_small_plan.h"
 
 // diagnostic build only (-DRSQP_STAMPS, tools/stamp_small_kernel.py): cycles per phase of block 0
 #ifdef RSQP_STAMPS
@@ -223,14 +223,13 @@ small_qp_kernel(QPPools P, int nq, int stride, int mode, int maxWSR) {
 
 #include "qp_small_g.h"
 
+static_assert(EngineG<3, 1, 9, 4>::MAXV == 72 && EngineG<3, 1, 9, 4>::MAXC == 32 && EngineG<2, 2, 8, 8>::MAXV == 64 && EngineG<2, 2, 8, 8>::MAXC == 64,
+              "the sizes rsqp_plan_small_launch sends to the tableau kernels");
+
 }  // namespace
 
-static const long long kMaxLds = 160 * 1024;
-
-static long long align16(long long v) { return (v + 15) & ~15LL; }
-
 int rsqp_small_qp_fits(int nVmax, int nCmax) {
-    return align16(rsqp_image_bytes(nVmax, nCmax)) <= kMaxLds;
+    return rsqp_align16(rsqp_image_bytes(nVmax, nCmax)) <= kSmallMaxLds;
 }
 
 static int env_int(const char *name, int dflt) {
@@ -246,175 +245,81 @@ SmallKnobs rsqp_small_knobs_from_env() {
     k.no_spin = getenv("RSQP_NO_SPIN") != nullptr;
     return k;
 }
-int rsqp_small_launch_is_tiny(const SmallKnobs &kn, const QPPools &p, int nVmax, int nCmax) {
-    return (kn.engine < 0 && p.tiny_ok && rsqp_tiny_fits(kn, nVmax, nCmax)) ? 1 : 0;
+
+namespace {
+// one instantiation of the null-space kernel: launches the plan it matches (the full LDS is allowed once per kernel and device)
+template <int E, class ENG, int L, bool ML, int W, int SHAPE>
+hipError_t launch_build(const SmallPlan &pl, const QPPools &p, int nq, int maxWSR, hipStream_t stream) {
+    static std::atomic<unsigned long long> set_{0};
+    // (the plan sizes the image by its own restatement of this engine's counts: compared once per build, over every size that fits)
+    static const bool agrees = [] {
+        for (int nV = 1; nV <= 128; nV++)
+            for (int nC = 0; nC <= 128; nC++)
+                if (ENG::image_doubles(nV, nC) != rsqp_plan_image_doubles(E, SHAPE != 0, nV, nC) ||
+                    ENG::image_ints(nV, nC) != rsqp_plan_image_ints(E, nV, nC)) return false;
+        return true;
+    }();
+    if (!agrees) return hipErrorInvalidValue;
+    rsqp_allow_full_lds(reinterpret_cast<const void *>(&small_qp_kernel<ENG, L, ML, W, SHAPE>), set_, (int)kSmallMaxLds);
+    hipLaunchKernelGGL((small_qp_kernel<ENG, L, ML, W, SHAPE>), dim3(pl.grid), dim3(pl.block), (size_t)pl.lds, stream, p, nq, pl.stride, pl.mode, maxWSR);
+    return hipGetLastError();
 }
-hipError_t rsqp_launch_small_qp(const SmallKnobs &kn, const QPPools &p_in, int nq, int nVmax, int nCmax, long long mat_bytes_max, int mode,
-                                int maxWSR, hipStream_t stream) {
+// every instantiation of this unit, by the plan's (engine, L, mat_lds, W, shape). The two quick-turnaround builds for tuning
+// (tools/small_experiment.sh) keep a part of the table: -DRSQP_SMALL_EXPERIMENT the 8-lane Givens / TQ kernels, with the builds for
+// 3 and 4 waves per SIMD the product does not have; -DRSQP_SMALL_EXPERIMENT=2 the four-wave explicit-inverse kernel (mid-size
+// problems, BASELINE configs[4]). A plan outside the table is an invalid launch
+struct Build {
+    int engine, L, mat_lds, W, shape;
+    hipError_t (*launch)(const SmallPlan &, const QPPools &, int, int, hipStream_t);
+};
+template <int E, class ENG, int L, bool ML, int W, int SHAPE = 0>
+constexpr Build build() { return {E, L, ML, W, SHAPE, &launch_build<E, ENG, L, ML, W, SHAPE>}; }
+constexpr int S82 = 8 * 256 + 2;      // the compile-time shape 8 x 2, target vectors in registers
+const Build kBuilds[] = {
+#if defined(RSQP_SMALL_EXPERIMENT) && RSQP_SMALL_EXPERIMENT == 2
+    build<1, EngineX<256, true>, 256, true, 1>(),
+#elif defined(RSQP_SMALL_EXPERIMENT)
+    build<0, Engine<8, true, true>, 8, true, 2, S82>(), build<0, Engine<8, true, true>, 8, true, 3, S82>(),
+    build<0, Engine<8, true, true>, 8, true, 4, S82>(),
+    build<0, Engine<8, true>, 8, true, 2>(), build<0, Engine<8, true>, 8, true, 3>(), build<0, Engine<8, true>, 8, true, 4>(),
+#else
+    build<1, EngineX<64, false>, 64, false, 3>(), build<1, EngineX<16, true>, 16, true, 2>(),
+    build<1, EngineX<32, true>, 32, true, 2>(), build<1, EngineX<256, true>, 256, true, 1>(),
+    build<1, EngineX<64, true>, 64, true, 4>(),
+    build<0, Engine<64, false>, 64, false, 3>(),
+    build<0, Engine<8, true, true>, 8, true, 2, S82>(), build<0, Engine<8, true>, 8, true, 2>(),
+    build<0, Engine<16, true>, 16, true, 2>(), build<0, Engine<16, true>, 16, true, 3>(), build<0, Engine<16, true>, 16, true, 4>(),
+    build<0, Engine<32, true>, 32, true, 2>(), build<0, Engine<32, true>, 32, true, 3>(), build<0, Engine<32, true>, 32, true, 4>(),
+    build<0, Engine<64, true>, 64, true, 3>(), build<0, Engine<64, true>, 64, true, 4>(), build<0, Engine<64, true>, 64, true, 6>(),
+#endif
+};
+}  // namespace
+
+// launches what the plan says (rsqp_small_plan.h): no decision is taken here
+hipError_t rsqp_launch_small_qp(const SmallKnobs &kn, const SmallPlan &pl, const QPPools &p_in, int nq, int maxWSR, hipStream_t stream) {
+    if (pl.empty) return hipSuccess;
+    if (pl.invalid) return hipErrorInvalidValue;
     QPPools p = p_in;
     p.only_bailed = 0;
-    p.k_debug_bail = kn.k_debug_bail;
-    if (nq <= 0) return hipSuccess;
-    if (align16(rsqp_image_bytes(nVmax, nCmax)) > kMaxLds) return hipErrorInvalidValue;
-    // formulation: 0 = Givens / TQ (Engine), 1 = explicit inverses (EngineX, qp_small_x.h), which keeps
-    // DENSE copies of A and H in LDS. Measured per shape on the 512-QP hs0xx batch (ms, TQ vs explicit):
-    // 5x1 0.14 / 0.16, 8x2 0.045 / 0.051, 8x3 0.25 / 0.21, 12x4 0.49 / 0.42, 16x6 0.73 / 0.55,
-    // 23x6 1.26 / 1.01, 37x14 2.57 / 1.51, 69x28 10.8 / 4.1 -- the chains of the TQ form grow with nZ.
-    const int forcedE = kn.engine;
-    // hs071-scale problems: the register-resident tableau kernel (qp_tiny.hip) serves every call shape
-    if (rsqp_small_launch_is_tiny(kn, p, nVmax, nCmax) && rsqp_lane_fits(kn, p, nq, nVmax, nCmax, mode)) return rsqp_launch_lane_qp(p, nq, maxWSR, stream);
-    if (rsqp_small_launch_is_tiny(kn, p, nVmax, nCmax)) return rsqp_launch_tiny_qp(kn, p, nq, nVmax, nCmax, mode, maxWSR, stream);
-    const int eng = forcedE == 0 || forcedE == 1 ? forcedE : (nVmax > 8 ? 1 : 0);
-    if (eng == 1 && mat_bytes_max >= 0) mat_bytes_max = 8LL * ((long long)nVmax * nVmax + (long long)nCmax * nVmax);
-    // uniform hs071-scale batches (8 x 2 through the QPhandler formulation; parameter scans of one NLP iterate) run
-    // the build with the shape as a compile-time constant and the target vectors in registers (see RegVec)
-    const int forcedL0 = kn.lanes;
-    const bool shape82 = eng == 0 && p.uniV == 8 && p.uniC == 2 && mat_bytes_max >= 0 &&
-                         (forcedL0 < 0 || forcedL0 == 8);        // only the 8-lane build has the shape instantiation
-    // LDS image of the chosen formulation (the persistent copy in HBM is sized for the larger one)
-    const long long imgd = eng == 1 ? EngineX<64, true>::image_doubles(nVmax, nCmax)
-                                    : (shape82 ? Engine<8, true, true>::image_doubles(nVmax, nCmax) : Engine<64, true>::image_doubles(nVmax, nCmax));
-    const long long imgi = eng == 1 ? EngineX<64, true>::image_ints(nVmax, nCmax) : Engine<64, true>::image_ints(nVmax, nCmax);
-    const long long img = (8 * imgd + 2 * imgi + 7) & ~7LL;
-    const bool mat_lds = mat_bytes_max >= 0 && align16(img + mat_bytes_max) <= kMaxLds;
-    // LDS of one problem: image, then its staged matrices, 16-byte granular.
-    long long stride = align16(img + (mat_lds ? mat_bytes_max : 0));
-    // (an odd number of 16-byte units would spread the problems of a wave over the banks, but the LDS is
-    // allocated in 512-byte steps and the 8-lane build needs 8 x 2880 = 45 x 512 bytes for 7 workgroups per CU)
-    // lanes per problem: the vectors of the engine have nV (+ nC) entries, a wave of 64 lanes is
-    // mostly idle on hs0xx-scale problems, so 64 / L of them share a wave. Problems in one wave
-    // follow their own control flow (exec masking); the LDS capacity bounds the problems in flight.
-    const int forcedL = kn.lanes, forcedW = kn.waves;
-    const int nmax = nVmax > nCmax ? nVmax : nCmax;
-    int L = nmax <= 8 ? 8 : (nmax <= 16 ? 16 : (nmax <= 32 ? 32 : 64));
-    if ((forcedL == 8 || forcedL == 16 || forcedL == 32 || forcedL == 64) && forcedL >= L) L = forcedL;   // never fewer lanes than entries
-    if (eng == 1 && L < 16) L = 16;   // the explicit-inverse build has no 8-lane instantiation
-    if (!mat_lds) L = 64;
-    while (L < 64 && (64 / L) * stride > kMaxLds) L *= 2;
-    if (L == 64 && stride > kMaxLds) stride = align16(mat_lds ? img + mat_bytes_max : img);
-    const bool wide0 = eng == 1 && mat_lds && L == 64 && nVmax > 32;
-    bool wide = false;
-    // several waves per problem: four (256 lanes, one wave per SIMD). The kernel keeps ~430 values live per lane
-    // (256 VGPRs + AGPRs), so an eight-wave build spills 233 of them (measured).
-    // With one wave per SIMD every wave instruction costs its full 4+ cycles: the four-wave kernel is bound by the
-    // instruction count per wave (~350 per 69 x 69 product stage), not by LDS bandwidth or barriers.
-    constexpr int wideL = 256;
-    if (wide0 && stride + 8 * wideL <= kMaxLds) { stride += 8 * wideL; wide = true; }   // one double per lane of the wide build
-    // bank spread of packed waves: a 32-lane LDS access group holds 32 / L problems, each touching 2 L consecutive
-    // banks of the 64 (ds_read_b64: bank = dword address mod 64; stores: 16-lane groups, mod 32). Their images must
-    // therefore start 2 L dwords apart modulo 64, i.e. stride = 8 L (mod 256) bytes -- with stride = 0 (mod 256)
-    // every vector access of an 8-lane build is a 4-way conflict (measured: 54 % of the LDS-array cycles, LDS busy
-    // 73 % of the kernel). The stride is padded to the next such value when that does not cost a resident workgroup.
-    if (L < 64) {
-        long long s1 = stride;
-        while ((s1 & 255) != ((8 * L) & 255)) s1 += 16;
-        auto wgs = [&](long long st) { const long long a = (((64 / L) * st) + 511) / 512 * 512; return a > 0 ? kMaxLds / a : 0; };
-        if (wgs(s1) == wgs(stride) && (64 / L) * s1 <= kMaxLds) stride = s1;
-    }
-    const int G = 64 / L, nblk = (nq + G - 1) / G;
-    const size_t lds = (size_t)(G * stride);
-    // minimum resident waves per SIMD = register budget. One problem per wave keeps the uniform
-    // state in SGPRs and runs best with 6 (small images) or 4 waves; packed waves hold that state
-    // in VGPRs and need ~230 of them, so they run 2 waves/SIMD without spills (measured on
-    // 16 384 hs071-scale QPs: L=16 W=2 159 M solves/s, W=3 142 M, W=4 116 M; L=64 W=6 74 M; with the
-    // single-trip loop hints L=16 187 M, and on 65 536 QPs L=8 219 M vs L=16 194 M).
-    // Packed builds with W=6 (80 VGPRs, ~180 spilled) returned wrong results and are not built.
-    int waves = L == 64 ? (nVmax <= 16 ? 6 : 4) : 2;
-    if (forcedW >= 2 && forcedW <= (L == 64 ? 6 : 4)) waves = forcedW;
-    // ---- batches of mid-size problems (cold starts and hot starts on new vectors): the tableau kernel first (qp_small_g.h: 3 phases
-    // per working-set change instead of ~50); members it cannot carry (non-symmetric H, LP, undecidable tests) come back with
-    // ret == RET_BAIL and are solved by the null-space kernel launched right behind it, which skips everybody else
-    // 32 row blocks x 8 column blocks of lanes: up to 72 variables x 32 constraints -- the 69 x 28 class of the hs0xx batch.
-    typedef EngineG<3, 1, 9, 4> EK;      // up to 72 variables x 32 constraints
-    typedef EngineG<2, 2, 8, 8> EK2;     // up to 64 variables x 64 constraints
-    // (only where the null-space kernel would give a problem four waves as well: batches of SMALL problems are throughput-bound
-    //  and better served by 16 / 32 lanes per problem, several problems per wave)
-    // (per-member modes: the kernel itself leaves the members whose mode it does not carry to the null-space kernel)
-    // (kn.no_tiny == 2, the LP launches of a batch: every member would come back with RET_BAIL -- no H, hreg != 0)
-    if (forcedE < 0 && kn.no_tiny < 2 && eng == 1 && (nVmax > 32 || nCmax > 32) && (p.member_mode || mode == 0 || mode == 1) && !p.done_flag) {
-#define KK_LAUNCH(RV_, RC_, CV_, CC_)                                                                                            \
-        do {                                                                                                                     \
-            hipLaunchKernelGGL((small_qpg_kernel<RV_, RC_, CV_, CC_>), dim3(nq), dim3(256), 0, stream, p, nq, mode, maxWSR);     \
-            p.only_bailed = 1;                                                                                                   \
-        } while (0)
-        if (nVmax <= EK::MAXV && nCmax <= EK::MAXC) KK_LAUNCH(3, 1, 9, 4);
-        else if (nVmax <= EK2::MAXV && nCmax <= EK2::MAXC) KK_LAUNCH(2, 2, 8, 8);
-#undef KK_LAUNCH
-    }
-#define SQ_LAUNCH_U(ENG, LL, ML, W, U)                                                                        \
-    do {                                                                                                      \
-        static std::atomic<unsigned long long> set_{0};                                                       \
-        rsqp_allow_full_lds(reinterpret_cast<const void *>(&small_qp_kernel<ENG<LL, ML>, LL, ML, W, U>), set_, (int)kMaxLds); \
-        hipLaunchKernelGGL((small_qp_kernel<ENG<LL, ML>, LL, ML, W, U>), dim3(nblk), dim3(LL > 64 ? LL : 64), lds, stream, p, nq, \
-                           (int)stride, mode, maxWSR);                                                        \
-    } while (0)
-    // compile-time shape NV x NC, target vectors in registers
-#define SQ_LAUNCH_SHAPE(LL, W, NV, NC)                                                                        \
-    do {                                                                                                      \
-        static std::atomic<unsigned long long> set_{0};                                                       \
-        rsqp_allow_full_lds(reinterpret_cast<const void *>(&small_qp_kernel<Engine<LL, true, true>, LL, true, W, NV * 256 + NC>), set_, (int)kMaxLds); \
-        hipLaunchKernelGGL((small_qp_kernel<Engine<LL, true, true>, LL, true, W, NV * 256 + NC>), dim3(nblk), dim3(64), lds, stream, p, nq, \
-                           (int)stride, mode, maxWSR);                                                        \
-    } while (0)
-#define SQ_LAUNCH_E(ENG, LL, ML, W) SQ_LAUNCH_U(ENG, LL, ML, W, 0)
-#define SQ_LAUNCH(LL, ML, W) SQ_LAUNCH_E(Engine, LL, ML, W)
-#define SQ_WAVES(LL)                                                                                          \
-    switch (waves) {                                                                                          \
-    case 3: SQ_LAUNCH(LL, true, 3); break;                                                                    \
-    case 4: SQ_LAUNCH(LL, true, 4); break;                                                                    \
-    default: SQ_LAUNCH(LL, true, 2); break;                                                                   \
-    }
-#if defined(RSQP_SMALL_EXPERIMENT) && RSQP_SMALL_EXPERIMENT == 2
-    // quick-turnaround build for tuning (tools/small_experiment.sh -DRSQP_SMALL_EXPERIMENT=2): only the four-wave
-    // explicit-inverse kernel (mid-size problems, BASELINE configs[4])
-    {
-        if (!(eng == 1 && wide)) return hipErrorInvalidValue;
-        SQ_LAUNCH_E(EngineX, 256, true, 1);
-        return hipGetLastError();
-    }
-#elif defined(RSQP_SMALL_EXPERIMENT)
-    // quick-turnaround build for tuning (tools/small_experiment.sh): only the 8-lane Givens / TQ kernel
-    {
-        const bool fixed = shape82;
-        if (L != 8 || eng != 0 || !mat_lds) return hipErrorInvalidValue;
-        if (fixed) { switch (waves) { case 3: SQ_LAUNCH_SHAPE(8, 3, 8, 2); break; case 4: SQ_LAUNCH_SHAPE(8, 4, 8, 2); break; default: SQ_LAUNCH_SHAPE(8, 2, 8, 2); } }
-        else { switch (waves) { case 3: SQ_LAUNCH_U(Engine, 8, true, 3, 0); break; case 4: SQ_LAUNCH_U(Engine, 8, true, 4, 0); break; default: SQ_LAUNCH_U(Engine, 8, true, 2, 0); } }
-        return hipGetLastError();
-    }
-#else
-    if (eng == 1) {
-        if (!mat_lds) SQ_LAUNCH_E(EngineX, 64, false, 3);
-        else if (L == 16) SQ_LAUNCH_E(EngineX, 16, true, 2);
-        else if (L == 32) SQ_LAUNCH_E(EngineX, 32, true, 2);
-        else if (wide) SQ_LAUNCH_E(EngineX, 256, true, 1);   // four waves per problem: the O(n^2) phases split over 256 lanes
-        else SQ_LAUNCH_E(EngineX, 64, true, 4);
-    } else if (!mat_lds) {
-        SQ_LAUNCH(64, false, 3);
-    } else if (L == 8) {
-        // shape build: 160 instead of 253 VGPRs, no per-vector address registers, straight-line vector loops; the
-        // occupancy of both builds is capped at 2 waves per SIMD by the LDS a wave of 8 problems needs
-        if (shape82) SQ_LAUNCH_SHAPE(8, 2, 8, 2);
-        else SQ_LAUNCH(8, true, 2);
-    } else if (shape82) {
-        return hipErrorInvalidValue;    // the image was sized for the 8-lane shape build: never launch another one on it
-    } else if (L == 16) {
-        SQ_WAVES(16)
-    } else if (L == 32) {
-        SQ_WAVES(32)
-    } else {
-        switch (waves) {
-        case 3: SQ_LAUNCH(64, true, 3); break;
-        case 6: SQ_LAUNCH(64, true, 6); break;
-        default: SQ_LAUNCH(64, true, 4); break;
-        }
-    }
+    p.k_debug_bail = pl.family == 3 ? -1 : kn.k_debug_bail;
+    p.skip_mark = pl.skip_mark;
+    if (pl.family == 3) return rsqp_launch_small_qp_hbm(pl, p, nq, maxWSR, stream);
+    if (pl.family == 2) return rsqp_launch_lane_qp(pl, p, nq, maxWSR, stream);
+    if (pl.family == 1) return rsqp_launch_tiny_qp(pl, p, nq, maxWSR, stream);
+    int W = pl.W;
+#if defined(RSQP_SMALL_EXPERIMENT) && RSQP_SMALL_EXPERIMENT != 2
+    if (pl.L == 8 && (pl.waves == 3 || pl.waves == 4)) W = pl.waves;
 #endif
-#undef SQ_LAUNCH_SHAPE
-#undef SQ_LAUNCH_E
-#undef SQ_LAUNCH_U
-#undef SQ_WAVES
-#undef SQ_LAUNCH
-    return hipGetLastError();
+    const Build *b = nullptr;
+    for (const Build &k : kBuilds)
+        if (k.engine == pl.engine && k.L == pl.L && k.mat_lds == pl.mat_lds && k.W == W && k.shape == pl.shape) b = &k;
+    if (!b) return hipErrorInvalidValue;
+    if (pl.first) {
+        if (pl.first == 1) hipLaunchKernelGGL((small_qpg_kernel<3, 1, 9, 4>), dim3(nq), dim3(256), 0, stream, p, nq, pl.mode, maxWSR);
+        else hipLaunchKernelGGL((small_qpg_kernel<2, 2, 8, 8>), dim3(nq), dim3(256), 0, stream, p, nq, pl.mode, maxWSR);
+        p.only_bailed = 1;
+    }
+    return b->launch(pl, p, nq, maxWSR, stream);
 }
 
 long long rsqp_mat_lds_bytes(int nV, int nC, int annz, int hnnz) { return mat_lds_bytes(nV, nC, annz, hnnz); }

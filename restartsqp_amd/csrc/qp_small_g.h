@@ -60,9 +60,7 @@ template <int S> __device__ __forceinline__ int gmin_i32(int v) {
     } else { v = min(v, xchg_i32<S>(v)); return gmin_i32<S + 1>(v); }
 }
 
-// a value the compiler must not look through: a one-hot weight (a == k ? 1.0 : 0.0) that multiplies register-array entries is
-// otherwise recognised as a select and turned into an INDEXED load from a copy of the array in scratch memory
-__device__ __forceinline__ double opaque(double v) { asm volatile("" : "+v"(v)); return v; }
+#include "qp_leaf.h"
 __device__ __forceinline__ int opaque_i(int v) { asm volatile("" : "+v"(v)); return v; }
 
 template <int RV, int RC, int CV, int CC>

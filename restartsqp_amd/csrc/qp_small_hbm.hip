@@ -18,7 +18,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "rsqp_internal.h"
+#include "rsqp_small_plan.h"
 
 #define RSQP_IMAGE_AS 1
 #define STAMP(k) do { } while (0)
@@ -134,18 +134,11 @@ int rsqp_hbm_qp_fits(int nVmax, int nCmax) {
     return nVmax >= 1 && nCmax >= 0 && nVmax <= RSQP_HBM_MAX_V && nCmax <= RSQP_HBM_MAX_C;
 }
 
-hipError_t rsqp_launch_small_qp_hbm(const SmallKnobs &kn, const QPPools &p_in, int nq, int nVmax, int nCmax, int mode, int maxWSR,
-                                    hipStream_t stream) {
-    QPPools p = p_in;
-    p.only_bailed = 0;
-    p.k_debug_bail = -1;
-    if (nq <= 0) return hipSuccess;
-    if (!rsqp_hbm_qp_fits(nVmax, nCmax) || mode < 0 || mode > 3) return hipErrorInvalidValue;
-    // formulation as in rsqp_launch_small_qp: explicit inverses above 8 variables unless RSQP_SMALL_ENGINE says otherwise
-    const int eng = kn.engine == 0 || kn.engine == 1 ? kn.engine : (nVmax > 8 ? 1 : 0);
-    if (eng == 1)   // four waves per problem, dense copies of A and H in the slice
-        hipLaunchKernelGGL((small_qph_kernel<EngineX<256, true>, 256, 1>), dim3(nq), dim3(256), 0, stream, p, nq, mode, maxWSR);
-    else            // the Givens / TQ engine has a one-wave build only; sparse matrices from global memory
-        hipLaunchKernelGGL((small_qph_kernel<Engine<64, false>, 64, 2>), dim3(nq), dim3(64), 0, stream, p, nq, mode, maxWSR);
+hipError_t rsqp_launch_small_qp_hbm(const SmallPlan &pl, const QPPools &p, int nq, int maxWSR, hipStream_t stream) {
+    if (pl.engine == 1 && pl.L == 256 && pl.W == 1)         // four waves per problem, dense copies of A and H in the slice
+        hipLaunchKernelGGL((small_qph_kernel<EngineX<256, true>, 256, 1>), dim3(pl.grid), dim3(pl.block), 0, stream, p, nq, pl.mode, maxWSR);
+    else if (pl.engine == 0 && pl.L == 64 && pl.W == 2)     // the Givens / TQ engine has a one-wave build only; sparse matrices from global memory
+        hipLaunchKernelGGL((small_qph_kernel<Engine<64, false>, 64, 2>), dim3(pl.grid), dim3(pl.block), 0, stream, p, nq, pl.mode, maxWSR);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }

@@ -27,7 +27,7 @@
 // working set by a sequence of pivots from -K (warm_setup), as setup_aux of the CPU restatement builds its factors.
 #include <cstdlib>
 
-#include "rsqp_internal.h"
+#include "rsqp_small_plan.h"
 #include "rsqp_kkt.h"
 
 #define LDS __attribute__((address_space(3)))
@@ -84,16 +84,7 @@ __device__ __forceinline__ void argmin8(double &t, int &id) { argmin_step<0>(t, 
 // value of lane `src` (0..7) of my group of 8
 __device__ __forceinline__ double fetch8(double v, int src) { return __shfl(v, src, 8); }
 __device__ __forceinline__ int fetch8i(int v, int src) { return __shfl(v, src, 8); }
-// a value the compiler must not look through (one-hot weights would otherwise become indexed loads from scratch memory)
-__device__ __forceinline__ double opaque(double v) { asm volatile("" : "+v"(v)); return v; }
-
-__device__ __forceinline__ double clampinf(double v) { return v > RSQP_INFTY ? RSQP_INFTY : (v < -RSQP_INFTY ? -RSQP_INFTY : v); }
-__device__ __forceinline__ double recip(double x) {      // v_rcp_f64 + two Newton steps: ~2^-52 relative, the same bits in every lane
-    double y = __builtin_amdgcn_rcp(x);
-    double e = fma(-x, y, 1.0); y = fma(y, e, y);
-    e = fma(-x, y, 1.0); y = fma(y, e, y);
-    return y;
-}
+#include "qp_leaf.h"
 
 constexpr int MV = 8;       // variable slots = lanes of a group
 #ifndef TINY_BLOCK
@@ -784,21 +775,18 @@ long long rsqp_tiny_state_bytes(int nCmax) {
     const long long N = MV + (nCmax <= 2 ? 2 : (nCmax <= 4 ? 4 : 8));
     return 8 * (N * N + 48 + 32 + 16) + 4 * 24;
 }
-// 1 if the batch shape is served by this engine
-int rsqp_tiny_fits(const SmallKnobs &kn, int nVmax, int nCmax) {
-    return !kn.no_tiny && nVmax <= MV && nCmax <= 8 && nVmax >= 1;
-}
-hipError_t rsqp_launch_tiny_qp(const SmallKnobs &kn, const QPPools &p, int nq, int nVmax, int nCmax, int mode, int maxWSR, hipStream_t stream) {
-    if (nq <= 0) return hipSuccess;
-    if (!rsqp_tiny_fits(kn, nVmax, nCmax)) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)((nq + TG - 1) / TG)), block(TB);
-    // (launches of at most one workgroup per CU -- the single QP of an SQP iteration above all -- get the builds for ONE wave per SIMD:
-    //  268 instead of 256 registers, none spilled to scratch, whose round trips sit in the chain of a lone wave: cold solve of the hs071 QP 30.5 ->
-    //  28.8 us through the Python loop, the solveQP replay 23.0 -> 22.6 us through the C++ boundary, batches of up to 8 192 QPs 3 % faster)
-    if (nCmax <= 2 && nq <= 32 * 256) hipLaunchKernelGGL((tiny_qp_kernel<2, 1>), grid, block, 0, stream, p, nq, mode, maxWSR);
-    else if (nCmax <= 2) hipLaunchKernelGGL((tiny_qp_kernel<2, 2>), grid, block, 0, stream, p, nq, mode, maxWSR);
-    else if (nCmax <= 4 && nq <= 32 * 256) hipLaunchKernelGGL((tiny_qp_kernel<4, 1>), grid, block, 0, stream, p, nq, mode, maxWSR);
-    else if (nCmax <= 4) hipLaunchKernelGGL((tiny_qp_kernel<4, 2>), grid, block, 0, stream, p, nq, mode, maxWSR);
-    else hipLaunchKernelGGL((tiny_qp_kernel<8, 1>), grid, block, 0, stream, p, nq, mode, maxWSR);
+// the plan's build (rsqp_small_plan.h: MC by the batch's largest nC; one wave per SIMD for launches of at most one workgroup per CU)
+hipError_t rsqp_launch_tiny_qp(const SmallPlan &pl, const QPPools &p, int nq, int maxWSR, hipStream_t stream) {
+    static_assert(MV == 8, "rsqp_plan_tiny_fits");
+    // (a tuning build with another -DTINY_BLOCK, tools/tiny_block_sweep.sh, regroups the plan's problems)
+    const dim3 grid(TB == kTinyBlock ? pl.grid : (unsigned)((nq + TG - 1) / TG)), block(TB);
+    switch (pl.mc * 10 + pl.W) {
+    case 21: hipLaunchKernelGGL((tiny_qp_kernel<2, 1>), grid, block, 0, stream, p, nq, pl.mode, maxWSR); break;
+    case 22: hipLaunchKernelGGL((tiny_qp_kernel<2, 2>), grid, block, 0, stream, p, nq, pl.mode, maxWSR); break;
+    case 41: hipLaunchKernelGGL((tiny_qp_kernel<4, 1>), grid, block, 0, stream, p, nq, pl.mode, maxWSR); break;
+    case 42: hipLaunchKernelGGL((tiny_qp_kernel<4, 2>), grid, block, 0, stream, p, nq, pl.mode, maxWSR); break;
+    case 81: hipLaunchKernelGGL((tiny_qp_kernel<8, 1>), grid, block, 0, stream, p, nq, pl.mode, maxWSR); break;
+    default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }

@@ -17,6 +17,7 @@
 #include "rsqp_host.h"
 #include "rsqp_large.h"
 #include "rsqp_matrix.h"
+#include "rsqp_small_plan.h"
 #include "rsqp_sparse.h"
 
 namespace { thread_local std::string g_err; }
@@ -201,6 +202,19 @@ bool infeasible(const rsqp_solver *s) { return s->status_word >= 100 && s->statu
 // =====================================================================================
 extern "C" const char *rsqp_version(void) { return "restartsqp_amd 0.1 (gfx950)"; }
 extern "C" const char *rsqp_last_error(void) { return g_err.c_str(); }
+extern "C" int rsqp_describe_small_launch(const int *in, int n_in, int *out, int n_out) {
+    if (!in || !out || n_in != RSQP_PLAN_IN_WORDS || n_out != RSQP_PLAN_OUT_WORDS) return fail(RSQP_ERR_ARG, "rsqp_describe_small_launch");
+    SmallKnobs kn;
+    kn.engine = in[0]; kn.lanes = in[1]; kn.waves = in[2]; kn.no_tiny = in[3]; kn.lane = in[4];
+    const int *w = in + 12;
+    const SmallFacts f{w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], w[8], w[9], w[10], w[11], w[12], w[13], w[14], in[10], in[11]};
+    const SmallPlan pl = rsqp_plan_small_launch(kn, f, in[5], in[6], in[7], in[8], in[9]);
+    const int o[RSQP_PLAN_OUT_WORDS] = {pl.invalid, pl.empty, pl.family, pl.engine, pl.L, pl.mat_lds, pl.W, pl.shape, pl.mc, pl.keep, pl.uni, pl.hb,
+                                        pl.first, (int)pl.grid, (int)pl.block, (int)pl.lds, pl.stride, pl.mode, pl.state_family, pl.skip_mark};
+    std::copy(o, o + RSQP_PLAN_OUT_WORDS, out);
+    return RSQP_OK;
+}
+
 extern "C" int rsqp_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -257,7 +271,7 @@ extern "C" int rsqp_create(int nV, int nC, int device, rsqp_solver **out) {
         // (a failed reservation is "no arena": set_A / set_H then allocate per array as the HBM-scale handles do -- ADVICE r4)
         // (hs071-scale handles keep the arena in host-mapped memory: set_A / set_H then cost a store each instead of a stream wait and a
         //  copy -- 78 -> 37 us on the first QP of an SQP run, later QPs unchanged; RSQP_ARENA_MAPPED=0 / 1 forces either form)
-        const bool am = s->kn.arena_mapped >= 0 ? s->kn.arena_mapped != 0 : rsqp_tiny_fits(s->kn, nV, nC) != 0;
+        const bool am = s->kn.arena_mapped >= 0 ? s->kn.arena_mapped != 0 : rsqp_plan_tiny_fits(s->kn, nV, nC) != 0;
         if (nC > 0 && s->A.reserve(nC, nV, am) != hipSuccess) (void)hipGetLastError();
         if (s->H.reserve(nV, nV, am) != hipSuccess) (void)hipGetLastError();
     } else {
@@ -579,22 +593,27 @@ extern "C" int rsqp_solve(rsqp_solver *s, int mode, int *nWSR, const double *x0,
         if (guess_b) { HIPCHK(s->d_guess.upload(guess_b, s->nV)); p.guess_b = s->d_guess.p; }
     }
     if (s->d_done && !s->kn.no_spin) { p.done_flag = s->d_done; p.done_val = ++s->done_seq; }
-    // the hs071-scale tableau kernel forms the certificate QPhandler::solveQP asks for at the end of the SAME launch
-    const bool fused_cert = p.done_flag && p.tiny_ok && rsqp_tiny_fits(s->kn, s->nV, s->nC) && !s->lp_mode &&
-                            s->A.initialised == (s->nC > 0) && s->kn.engine < 0;
-    if (fused_cert) { p.cert_out = s->d_kkt.p; p.cert_Wb = s->d_Wb.p; p.cert_Wc = s->d_Wc.p; }
-    {   // the tableau kernel and the LDS-resident kernels keep different layouts in the same state block: a solve that changes
-        // the family (H lost or regained its symmetry between two solves) starts cold instead of restoring the other's bytes
-        const int fam = rsqp_small_launch_is_tiny(kn, p, s->nV, s->nC);
-        if ((mode == RSQP_MODE_HOT_VECTORS || mode == RSQP_MODE_HOT_MATRICES) && s->state_engine != fam) { mode = RSQP_MODE_COLD; s->last_mode = mode; }
-        s->state_engine = fam;
-    }
     const long long mat_bytes = rsqp_mat_lds_bytes(s->nV, s->nC, s->A.initialised ? s->A.nnz : 0, s->H.initialised ? s->H.nnz : 0);
+    // the plan of the solve (rsqp_small_plan.h). The tableau kernel and the LDS-resident kernels keep different layouts in the same
+    // state block: a solve that changes the family (H lost or regained its symmetry between two solves) starts cold instead of
+    // restoring the other's bytes -- the plan's mode says so
+    auto plan = [&](const SmallKnobs &k, int m) {
+        const SmallPlan pl = rsqp_plan_small_launch(k, rsqp_small_facts(p, false, s->state_engine), 1, s->nV, s->nC, mat_bytes, m);
+        s->state_engine = pl.state_family;
+        s->last_mode = pl.mode;
+        return pl;
+    };
+    // the hs071-scale tableau kernel forms the certificate QPhandler::solveQP asks for at the end of the SAME launch
+    // (asked for before the plan is made: a launch with a doorbell never takes the lane-per-problem kernel, with or without it)
+    if (p.done_flag && !s->lp_mode && s->A.initialised == (s->nC > 0)) { p.cert_out = s->d_kkt.p; p.cert_Wb = s->d_Wb.p; p.cert_Wc = s->d_Wc.p; }
+    const SmallPlan pl = plan(kn, mode);
+    const bool fused_cert = p.cert_out && pl.family == 1;
+    if (!fused_cert) { p.cert_out = nullptr; p.cert_Wb = nullptr; p.cert_Wc = nullptr; }
     // one solve of the handle: launch (with the certificate behind it, where the call has one), wait, fetch.
     // The results live in host-mapped memory and the kernel raises a host-mapped flag behind them: spinning on it saves
     // the ~10 us a blocking hipStreamSynchronize takes to wake up (a single hs071-scale solve is ~30 us end to end)
-    auto run = [&](const SmallKnobs &k, int m, int maxWSR, bool certify) {
-        const hipError_t e = rsqp_launch_small_qp(k, p, 1, s->nV, s->nC, mat_bytes, m, maxWSR, s->stream);
+    auto run = [&](const SmallKnobs &k, const SmallPlan &pl, int maxWSR, bool certify) {
+        const hipError_t e = rsqp_launch_small_qp(k, pl, p, 1, maxWSR, s->stream);
         if (e != hipSuccess) return fail(RSQP_ERR_DEVICE, std::string("QP kernel launch: ") + hipGetErrorString(e));
         if (certify) {
             if (fused_cert) { s->spec_cert = true; s->spec_cert_val = p.done_val; s->cert_pending = false; }
@@ -604,20 +623,17 @@ extern "C" int rsqp_solve(rsqp_solver *s, int mode, int *nWSR, const double *x0,
         else HIPCHK(hipStreamSynchronize(s->stream));
         return fetch_results(s);
     };
-    if ((rc = run(kn, mode, *nWSR, true)) != RSQP_OK) return rc;
+    if ((rc = run(kn, pl, *nWSR, true)) != RSQP_OK) return rc;
     if (s->state_engine == 1 && s->last_ret == RET_SETUP_FAILED) {
         // the register-resident tableau kernel gave up on a pivot in its rounding band (it has no hand-over of its own: the mid-size
         // tableau kernel bails to the null-space kernel inside the launcher): the LDS-resident Givens / TQ kernel takes the
         // same call over -- from scratch where the call wanted the tableau kernel's stored state
         SmallKnobs k2 = s->kn;
         k2.no_tiny = 1;
-        int mode2 = (mode == RSQP_MODE_HOT_VECTORS || mode == RSQP_MODE_HOT_MATRICES) ? RSQP_MODE_COLD : mode;
         p.cert_out = nullptr; p.cert_Wb = nullptr; p.cert_Wc = nullptr;
         if (p.done_flag) p.done_val = ++s->done_seq;
         s->spec_cert = false; s->cert_pending = false;
-        s->state_engine = 0;
-        s->last_mode = mode2;
-        if ((rc = run(k2, mode2, nWSR_in, false)) != RSQP_OK) return rc;
+        if ((rc = run(k2, plan(k2, mode), nWSR_in, false)) != RSQP_OK) return rc;
     }
     HIPCHK(s->d_nwsr.download(nWSR, 1));
     return RSQP_OK;

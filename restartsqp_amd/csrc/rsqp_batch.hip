@@ -4,6 +4,7 @@
 //
 // The status mapping is restated from the reference adapter src/qpOASESInterface.cpp (:332-357) as rsqp_api.hip restates it.
 #include "rsqp_batch.h"
+#include "rsqp_small_plan.h"
 #include "rsqp_sparse.h"
 
 // =====================================================================================
@@ -260,32 +261,26 @@ int ensure_warm_pools(rsqp_batch *b) {
     return RSQP_OK;
 }
 
-// kernel family a launch on this batch runs: 3 HBM-resident, 1 hs071-scale tableau (+ lane-per-problem), 0 LDS-resident
-int batch_family(const rsqp_batch *b, const QPPools &p, bool lp) {
-    return b->hbm ? 3 : rsqp_small_launch_is_tiny(knobs_of(b, lp), p, b->nVmax, b->nCmax);
+// the plan of a launch on this batch (rsqp_small_plan.h): the batch remembers by itself when a launch keeps no state
+static SmallPlan plan_of(const rsqp_batch *b, const QPPools &p, int mode, bool lp) {
+    SmallFacts f = rsqp_small_facts(p, b->hbm, b->state_engine);
+    f.skip_mark = 1;
+    return rsqp_plan_small_launch(knobs_of(b, lp), f, b->nq, b->nVmax, b->nCmax, b->mat_bytes_max, mode);
 }
+
+// layout a launch on this batch leaves in the state blocks: 3 HBM-resident, 1 hs071-scale tableau (+ lane-per-problem), 0 LDS-resident
+int batch_family(const rsqp_batch *b, const QPPools &p, bool lp) { return plan_of(b, p, RSQP_MODE_COLD, lp).state_family; }
 
 // one solve launch of the whole batch (p.member_mode: of the members it names). first: the launch rsqp_batch_get_last_kernel reports;
 // lp: a launch of rsqp_batch_optimize_lp (pools_of, knobs_of)
 int launch_batch(rsqp_batch *b, QPPools &p, int mode, int max_nWSR, bool first, bool lp) {
-    const SmallKnobs kn = knobs_of(b, lp);
-    const int fam = batch_family(b, p, lp);
-    // the kernel families keep different layouts in the same state block: a hot start on another family's state starts cold
-    // (per-member modes: the plan kernel was told, and `mode` is not read)
-    if (!p.member_mode && (mode == RSQP_MODE_HOT_VECTORS || mode == RSQP_MODE_HOT_MATRICES) && b->state_engine != fam) mode = RSQP_MODE_COLD;
-    // every member of the launch has a state of this family now; one that sits out keeps what it had
-    b->state_engine = (p.member_mode && b->sitters && b->state_engine != fam) ? -2 : fam;
-    hipError_t e;
-    if (b->hbm) {
-        if (first) { b->last_kernel = 3; b->last_hblock = 0; }
-        e = rsqp_launch_small_qp_hbm(kn, p, b->nq, b->nVmax, b->nCmax, mode, max_nWSR, b->stream);
-    } else {
-        // a cold-start-only batch on the tableau kernel keeps no state and leaves no mark: the handle remembers it instead
-        if (fam == 1 && !b->keep_state) { p.skip_mark = 1; b->state_engine = -1; }
-        if (first) b->last_kernel = fam == 1 ? (rsqp_lane_fits(kn, p, b->nq, b->nVmax, b->nCmax, mode) ? 2 : 1) : 0;
-        if (first) b->last_hblock = b->last_kernel == 2 ? rsqp_lane_hblock(p) : 0;
-        e = rsqp_launch_small_qp(kn, p, b->nq, b->nVmax, b->nCmax, b->mat_bytes_max, mode, max_nWSR, b->stream);
-    }
+    const SmallPlan pl = plan_of(b, p, mode, lp);
+    // every member of the launch has a state of this family now; one that sits out keeps what it had. A launch that keeps no state
+    // leaves no mark either: the record here says so
+    const int fam = pl.state_family;
+    b->state_engine = pl.skip_mark ? -1 : ((p.member_mode && b->sitters && b->state_engine != fam) ? -2 : fam);
+    if (first) { b->last_kernel = pl.family; b->last_hblock = pl.hb; }
+    const hipError_t e = rsqp_launch_small_qp(knobs_of(b, lp), pl, p, b->nq, max_nWSR, b->stream);
     if (e != hipSuccess) return fail(RSQP_ERR_DEVICE, std::string("QP kernel launch: ") + hipGetErrorString(e));
     return RSQP_OK;
 }

@@ -79,14 +79,14 @@ struct QPPools {
                       //    (rsqp_batch::state_engine = -1: the next hot start runs cold), so the kernel does not touch the state block at
                       //    all -- the "not initialised" mark was one scattered 64-byte line per QP
     int lane_hblock;  // 4: one pattern (uni_pat) whose H has every entry in its leading 4 x 4 block (or no entry): the lane-per-problem
-                      //    kernel keeps that block alone (rsqp_lane_hblock, qp_lane.hip); anything else: the full triangle
+                      //    kernel keeps that block alone (SmallPlan::hb, qp_lane.hip); anything else: the full triangle
     int keep_state;   // 1: write the hot-start part of the engine image back to HBM at the end of a solve (what the
                       //    SQProblem object keeps between calls); 0: cold-start-only batches skip that write --
                       //    the image is marked "not initialised", a later hot start falls back to a cold start
     const int *member_mode;   // non-null (rsqp_batch_optimize_qp): member q starts as member_mode[q] says (0..3 as the `mode` argument of the
                       //    kernels, which is then ignored); a negative value = the member is not in this launch and nothing of it is
                       //    touched. In one launch every mode-3 member has the same warm-start inputs present (x0 / y0 / guess_b are
-                      //    batch-wide pointers). The lane-per-problem kernel never sees such a launch (rsqp_lane_fits)
+                      //    batch-wide pointers). The lane-per-problem kernel never sees such a launch (rsqp_plan_lane_fits)
 };
 
 // optimizeQP's choice of the call shape (src/qpOASESInterface.cpp:150-208) from get_Matrix_change_status (:817-833), stated ONCE for
@@ -153,24 +153,17 @@ inline void rsqp_allow_full_lds(const void *fn, std::atomic<unsigned long long> 
     }
 }
 
-// launchers (defined in the .hip files)
-hipError_t rsqp_launch_small_qp(const SmallKnobs &kn, const QPPools &p, int nq, int nVmax, int nCmax, long long mat_bytes_max, int mode,
-                                int maxWSR, hipStream_t stream);
+// launchers (defined in the .hip files). Which kernel a launch runs is decided in rsqp_small_plan.h and nowhere else: the callers compute
+// the SmallPlan of a launch and rsqp_launch_small_qp executes it through the launcher of the plan's family
+struct SmallPlan;
+hipError_t rsqp_launch_small_qp(const SmallKnobs &kn, const SmallPlan &pl, const QPPools &p, int nq, int maxWSR, hipStream_t stream);
 long long rsqp_mat_lds_bytes(int nV, int nC, int annz, int hnnz);
 int rsqp_small_qp_fits(int nVmax, int nCmax);
 // qp_tiny.hip: the register-resident tableau kernel for problems of at most 8 variables and 8 constraints
-int rsqp_tiny_fits(const SmallKnobs &kn, int nVmax, int nCmax);
+hipError_t rsqp_launch_tiny_qp(const SmallPlan &pl, const QPPools &p, int nq, int maxWSR, hipStream_t stream);
 // qp_lane.hip: one lane per problem, for cold starts of large one-shape batches of at most 8 x 2
-int rsqp_lane_fits(const SmallKnobs &kn, const QPPools &p, int nq, int nVmax, int nCmax, int mode);
-int rsqp_lane_hblock(const QPPools &p);      // the build rsqp_launch_lane_qp takes for p: 4 (leading block of H) or 8 (full H)
-hipError_t rsqp_launch_lane_qp(const QPPools &p, int nq, int maxWSR, hipStream_t stream);
-// 1 when rsqp_launch_small_qp hands this launch to the register-resident tableau kernel (qp_tiny.hip), whose hot-start state has
-// another layout than the LDS-resident kernels': the caller forces a cold start when the answer changes between two solves of a
-// handle or batch
-int rsqp_small_launch_is_tiny(const SmallKnobs &kn, const QPPools &p, int nVmax, int nCmax);
-hipError_t rsqp_launch_tiny_qp(const SmallKnobs &kn, const QPPools &p, int nq, int nVmax, int nCmax, int mode, int maxWSR, hipStream_t stream);
+hipError_t rsqp_launch_lane_qp(const SmallPlan &pl, const QPPools &p, int nq, int maxWSR, hipStream_t stream);
 // qp_small_hbm.hip: the null-space engines with their images in HBM, one workgroup per problem, for batches beyond
 // rsqp_small_qp_fits (every member of such a batch, the small ones included); members up to RSQP_HBM_MAX_V x RSQP_HBM_MAX_C
 int rsqp_hbm_qp_fits(int nVmax, int nCmax);
-hipError_t rsqp_launch_small_qp_hbm(const SmallKnobs &kn, const QPPools &p, int nq, int nVmax, int nCmax, int mode, int maxWSR,
-                                    hipStream_t stream);
+hipError_t rsqp_launch_small_qp_hbm(const SmallPlan &pl, const QPPools &p, int nq, int maxWSR, hipStream_t stream);
