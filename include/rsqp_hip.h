@@ -448,6 +448,10 @@ int rsqp_batch_get_lane_hblock(const rsqp_batch *b);
 #define RSQP_PLAN_IN_WORDS 27
 #define RSQP_PLAN_OUT_WORDS 20
 int rsqp_describe_small_launch(const int *in, int n_in, int *out, int n_out);
+/* the plan of the launch rsqp_batch_get_last_kernel reports: out[RSQP_PLAN_OUT_WORDS], the words and order of
+ * rsqp_describe_small_launch's output -- which instantiation ran, not only which family. Returns RSQP_ERR_ARG on a null pointer,
+ * another count, or a batch that has not launched yet. */
+int rsqp_batch_get_last_plan(const rsqp_batch *b, int *out, int nout);
 /* device time of the last rsqp_batch_solve in milliseconds (HIP events on its stream) */
 float rsqp_batch_last_solve_ms(rsqp_batch *b);
 /* HIP-event stopwatch on the batch's stream: start records an event, stop records a

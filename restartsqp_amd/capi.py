@@ -108,6 +108,7 @@ SYMBOLS = {
     "rsqp_batch_get_last_kernel": (C.c_int, [C.c_void_p]),
     "rsqp_batch_get_lane_hblock": (C.c_int, [C.c_void_p]),
     "rsqp_describe_small_launch": (C.c_int, [ip, C.c_int, ip, C.c_int]),
+    "rsqp_batch_get_last_plan": (C.c_int, [C.c_void_p, ip, C.c_int]),
     "rsqp_batch_last_solve_ms": (C.c_float, [C.c_void_p]),
     "rsqp_batch_timer_start": (C.c_int, [C.c_void_p]),
     "rsqp_batch_timer_stop_ms": (C.c_float, [C.c_void_p]),
@@ -189,6 +190,24 @@ def describe_small_launch(**words):
     out = np.zeros(len(SMALL_LAUNCH_OUT), np.int32)
     check(lib().rsqp_describe_small_launch(_ip(a), len(a), _ip(out), len(out)))
     return dict(zip(SMALL_LAUNCH_OUT, out.tolist()))
+
+
+def plan_builds(plan):
+    """the kernel instantiations a launch plan (describe_small_launch, Batch.last_plan) starts, each by the plan words that tell it
+    from the other builds of its kernel: ("qp", engine, L, mat_lds, W, shape) small_qp_kernel, ("qpg", first) small_qpg_kernel,
+    which goes first where the plan says so, ("tiny", mc, W) tiny_qp_kernel, ("lane", keep, uni, hb) lane_qp_kernel,
+    ("qph", engine) small_qph_kernel. An invalid or empty plan starts none"""
+    if plan["invalid"] or plan["empty"]:
+        return []
+    fam = plan["family"]
+    if fam == 1:
+        return [("tiny", plan["mc"], plan["W"])]
+    if fam == 2:
+        return [("lane", plan["keep"], plan["uni"], plan["hb"])]
+    if fam == 3:
+        return [("qph", plan["engine"])]
+    first = [("qpg", plan["first"])] if plan["first"] else []
+    return first + [("qp", plan["engine"], plan["L"], plan["mat_lds"], plan["W"], plan["shape"])]
 
 
 def device_torch():
@@ -706,6 +725,13 @@ class Batch:
         """the lane-per-problem kernel's build of the last launch: 4 = H as its leading 4 x 4 block, 8 = the full triangle
         (RSQP_LANE_HBLOCK=0 forces it), 0 = another kernel ran (rsqp_batch_get_lane_hblock)"""
         return lib().rsqp_batch_get_lane_hblock(self._h)
+
+    def last_plan(self):
+        """the launch plan of the solve last_kernel() reports, as a dict over SMALL_LAUNCH_OUT: which instantiation ran
+        (rsqp_batch_get_last_plan)"""
+        out = np.zeros(len(SMALL_LAUNCH_OUT), np.int32)
+        check(lib().rsqp_batch_get_last_plan(self._h, _ip(out), len(out)))
+        return dict(zip(SMALL_LAUNCH_OUT, out.tolist()))
 
     def last_solve_ms(self):
         return lib().rsqp_batch_last_solve_ms(self._h)

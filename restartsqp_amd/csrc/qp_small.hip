@@ -290,7 +290,7 @@ const Build kBuilds[] = {
     build<0, Engine<8, true, true>, 8, true, 2, S82>(), build<0, Engine<8, true>, 8, true, 2>(),
     build<0, Engine<16, true>, 16, true, 2>(), build<0, Engine<16, true>, 16, true, 3>(), build<0, Engine<16, true>, 16, true, 4>(),
     build<0, Engine<32, true>, 32, true, 2>(), build<0, Engine<32, true>, 32, true, 3>(), build<0, Engine<32, true>, 32, true, 4>(),
-    build<0, Engine<64, true>, 64, true, 3>(), build<0, Engine<64, true>, 64, true, 4>(), build<0, Engine<64, true>, 64, true, 6>(),
+    build<0, Engine<64, true>, 64, true, 3>(), build<0, Engine<64, true>, 64, true, 4>(),      // (W = 6: wrong results, rsqp_small_plan.h)
 #endif
 };
 }  // namespace

@@ -430,13 +430,17 @@ struct EngineT {
                 const double xiv = (vV() && sv != 0) ? sgn * sg * ev : 0.0, xic = (vC() && sc != 0) ? sgn * sg * ec : 0.0;
                 double bt = RSQP_INFTY;
                 int bid = 0x7fffffff;
+                // (a coefficient of the dependency that is zero by the sparsity of A carries the rounding of the update-only
+                //  tableau, which grows with the row: seen 3.5e-13 beside entries of 127, taken as a partner with a step of 1e13.
+                //  The denominator test is therefore relative to the largest coefficient once that exceeds 1)
+                const double eden = RSQP_EPS_DEN * fmax(1.0, max8(fmax(fabs(xiv), fabs(xic))));
                 if (vC() && sc != 0) {
                     const double num = sc == -1 ? yc : -yc, den = sc == -1 ? xic : -xic;
-                    if (den > RSQP_EPS_DEN) { bt = (num > 0.0 ? num : 0.0) / den; bid = l; }
+                    if (den > eden) { bt = (num > 0.0 ? num : 0.0) / den; bid = l; }
                 }
                 if (vV() && sv != 0) {
                     const double num = sv == -1 ? yv : -yv, den = sv == -1 ? xiv : -xiv;
-                    if (den > RSQP_EPS_DEN) { const double t = (num > 0.0 ? num : 0.0) / den; if (t < bt) { bt = t; bid = nC + l; } }
+                    if (den > eden) { const double t = (num > 0.0 ? num : 0.0) / den; if (t < bt) { bt = t; bid = nC + l; } }
                 }
                 argmin8(bt, bid);
                 if (bid == 0x7fffffff) {

@@ -202,16 +202,19 @@ bool infeasible(const rsqp_solver *s) { return s->status_word >= 100 && s->statu
 // =====================================================================================
 extern "C" const char *rsqp_version(void) { return "restartsqp_amd 0.1 (gfx950)"; }
 extern "C" const char *rsqp_last_error(void) { return g_err.c_str(); }
+// a plan as the RSQP_PLAN_OUT_WORDS words of rsqp_hip.h (rsqp_describe_small_launch, rsqp_batch_get_last_plan)
+void rsqp_plan_words(const SmallPlan &pl, int *out) {
+    const int o[RSQP_PLAN_OUT_WORDS] = {pl.invalid, pl.empty, pl.family, pl.engine, pl.L, pl.mat_lds, pl.W, pl.shape, pl.mc, pl.keep, pl.uni, pl.hb,
+                                        pl.first, (int)pl.grid, (int)pl.block, (int)pl.lds, pl.stride, pl.mode, pl.state_family, pl.skip_mark};
+    std::copy(o, o + RSQP_PLAN_OUT_WORDS, out);
+}
 extern "C" int rsqp_describe_small_launch(const int *in, int n_in, int *out, int n_out) {
     if (!in || !out || n_in != RSQP_PLAN_IN_WORDS || n_out != RSQP_PLAN_OUT_WORDS) return fail(RSQP_ERR_ARG, "rsqp_describe_small_launch");
     SmallKnobs kn;
     kn.engine = in[0]; kn.lanes = in[1]; kn.waves = in[2]; kn.no_tiny = in[3]; kn.lane = in[4];
     const int *w = in + 12;
     const SmallFacts f{w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], w[8], w[9], w[10], w[11], w[12], w[13], w[14], in[10], in[11]};
-    const SmallPlan pl = rsqp_plan_small_launch(kn, f, in[5], in[6], in[7], in[8], in[9]);
-    const int o[RSQP_PLAN_OUT_WORDS] = {pl.invalid, pl.empty, pl.family, pl.engine, pl.L, pl.mat_lds, pl.W, pl.shape, pl.mc, pl.keep, pl.uni, pl.hb,
-                                        pl.first, (int)pl.grid, (int)pl.block, (int)pl.lds, pl.stride, pl.mode, pl.state_family, pl.skip_mark};
-    std::copy(o, o + RSQP_PLAN_OUT_WORDS, out);
+    rsqp_plan_words(rsqp_plan_small_launch(kn, f, in[5], in[6], in[7], in[8], in[9]), out);
     return RSQP_OK;
 }
 

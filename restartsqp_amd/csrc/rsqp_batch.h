@@ -56,6 +56,7 @@ struct rsqp_batch {
     // -2 the members differ -- word OPT_FAM of each says (a call some members sat out ran on another family)
     int state_engine = -1;
     int last_kernel = -1;                 // rsqp_batch_get_last_kernel
+    int last_plan[RSQP_PLAN_OUT_WORDS] = {};      // rsqp_batch_get_last_plan: the plan of that launch, as rsqp_plan_words writes it
     // the lane-per-problem kernel's build (qp_lane.hip): lane_hblock = 4 when the batch's one pattern keeps H inside its leading
     // 4 x 4 block (judged once, at create: values change later, patterns never), else 8; last_hblock = what the last launch took
     int lane_hblock = 8, last_hblock = 0; // rsqp_batch_get_lane_hblock

@@ -279,7 +279,7 @@ int launch_batch(rsqp_batch *b, QPPools &p, int mode, int max_nWSR, bool first, 
     // leaves no mark either: the record here says so
     const int fam = pl.state_family;
     b->state_engine = pl.skip_mark ? -1 : ((p.member_mode && b->sitters && b->state_engine != fam) ? -2 : fam);
-    if (first) { b->last_kernel = pl.family; b->last_hblock = pl.hb; }
+    if (first) { b->last_kernel = pl.family; b->last_hblock = pl.hb; rsqp_plan_words(pl, b->last_plan); }
     const hipError_t e = rsqp_launch_small_qp(knobs_of(b, lp), pl, p, b->nq, max_nWSR, b->stream);
     if (e != hipSuccess) return fail(RSQP_ERR_DEVICE, std::string("QP kernel launch: ") + hipGetErrorString(e));
     return RSQP_OK;
@@ -327,6 +327,12 @@ extern "C" int rsqp_batch_solve(rsqp_batch *b, int mode, int max_nWSR) {
 
 extern "C" int rsqp_batch_get_last_kernel(const rsqp_batch *b) { return b ? b->last_kernel : -1; }
 extern "C" int rsqp_batch_get_lane_hblock(const rsqp_batch *b) { return b ? b->last_hblock : 0; }
+extern "C" int rsqp_batch_get_last_plan(const rsqp_batch *b, int *out, int nout) {
+    if (!b || !out || nout != RSQP_PLAN_OUT_WORDS) return fail(RSQP_ERR_ARG, "rsqp_batch_get_last_plan");
+    if (b->last_kernel < 0) return fail(RSQP_ERR_ARG, "rsqp_batch_get_last_plan: the batch has not launched yet");
+    std::copy(b->last_plan, b->last_plan + RSQP_PLAN_OUT_WORDS, out);
+    return RSQP_OK;
+}
 
 extern "C" int rsqp_batch_set_keep_state(rsqp_batch *b, int keep) {
     if (!b) return fail(RSQP_ERR_ARG, "null batch");

@@ -15,6 +15,9 @@ inline int fail(int code, const std::string &msg) { return rsqp_fail_msg(code, m
             return rsqp_fail_msg(RSQP_ERR_DEVICE, (std::string(#call) + ": " + hipGetErrorString(e_)).c_str());   \
     } while (0)
 
+struct SmallPlan;                               // rsqp_small_plan.h
+void rsqp_plan_words(const SmallPlan &pl, int *out);   // rsqp_api.hip: the plan as the RSQP_PLAN_OUT_WORDS words of rsqp_hip.h
+
 inline int exitflag_of(int status_word, int ret) {
     // qpOASESInterface::get_status (src/qpOASESInterface.cpp:332-357)
     if (status_word >= 200) return RSQP_QPERROR_UNBOUNDED;

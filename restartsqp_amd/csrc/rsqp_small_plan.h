@@ -171,13 +171,17 @@ inline SmallPlan rsqp_plan_small_launch(const SmallKnobs &kn, const SmallFacts &
     }
     const int G = 64 / L;
     // minimum resident waves per SIMD = register budget. One problem per wave keeps the uniform
-    // state in SGPRs and runs best with 6 (small images) or 4 waves; packed waves hold that state
+    // state in SGPRs and runs with 4 waves; packed waves hold that state
     // in VGPRs and need ~230 of them, so they run 2 waves/SIMD without spills (measured on
     // 16 384 hs071-scale QPs: L=16 W=2 159 M solves/s, W=3 142 M, W=4 116 M; L=64 W=6 74 M; with the
     // single-trip loop hints L=16 187 M, and on 65 536 QPs L=8 219 M vs L=16 194 M).
     // Packed builds with W=6 (80 VGPRs, ~180 spilled) returned wrong results and are not built.
-    int waves = L == 64 ? (nVmax <= 16 ? 6 : 4) : 2;
-    if (forcedW >= 2 && forcedW <= (L == 64 ? 6 : 4)) waves = forcedW;
+    // Neither is the one-problem-per-wave Givens / TQ build with W=6 (Engine<64, true>, once the default for nVmax <= 16): on
+    // 1 000 random QPs of at most 8 x 15 under RSQP_SMALL_LANES=64 it returned status "solved" with the right nWSR and a
+    // wrong x for 128 members, where its W=3 and W=4 builds and the 16- and 32-lane builds were right on all of them
+    // (tests/test_gpu_small_builds.py runs that batch on the two builds that stay). RSQP_SMALL_WAVES=6 falls back to W=4.
+    int waves = L == 64 ? 4 : 2;
+    if (forcedW >= 2 && forcedW <= 4) waves = forcedW;
     // ---- batches of mid-size problems (cold starts and hot starts on new vectors): the tableau kernel first (qp_small_g.h: 3 phases
     // per working-set change instead of ~50); members it cannot carry (non-symmetric H, LP, undecidable tests) come back with
     // ret == RET_BAIL and are solved by the null-space kernel launched right behind it, which skips everybody else
@@ -210,7 +214,7 @@ inline SmallPlan rsqp_plan_small_launch(const SmallKnobs &kn, const SmallFacts &
     } else if (L == 16 || L == 32) {
         pl.W = waves == 3 || waves == 4 ? waves : 2;
     } else {
-        pl.W = waves == 3 || waves == 6 ? waves : 4;
+        pl.W = waves == 3 ? 3 : 4;
     }
     return pl;
 }

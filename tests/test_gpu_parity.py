@@ -742,8 +742,9 @@ def test_single_qp_handles_on_degenerate_hs071_scale_inputs(capi, oracle):
 def test_packed_waves_match_one_problem_per_wave():
     """64/L problems share a wave in the LDS engine (L = 16 / 32 lanes per problem). Every packing
     must return bit-identical x, y, working sets, nWSR and objective, cold and hot start, on
-    heterogeneous batches (problems of one wave diverge). Each setting runs in its own process
-    because the launcher reads RSQP_SMALL_LANES once."""
+    heterogeneous batches (problems of one wave diverge). tools/small_pack_check.py runs each setting in a
+    process of its own (the switches are read per handle, at rsqp_batch_create) and fails a setting whose
+    launches did not run the build it asked for, or ran the reference setting's build."""
     import subprocess, sys, os
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "tools", "small_pack_check.py"), "--quick"],
@@ -756,8 +757,9 @@ def test_packed_waves_match_one_problem_per_wave():
 def test_both_formulations_pass_the_parity_suite(engine):
     """The LDS engine exists in two formulations -- Givens / TQ (qp_small.hip Engine, default for
     nV <= 8) and explicit inverses (qp_small_x.h EngineX, default above) -- chosen per batch from
-    nVmax. Force each of them on every batch of this file (the launcher reads RSQP_SMALL_ENGINE once
-    per process, hence the subprocess): both must match the oracle's working sets, nWSR, x and y."""
+    nVmax. Force each of them on every batch of this file (RSQP_SMALL_ENGINE is read per handle, when it is
+    created; the subprocess gives every test of the file the setting): both must match the oracle's working
+    sets, nWSR, x and y."""
     import subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, RSQP_SMALL_ENGINE=engine)
