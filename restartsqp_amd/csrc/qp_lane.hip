@@ -180,6 +180,101 @@ struct LaneT {
                  if (m < cnt) T[(s0 + e) * WL + qq] = w[t];
              });
     }
+    // ---- the same for a FULL wave (nqw == 64) whose pools are 16-byte aligned: the run of an array is exactly 64 n elements and
+    // starts on a multiple of 512 n bytes, so lane j moves 16 bytes per instruction (two doubles / four ints: group c * 64 + p(j) of the
+    // run) with no clamp and no bounds test per element -- a run of odd n ends in a half group of lanes, nothing is read or written
+    // beyond it. Owner and entry of a lane's first element come from one quotient per array SIZE and advance from group to group by
+    // add and carry (Walk). p(j) = 4 (j & 15) + (j >> 4): a 16-byte access of 64 lanes is one kilobyte whatever the order of the lanes
+    // inside it, and the LDS serves an 8-byte store (or one half of a two-address access) in groups of 16 consecutive lanes, 32 banks
+    // of 4 bytes: the bank of slot (e, owner) is 2 owner mod 32, so the 16 lanes of a group must hold 16 different owners mod 16.
+    // In natural order 16 lanes hold 32 / n owners (4 at n = 8: 4-way conflicts); with p(j) lane j of a group holds element 8 (j & 15)
+    // of the chunk, owner 8 (j & 15) / n -- distinct up to n = 8, two by two beyond (A, H, y: 2-way, which an 8-byte store hides
+    // behind its data transfer). Measured on the headline batch: 1 780 conflict cycles per wave with the 8-byte path, 1 036 with
+    // 16 bytes in natural order, 232 with p(j).
+    static constexpr bool PERM = true;
+    static __device__ __forceinline__ int pair_of(int lane) { return PERM ? ((lane & 15) << 2) | (lane >> 4) : lane; }
+    struct Walk { int qq, e, dq, dr; };
+    // element U * p of a run with n per problem; (dq, dr) = the step of U * 64 elements to the lane's next group
+    template <int U> static __device__ __forceinline__ Walk walk(int n, int p) {
+        const float rn = 1.0f / (float)n;
+        Walk w;
+        const int m = U * p;
+        w.qq = (int)(((float)m + 0.5f) * rn); w.e = m - w.qq * n;                              // (m < 64 * 64: the quotients are exact)
+        w.dq = (int)(((float)(U * WL) + 0.5f) * rn); w.dr = U * WL - w.dq * n;
+        return w;
+    }
+    static __device__ __forceinline__ void next_group(Walk &w, int n) {
+        w.qq += w.dq; w.e += w.dr;
+        const bool carry = w.e >= n;
+        w.e = carry ? w.e - n : w.e; w.qq = carry ? w.qq + 1 : w.qq;
+    }
+    // EVEN: n is even (wave-uniform, chosen by the caller) -- every group of lanes is full and a pair never straddles two owners
+    template <int CH, bool EVEN> __device__ __forceinline__ void load_pairs(const double *src, int n, int p, double (&w)[CH]) const {
+        static_assert((CH & 1) == 0, "pairs");
+        const double2 *s2 = reinterpret_cast<const double2 *>(src) + p;
+        SFOR(c, CH / 2, if (2 * c < n) {
+                 if (EVEN || c * WL + p < 32 * n) { const double2 v = s2[c * WL]; w[2 * c] = v.x; w[2 * c + 1] = v.y; }
+             });
+    }
+    // pairs into slots s0 + entry of their owners
+    template <int CH, bool EVEN> __device__ __forceinline__ void drop_pairs(ldouble *T, int s0, int n, int p, Walk wk, const double (&w)[CH]) const {
+        SFOR(c, CH / 2, if (2 * c < n) {
+                 if (EVEN || c * WL + p < 32 * n) {
+                     ldouble *a = T + (s0 + wk.e) * WL + wk.qq;
+                     a[0] = w[2 * c];
+                     if constexpr (EVEN) a[WL] = w[2 * c + 1];
+                     else (wk.e + 1 == n ? T + s0 * WL + wk.qq + 1 : a + WL)[0] = w[2 * c + 1];
+                 }
+                 next_group(wk, n);
+             });
+    }
+    // pairs of a matrix: entry e goes to slot tab[e] (a full wave's table names a spare slot for the entries to skip)
+    template <int CH, bool EVEN> __device__ __forceinline__ void drop_pair_entries(ldouble *T, const __attribute__((address_space(3))) int *tab, int n,
+                                                                                   int p, Walk wk, const double (&w)[CH]) const {
+        SFOR(c, CH / 2, if (2 * c < n) {
+                 if (EVEN || c * WL + p < 32 * n) {
+                     const bool over = !EVEN && wk.e + 1 == n;
+                     const int e1 = over ? 0 : wk.e + 1, q1 = over ? wk.qq + 1 : wk.qq;
+                     const int d0 = tab[wk.e], d1 = tab[e1];
+                     T[d0 * WL + wk.qq] = w[2 * c];
+                     T[d1 * WL + q1] = w[2 * c + 1];
+                 }
+                 next_group(wk, n);
+             });
+    }
+    // the reverse for results: x / y as pairs in the order p(j); the working sets (the low halves of their slots) four ints at a time
+    // in natural lane order (a 4-byte read is served in groups of 32 lanes, and four consecutive ints mostly share an owner)
+    template <int CH, bool EVEN> __device__ __forceinline__ void put_pairs(double *dst, int n, int p, const ldouble *T, int s0) const {
+        static_assert((CH & 1) == 0, "pairs");
+        Walk wk = walk<2>(n, p);
+        double2 *d2 = reinterpret_cast<double2 *>(dst) + p;
+        SFOR(c, CH / 2, if (2 * c < n) {
+                 if (EVEN || c * WL + p < 32 * n) {
+                     const ldouble *a = T + (s0 + wk.e) * WL + wk.qq;
+                     double2 v;
+                     v.x = a[0];
+                     if constexpr (EVEN) v.y = a[WL];
+                     else v.y = (wk.e + 1 == n ? T + s0 * WL + wk.qq + 1 : a + WL)[0];
+                     d2[c * WL] = v;
+                 }
+                 next_group(wk, n);
+             });
+    }
+    template <int CH> __device__ __forceinline__ void put_quads(int *dst, int n, int lane, const ldouble *T, int s0) const {
+        typedef const __attribute__((address_space(3))) int clint;
+        Walk wk = walk<4>(n, lane);
+        int4 *d4 = reinterpret_cast<int4 *>(dst) + lane;
+        SFOR(c, (CH + 3) / 4, if (4 * c < n) {
+                 if (c * WL + lane < 16 * n) {
+                     int v[4], qq = wk.qq, e = wk.e;
+                     SFOR(u, 4, v[u] = ((clint *)(T + (s0 + e) * WL + qq))[0];
+                          const bool wrap = e + 1 == n; e = wrap ? 0 : e + 1; qq = wrap ? qq + 1 : qq;);
+                     d4[c * WL] = make_int4(v[0], v[1], v[2], v[3]);
+                 }
+                 next_group(wk, n);
+             });
+    }
+#define BYPARITY(n, ...) do { if ((n) & 1) { constexpr bool EV = false; __VA_ARGS__ } else { constexpr bool EV = true; __VA_ARGS__ } } while (0)
     // ---- the state blocks of the wave's problems (QPPools::keep_state: what the next hot start continues from), LDS -> HBM. A
     // problem's block is N N + 96 doubles + 20 ints, consecutive, blocks `stride` doubles apart (the layout of qp_tiny.hip, see
     // LANE_TINY_MAGIC). A lane storing its own block piece by piece touches 64 lines per instruction for 8 bytes of each -- 0.17 ms
@@ -301,6 +396,14 @@ struct LaneT {
         static_assert(3 * MV + 2 * MC <= NT && NA <= HC, "staging slots");
         const int cV = nqw * nV, cC = nqw * nC, cA = nqw * annz, cH = nqw * hnnz;
         const bool hfast = hnnz > 0 && hnnz <= HC;
+        // a full wave of 16-byte aligned pools moves 16 bytes per lane (load_pairs); with H as its block, the block's entries land in
+        // spare slots behind the vectors in the SAME pass (SH ..), and the entries to skip in slot SPARE
+        constexpr int SH = 3 * MV + 2 * MC, SPARE = NT - 1;
+        static_assert(SH + 10 <= SPARE && MV * (MV + 1) / 2 <= SPARE, "spare slots of the full wave's pass");
+        const bool full = nqw == WL && annz <= NA &&
+                          (((size_t)P.g | (size_t)P.lb | (size_t)P.ub | (size_t)P.lbA | (size_t)P.ubA | (size_t)P.Aval | (size_t)P.Hval) & 15) == 0;
+        const bool onepass = HB < MV && full;
+        const int pp = pair_of(lane);
         // lanes beyond the batch (last wave) take the LAST problem's values: they run the same path beside it, store nothing, and
         // stay for the joint work of the wave (staging here, the stores of the results at the end)
         const ldouble *S = T + (lane < nqw ? lane : nqw - 1);
@@ -309,12 +412,20 @@ struct LaneT {
         // (member 0's arrays): lane e < 16 takes entry e of A, lane 16 + e entry e of H -- its row index, its column by counting
         // the column pointers it has passed (wave-uniform scalars)
         double wg[MV], wl[MV], wu[MV], wla[MC], wua[MC], wa[NA], wh[HC];
+        if (full) {
+            BYPARITY(nV, load_pairs<MV, EV>(P.g + q0 * nV, nV, pp, wg); load_pairs<MV, EV>(P.lb + q0 * nV, nV, pp, wl);
+                     load_pairs<MV, EV>(P.ub + q0 * nV, nV, pp, wu););
+            if (nC > 0) BYPARITY(nC, load_pairs<MC, EV>(P.lbA + q0 * nC, nC, pp, wla); load_pairs<MC, EV>(P.ubA + q0 * nC, nC, pp, wua););
+            if (annz > 0) BYPARITY(annz, load_pairs<NA, EV>(P.Aval + q0 * annz, annz, pp, wa););
+            if (hfast) BYPARITY(hnnz, load_pairs<HC, EV>(P.Hval + q0 * hnnz, hnnz, pp, wh););
+        } else {
         load_block<MV>(P.g + q0 * nV, nV, 0, cV, lane, wg);
         load_block<MV>(P.lb + q0 * nV, nV, 0, cV, lane, wl);
         load_block<MV>(P.ub + q0 * nV, nV, 0, cV, lane, wu);
         if (nC > 0) { load_block<MC>(P.lbA + q0 * nC, nC, 0, cC, lane, wla); load_block<MC>(P.ubA + q0 * nC, nC, 0, cC, lane, wua); }
         if (annz > 0) load_block<NA>(P.Aval + q0 * annz, annz, 0, cA, lane, wa);
         if (hfast) load_block<HC>(P.Hval + q0 * hnnz, hnnz, 0, cH, lane, wh);
+        }
         if constexpr (UNI) {
         const bool forH = lane >= HC;
         const int pe = forH ? lane - HC : lane, pn = forH ? (hfast ? hnnz : 0) : annz;
@@ -326,15 +437,31 @@ struct LaneT {
         LSTAMP(10);
         // (an entry of H outside the block cannot come: the host checked the pattern; it would be skipped, not written out of place)
         const bool hin = prow <= pcol && (HB == MV || pcol < HB);
-        if (lane < 2 * HC) tab[lane] = pe < pn ? (forH ? (hin ? ((pcol * (pcol + 1)) >> 1) + prow : -1) : NT + prow * MV + pcol) : -1;
+        const int hs0 = onepass ? SH : 0, skip = full ? SPARE : -1;
+        if (lane < 2 * HC) tab[lane] = pe < pn ? (forH ? (hin ? hs0 + ((pcol * (pcol + 1)) >> 1) + prow : skip) : NT + prow * MV + pcol) : skip;
         }
         SFOR(e, NA, K[e * WL] = 0.0;);
+        if constexpr (HB < MV) {
+            if (full) { SFOR(e, NH, G[(SH + e) * WL] = 0.0;); }
+        }
         wave_sync();
+        if (full) {
+            BYPARITY(nV, const Walk wk = walk<2>(nV, pp);
+                     drop_pairs<MV, EV>(T, SV, nV, pp, wk, wg); drop_pairs<MV, EV>(T, SV + MV, nV, pp, wk, wl);
+                     drop_pairs<MV, EV>(T, SV + 2 * MV, nV, pp, wk, wu););
+            if (nC > 0) BYPARITY(nC, const Walk wk = walk<2>(nC, pp);
+                                 drop_pairs<MC, EV>(T, SC, nC, pp, wk, wla); drop_pairs<MC, EV>(T, SC + MC, nC, pp, wk, wua););
+            if (annz > 0) BYPARITY(annz, drop_pair_entries<NA, EV>(T, tab, annz, pp, walk<2>(annz, pp), wa););
+            if constexpr (HB < MV) {
+                if (hfast) BYPARITY(hnnz, drop_pair_entries<HC, EV>(T, tab + HC, hnnz, pp, walk<2>(hnnz, pp), wh););
+            }
+        } else {
         drop_block<MV>(T, SV, nV, 0, cV, lane, wg);
         drop_block<MV>(T, SV + MV, nV, 0, cV, lane, wl);
         drop_block<MV>(T, SV + 2 * MV, nV, 0, cV, lane, wu);
         if (nC > 0) { drop_block<MC>(T, SC, nC, 0, cC, lane, wla); drop_block<MC>(T, SC + MC, nC, 0, cC, lane, wua); }
         if (annz > 0) drop_entries<NA>(T, tab, annz, cA, lane, wa);          // (straight to their places in the dense copy)
+        }
         wave_sync();
         LSTAMP(11);
         // ---- my vectors (slots beyond the sizes: neutral values)
@@ -355,10 +482,15 @@ struct LaneT {
         // ---- H: the upper triangle of its block is collected in slots 0 .. NH - 1 (H arrives with both triangles: the table skips the lower one).
         // Up to 16 entries per problem (the headline's H has 11) come through the table like A; a fuller H is gathered by its owner
         // (a round of 16 load instructions covers ALL entries of 1024 / hnnz problems, not 16 entries of each)
+        if (!onepass) {
         SFOR(e, NH, G[e * WL] = 0.0;);
         wave_sync();
-        if (hfast) {
-            drop_entries<HC>(T, tab + HC, hnnz, cH, lane, wh);
+        }
+        if (onepass) {
+            // (the block came with the vectors: it waits in slots SH .., which nobody writes before the tableau is built)
+        } else if (hfast) {
+            if (full) BYPARITY(hnnz, drop_pair_entries<HC, EV>(T, tab + HC, hnnz, pp, walk<2>(hnnz, pp), wh););
+            else drop_entries<HC>(T, tab + HC, hnnz, cH, lane, wh);
             wave_sync();
             if (lane >= nqw) {
                 SFOR(e, NH, G[e * WL] = S[e * WL];);
@@ -384,7 +516,8 @@ struct LaneT {
         }
         // (H + hreg I: the LP regularisation; hscale = the largest diagonal entry -- beyond the block the diagonal is 0 and moves nothing)
         hscale = 0.0;
-        SFOR(k, HB, SFOR(j, k + 1, double w = G[tri(j, k) * WL];
+        const ldouble *GH = G + (onepass ? SH * WL : 0);
+        SFOR(k, HB, SFOR(j, k + 1, double w = GH[tri(j, k) * WL];
                          if (j == k) { w = (k < nV) ? w + hreg : w; hscale = fmax(hscale, k < nV ? fabs(w) : 0.0); }
                          Hr[tri(j, k)] = w;););
         LSTAMP(13);
@@ -796,10 +929,19 @@ __global__ void __launch_bounds__(WL) lane_qp_kernel(QPPools P, int nq, int maxW
         SFOR(l, MV, if (l < nV) E.G[(SY + l) * WL] = E.yv[l];);
         SFOR(i, MC, if (i < nC) E.G[(SY + nV + i) * WL] = E.yc[i]; ((lint *)(E.G + (SW + i) * WL))[0] = E.sc[i];);
         E.wave_sync();
+        if (nqw == WL && (((size_t)P.x | (size_t)P.y | (size_t)P.ws_b | (size_t)P.ws_c) & 15) == 0) {
+            // (a full wave: 16 bytes per lane, as it was staged)
+            const int pp = ENG::pair_of(lane);
+            BYPARITY(nV, E.template put_pairs<MV, EV>(P.x + (long long)q0 * nV, nV, pp, T, SX););
+            BYPARITY(nV + nC, E.template put_pairs<MV + MC, EV>(P.y + (long long)q0 * (nV + nC), nV + nC, pp, T, SY););
+            E.template put_quads<MV>(P.ws_b + (long long)q0 * nV, nV, lane, T, SB);
+            if (nC > 0) E.template put_quads<MC>(P.ws_c + (long long)q0 * nC, nC, lane, T, SW);
+        } else {
         E.template put_block<MV>(P.x + (long long)q0 * nV, nV, nqw * nV, lane, T, SX);
         E.template put_block<MV + MC>(P.y + (long long)q0 * (nV + nC), nV + nC, nqw * (nV + nC), lane, T, SY);
         E.template put_block<MV>(P.ws_b + (long long)q0 * nV, nV, nqw * nV, lane, T, SB);
         if (nC > 0) E.template put_block<MC>(P.ws_c + (long long)q0 * nC, nC, nqw * nC, lane, T, SW);
+        }
     }
     if (q < nq) {
         const int st = E.status;
