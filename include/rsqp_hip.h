@@ -180,7 +180,8 @@ int rsqp_optimize_qp(rsqp_solver *s, int *nWSR_used);
 /* optimizeLP (qpOASESInterface.cpp:227-284): the same engine with H = 0 and the lp_maxiter
  * budget. As qpOASES does for an all-zero Hessian, the LP is solved as the QP with
  * H = regVal*I, regVal = |g|_2 * 1e3*EPS, followed by one regularisation (proximal) step.
- * Any H set on this handle is ignored. handle_error's LP branch (:688-717) included. */
+ * Any H set on this handle is ignored, by rsqp_test_optimality after the call as well (it certifies the LP, on either engine).
+ * handle_error's LP branch (:688-717) included. */
 int rsqp_optimize_lp(rsqp_solver *s, int *nWSR_used);
 /* low-level: one SQProblem::init / hotstart call. nWSR: in = limit, out = used.
  * x0, y0, guess_b (qpOASES convention -1/0/+1) may be NULL. */
@@ -464,8 +465,15 @@ float rsqp_batch_timer_stop_ms(rsqp_batch *b);
 /* results, concatenated like the inputs; any pointer may be NULL */
 int rsqp_batch_get_results(rsqp_batch *b, double *x, double *y, int *ws_b, int *ws_c, int *status,
                            int *nWSR, double *obj);
+/* verification: overwrite the result pools the certificate, the getters and the record packer read (the mirror of
+ * rsqp_batch_get_results); any pointer may be NULL. Stored hot-start state is not touched; the next solve overwrites them. */
+int rsqp_batch_set_results(rsqp_batch *b, const double *x, const double *y, const int *ws_b, const int *ws_c);
 /* fused KKT certificate for every problem of the batch (one launch) */
 int rsqp_batch_test_optimality(rsqp_batch *b, rsqp_optimality_status *out /* nq */, int *ok /* nq */);
+/* verification: the working sets as the last rsqp_batch_test_optimality mapped them (ACTIVE_ABOVE / ACTIVE_BELOW / ACTIVE_BOTH_SIDE /
+ * INACTIVE as rsqp_get_working_set reports them for a single handle; an invalid entry reads 12345), concatenated like ws_b and ws_c
+ * of rsqp_batch_get_results; either pointer may be NULL. RSQP_ERR_ARG before the first certificate. */
+int rsqp_batch_get_working_set(rsqp_batch *b, int *W_b, int *W_c);
 /* fixed-stride result records written to DEVICE memory, for the gather of a sharded batch over RCCL
  * (the path has no other exchange). Per problem, stride = 4 + 3 nVmax + 2 nCmax doubles:
  *   {Exitflag, nWSR, objective, KKT_error (0 before rsqp_batch_test_optimality), x[nVmax],

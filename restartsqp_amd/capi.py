@@ -113,7 +113,9 @@ SYMBOLS = {
     "rsqp_batch_timer_start": (C.c_int, [C.c_void_p]),
     "rsqp_batch_timer_stop_ms": (C.c_float, [C.c_void_p]),
     "rsqp_batch_get_results": (C.c_int, [C.c_void_p, dp, dp, ip, ip, ip, ip, dp]),
+    "rsqp_batch_set_results": (C.c_int, [C.c_void_p, dp, dp, ip, ip]),
     "rsqp_batch_test_optimality": (C.c_int, [C.c_void_p, C.c_void_p, ip]),
+    "rsqp_batch_get_working_set": (C.c_int, [C.c_void_p, ip, ip]),
     "rsqp_batch_record_stride": (C.c_int, [C.c_void_p]),
     "rsqp_batch_pack_records_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rsqp_batch_pack_records_host": (C.c_int, [C.c_void_p, dp]),
@@ -775,6 +777,30 @@ class Batch:
         ok = np.zeros(self.nq, np.int32)
         check(lib().rsqp_batch_test_optimality(self._h, C.cast(st, C.c_void_p), _ip(ok)))
         return ok, [st[q].KKT_error for q in range(self.nq)]
+
+    CERTIFICATE_FIELDS = ("primal_violation", "dual_violation", "compl_violation", "stationarity_violation", "KKT_error")
+
+    def certificates(self):
+        """the whole certificate of every member: (ok, fields) with ok[q] = 1 optimal / 0 not / ERR_WORKING_SET and fields an array
+        [nq, 5] over CERTIFICATE_FIELDS (rsqp_batch_test_optimality)"""
+        st = (OptimalityStatus * self.nq)()
+        ok = np.zeros(self.nq, np.int32)
+        check(lib().rsqp_batch_test_optimality(self._h, C.cast(st, C.c_void_p), _ip(ok)))
+        return ok, np.array([[getattr(st[q], f) for f in self.CERTIFICATE_FIELDS] for q in range(self.nq)]).reshape(self.nq, 5)
+
+    def mapped_working_sets(self):
+        """(W_b, W_c) per member as the last certificate mapped them (rsqp_batch_get_working_set)"""
+        Wb, Wc = np.zeros(int(self.offV[-1]), np.int32), np.zeros(int(self.offC[-1]), np.int32)
+        check(lib().rsqp_batch_get_working_set(self._h, _ip(Wb), _ip(Wc)))
+        return [(Wb[self.offV[q]:self.offV[q + 1]], Wc[self.offC[q]:self.offC[q + 1]]) for q in range(self.nq)]
+
+    def set_results(self, x=None, y=None, ws_b=None, ws_c=None):
+        """verification: overwrite the result pools (the layout of rsqp_batch_get_results: x and ws_b sum(nV) entries, y member by
+        member bounds then constraints, ws_c sum(nC)); None leaves a pool as it is (rsqp_batch_set_results)"""
+        sV, sC = int(self.offV[-1]), int(self.offC[-1])
+        x, y = self._sized(x, sV, "x"), self._sized(y, sV + sC, "y")
+        ws_b, ws_c = self._sized(ws_b, sV, "ws_b", np.int32), self._sized(ws_c, sC, "ws_c", np.int32)
+        check(lib().rsqp_batch_set_results(self._h, _dp(x), _dp(y), _ip(ws_b), _ip(ws_c)))
 
     def allgather_records(self, comm, count_per_rank, all_dev_ptr):
         """native RCCL: pack this rank's records into its slot of the DEVICE buffer at `all_dev_ptr`

@@ -73,6 +73,9 @@ template <int S> __device__ __forceinline__ double xchg_f64(double x) {
     return __hiloint2double(xchg_i32<S>(__double2hiint(x)), xchg_i32<S>(__double2loint(x)));
 }
 __device__ __forceinline__ double sum8(double v) { v += xchg_f64<0>(v); v += xchg_f64<1>(v); v += xchg_f64<2>(v); return v; }
+// the sum of a group of 8 lanes in the order block_sum_256 of sparse.hip takes over the first 8 lanes of a workgroup (lanes 4, 2, 1
+// apart): the certificate fused into this kernel then has the bytes of the one kkt_body forms of the same point
+__device__ __forceinline__ double sum8_as_kkt(double v) { v += __shfl_xor(v, 4, 8); v += xchg_f64<1>(v); v += xchg_f64<0>(v); return v; }
 __device__ __forceinline__ double max8(double v) { v = fmax(v, xchg_f64<0>(v)); v = fmax(v, xchg_f64<1>(v)); v = fmax(v, xchg_f64<2>(v)); return v; }
 __device__ __forceinline__ int or8(int v) { v |= xchg_i32<0>(v); v |= xchg_i32<1>(v); v |= xchg_i32<2>(v); return v; }
 template <int S> __device__ __forceinline__ void argmin_step(double &t, int &id) {
@@ -211,15 +214,21 @@ struct EngineT {
 
     // ------------------------------------------------------------------ products with the data (LDS copy of K)
     // gyx = (A'y_C - H x) of my variable row, axx = (A x) of my constraint row, hxx = (H x) of my variable row
-    __device__ __forceinline__ void exact_products(double &gyx, double &axx, double &hxx) const {
+    // (aty = (A'y_C) of my variable row by itself: the certificate associates the stationarity term as kkt_body of sparse.hip does)
+    __device__ __forceinline__ void exact_products(double &gyx, double &axx, double &hxx, double &aty) const {
         double all[N];
         gather(xv, yc, all);
-        double h = 0.0, aty = 0.0, a = 0.0;
+        double h = 0.0, a = 0.0;
+        aty = 0.0;
 #pragma unroll
         for (int k = 0; k < MV; k++) { h = fma(Kd[l * N + k], all[k], h); a = fma(Kd[(MV + (l < MC ? l : 0)) * N + k], all[k], a); }
 #pragma unroll
         for (int k = 0; k < MC; k++) aty = fma(Kd[l * N + MV + k], all[MV + k], aty);
         gyx = aty - h; axx = a; hxx = h;
+    }
+    __device__ __forceinline__ void exact_products(double &gyx, double &axx, double &hxx) const {
+        double aty;
+        exact_products(gyx, axx, hxx, aty);
     }
 
     // ------------------------------------------------------------------ pivots (every lane holds the pivot column(s) u / u2)
@@ -740,8 +749,8 @@ __global__ void __launch_bounds__(TB, W) tiny_qp_kernel(QPPools P, int nq, int m
         // written, from the rows this lane holds: A x, A'y_C - H x of the final iterate are exact products of finish()
         const double lraw = l < d.nV ? P.lb[d.offV + l] : 0.0, uraw = l < d.nV ? P.ub[d.offV + l] : 0.0;
         const double laraw = l < d.nC ? P.lbA[d.offC + l] : 0.0, uaraw = l < d.nC ? P.ubA[d.offC + l] : 0.0;
-        double gyx, axx, hxx;
-        E.exact_products(gyx, axx, hxx);
+        double gyx, axx, hxx, aty;
+        E.exact_products(gyx, axx, hxx, aty);
         double primal = 0.0, dual = 0.0, compl_ = 0.0, stat = 0.0;
         int bad = 0;
         if (l < d.nV) {
@@ -750,7 +759,7 @@ __global__ void __launch_bounds__(TB, W) tiny_qp_kernel(QPPools P, int nq, int m
             P.cert_Wb[d.offV + l] = Wm;
             primal += fmax(0.0, lo_ - E.xv) + -fmin(0.0, up_ - E.xv);
             kkt_terms(Wm, E.yv, E.xv, lo_, up_, dual, compl_, bad);
-            stat += fabs(gyx + E.yv - E.gN);                         // A'y_C + y_B - g - H x
+            stat += fabs(aty + E.yv - E.gN - hxx);                   // A'y_C + y_B - g - H x, associated as in kkt_body
         }
         if (l < d.nC) {
             const double lo_ = fmax(laraw, -RSQP_K_INFTY), up_ = fmin(uaraw, RSQP_K_INFTY);
@@ -759,7 +768,7 @@ __global__ void __launch_bounds__(TB, W) tiny_qp_kernel(QPPools P, int nq, int m
             primal += fmax(0.0, lo_ - axx) + -fmin(0.0, up_ - axx);
             kkt_terms(Wm, E.yc, axx, lo_, up_, dual, compl_, bad);
         }
-        primal = sum8(primal); dual = sum8(dual); compl_ = sum8(compl_); stat = sum8(stat);
+        primal = sum8_as_kkt(primal); dual = sum8_as_kkt(dual); compl_ = sum8_as_kkt(compl_); stat = sum8_as_kkt(stat);
         bad = or8(bad);
         if (l == 0) {
             double *o = P.cert_out + 6LL * q;

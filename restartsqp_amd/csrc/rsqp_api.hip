@@ -864,7 +864,7 @@ int run_certificate(rsqp_solver *s, rsqp_optimality_status *out, int *W_c, int *
         } else {
             HIPCHK(hipMemsetAsync(s->d_ATy.p, 0, sizeof(double) * s->nV, s->stream));
         }
-        if (s->H.initialised) {
+        if (s->H.initialised && !s->lp_mode) {   // (behind an LP call the certificate is the LP's: no H, as the LDS-scale one and the batch's)
             if ((rc = spmv_csc(s, s->H, s->d_x.p, s->d_Hx.p)) != RSQP_OK) return rc;             // H x (symmetric)
         } else {
             HIPCHK(hipMemsetAsync(s->d_Hx.p, 0, sizeof(double) * s->nV, s->stream));

@@ -391,6 +391,17 @@ extern "C" int rsqp_batch_get_results(rsqp_batch *b, double *x, double *y, int *
     return RSQP_OK;
 }
 
+extern "C" int rsqp_batch_set_results(rsqp_batch *b, const double *x, const double *y, const int *ws_b, const int *ws_c) {
+    if (!b) return fail(RSQP_ERR_ARG, "null batch");
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    if (x) HIPCHK(b->x.upload(x, b->sumV));
+    if (y) HIPCHK(b->y.upload(y, b->sumV + b->sumC));
+    if (ws_b) HIPCHK(b->ws_b.upload(ws_b, b->sumV));
+    if (ws_c) HIPCHK(b->ws_c.upload(ws_c, b->sumC));
+    return RSQP_OK;
+}
+
 extern "C" int rsqp_batch_test_optimality(rsqp_batch *b, rsqp_optimality_status *out, int *ok) {
     if (!b) return fail(RSQP_ERR_ARG, "null batch");
     HIPCHK(hipSetDevice(b->device));
@@ -424,6 +435,16 @@ extern "C" int rsqp_batch_test_optimality(rsqp_batch *b, rsqp_optimality_status 
         }
         if (ok) ok[q] = o[6 * q + 5] != 0.0 ? RSQP_ERR_WORKING_SET : (o[6 * q + 4] > 1.0e-6 ? 0 : 1);
     }
+    return RSQP_OK;
+}
+
+extern "C" int rsqp_batch_get_working_set(rsqp_batch *b, int *W_b, int *W_c) {
+    if (!b) return fail(RSQP_ERR_ARG, "null batch");
+    if (!b->Wb.p) return fail(RSQP_ERR_ARG, "rsqp_batch_get_working_set: rsqp_batch_test_optimality has not run yet");
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    if (W_b) HIPCHK(b->Wb.download(W_b, b->sumV));
+    if (W_c) HIPCHK(b->Wc.download(W_c, b->sumC));
     return RSQP_OK;
 }
 

@@ -693,6 +693,8 @@ __global__ void fold_values(int n, const int *__restrict__ ptr, const int *__res
 // ---------------------------------------------------------------------------------
 constexpr int KKT_NT = 256;
 
+// (the order -- lanes 32 .. 1 apart, then the four waves -- is part of what a handle returns: sum8_as_kkt of qp_tiny.hip takes the same
+//  order over its 8 lanes, so that the certificate fused into tiny_qp_kernel has the bytes of this one)
 __device__ inline double block_sum_256(double v, double *sh) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     __syncthreads();
@@ -747,6 +749,9 @@ kkt_kernel(RsqpKktArgs a) {
 }
 
 // products for a batch of SMALL problems: one workgroup per problem, lane per row/column
+// (each a chain s = fma(value, entry, s) from 0.0 over the stored entries in ascending order -- the contraction hipcc applies to
+//  `s += a * b` -- which is what exact_products of qp_tiny.hip computes over its dense rows, zeros included: the certificate fused
+//  into tiny_qp_kernel has the bytes of kkt_body's. tests/test_gpu_certificate.py (B1, B3) compares the two byte for byte)
 __device__ __forceinline__ void small_products_body(const QPDesc *desc, const int *Ajc, const int *Air, const double *Aval,
                       const int *Arp, const int *Aci, const double *Arv, const int *Hjc, const int *Hir,
                       const double *Hval, const double *x, const double *y, double *Ax, double *ATy,
