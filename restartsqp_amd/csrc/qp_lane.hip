@@ -29,17 +29,20 @@ typedef LDS double ldouble;
 
 // diagnostic build only (-DRSQP_STAMPS, tools/stamp_lane_kernel.py): cycles per phase of wave 0
 #ifdef RSQP_STAMPS
-__device__ unsigned long long g_lane_stamps[16];
+constexpr int kLaneStamps = 24;
+__device__ unsigned long long g_lane_stamps[kLaneStamps];
 #define LSTAMP(k)                                                                                        \
     do {                                                                                                 \
         long long t_ = clock64();                                                                        \
         if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&g_lane_stamps[k], (unsigned long long)(t_ - tlast)); \
         tlast = t_;                                                                                      \
     } while (0)
+// stamps INSIDE a phase (the parts of a working-set change): the product build has no fence there
+#define LSTAMP_IN(k) LSTAMP(k)
 extern "C" void rsqp_debug_lane_stamps(unsigned long long *out, int reset) {
-    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_lane_stamps), sizeof(unsigned long long) * 16);
+    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_lane_stamps), sizeof(unsigned long long) * kLaneStamps);
     if (reset) {
-        unsigned long long z[16] = {0};
+        unsigned long long z[kLaneStamps] = {0};
         (void)hipMemcpyToSymbol(HIP_SYMBOL(g_lane_stamps), z, sizeof(z));
     }
 }
@@ -49,6 +52,7 @@ extern "C" void rsqp_debug_lane_stamps(unsigned long long *out, int reset) {
 // name) leave no room for that -- 0.0566 ms per launch of the headline batch without, 0.0433 ms with them (the build with the
 // time stamps had been the faster one). Finer fences (per slot, inside the pivots) measured no better (0.0442 ms)
 #define LSTAMP(k) __builtin_amdgcn_sched_barrier(0)
+#define LSTAMP_IN(k)
 #endif
 
 namespace {
@@ -75,7 +79,7 @@ __host__ __device__ constexpr int tri(int j, int k) { return j <= k ? k * (k + 1
 // word for the whole batch (QPPools::lane_hblock). In the QPhandler formulation [x u v] the slacks have no curvature, so the
 // headline's H (11 entries on 4 variables) takes 10 register pairs instead of 36; everything beyond the block is the +0 the full
 // build holds there, and the products with it are left out: fma(+0, x, h) is h for finite x (h starts at +0), bit for bit
-template <int MC, int HB>
+template <int MC, int HB, int CH1 = 2, int CH2 = 2>
 struct LaneT {
     static_assert(HB == 4 || HB == MV, "leading block of H");
     static constexpr int N = MV + MC, NT = N * (N + 1) / 2, NH = HB * (HB + 1) / 2, NA = MC * MV, REFRESH = 8;
@@ -116,7 +120,13 @@ struct LaneT {
                 h[j] = fma(w, xv[k], h[j]);
                 if (j != k) h[k] = fma(w, xv[j], h[k]);););
         // (h[k] above: the terms j < k arrive in its own pass, the diagonal last of that pass, the terms beyond in later passes)
-        SFOR(k, MV, SFOR(i, MC, const double w = As(i, k);
+        // (GROUPED: A's reads go out together, ahead of the sums -- see sweep_triangle)
+        double ak[NA];
+        if constexpr (GROUPED) {
+            SFOR(k, MV, SFOR(i, MC, ak[i * MV + k] = As(i, k);););
+            __builtin_amdgcn_sched_group_barrier(0x100, NA, 0);
+        }
+        SFOR(k, MV, SFOR(i, MC, double w; if constexpr (GROUPED) w = ak[i * MV + k]; else w = As(i, k);
                 a[i] = fma(w, xv[k], a[i]);
                 aty[k] = fma(w, yc[i], aty[k]);););
                 SFOR(k, MV, gyx[k] = aty[k] - h[k]; hxx[k] = h[k];);
@@ -131,13 +141,38 @@ struct LaneT {
     }
 
     // ------------------------------------------------------------------ pivots
+    // G_jk <- f(j, k, G_jk) for every stored pair, CH entries at a time: a chunk's reads go out together, then its arithmetic (VPE
+    // vector instructions per entry), then its stores. The entries are independent, so the order between them is free; the groups
+    // pin it, because the scheduler, with the register file full of persistent state, otherwise sends every pair of entries
+    // through one register quad -- read, wait, two FMAs, store, 28 times --, and a lone wave on its SIMD waits out each of those
+    // LDS round trips. CH = 2 is that text, pair by pair: the builds whose registers have no room for a chunk
+    // (state kept, H in full) stay on it. CH1 / CH2: the chunks of pivot1 / pivot2 (kernel's choice, see lane_qp_kernel)
+    static constexpr bool GROUPED = CH1 > 2;         // this build pins its LDS reads into groups elsewhere too (g_from_K, exact_products)
+    static constexpr int col_of(int e) { int k = 0; while ((k + 1) * (k + 2) / 2 <= e) k++; return k; }
+    template <int CH, int VPE, class F> __device__ __forceinline__ void sweep_triangle(F &&f) {
+        SFOR(c, (NT + CH - 1) / CH,
+             constexpr int n = (c + 1) * CH <= NT ? CH : NT - c * CH;
+             double v[CH];
+             SFOR(i, n, v[i] = G[(c * CH + i) * WL];);
+             SFOR(i, n, constexpr int e = c * CH + i; constexpr int k = col_of(e); constexpr int j = e - k * (k + 1) / 2;
+                  v[i] = f(std::integral_constant<int, j>{}, std::integral_constant<int, k>{}, v[i]););
+             SFOR(i, n, G[(c * CH + i) * WL] = v[i];);
+             // (the compiler moves two neighbouring entries per LDS instruction, ds_read2st64_b64 / ds_write2st64_b64)
+             if constexpr (CH > 2) {
+                 __builtin_amdgcn_sched_group_barrier(0x100, (n + 1) / 2, 0);
+                 __builtin_amdgcn_sched_group_barrier(0x002, VPE * n, 0);
+                 __builtin_amdgcn_sched_group_barrier(0x200, (n + 1) / 2, 0);
+             });
+    }
     // principal pivot on slot q: G <- G0 - (1 / pi) u~ u~', G0 = G with row and column q zeroed, u~ = u except u~_q = sgn.
     // Every stored pair gets the update; row q (whose old entries do not enter) is then written from scratch.
     __device__ __forceinline__ void pivot1(const double (&u)[N], int q, double sgn, double pi) {
         const double c = -recip(pi);
         double ut[N], t[N];
         SFOR(k, N, ut[k] = k == q ? sgn : u[k]; t[k] = c * ut[k];);
-        SFOR(k, N, SFOR(j, (k) + 1, G[tri(j, k) * WL] = fma(t[j], ut[k], G[tri(j, k) * WL]);););
+        sweep_triangle<CH1, 1>([&](auto jc, auto kc, double w_) {
+            constexpr int j = decltype(jc)::value; constexpr int k = decltype(kc)::value;
+            return fma(t[j], ut[k], w_); });
         double w[N];
         const double tq = c * sgn;
         SFOR(k, N, w[k] = tq * ut[k];);
@@ -153,7 +188,9 @@ struct LaneT {
             cp[k] = fma(w11, a[k], w12 * b[k]);
             cq[k] = fma(w12, a[k], w22 * b[k]););
             // (one pass; as two passes of one rank-1 term each -- 20 instead of 40 doubles of vectors live -- 0.0449 against 0.0433 ms)
-        SFOR(k, N, SFOR(j, (k) + 1, G[tri(j, k) * WL] = fma(-a[j], cp[k], fma(-b[j], cq[k], G[tri(j, k) * WL]));););
+        sweep_triangle<CH2, 2>([&](auto jc, auto kc, double w_) {
+            constexpr int j = decltype(jc)::value; constexpr int k = decltype(kc)::value;
+            return fma(-a[j], cp[k], fma(-b[j], cq[k], w_)); });
         double w[N];
         SFOR(k, N, w[k] = -sp * cp[k];);
         store_row(p, w);
@@ -528,7 +565,18 @@ struct LaneT {
     }
     __device__ __forceinline__ void g_from_K() {     // S empty: G = -K
         SFOR(k, MV, SFOR(j, k + 1, if constexpr (k < HB) G[tri(j, k) * WL] = -Hs(j, k); else G[tri(j, k) * WL] = -0.0;););
-        SFOR(i, MC, SFOR(k, MV, G[tri(k, MV + i) * WL] = -As(i, k);); SFOR(j, i + 1, G[tri(MV + j, MV + i) * WL] = 0.0;););
+        if constexpr (GROUPED) {
+            // (the builds with chunked pivots: A's reads together in front of its stores, pinned like a chunk's -- one pair at a
+            //  time through one register quad they are NA / 2 round trips)
+            double a[NA];
+            SFOR(e, NA, a[e] = K[e * WL];);
+            SFOR(i, MC, SFOR(k, MV, G[tri(k, MV + i) * WL] = -a[i * MV + k];); SFOR(j, i + 1, G[tri(MV + j, MV + i) * WL] = 0.0;););
+            __builtin_amdgcn_sched_group_barrier(0x100, NA / 2, 0);
+            __builtin_amdgcn_sched_group_barrier(0x002, NA, 0);
+            __builtin_amdgcn_sched_group_barrier(0x200, NA / 2, 0);
+        } else {
+            SFOR(i, MC, SFOR(k, MV, G[tri(k, MV + i) * WL] = -As(i, k);); SFOR(j, i + 1, G[tri(MV + j, MV + i) * WL] = 0.0;););
+        }
     }
     __device__ __forceinline__ bool bounds_inconsistent() const {
         bool bad = false;
@@ -677,14 +725,18 @@ struct LaneT {
                 const double det = pp * qq - pq * pq;
                 if (!(det < 0.0) || !(-det > 1e-10 * fmax(fabs(pp * qq), pq * pq))) return RET_SETUP_FAILED;
                 const double rd = recip(det);
+                LSTAMP_IN(14);
                 pivot2(u2, u, p, pk == 1 ? -1.0 : 1.0, q, kind == 3 ? 1.0 : -1.0, qq * rd, -pq * rd, pp * rd);
+                LSTAMP_IN(16);
                 since_refresh = REFRESH;
             } else {
                 if (kind == 3) { if (!(pi * hscale > 1e-10 * na2)) return RET_SETUP_FAILED; }
                 else if (!(pi * hscale > 1e-10)) return RET_SETUP_FAILED;
             }
         }
+        LSTAMP_IN(14);
         if (pk == 0) pivot1(u, q, (kind == 2 || kind == 3) ? 1.0 : -1.0, pi);
+        LSTAMP_IN(16);
         // ---- the working set
         const bool leaves = (kind == 1) | (kind == 2);
         const int snew = leaves ? 0 : side;
@@ -863,7 +915,10 @@ constexpr int LANE_TINY_MAGIC = 0x7a11e;
 template <int MC, bool KEEP, bool UNI, int HB>
 __global__ void __launch_bounds__(WL) lane_qp_kernel(QPPools P, int nq, int maxWSR) {
     static_assert(UNI || HB == MV, "the block build serves one-pattern batches");
-    typedef LaneT<MC, HB> ENG;
+    // the pivots' chunks (sweep_triangle): 14 entries for pivot1, 6 for pivot2 (which holds 40 doubles of vectors beside them) in
+    // the headline build; with the state kept or H in full every chunking tried spilled vector registers, so those go pair by pair
+    constexpr bool CHUNKS = !KEEP && HB < MV;
+    typedef LaneT<MC, HB, CHUNKS ? 14 : 2, CHUNKS ? 6 : 2> ENG;
     constexpr int N = ENG::N;
     __shared__ __attribute__((aligned(16))) double lds[(ENG::NT + ENG::NA) * WL + 16];      // (+ the staging table: 32 ints)
     ldouble *T = (ldouble *)lds;

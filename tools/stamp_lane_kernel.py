@@ -5,7 +5,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 if not os.environ.get("NO_BUILD"):
     subprocess.check_call([os.path.join(ROOT, "tools", "lane_experiment.sh"), "-DRSQP_STAMPS"] + os.environ.get("EXTRA_DEFS", "").split())
-os.environ["RSQP_LIB"] = os.path.join(ROOT, "restartsqp_amd", "lib", "librsqp_exp.so")
+# (STAMP_LIB: a stamped library built before, e.g. the parent's beside the new one; with NO_BUILD)
+os.environ["RSQP_LIB"] = os.environ.get("STAMP_LIB") or os.path.join(ROOT, "restartsqp_amd", "lib", "librsqp_exp.so")
 os.environ["RSQP_LANE"] = "1"
 from restartsqp_amd import capi, problems
 L = capi.lib()
@@ -16,7 +17,7 @@ which = os.environ.get("STAMP_MODE", "cold")
 probs = problems.hs071_scale_batch(nq)
 b = capi.Batch(probs)
 b.set_keep_state(which != "cold")
-buf = (C.c_ulonglong * 16)()
+buf = (C.c_ulonglong * 24)()                      # (kLaneStamps of qp_lane.hip)
 b.solve(capi.MODE_COLD, 1000)
 assert b.last_kernel() == 2
 L.rsqp_debug_lane_stamps(buf, 1)
@@ -27,7 +28,8 @@ L.rsqp_debug_lane_stamps(buf, 0)
 names = {10: "staging: loads issued, pattern pointers", 11: "staging: loads arrived, dropped into LDS", 12: "staging: own vectors, A scattered",
          13: "staging: H scattered and read", 0: "staging: rest", 1: "set-up (auxiliary QP)", 2: "homotopy: tail of the last pass",
          5: "homotopy: x on bounds, refresh, drift, input", 6: "homotopy: out = G in", 7: "homotopy: dx / dy, candidates (divisions)",
-         8: "homotopy: decode, step", 9: "homotopy: change (row fetch, tests, pivot, working set)",
+         8: "homotopy: decode, step", 14: "homotopy: change: row fetch, tests", 16: "homotopy: change: pivot (pivot1 / pivot2, row store)",
+         9: "homotopy: change: working set",
          3: "refinement step + exact products + objective", 15: "state block written back", 4: "results to HBM"}
 tot = sum(buf[k] for k in names)
 for k, n in names.items():
