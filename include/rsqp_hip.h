@@ -554,4 +554,6 @@ int rsqp_dense_chol_inverse(int n, double *G, double *Ginv, double pd_rel, doubl
 #ifdef __cplusplus
 }
 #endif
+/* the hand-over of a handle for the members of a batch (set / get of the switch): declared in a header of its own */
+#include "rsqp_hip_handover.h"
 #endif

@@ -24,8 +24,9 @@ LAST_ACTION = None
 
 def _headers():
     """every header of csrc/ (incl. qp_small_x.h, which qp_small.hip includes) + the public C ABI"""
+    inc = os.path.join(_HERE, "..", "include")      # (rsqp_hip.h and the extension header it includes)
     return [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h")] + \
-           [os.path.join(_HERE, "..", "include", "rsqp_hip.h")]
+           [os.path.join(inc, f) for f in sorted(os.listdir(inc)) if f.endswith(".h")]
 
 
 def _obj(src):

@@ -138,6 +138,13 @@ SYMBOLS = {
 }
 
 
+# ... and of its extension include/rsqp_hip_handover.h (the hand-over switch of a batch), bound by lib() like the table above
+HANDOVER_SYMBOLS = {
+    "rsqp_batch_set_handover": (C.c_int, [C.c_void_p, C.c_int]),
+    "rsqp_batch_get_handover": (C.c_int, [C.c_void_p, ip, ip]),
+}
+
+
 class OptimalityStatus(C.Structure):
     _fields_ = [("primal_violation", C.c_double), ("dual_violation", C.c_double),
                 ("compl_violation", C.c_double), ("stationarity_violation", C.c_double),
@@ -168,7 +175,7 @@ def lib():
             raise ImportError("%s not built: run `python -c 'import __graft_entry__ as g; g.build()'`" % LIB_PATH)
         _TORCH_FIRST = "torch" in sys.modules
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
+        for name, (res, args) in list(SYMBOLS.items()) + list(HANDOVER_SYMBOLS.items()):
             f = getattr(L, name)
             f.restype = res
             f.argtypes = args
@@ -717,6 +724,24 @@ class Batch:
 
     def set_keep_state(self, keep):
         check(lib().rsqp_batch_set_keep_state(self._h, int(bool(keep))))
+
+    def set_handover(self, on):
+        """on: every launch on the register-resident tableau kernels (last_kernel() 1 or 2) is followed by a masked launch of the
+        Givens / TQ kernel that takes over the members they give up on at set-up, as a single Solver re-solves such a call
+        (rsqp_batch_set_handover); off (the default): those members come back unsolved"""
+        check(lib().rsqp_batch_set_handover(self._h, int(bool(on))))
+
+    def handover(self, handed=None):
+        """(handed, count) of the last solve / optimize call: handed[q] = 1 where member q was handed over to the Givens / TQ kernel
+        (in either solve of an optimize call), count of them (rsqp_batch_get_handover). handed: an int32 array of nq entries to fill"""
+        if handed is None:
+            handed = np.zeros(self.nq, np.int32)
+        elif not (isinstance(handed, np.ndarray) and handed.dtype == np.int32 and handed.ndim == 1 and handed.size == self.nq
+                  and handed.flags.c_contiguous):
+            raise ValueError("handed: a contiguous int32 array of %d entries, one per member" % self.nq)
+        count = C.c_int(0)
+        check(lib().rsqp_batch_get_handover(self._h, _ip(handed), C.byref(count)))
+        return handed, count.value
 
     def last_kernel(self):
         """0 LDS null-space kernels, 1 tableau kernel with 8 lanes per problem, 2 lane-per-problem kernel, 3 HBM-resident

@@ -72,17 +72,30 @@ __host__ __device__ inline long long mat_lds_bytes(int nV, int nC, int annz, int
 // ONE per-lane base address instead of in a register of its own, and every loop over a vector is straight-line.
 // (Passing the uniform shape as kernel ARGUMENTS instead -- wave-uniform scalars -- measured 221 VGPRs instead
 // of 256 but 214 vs 226 M solves/s on 65 536 hs071-scale QPs: not built.)
-template <class ENG, int L, bool MAT_LDS, int W, int SHAPE>
-__global__ void __launch_bounds__(L > 64 ? L : 64, W)
-small_qp_kernel(QPPools P, int nq, int stride, int mode, int maxWSR) {
+// HAND: the build of the hand-over launch of a batch (rsqp_launch_small_handover, small_qp_handover_kernel below): it runs the
+// members a hs071-scale tableau kernel left with ret == RET_SETUP_FAILED as rsqp_solve's retry runs a handle, and leaves their state
+// blocks to that kernel. The builds of every other launch carry nothing of it
+template <class ENG, int L, bool MAT_LDS, int SHAPE, bool HAND>
+__device__ __forceinline__ void small_qp_solve(const QPPools &P, int nq, int stride, int mode, int maxWSR, int *handed, int mark_at) {
     constexpr int NVC = SHAPE >> 8, NCC = SHAPE & 255;
     extern __shared__ __attribute__((aligned(16))) char smem_generic[];
     const int lane = L >= 64 ? (int)threadIdx.x : (int)threadIdx.x & (L - 1);
     const int grp = L >= 64 ? 0 : (int)threadIdx.x / L;  // L >= 64: everything below stays workgroup-uniform
     const int q = L >= 64 ? (int)blockIdx.x : blockIdx.x * (64 / L) + grp;
     if (q >= nq) return;  // no workgroup barrier anywhere below: idle groups may leave
-    if (P.only_bailed && P.ret[q] != RET_BAIL) return;   // second pass behind the tableau kernel (qp_small_g.h)
+    if constexpr (!HAND) {
+        if (P.only_bailed && P.ret[q] != RET_BAIL) return;   // second pass behind the tableau kernel (qp_small_g.h)
+    }
     if (P.member_mode) { mode = P.member_mode[q]; if (mode < 0) return; }   // per-member call shape; < 0: not in this launch
+    if constexpr (HAND) {
+        // second pass behind a hs071-scale tableau kernel: the members it gave up on. Asked AFTER the member's mode: the ret of a
+        // member that is not in the launch is a stale one
+        if (P.ret[q] != RET_SETUP_FAILED) return;
+        // the stored state is the tableau kernel's: a hot start begins cold, as rsqp_solve's retry does on a handle (a warm
+        // re-initialisation keeps its inputs). The member raises its flag, and the count the first time in a call
+        if (mode == 1 || mode == 2) mode = 0;
+        if (handed && lane == 0 && handed[q] == 0) { handed[q] = 1; atomicAdd(handed + nq, 1); }
+    }
     lchar *smem = (lchar *)smem_generic + grp * stride;
     QPDesc d = P.desc[q];
     if constexpr (SHAPE > 0) { d.nV = NVC; d.nC = NCC; }
@@ -212,6 +225,17 @@ small_qp_kernel(QPPools P, int nq, int stride, int mode, int maxWSR) {
     if (P.done_flag) __threadfence_system();      // the results above are in host-mapped memory: visible before the flag
     SYNC();
     if (P.done_flag && q == 0 && lane == 0) *reinterpret_cast<volatile int *>(P.done_flag) = P.done_val;
+    if constexpr (HAND) {
+        // the member's next call goes to the tableau kernel first again, which must read "not initialised" here: in ITS layout,
+        // mark_at doubles into the block (< 0: that launch keeps no state and leaves no mark, neither does this one). Nothing of
+        // this engine's image is stored: no call would ever read it
+        if (lane == 0 && mark_at >= 0) {
+            int *si = reinterpret_cast<int *>(img + mark_at);
+            si[16] = QPS_NOTINITIALISED; si[18] = TINY_MAGIC;
+        }
+        STAMP(9);
+        return;
+    }
     if (P.keep_state) {
         for (int k = lane; k < np; k += L) img[k] = simg[k];
         for (int k = lane; k < ni; k += L) iimg[k] = siimg[k];
@@ -219,6 +243,17 @@ small_qp_kernel(QPPools P, int nq, int stride, int mode, int maxWSR) {
         iimg[(int)(E.iscal - siimg) + 3] = QPS_NOTINITIALISED;
     }
     STAMP(9);
+}
+
+template <class ENG, int L, bool MAT_LDS, int W, int SHAPE>
+__global__ void __launch_bounds__(L > 64 ? L : 64, W)
+small_qp_kernel(QPPools P, int nq, int stride, int mode, int maxWSR) {
+    small_qp_solve<ENG, L, MAT_LDS, SHAPE, false>(P, nq, stride, mode, maxWSR, nullptr, -1);
+}
+template <class ENG, int L, bool MAT_LDS, int W, int SHAPE>
+__global__ void __launch_bounds__(L > 64 ? L : 64, W)
+small_qp_handover_kernel(QPPools P, int nq, int stride, int mode, int maxWSR, int *handed, int mark_at) {
+    small_qp_solve<ENG, L, MAT_LDS, SHAPE, true>(P, nq, stride, mode, maxWSR, handed, mark_at);
 }
 
 #include "qp_small_g.h"
@@ -248,32 +283,50 @@ SmallKnobs rsqp_small_knobs_from_env() {
 
 namespace {
 // one instantiation of the null-space kernel: launches the plan it matches (the full LDS is allowed once per kernel and device)
+// (the plan sizes the image by its own restatement of the engine's counts: compared once per build, over every size that fits)
+template <int E, class ENG, int SHAPE>
+bool plan_agrees() {
+    for (int nV = 1; nV <= 128; nV++)
+        for (int nC = 0; nC <= 128; nC++)
+            if (ENG::image_doubles(nV, nC) != rsqp_plan_image_doubles(E, SHAPE != 0, nV, nC) ||
+                ENG::image_ints(nV, nC) != rsqp_plan_image_ints(E, nV, nC)) return false;
+    return true;
+}
 template <int E, class ENG, int L, bool ML, int W, int SHAPE>
 hipError_t launch_build(const SmallPlan &pl, const QPPools &p, int nq, int maxWSR, hipStream_t stream) {
     static std::atomic<unsigned long long> set_{0};
-    // (the plan sizes the image by its own restatement of this engine's counts: compared once per build, over every size that fits)
-    static const bool agrees = [] {
-        for (int nV = 1; nV <= 128; nV++)
-            for (int nC = 0; nC <= 128; nC++)
-                if (ENG::image_doubles(nV, nC) != rsqp_plan_image_doubles(E, SHAPE != 0, nV, nC) ||
-                    ENG::image_ints(nV, nC) != rsqp_plan_image_ints(E, nV, nC)) return false;
-        return true;
-    }();
+    static const bool agrees = plan_agrees<E, ENG, SHAPE>();
     if (!agrees) return hipErrorInvalidValue;
     rsqp_allow_full_lds(reinterpret_cast<const void *>(&small_qp_kernel<ENG, L, ML, W, SHAPE>), set_, (int)kSmallMaxLds);
     hipLaunchKernelGGL((small_qp_kernel<ENG, L, ML, W, SHAPE>), dim3(pl.grid), dim3(pl.block), (size_t)pl.lds, stream, p, nq, pl.stride, pl.mode, maxWSR);
     return hipGetLastError();
 }
+// ... and its hand-over build (small_qp_handover_kernel)
+template <int E, class ENG, int L, bool ML, int W, int SHAPE>
+hipError_t launch_handover_build(const SmallPlan &pl, const QPPools &p, int nq, int maxWSR, int *handed, int mark_at, hipStream_t stream) {
+    static std::atomic<unsigned long long> set_{0};
+    static const bool agrees = plan_agrees<E, ENG, SHAPE>();
+    if (!agrees) return hipErrorInvalidValue;
+    rsqp_allow_full_lds(reinterpret_cast<const void *>(&small_qp_handover_kernel<ENG, L, ML, W, SHAPE>), set_, (int)kSmallMaxLds);
+    hipLaunchKernelGGL((small_qp_handover_kernel<ENG, L, ML, W, SHAPE>), dim3(pl.grid), dim3(pl.block), (size_t)pl.lds, stream, p, nq, pl.stride,
+                       pl.mode, maxWSR, handed, mark_at);
+    return hipGetLastError();
+}
 // every instantiation of this unit, by the plan's (engine, L, mat_lds, W, shape). The two quick-turnaround builds for tuning
 // (tools/small_experiment.sh) keep a part of the table: -DRSQP_SMALL_EXPERIMENT the 8-lane Givens / TQ kernels, with the builds for
 // 3 and 4 waves per SIMD the product does not have; -DRSQP_SMALL_EXPERIMENT=2 the four-wave explicit-inverse kernel (mid-size
-// problems, BASELINE configs[4]). A plan outside the table is an invalid launch
+// problems, BASELINE configs[4]). A plan outside the table is an invalid launch.
+// handover: the build of the hand-over launch, for the plans rsqp_plan_small_launch gives a launch of at most 8 x 8 without the tableau
+// kernels (SmallKnobs::no_tiny = 1) -- the Givens / TQ engine with its matrices in LDS, whatever lanes and waves the knobs ask for
 struct Build {
     int engine, L, mat_lds, W, shape;
     hipError_t (*launch)(const SmallPlan &, const QPPools &, int, int, hipStream_t);
+    hipError_t (*handover)(const SmallPlan &, const QPPools &, int, int, int *, int, hipStream_t);
 };
 template <int E, class ENG, int L, bool ML, int W, int SHAPE = 0>
-constexpr Build build() { return {E, L, ML, W, SHAPE, &launch_build<E, ENG, L, ML, W, SHAPE>}; }
+constexpr Build build() { return {E, L, ML, W, SHAPE, &launch_build<E, ENG, L, ML, W, SHAPE>, nullptr}; }
+template <int E, class ENG, int L, bool ML, int W, int SHAPE = 0>
+constexpr Build build_h() { return {E, L, ML, W, SHAPE, &launch_build<E, ENG, L, ML, W, SHAPE>, &launch_handover_build<E, ENG, L, ML, W, SHAPE>}; }
 constexpr int S82 = 8 * 256 + 2;      // the compile-time shape 8 x 2, target vectors in registers
 const Build kBuilds[] = {
 #if defined(RSQP_SMALL_EXPERIMENT) && RSQP_SMALL_EXPERIMENT == 2
@@ -287,12 +340,17 @@ const Build kBuilds[] = {
     build<1, EngineX<32, true>, 32, true, 2>(), build<1, EngineX<256, true>, 256, true, 1>(),
     build<1, EngineX<64, true>, 64, true, 4>(),
     build<0, Engine<64, false>, 64, false, 3>(),
-    build<0, Engine<8, true, true>, 8, true, 2, S82>(), build<0, Engine<8, true>, 8, true, 2>(),
-    build<0, Engine<16, true>, 16, true, 2>(), build<0, Engine<16, true>, 16, true, 3>(), build<0, Engine<16, true>, 16, true, 4>(),
-    build<0, Engine<32, true>, 32, true, 2>(), build<0, Engine<32, true>, 32, true, 3>(), build<0, Engine<32, true>, 32, true, 4>(),
-    build<0, Engine<64, true>, 64, true, 3>(), build<0, Engine<64, true>, 64, true, 4>(),      // (W = 6: wrong results, rsqp_small_plan.h)
+    build_h<0, Engine<8, true, true>, 8, true, 2, S82>(), build_h<0, Engine<8, true>, 8, true, 2>(),
+    build_h<0, Engine<16, true>, 16, true, 2>(), build_h<0, Engine<16, true>, 16, true, 3>(), build_h<0, Engine<16, true>, 16, true, 4>(),
+    build_h<0, Engine<32, true>, 32, true, 2>(), build_h<0, Engine<32, true>, 32, true, 3>(), build_h<0, Engine<32, true>, 32, true, 4>(),
+    build_h<0, Engine<64, true>, 64, true, 3>(), build_h<0, Engine<64, true>, 64, true, 4>(),      // (W = 6: wrong results, rsqp_small_plan.h)
 #endif
 };
+const Build *find_build(const SmallPlan &pl, int W) {
+    for (const Build &k : kBuilds)
+        if (k.engine == pl.engine && k.L == pl.L && k.mat_lds == pl.mat_lds && k.W == W && k.shape == pl.shape) return &k;
+    return nullptr;
+}
 }  // namespace
 
 // launches what the plan says (rsqp_small_plan.h): no decision is taken here
@@ -310,9 +368,7 @@ hipError_t rsqp_launch_small_qp(const SmallKnobs &kn, const SmallPlan &pl, const
 #if defined(RSQP_SMALL_EXPERIMENT) && RSQP_SMALL_EXPERIMENT != 2
     if (pl.L == 8 && (pl.waves == 3 || pl.waves == 4)) W = pl.waves;
 #endif
-    const Build *b = nullptr;
-    for (const Build &k : kBuilds)
-        if (k.engine == pl.engine && k.L == pl.L && k.mat_lds == pl.mat_lds && k.W == W && k.shape == pl.shape) b = &k;
+    const Build *b = find_build(pl, W);
     if (!b) return hipErrorInvalidValue;
     if (pl.first) {
         if (pl.first == 1) hipLaunchKernelGGL((small_qpg_kernel<3, 1, 9, 4>), dim3(nq), dim3(256), 0, stream, p, nq, pl.mode, maxWSR);
@@ -320,6 +376,24 @@ hipError_t rsqp_launch_small_qp(const SmallKnobs &kn, const SmallPlan &pl, const
         p.only_bailed = 1;
     }
     return b->launch(pl, p, nq, maxWSR, stream);
+}
+
+hipError_t rsqp_launch_small_handover(const SmallKnobs &kn, const SmallPlan &pl, const SmallPlan &tableau, const QPPools &p_in, int nq,
+                                      int maxWSR, int *handed, hipStream_t stream) {
+    if (pl.empty) return hipSuccess;
+    // (the plan of a launch the tableau kernels serve, without them: an LDS-resident null-space kernel by itself)
+    if (pl.invalid || pl.family != 0 || pl.first || (tableau.family != 1 && tableau.family != 2)) return hipErrorInvalidValue;
+    QPPools p = p_in;
+    p.only_bailed = 0;        // (the build itself takes the members with ret == RET_SETUP_FAILED, and nobody else)
+    p.k_debug_bail = kn.k_debug_bail;
+    p.skip_mark = pl.skip_mark;
+    // where the tableau kernel of that launch keeps its ints (-1: it keeps no state and leaves no mark)
+    long long at = -1;
+    if (p.keep_state || !tableau.skip_mark)
+        at = tableau.mc == 2 ? tiny_state_doubles<2>() : (tableau.mc == 4 ? tiny_state_doubles<4>() : tiny_state_doubles<8>());
+    const Build *b = find_build(pl, pl.W);
+    if (!b || !b->handover) return hipErrorInvalidValue;
+    return b->handover(pl, p, nq, maxWSR, handed, (int)at, stream);
 }
 
 long long rsqp_mat_lds_bytes(int nV, int nC, int annz, int hnnz) { return mat_lds_bytes(nV, nC, annz, hnnz); }

@@ -629,9 +629,7 @@ struct EngineT {
 // made every store of a wave 64 separate 8-byte pieces): [N x N tableau, entry k of every slot's row together: position k N + slot; the
 // matrix is symmetric, so this is its transpose up to rounding][6 fields x 8 variable slots: x g lo up gy y][4 fields x 8 constraint
 // slots: A x, loA, upA, y][G_ll of the 8 variable slots][G_{8+l,8+l} of the 8 constraint slots][ints: sv (8), sc (8), status, masks, magic,
-// pivots]
-template <int MC> __device__ __forceinline__ long long tiny_state_doubles() { return (long long)(MV + MC) * (MV + MC) + 8LL * 6 + 8LL * 4 + 8LL * 2; }
-constexpr int TINY_MAGIC = 0x7a11e;
+// pivots] (tiny_state_doubles<MC>() and TINY_MAGIC: rsqp_small_plan.h, which the hand-over launch of qp_small.hip reads as well)
 
 template <int MC, int W, bool GL = false>
 __global__ void __launch_bounds__(TB, W) tiny_qp_kernel(QPPools P, int nq, int mode_in, int maxWSR) {

@@ -131,6 +131,11 @@ struct rsqp_batch {
     // nWSR_used of the members, written by the kernels straight into host-mapped memory: ready behind the call's one wait, no copy
     // (and no second wait) behind it
     HostBuf<int> used;
+    // rsqp_batch_set_handover: every launch on the hs071-scale tableau kernels (families 1, 2) is followed by the hand-over launch
+    // (launch_batch). handed: nq flags + their count, cleared where a solve / optimize call with the switch on begins, written by the
+    // members that are taken over; handed_valid: the last call was such a call (else rsqp_batch_get_handover reports zeros)
+    bool handover = false, handed_valid = false;
+    DevBuf<int> handed;
     int qp_maxiter = 1000;                // rsqp_batch_set_options
     bool mats_updated = false;            // rsqp_batch_set_matrix_values since the last optimize call (Update_A / Update_H of everybody)
     bool opt_started = false;             // an rsqp_batch_optimize_qp has run: members are in different states from here on
@@ -151,6 +156,8 @@ namespace rsqp_batch_units {
 QPPools pools_of(rsqp_batch *b, bool lp);
 int batch_family(const rsqp_batch *b, const QPPools &p, bool lp);
 int launch_batch(rsqp_batch *b, QPPools &p, int mode, int max_nWSR, bool first, bool lp);
+// where a solve / optimize call begins: the hand-over flags and their count cleared (on the stream) when the switch is on
+int begin_handover(rsqp_batch *b);
 int ensure_opt(rsqp_batch *b);
 int ensure_warm_pools(rsqp_batch *b);
 int ensure_scratch(rsqp_batch *b, size_t words);

@@ -261,11 +261,14 @@ int ensure_warm_pools(rsqp_batch *b) {
     return RSQP_OK;
 }
 
-// the plan of a launch on this batch (rsqp_small_plan.h): the batch remembers by itself when a launch keeps no state
-static SmallPlan plan_of(const rsqp_batch *b, const QPPools &p, int mode, bool lp) {
+// the plan of a launch on this batch (rsqp_small_plan.h): the batch remembers by itself when a launch keeps no state.
+// handover: the plan of the same launch without the hs071-scale tableau kernels, as rsqp_solve plans its retry on a handle
+static SmallPlan plan_of(const rsqp_batch *b, const QPPools &p, int mode, bool lp, bool handover = false) {
     SmallFacts f = rsqp_small_facts(p, b->hbm, b->state_engine);
     f.skip_mark = 1;
-    return rsqp_plan_small_launch(knobs_of(b, lp), f, b->nq, b->nVmax, b->nCmax, b->mat_bytes_max, mode);
+    SmallKnobs k = knobs_of(b, lp);
+    if (handover && k.no_tiny == 0) k.no_tiny = 1;
+    return rsqp_plan_small_launch(k, f, b->nq, b->nVmax, b->nCmax, b->mat_bytes_max, mode);
 }
 
 // layout a launch on this batch leaves in the state blocks: 3 HBM-resident, 1 hs071-scale tableau (+ lane-per-problem), 0 LDS-resident
@@ -280,8 +283,23 @@ int launch_batch(rsqp_batch *b, QPPools &p, int mode, int max_nWSR, bool first, 
     const int fam = pl.state_family;
     b->state_engine = pl.skip_mark ? -1 : ((p.member_mode && b->sitters && b->state_engine != fam) ? -2 : fam);
     if (first) { b->last_kernel = pl.family; b->last_hblock = pl.hb; rsqp_plan_words(pl, b->last_plan); }
-    const hipError_t e = rsqp_launch_small_qp(knobs_of(b, lp), pl, p, b->nq, max_nWSR, b->stream);
+    hipError_t e = rsqp_launch_small_qp(knobs_of(b, lp), pl, p, b->nq, max_nWSR, b->stream);
     if (e != hipSuccess) return fail(RSQP_ERR_DEVICE, std::string("QP kernel launch: ") + hipGetErrorString(e));
+    // rsqp_batch_set_handover: the members a hs071-scale tableau kernel gave up on go to the null-space kernel right behind it, with
+    // the budget of the launch afresh (nWSR_in of rsqp_solve's retry). The records above stay what the tableau launch left: the
+    // next call goes to the tableau kernel first again, and a member taken over has left its state block to it
+    if (b->handover && (pl.family == 1 || pl.family == 2)) {
+        e = rsqp_launch_small_handover(knobs_of(b, lp), plan_of(b, p, mode, lp, true), pl, p, b->nq, max_nWSR, b->handed.p, b->stream);
+        if (e != hipSuccess) return fail(RSQP_ERR_DEVICE, std::string("hand-over launch: ") + hipGetErrorString(e));
+    }
+    return RSQP_OK;
+}
+
+int begin_handover(rsqp_batch *b) {
+    b->handed_valid = b->handover;
+    if (!b->handover) return RSQP_OK;
+    if (!b->handed.p) HIPCHK(b->handed.alloc((size_t)b->nq + 1));
+    HIPCHK(hipMemsetAsync(b->handed.p, 0, sizeof(int) * ((size_t)b->nq + 1), b->stream));
     return RSQP_OK;
 }
 }  // namespace rsqp_batch_units
@@ -317,9 +335,10 @@ extern "C" int rsqp_batch_solve(rsqp_batch *b, int mode, int max_nWSR) {
         if (b->have_y0) p.y0 = b->wy0.p;
         if (b->have_gb) p.guess_b = b->wgb.p;
     }
-    if (!b->timing) HIPCHK(hipEventRecord(b->ev0, b->stream));
-    const int rc = launch_batch(b, p, mode, max_nWSR, true, false);
+    int rc = begin_handover(b);
     if (rc != RSQP_OK) return rc;
+    if (!b->timing) HIPCHK(hipEventRecord(b->ev0, b->stream));
+    if ((rc = launch_batch(b, p, mode, max_nWSR, true, false)) != RSQP_OK) return rc;
     b->cert_lp = false;
     if (!b->timing) HIPCHK(hipEventRecord(b->ev1, b->stream));
     return RSQP_OK;
@@ -337,6 +356,26 @@ extern "C" int rsqp_batch_get_last_plan(const rsqp_batch *b, int *out, int nout)
 extern "C" int rsqp_batch_set_keep_state(rsqp_batch *b, int keep) {
     if (!b) return fail(RSQP_ERR_ARG, "null batch");
     b->keep_state = keep != 0;
+    return RSQP_OK;
+}
+
+extern "C" int rsqp_batch_set_handover(rsqp_batch *b, int on) {
+    if (!b) return fail(RSQP_ERR_ARG, "null batch");
+    b->handover = on != 0;
+    return RSQP_OK;
+}
+
+extern "C" int rsqp_batch_get_handover(rsqp_batch *b, int *handed, int *count) {
+    if (!b) return fail(RSQP_ERR_ARG, "null batch");
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    if (!b->handed_valid) {      // the last call ran with the switch off (or nothing has run): nobody was handed over
+        if (handed) std::fill(handed, handed + b->nq, 0);
+        if (count) *count = 0;
+        return RSQP_OK;
+    }
+    if (handed) HIPCHK(b->handed.download(handed, b->nq));
+    if (count) HIPCHK(hipMemcpy(count, b->handed.p + b->nq, sizeof(int), hipMemcpyDeviceToHost));
     return RSQP_OK;
 }
 

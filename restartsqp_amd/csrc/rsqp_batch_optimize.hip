@@ -136,6 +136,7 @@ int begin_optimize(rsqp_batch *b, int kind) {
         b->opt_started = false;
     }
     b->last_kind = kind;
+    if ((rc = begin_handover(b)) != RSQP_OK) return rc;   // (an LP call hands nobody over: its launches stay off the tableau kernels)
     if (!b->timing) HIPCHK(hipEventRecord(b->ev0, b->stream));
     return RSQP_OK;
 }

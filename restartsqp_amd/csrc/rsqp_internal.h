@@ -157,6 +157,14 @@ inline void rsqp_allow_full_lds(const void *fn, std::atomic<unsigned long long> 
 // the SmallPlan of a launch and rsqp_launch_small_qp executes it through the launcher of the plan's family
 struct SmallPlan;
 hipError_t rsqp_launch_small_qp(const SmallKnobs &kn, const SmallPlan &pl, const QPPools &p, int nq, int maxWSR, hipStream_t stream);
+// the hand-over launch of a batch (rsqp_batch_set_handover), behind a launch of the hs071-scale tableau kernels (plan `tableau`, family
+// 1 or 2) on the same stream: the null-space kernel of `pl` -- the plan of the same launch with SmallKnobs::no_tiny = 1, as rsqp_solve
+// retries on a handle -- runs the members that launch left with ret == RET_SETUP_FAILED, and nobody else. Such a member starts cold
+// where its call shape was a hot start (the stored state is the tableau kernel's), keeps a warm re-initialisation, gets maxWSR
+// afresh, and its state block is left as the tableau kernel's "not initialised" (nothing is written where `tableau` keeps no state
+// and leaves no mark). handed: nq flags + one count (or null); a member taken over raises its flag, the first time also the count
+hipError_t rsqp_launch_small_handover(const SmallKnobs &kn, const SmallPlan &pl, const SmallPlan &tableau, const QPPools &p, int nq,
+                                      int maxWSR, int *handed, hipStream_t stream);
 long long rsqp_mat_lds_bytes(int nV, int nC, int annz, int hnnz);
 int rsqp_small_qp_fits(int nVmax, int nCmax);
 // qp_tiny.hip: the register-resident tableau kernel for problems of at most 8 variables and 8 constraints

@@ -44,6 +44,12 @@ struct SmallPlan {
 constexpr long long kSmallMaxLds = 160 * 1024;
 constexpr int kTinyBlock = 256, kLaneBlock = 64;     // threads per workgroup of qp_tiny.hip (8 per problem) / qp_lane.hip (1 per problem)
 inline long long rsqp_align16(long long v) { return (v + 15) & ~15LL; }
+// the hs071-scale tableau kernels' layout of a state block (qp_tiny.hip, written by qp_lane.hip as well): tiny_state_doubles<MC>()
+// doubles -- the (8 + MC)^2 tableau, 6 fields x 8 variable slots, 4 fields x 8 constraint slots, the two diagonals -- then the ints:
+// sv (8), sc (8), status [16], masks [17], TINY_MAGIC [18], pivots [19]. A block whose ints say TINY_MAGIC and QPS_NOTINITIALISED is
+// one no hot start continues from. MC = SmallPlan::mc of the launch
+template <int MC> __host__ __device__ __forceinline__ constexpr long long tiny_state_doubles() { return (long long)(8 + MC) * (8 + MC) + 8LL * 6 + 8LL * 4 + 8LL * 2; }
+constexpr int TINY_MAGIC = 0x7a11e;
 
 // 1 if the batch shape is served by the register-resident tableau kernel (qp_tiny.hip: at most 8 variables, 8 constraints)
 inline int rsqp_plan_tiny_fits(const SmallKnobs &kn, int nVmax, int nCmax) { return !kn.no_tiny && nVmax <= 8 && nCmax <= 8 && nVmax >= 1; }

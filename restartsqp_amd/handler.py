@@ -184,10 +184,13 @@ class BatchQPhandler:
 
     Arrays are pooled over the batch (x_k, grad: NLP layout; c_k: the layout of lbA); only the named members' entries are read.
     delta and rho are scalars or one entry per member. on_device: x_k, c_k and grad are torch tensors on the batch's device, the
-    words and the iterate stay there, and ``step(on_device=True)`` leaves the step data there as well."""
+    words and the iterate stay there, and ``step(on_device=True)`` leaves the step data there as well. handover: members the
+    register-resident tableau kernels give up on are re-solved on the Givens / TQ kernel inside the call, as a single QPhandler's
+    solver does (``Batch.set_handover``); off by default, it costs a kernel launch per solve."""
 
-    def __init__(self, batch, x_l, x_u, c_l=None, c_u=None, on_device=False):
+    def __init__(self, batch, x_l, x_u, c_l=None, c_u=None, on_device=False, handover=False):
         self.batch, self.on_device = batch, bool(on_device)
+        batch.set_handover(handover)
         batch.handler_set_problem(x_l, x_u, c_l, c_u)
         self.m = np.asarray(batch.nC, dtype=np.int64)
         self.n = np.asarray(batch.nV, dtype=np.int64) - 2 * self.m

@@ -203,6 +203,32 @@ def hs071_scale_batch(nq, seed=20260103):
     return [base] + [perturb(rng, base) for _ in range(nq - 1)]
 
 
+def stiff_free_batch(rng, nV, nC, n, every=3, stiff=1.0e10):
+    """n QPs of one shape and one pattern whose members t % every == 0 the register-resident tableau kernels give up on at
+    set-up (RET_SETUP_FAILED) while the problem itself is perfectly conditioned: variable 0 has no bounds, so a cold start has
+    to take it into the working set as a free variable, and the Hessian entry of the last variable j = nV - 1 is `stiff` -- the
+    tableau kernels judge a free variable's curvature against 1e-8 of the LARGEST diagonal entry of H. Variable j is decoupled
+    (row and column j of H hold the diagonal entry alone) and pinned at its lower bound by g[j] = 100 on 0 <= x_j <= 1, so it
+    never enters a factorisation: a null-space active-set method solves a stiff member exactly as it solves the member with
+    H[j, j] = 1. The other members are ordinary perturbations of the same base."""
+    j = nV - 1
+    base = random_qp(rng, nV, nC, density=1.0, name="stiff-free-%dx%d" % (nV, nC))
+    M = rng.normal(size=(nV, nV))
+    H = M @ M.T / nV + np.eye(nV)
+    H[j, :] = 0.0; H[:, j] = 0.0; H[j, j] = 1.0
+    base.H_jc, base.H_ir, base.H_val = dense_to_csc(H)
+    out = []
+    for t in range(n):
+        q = perturb(rng, base, 0.05)
+        q.H_val = base.H_val.copy()
+        q.lb[j] = 0.0; q.ub[j] = 1.0; q.g[j] = 100.0
+        if t % every == 0:
+            q.lb[0] = -np.inf; q.ub[0] = np.inf
+            q.H_val[-1] = stiff      # (column j holds its diagonal entry alone: the last value of the CSC array)
+        out.append(q)
+    return out
+
+
 # ------------------------------------------------------------------------------------
 # SURVEY.md 8(d) synthetic configurations
 # ------------------------------------------------------------------------------------
