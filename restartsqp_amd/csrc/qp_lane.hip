@@ -79,7 +79,10 @@ __host__ __device__ constexpr int tri(int j, int k) { return j <= k ? k * (k + 1
 // word for the whole batch (QPPools::lane_hblock). In the QPhandler formulation [x u v] the slacks have no curvature, so the
 // headline's H (11 entries on 4 variables) takes 10 register pairs instead of 36; everything beyond the block is the +0 the full
 // build holds there, and the products with it are left out: fma(+0, x, h) is h for finite x (h starts at +0), bit for bit
-template <int MC, int HB, int CH1 = 2, int CH2 = 2>
+// ROLES: the ratio test of homotopy() BRANCHES on the role of a variable slot (free / fixed) instead of computing both roles and
+// selecting, and the re-relaxation in front of the homotopy, which a cold start cannot need, is left out (kernel's choice, see
+// lane_qp_kernel: the headline build only)
+template <int MC, int HB, int CH1 = 2, int CH2 = 2, bool ROLES = false>
 struct LaneT {
     static_assert(HB == 4 || HB == MV, "leading block of H");
     static constexpr int N = MV + MC, NT = N * (N + 1) / 2, NH = HB * (HB + 1) / 2, NA = MC * MV, REFRESH = 8;
@@ -629,7 +632,8 @@ struct LaneT {
     // ------------------------------------------------------------------ one working-set change
     // kind 1 constraint idx leaves | 2 bound of idx leaves | 3 constraint idx enters at `side` | 4 variable idx gets fixed at `side`
     // (style of the slot passes here and in homotopy(): every arm of a choice is computed first, then selected -- plain selects
-    //  between values; a ternary with arithmetic in its arms becomes a tree of divergent branches per slot)
+    //  between values; a ternary with arithmetic in its arms becomes a tree of divergent branches per slot. The one exception is
+    //  measured: the variable slots of homotopy()'s ratio test in the headline build, ROLES)
     __device__ __forceinline__ int change(int kind, int idx, int side, double tau, bool &treat_done) {
         const bool isc = (kind == 1) | (kind == 3);
         const int q = isc ? MV + idx : idx;
@@ -756,6 +760,11 @@ struct LaneT {
         int iter = 0, rcode = RET_OK;
         status = QPS_PERFORMINGHOMOTOPY;
         since_refresh = REFRESH;
+        // limits that are infinite where the targets are finite get relaxed ones (a hot start's concern, kept from qp_tiny.hip). This
+        // kernel only runs cold starts, and after setup_cold() the pass changes nothing: lo is x (finite) for a variable at its lower
+        // bound and fmin(loN, x - relaxation) otherwise, so lo <= -INFTY implies loN <= -INFTY, and c1 asks for the opposite; the same
+        // holds for up / upN, loA / cloN, upA / cupN, and the slots beyond nV / nC hold 0 / the infinite targets. ROLES leaves it out
+        if constexpr (!ROLES) {
         SFOR(l, MV, const double l1 = fmin(loN[l], xv[l] - RSQP_BOUND_RELAXATION), u1 = fmax(upN[l], xv[l] + RSQP_BOUND_RELAXATION);
              const bool c1 = (sv[l] != -1) & (lo[l] <= -RSQP_INFTY) & (loN[l] > -RSQP_INFTY);
              const bool c2 = (sv[l] != 1) & (up[l] >= RSQP_INFTY) & (upN[l] < RSQP_INFTY);
@@ -764,6 +773,7 @@ struct LaneT {
              const bool c1 = (sc[i] != -1) & (loA[i] <= -RSQP_INFTY) & (cloN[i] > -RSQP_INFTY);
              const bool c2 = (sc[i] != 1) & (upA[i] >= RSQP_INFTY) & (cupN[i] < RSQP_INFTY);
              loA[i] = c1 ? l1 : loA[i]; upA[i] = c2 ? u1 : upA[i];);
+        }
         for (;;) {
             // ---- x exactly on its active bounds; (exact products); drift correction + input of the product
             SFOR(l, MV, const int s_ = opq(sv[l]); const double xb = s_ == -1 ? lo[l] : up[l]; xv[l] = s_ != 0 ? xb : xv[l];);
@@ -810,6 +820,23 @@ struct LaneT {
                  const int id1 = act ? i : nC + nV + i;
                  cand(num1, den1, id1, (i < nC) & (act | (cloN[i] > -RSQP_INFTY)));
                  cand(upA[i] - ax[i], dax[i] - (cupN[i] - upA[i]), 2 * nC + nV + i, (i < nC) & !act & (cupN[i] < RSQP_INFTY)););
+            if constexpr (ROLES) {
+            // one arm per role of a variable slot: a fixed slot (all eight of the headline's first pass, seven and six in the next
+            // two) no longer pays for the free role's two bound candidates, their masks and the selects between the roles. Per
+            // lane the operands, the candidate ids and their order are the ones below; lanes that disagree on a slot's role run
+            // both arms, as the selects did. (The same arms for the constraint slots, for the drift / input pass and for the
+            // exchange's ratio test measured slower or no different on the headline batch: DESIGN.md 4.3b)
+            SFOR(l, MV, const int s_ = opq(sv[l]); const double ov = o[l], dg = gN[l] - g[l];
+                 if (s_ == 0) {
+                     dxv[l] = ov; dyv[l] = 0.0; hd[l] = -dg;
+                     cand(xv[l] - lo[l], (loN[l] - lo[l]) - ov, 3 * nC + nV + l, (l < nV) & (loN[l] > -RSQP_INFTY));
+                     cand(up[l] - xv[l], ov - (upN[l] - up[l]), 3 * nC + 2 * nV + l, (l < nV) & (upN[l] < RSQP_INFTY));
+                 } else {
+                     const bool wl = s_ == -1; const double dgo = dg - ov;
+                     dxv[l] = in[l]; dyv[l] = dgo; hd[l] = -ov;
+                     cand(wl ? yv[l] : -yv[l], wl ? -dgo : dgo, nC + l, l < nV);
+                 });
+            } else {
             SFOR(l, MV, const int s_ = opq(sv[l]); const double ov = o[l], dg = gN[l] - g[l], nov = -ov, dgo = dg - ov, ndg = -dg;
                  const bool fr = s_ == 0, wl = s_ == -1;
                  dxv[l] = fr ? ov : in[l]; dyv[l] = fr ? 0.0 : dgo; hd[l] = fr ? ndg : nov;
@@ -819,6 +846,7 @@ struct LaneT {
                  const int id1 = fr ? 3 * nC + nV + l : nC + l;
                  cand(num1, den1, id1, (l < nV) & (!fr | (loN[l] > -RSQP_INFTY)));
                  cand(up[l] - xv[l], dxv[l] - (upN[l] - up[l]), 3 * nC + 2 * nV + l, (l < nV) & fr & (upN[l] < RSQP_INFTY)););
+            }
             if (!(bt < 1.0)) { bt = 1.0; bid = 0x7fffffff; }
             LSTAMP(7);
             int kind = 0, idx = -1, side = 0;
@@ -918,7 +946,10 @@ __global__ void __launch_bounds__(WL) lane_qp_kernel(QPPools P, int nq, int maxW
     // the pivots' chunks (sweep_triangle): 14 entries for pivot1, 6 for pivot2 (which holds 40 doubles of vectors beside them) in
     // the headline build; with the state kept or H in full every chunking tried spilled vector registers, so those go pair by pair
     constexpr bool CHUNKS = !KEEP && HB < MV;
-    typedef LaneT<MC, HB, CHUNKS ? 14 : 2, CHUNKS ? 6 : 2> ENG;
+    // the ratio test's arms per role (LaneT::ROLES): the same build only -- in the two builds that keep the state with H in full the
+    // arms spilled vector registers to scratch memory
+    constexpr bool ROLES = CHUNKS;
+    typedef LaneT<MC, HB, CHUNKS ? 14 : 2, CHUNKS ? 6 : 2, ROLES> ENG;
     constexpr int N = ENG::N;
     __shared__ __attribute__((aligned(16))) double lds[(ENG::NT + ENG::NA) * WL + 16];      // (+ the staging table: 32 ints)
     ldouble *T = (ldouble *)lds;
