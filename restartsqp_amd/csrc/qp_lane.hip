@@ -18,8 +18,8 @@
 //     register array indexed by compile-time slots; "slot idx of my problem" is a predicated pass over the slots;
 //   * nothing crosses lanes: no permutes, no barriers, no reductions -- a wave is 64 independent scalar programs in lockstep
 //     (identical paths for perturbations of one QP; diverging members cost the union of their paths, as in any SIMT code).
-// One wave per workgroup, LDS 36.4 KB (MC = 2): four waves per CU, one per SIMD with the whole register file (512 per lane) --
-// 65 536 problems in flight on the 256 CUs.
+// One wave per workgroup, LDS 36.4 KB (MC = 2; 40.4 KB in the builds that stage in dependency order, see stage_matrices): four
+// waves per CU, one per SIMD with the whole register file (512 per lane) -- 65 536 problems in flight on the 256 CUs.
 #include <type_traits>
 
 #include "rsqp_small_plan.h"
@@ -255,6 +255,14 @@ struct LaneT {
         SFOR(c, CH / 2, if (2 * c < n) {
                  if (EVEN || c * WL + p < 32 * n) { const double2 v = s2[c * WL]; w[2 * c] = v.x; w[2 * c + 1] = v.y; }
              });
+    }
+    // the same with EVERY group's load issued, whatever n: a lane beyond the run (odd n), or a group beyond it, reads the run's
+    // first pair again, which drop_pairs never looks at. The number of loads in flight behind an array is then a compile-time
+    // constant, and the wait for that array leaves the later ones outstanding (stage_matrices)
+    template <int CH> __device__ __forceinline__ void load_pairs_all(const double *src, int n, int p, double (&w)[CH]) const {
+        static_assert((CH & 1) == 0, "pairs");
+        const double2 *s2 = reinterpret_cast<const double2 *>(src);
+        SFOR(c, CH / 2, const int m = c * WL + p; const double2 v = s2[m < 32 * n ? m : 0]; w[2 * c] = v.x; w[2 * c + 1] = v.y;);
     }
     // pairs into slots s0 + entry of their owners
     template <int CH, bool EVEN> __device__ __forceinline__ void drop_pairs(ldouble *T, int s0, int n, int p, Walk wk, const double (&w)[CH]) const {
@@ -566,6 +574,102 @@ struct LaneT {
         SFOR(i, MC, const bool c = i < nC;
              cloN[i] = c ? clampinf(la_[i]) : -RSQP_INFTY; cupN[i] = c ? clampinf(ua_[i]) : RSQP_INFTY;);
     }
+    // ---- the same staging in DEPENDENCY ORDER, for the waves stage() serves in one pass (H as its block, a full wave, aligned
+    // pools: ordered_wave). The wave's 26 KB arrive at 8 bytes per cycle and CU, every wave of the chip asking at once, and
+    // stage() waits for the last byte before anything is computed. The tableau of the empty working set, Hr and hscale need
+    // A and H only; the set-up needs the bounds; g is first read in the homotopy. The counter of outstanding loads retires
+    // them in issue order, so the loads go out as (pattern rows,) A, H, lb, ub, lbA, ubA, g -- all of them before anything
+    // waits, as in stage() -- and are consumed in that order: the tableau is built while the vectors are still on their way.
+    // The vectors can then no longer transpose through the tableau's slots: they pass, one array (the two of the constraints
+    // together) at a time, through SPV spare slots behind A (drop, wave_sync, read, wave_sync); the pattern table, which
+    // lies there, is dead once A and H are dropped. The LDS reads and writes of my own column need no barrier between them.
+    static constexpr int SPV = MV;                       // spare slots of the ordered build, behind the tableau and A
+    struct Inflight { double wg[MV], wl[MV], wu[MV], wla[MC], wua[MC]; int pp; };
+    __device__ __forceinline__ bool ordered_wave(const QPPools &P, int nqw) const {         // (stage()'s `onepass`)
+        return HB < MV && nqw == WL && P.uni_annz <= NA &&
+               (((size_t)P.g | (size_t)P.lb | (size_t)P.ub | (size_t)P.lbA | (size_t)P.ubA | (size_t)P.Aval | (size_t)P.Hval) & 15) == 0;
+    }
+    // loads issued; A and H taken; Hr, hscale; G = -K
+    __device__ __forceinline__ void stage_matrices(const QPPools &P, long long q0, int lane, ldouble *T, Inflight &F) {
+        typedef __attribute__((address_space(3))) int lint;
+        static_assert(HB < MV, "the block build");
+        constexpr int HC = 16, SH = 3 * MV + 2 * MC, SPARE = NT - 1;
+        const int annz = P.uni_annz, hnnz = P.uni_haveH ? P.uni_hnnz : 0;
+        const bool hfast = hnnz > 0 && hnnz <= HC;
+        const int pp = pair_of(lane);
+        F.pp = pp;
+        lint *tab = (lint *)(T + (NT + NA) * WL);
+        // the pattern's row of my table entry FIRST (lane e < 16 entry e of A, lane 16 + e entry e of H, as in stage()): it is
+        // the first thing needed, and behind the data it would be the last thing to arrive
+        const bool forH = lane >= HC;
+        const int pe = forH ? lane - HC : lane, pn = forH ? (hfast ? hnnz : 0) : annz;
+        int prow = 0;
+        if (pe < pn) prow = forH ? P.Hir[pe] : P.Air[pe];
+        int ja[MV], jh[MV];
+        SFOR(j, MV, ja[j] = P.Ajc[j + 1 <= nV ? j + 1 : nV]; jh[j] = hfast ? P.Hjc[j + 1 <= nV ? j + 1 : nV] : 0;);
+        __builtin_amdgcn_sched_barrier(0);
+        double wa[NA], wh[HC];
+        if (annz > 0) load_pairs_all<NA>(P.Aval + q0 * annz, annz, pp, wa);
+        if (hfast) load_pairs_all<HC>(P.Hval + q0 * hnnz, hnnz, pp, wh);
+        load_pairs_all<MV>(P.lb + q0 * nV, nV, pp, F.wl);
+        load_pairs_all<MV>(P.ub + q0 * nV, nV, pp, F.wu);
+        if (nC > 0) { load_pairs_all<MC>(P.lbA + q0 * nC, nC, pp, F.wla); load_pairs_all<MC>(P.ubA + q0 * nC, nC, pp, F.wua); }
+        load_pairs_all<MV>(P.g + q0 * nV, nV, pp, F.wg);
+        __builtin_amdgcn_sched_barrier(0);
+        int pcol = 0;
+        SFOR1(j, MV, const int jj = forH ? jh[j - 1] : ja[j - 1]; pcol += (j <= nV && pe >= jj) ? 1 : 0;);
+        LSTAMP(10);
+        const bool hin = prow <= pcol && pcol < HB;
+        if (lane < 2 * HC) tab[lane] = pe < pn ? (forH ? (hin ? SH + ((pcol * (pcol + 1)) >> 1) + prow : SPARE) : NT + prow * MV + pcol) : SPARE;
+        SFOR(e, NA, K[e * WL] = 0.0;);
+        SFOR(e, NH, G[(SH + e) * WL] = 0.0;);
+        wave_sync();
+        if (annz > 0) BYPARITY(annz, drop_pair_entries<NA, EV>(T, tab, annz, pp, walk<2>(annz, pp), wa););
+        if (hfast) BYPARITY(hnnz, drop_pair_entries<HC, EV>(T, tab + HC, hnnz, pp, walk<2>(hnnz, pp), wh););
+        wave_sync();
+        LSTAMP(11);
+        hscale = 0.0;
+        const ldouble *GH = G + SH * WL;
+        SFOR(k, HB, SFOR(j, k + 1, double w = GH[tri(j, k) * WL];
+                         if (j == k) { w = (k < nV) ? w + hreg : w; hscale = fmax(hscale, k < nV ? fabs(w) : 0.0); }
+                         Hr[tri(j, k)] = w;););
+        g_from_K();
+        LSTAMP(17);
+    }
+    // one array's pairs into spare slots s0 .. of their owners
+    template <int CH> __device__ __forceinline__ void take_pass(ldouble *T, int n, int pp, const double (&w)[CH], int s0) {
+        BYPARITY(n, drop_pairs<CH, EV>(T, NT + NA + s0, n, pp, walk<2>(n, pp), w););
+    }
+    __device__ __forceinline__ void take_bounds(ldouble *T, int lane, const Inflight &F) {
+        const ldouble *S = T + lane + (NT + NA) * WL;
+        double lb_[MV], ub_[MV], la_[MC], ua_[MC];
+        take_pass<MV>(T, nV, F.pp, F.wl, 0);
+        wave_sync();
+        SFOR(l, MV, const double a1 = S[l * WL]; lb_[l] = l < nV ? a1 : 0.0;);
+        wave_sync();
+        take_pass<MV>(T, nV, F.pp, F.wu, 0);
+        wave_sync();
+        SFOR(l, MV, const double a2 = S[l * WL]; ub_[l] = l < nV ? a2 : 0.0;);
+        wave_sync();
+        if (nC > 0) { take_pass<MC>(T, nC, F.pp, F.wla, 0); take_pass<MC>(T, nC, F.pp, F.wua, MC); }
+        wave_sync();
+        SFOR(i, MC, const bool c = i < nC;
+             const double a0 = S[i * WL], a1 = S[(MC + i) * WL];
+             la_[i] = c ? a0 : -RSQP_INFTY; ua_[i] = c ? a1 : RSQP_INFTY;);
+        wave_sync();
+        SFOR(l, MV, const bool v = l < nV;
+             loN[l] = v ? clampinf(lb_[l]) : 0.0; upN[l] = v ? clampinf(ub_[l]) : 0.0;);
+        SFOR(i, MC, const bool c = i < nC;
+             cloN[i] = c ? clampinf(la_[i]) : -RSQP_INFTY; cupN[i] = c ? clampinf(ua_[i]) : RSQP_INFTY;);
+        LSTAMP(12);
+    }
+    __device__ __forceinline__ void take_g(ldouble *T, int lane, const Inflight &F) {
+        const ldouble *S = T + lane + (NT + NA) * WL;
+        take_pass<MV>(T, nV, F.pp, F.wg, 0);
+        wave_sync();
+        SFOR(l, MV, const double a0 = S[l * WL]; gN[l] = l < nV ? a0 : 0.0;);
+        LSTAMP(18);
+    }
     __device__ __forceinline__ void g_from_K() {     // S empty: G = -K
         SFOR(k, MV, SFOR(j, k + 1, if constexpr (k < HB) G[tri(j, k) * WL] = -Hs(j, k); else G[tri(j, k) * WL] = -0.0;););
         if constexpr (GROUPED) {
@@ -591,7 +695,8 @@ struct LaneT {
     // ------------------------------------------------------------------ auxiliary QP of a cold start (setup_aux of the CPU restatement)
     // x = 0, y = 0, every variable on a finite bound (lower first); variables without one are free and enter S by principal pivots
     // (those with curvature, repeatedly: a pivot may give the next one its curvature). false: free variables are left over
-    __device__ __forceinline__ bool setup_cold() {
+    // (built: the tableau of the empty working set is in place already -- stage_matrices)
+    __device__ __forceinline__ bool setup_cold(bool built = false) {
         status = QPS_PREPARINGAUXILIARYQP;
         infeasible = unbounded = 0;
         int pf = 0;
@@ -601,7 +706,7 @@ struct LaneT {
             sv[l] = l < nV ? s : -1;
             pf |= (l < nV && s == 0) ? 1 << l : 0;);
             SFOR(i, MC, yc[i] = 0.0; ax[i] = 0.0; sc[i] = 0;);
-        g_from_K();
+        if (!built) g_from_K();
         fmask = amask = 0;
         for (int round = 0; round < 2 * N && pf != 0; round++) {
             bool progress = false;
@@ -949,9 +1054,16 @@ __global__ void __launch_bounds__(WL) lane_qp_kernel(QPPools P, int nq, int maxW
     // the ratio test's arms per role (LaneT::ROLES): the same build only -- in the two builds that keep the state with H in full the
     // arms spilled vector registers to scratch memory
     constexpr bool ROLES = CHUNKS;
+    // staging in dependency order (stage_matrices): the builds with H as its block -- both compile without a vector register spilled
+    // and without scratch memory; the others keep their text, their LDS block and their device code. The results ahead of the
+    // objective (below): the headline build only, a kept state keeps its order
+    constexpr bool ORDERED = HB < MV;
     typedef LaneT<MC, HB, CHUNKS ? 14 : 2, CHUNKS ? 6 : 2, ROLES> ENG;
     constexpr int N = ENG::N;
-    __shared__ __attribute__((aligned(16))) double lds[(ENG::NT + ENG::NA) * WL + 16];      // (+ the staging table: 32 ints)
+    // (+ the staging table: 32 ints; in the ordered build it lies in the first of the spare slots the vectors pass through)
+    constexpr int LDSD = (ENG::NT + ENG::NA) * WL + (ORDERED ? ENG::SPV * WL : 16);
+    static_assert(LDSD * sizeof(double) <= 40960, "four waves per CU");
+    __shared__ __attribute__((aligned(16))) double lds[LDSD];
     ldouble *T = (ldouble *)lds;
     const int lane = (int)threadIdx.x;
     const int q0 = (int)blockIdx.x * WL, q = q0 + lane;
@@ -965,9 +1077,36 @@ __global__ void __launch_bounds__(WL) lane_qp_kernel(QPPools P, int nq, int maxW
     E.tlast = clock64();
     long long &tlast = E.tlast;
 #endif
+    int rcode = RET_OK, nWSR = 0, setup_pivots = 0;
+    if constexpr (ORDERED) {
+        // a full wave of aligned pools: the tableau from A and H while the vectors arrive, the set-up from the bounds while g
+        // arrives. The passes of the vectors through LDS are the whole wave's work, so the lanes split (inconsistent bounds,
+        // free-variable pivots) only between them
+        typename ENG::Inflight F;
+        const bool early = E.ordered_wave(P, nqw);
+        if (early) { E.stage_matrices(P, q0, lane, T, F); E.take_bounds(T, lane, F); }
+        else E.template stage<UNI>(P, q0, lane, nqw, T);
+        LSTAMP(0);
+        const bool bad = E.bounds_inconsistent();
+        bool ok = true;
+        if (bad) {
+            E.infeasible = 1;
+            rcode = RET_INFEASIBLE;
+            SFOR(l, MV, E.xv[l] = 0.0; E.yv[l] = 0.0; E.sv[l] = -1; E.g[l] = E.gy[l] = 0.0; E.lo[l] = E.up[l] = 0.0;);
+            SFOR(i, MC, E.yc[i] = 0.0; E.sc[i] = 0; E.ax[i] = 0.0; E.loA[i] = E.upA[i] = 0.0;);
+            if (!early) E.g_from_K();         // (early: nothing has touched the tableau since it was built)
+        } else ok = E.setup_cold(early);
+        LSTAMP(1);
+        if (early) E.take_g(T, lane, F);
+        if (!bad) {
+            setup_pivots = E.nFR() + E.nAC();
+            if (!ok) rcode = RET_SETUP_FAILED;
+            else rcode = E.homotopy(maxWSR, nWSR);
+            LSTAMP(2);
+        }
+    } else {
     E.template stage<UNI>(P, q0, lane, nqw, T);
     LSTAMP(0);
-    int rcode = RET_OK, nWSR = 0, setup_pivots = 0;
     if (E.bounds_inconsistent()) {
         // qpOASES areBoundsConsistent: infeasible before any change
         E.infeasible = 1;
@@ -983,9 +1122,17 @@ __global__ void __launch_bounds__(WL) lane_qp_kernel(QPPools P, int nq, int maxW
         else rcode = E.homotopy(maxWSR, nWSR);
         LSTAMP(2);
     }
+    }
     // (the refinement step repairs what the update-only tableau accumulates: with at most 4 pivots there is nothing to repair yet)
     const int pivots = setup_pivots + nWSR;
-    const double obj = E.finish(rcode == RET_OK && pivots > 4);
+    const bool refine = rcode == RET_OK && pivots > 4;
+    // no lane of the wave refines (the headline's members make two pivots): finish() then changes neither x, y nor the working
+    // sets, and reads A's dense copy, H's registers and the state, not the slots the results pass through -- the results' stores go
+    // out first and the products and the objective run under them. One lane that refines keeps the order for its whole wave
+    bool results_first = false;
+    if constexpr (ORDERED && !KEEP) results_first = __builtin_amdgcn_ballot_w64(refine) == 0;
+    double obj = 0.0;
+    if (!results_first) obj = E.finish(refine);
     LSTAMP(3);
     if constexpr (KEEP) {
         // ---- the state first (its tableau part IS the LDS slots the rest is about to pass through)
@@ -1028,6 +1175,10 @@ __global__ void __launch_bounds__(WL) lane_qp_kernel(QPPools P, int nq, int maxW
         E.template put_block<MV>(P.ws_b + (long long)q0 * nV, nV, nqw * nV, lane, T, SB);
         if (nC > 0) E.template put_block<MC>(P.ws_c + (long long)q0 * nC, nC, nqw * nC, lane, T, SW);
         }
+    }
+    if constexpr (ORDERED) {
+        LSTAMP(19);
+        if (results_first) obj = E.finish(false);
     }
     if (q < nq) {
         const int st = E.status;

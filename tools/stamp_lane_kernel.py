@@ -26,11 +26,13 @@ for k in range(reps):
     b.solve(capi.MODE_COLD, 1000)
 L.rsqp_debug_lane_stamps(buf, 0)
 names = {10: "staging: loads issued, pattern pointers", 11: "staging: loads arrived, dropped into LDS", 12: "staging: own vectors, A scattered",
-         13: "staging: H scattered and read", 0: "staging: rest", 1: "set-up (auxiliary QP)", 2: "homotopy: tail of the last pass",
+         13: "staging: H scattered and read", 17: "staging in dependency order: H read, tableau built", 0: "staging: rest", 1: "set-up (auxiliary QP)", 18: "staging in dependency order: g arrived, taken", 2: "homotopy: tail of the last pass",
          5: "homotopy: x on bounds, refresh, drift, input", 6: "homotopy: out = G in", 7: "homotopy: dx / dy, candidates (divisions)",
          8: "homotopy: decode, step", 14: "homotopy: change: row fetch, tests", 16: "homotopy: change: pivot (pivot1 / pivot2, row store)",
          9: "homotopy: change: working set",
-         3: "refinement step + exact products + objective", 15: "state block written back", 4: "results to HBM"}
+         3: "refinement step + exact products + objective", 15: "state block written back", 19: "results: x, y, working sets issued",
+         4: "results to HBM (results first: objective, status words)"}
+# (a wave staged in dependency order -- qp_lane.hip, stage_matrices: 11 = A and H arrived and dropped, 12 = the bounds taken in rounds)
 tot = sum(buf[k] for k in names)
 for k, n in names.items():
     print("%-60s %9.0f cycles  %5.1f %%" % (n, buf[k] / reps, 100.0 * buf[k] / max(tot, 1)))
