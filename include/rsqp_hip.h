@@ -556,4 +556,6 @@ int rsqp_dense_chol_inverse(int n, double *G, double *Ginv, double pd_rel, doubl
 #endif
 /* the hand-over of a handle for the members of a batch (set / get of the switch): declared in a header of its own */
 #include "rsqp_hip_handover.h"
+/* the shape word of the lane-per-problem kernel's build (rsqp_batch_get_lane_shape): the same way */
+#include "rsqp_hip_lane.h"
 #endif

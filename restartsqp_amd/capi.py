@@ -138,6 +138,10 @@ SYMBOLS = {
 }
 
 
+# ... of its extension include/rsqp_hip_lane.h (which build of the lane-per-problem kernel a batch's last launch took)
+LANE_SYMBOLS = {
+    "rsqp_batch_get_lane_shape": (C.c_int, [C.c_void_p]),
+}
 # ... and of its extension include/rsqp_hip_handover.h (the hand-over switch of a batch), bound by lib() like the table above
 HANDOVER_SYMBOLS = {
     "rsqp_batch_set_handover": (C.c_int, [C.c_void_p, C.c_int]),
@@ -175,7 +179,7 @@ def lib():
             raise ImportError("%s not built: run `python -c 'import __graft_entry__ as g; g.build()'`" % LIB_PATH)
         _TORCH_FIRST = "torch" in sys.modules
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SYMBOLS.items()) + list(HANDOVER_SYMBOLS.items()):
+        for name, (res, args) in list(SYMBOLS.items()) + list(LANE_SYMBOLS.items()) + list(HANDOVER_SYMBOLS.items()):
             f = getattr(L, name)
             f.restype = res
             f.argtypes = args
@@ -752,6 +756,11 @@ class Batch:
         """the lane-per-problem kernel's build of the last launch: 4 = H as its leading 4 x 4 block, 8 = the full triangle
         (RSQP_LANE_HBLOCK=0 forces it), 0 = another kernel ran (rsqp_batch_get_lane_hblock)"""
         return lib().rsqp_batch_get_lane_hblock(self._h)
+
+    def lane_shape(self):
+        """8 * 256 + 2 = the last launch ran the lane-per-problem kernel's full-shape build (nV = 8, nC = 2 as compile-time
+        constants), 0 = its shape was a run-time value (RSQP_LANE_SHAPE=0 forces it) or another kernel ran (rsqp_batch_get_lane_shape)"""
+        return lib().rsqp_batch_get_lane_shape(self._h)
 
     def last_plan(self):
         """the launch plan of the solve last_kernel() reports, as a dict over SMALL_LAUNCH_OUT: which instantiation ran

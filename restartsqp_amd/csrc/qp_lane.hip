@@ -71,6 +71,11 @@ template <int I, int E, class F> __device__ __forceinline__ void sfor_(F &&f) {
 // derived from it (free / at lower / at upper) are re-formed per pass (one compare) instead of kept in scalar registers across the
 // whole iteration, from where they were spilled to lanes of vector registers and read back (2-3 % of the kernel)
 __device__ __forceinline__ int opq(int v) { asm volatile("" : "+v"(v)); return v; }
+// a product that is not contracted into the sum that takes it
+__device__ __forceinline__ double mul_alone(double a, double b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
 __host__ __device__ constexpr int tri(int j, int k) { return j <= k ? k * (k + 1) / 2 + j : j * (j + 1) / 2 + k; }
 
 #include "qp_leaf.h"
@@ -82,8 +87,21 @@ __host__ __device__ constexpr int tri(int j, int k) { return j <= k ? k * (k + 1
 // ROLES: the ratio test of homotopy() BRANCHES on the role of a variable slot (free / fixed) instead of computing both roles and
 // selecting, and the re-relaxation in front of the homotopy, which a cold start cannot need, is left out (kernel's choice, see
 // lane_qp_kernel: the headline build only)
-template <int MC, int HB, int CH1 = 2, int CH2 = 2, bool ROLES = false>
+// SHV / SHC: the batch's shape as compile-time words (the full-shape build, 8 x 2), or -1: the run-time words P.uniV / P.uniC. With
+// the constants every `l < nV` / `i < nC` of the slot passes, the candidate ids and the parity arms of the staging and results
+// helpers fold: one text, the shape decides what is left of it (lane_qp_body)
+template <int S> struct ShapeWord {
+    __device__ __forceinline__ ShapeWord &operator=(int) { return *this; }
+    __device__ __forceinline__ constexpr operator int() const { return S; }
+};
+template <> struct ShapeWord<-1> {
+    int v;
+    __device__ __forceinline__ ShapeWord &operator=(int w) { v = w; return *this; }
+    __device__ __forceinline__ operator int() const { return v; }
+};
+template <int MC, int HB, int CH1 = 2, int CH2 = 2, bool ROLES = false, int SHV = -1, int SHC = -1>
 struct LaneT {
+    static_assert((SHV < 0) == (SHC < 0) && SHV <= MV && SHC <= MC, "both words of the shape, or neither");
     static_assert(HB == 4 || HB == MV, "leading block of H");
     static constexpr int N = MV + MC, NT = N * (N + 1) / 2, NH = HB * (HB + 1) / 2, NA = MC * MV, REFRESH = 8;
     ldouble *G, *K;                      // my problem's tableau / the dense A of the data: entry e at [e * WL]
@@ -91,7 +109,8 @@ struct LaneT {
     double xv[MV], lo[MV], up[MV], loN[MV], upN[MV], yv[MV], g[MV], gN[MV], gy[MV];
     double ax[MC], loA[MC], upA[MC], cloN[MC], cupN[MC], yc[MC];
     int sv[MV], sc[MC];
-    int nV, nC, fmask, amask, status, infeasible, unbounded, nflips, since_refresh;
+    ShapeWord<SHV> nV; ShapeWord<SHC> nC;
+    int fmask, amask, status, infeasible, unbounded, nflips, since_refresh;
     double hscale, hreg;
     long long tlast;                     // (-DRSQP_STAMPS builds)
 
@@ -1026,9 +1045,10 @@ struct LaneT {
         }
         exact_products(gyx, axx, hxx);
         double t[MV];
-        // (the objective excludes the LP regularisation)
+        // (the objective excludes the LP regularisation; mul_alone: a product of its own, as it is behind the select on a run-time nV --
+        //  with nV a constant the select folds, and the compiler would contract the product into the sums below: another last bit)
         SFOR(l, MV, if (refine && l < nV) yv[l] = sv[l] != 0 ? gN[l] - gyx[l] : 0.0;
-             t[l] = l < nV ? xv[l] * fma(0.5, hxx[l] - hreg * xv[l], gN[l]) : 0.0;);
+             t[l] = l < nV ? mul_alone(xv[l], fma(0.5, hxx[l] - hreg * xv[l], gN[l])) : 0.0;);
         SFOR(i, MC, ax[i] = i < nC ? axx[i] : 0.0;);
         return ((t[0] + t[1]) + (t[2] + t[3])) + ((t[7] + t[6]) + (t[5] + t[4]));      // (the order of qp_tiny.hip's lane tree)
     }
@@ -1045,8 +1065,9 @@ struct LaneT {
 // with one wave per SIMD to hide the round trips, 100-144 KB of code, 340-960 registers spilled to scratch. Removed.)
 constexpr int LANE_TINY_MAGIC = 0x7a11e;
 
-template <int MC, bool KEEP, bool UNI, int HB>
-__global__ void __launch_bounds__(WL) lane_qp_kernel(QPPools P, int nq, int maxWSR) {
+// the kernel's body; SHV x SHC: the shape as constants (lane_qp_shape_kernel), or -1: run-time words (lane_qp_kernel)
+template <int MC, bool KEEP, bool UNI, int HB, int SHV, int SHC>
+__device__ __forceinline__ void lane_qp_body(const QPPools &P, int nq, int maxWSR) {
     static_assert(UNI || HB == MV, "the block build serves one-pattern batches");
     // the pivots' chunks (sweep_triangle): 14 entries for pivot1, 6 for pivot2 (which holds 40 doubles of vectors beside them) in
     // the headline build; with the state kept or H in full every chunking tried spilled vector registers, so those go pair by pair
@@ -1058,7 +1079,7 @@ __global__ void __launch_bounds__(WL) lane_qp_kernel(QPPools P, int nq, int maxW
     // and without scratch memory; the others keep their text, their LDS block and their device code. The results ahead of the
     // objective (below): the headline build only, a kept state keeps its order
     constexpr bool ORDERED = HB < MV;
-    typedef LaneT<MC, HB, CHUNKS ? 14 : 2, CHUNKS ? 6 : 2, ROLES> ENG;
+    typedef LaneT<MC, HB, CHUNKS ? 14 : 2, CHUNKS ? 6 : 2, ROLES, SHV, SHC> ENG;
     constexpr int N = ENG::N;
     // (+ the staging table: 32 ints; in the ordered build it lies in the first of the spare slots the vectors pass through)
     constexpr int LDSD = (ENG::NT + ENG::NA) * WL + (ORDERED ? ENG::SPV * WL : 16);
@@ -1188,12 +1209,29 @@ __global__ void __launch_bounds__(WL) lane_qp_kernel(QPPools P, int nq, int maxW
     LSTAMP(4);
 }
 
+template <int MC, bool KEEP, bool UNI, int HB>
+__global__ void __launch_bounds__(WL) lane_qp_kernel(QPPools P, int nq, int maxWSR) {
+    lane_qp_body<MC, KEEP, UNI, HB, -1, -1>(P, nq, maxWSR);
+}
+// the full-shape build: every member NV x NC (the plan's word, SmallPlan::lane_shape); the ragged last wave of such a batch runs it too
+template <int MC, bool KEEP, bool UNI, int HB, int NV, int NC>
+__global__ void __launch_bounds__(WL) lane_qp_shape_kernel(QPPools P, int nq, int maxWSR) {
+    lane_qp_body<MC, KEEP, UNI, HB, NV, NC>(P, nq, maxWSR);
+}
+
 }  // namespace
 
-// the plan's build (rsqp_small_plan.h): state kept or not; one pattern or patterns of their own; H as its leading 4 x 4 block or in full
+// the plan's build (rsqp_small_plan.h): state kept or not; one pattern or patterns of their own; H as its leading 4 x 4 block or in full;
+// SmallPlan::lane_shape: the full-shape build of the one-pattern block builds (8 x 2 as constants), or 0
 hipError_t rsqp_launch_lane_qp(const SmallPlan &pl, const QPPools &p, int nq, int maxWSR, hipStream_t stream) {
     static_assert(MV == 8 && WL == kLaneBlock, "rsqp_plan_lane_fits");
     const dim3 grid(pl.grid), block(pl.block);
+    if (pl.lane_shape == 8 * 256 + 2 && pl.mc == 2 && pl.uni == 1 && pl.hb == 4) {
+        if (pl.keep) hipLaunchKernelGGL((lane_qp_shape_kernel<2, true, true, 4, 8, 2>), grid, block, 0, stream, p, nq, maxWSR);
+        else hipLaunchKernelGGL((lane_qp_shape_kernel<2, false, true, 4, 8, 2>), grid, block, 0, stream, p, nq, maxWSR);
+        return hipGetLastError();
+    }
+    if (pl.lane_shape != 0) return hipErrorInvalidValue;
     switch (pl.mc * 1000 + pl.keep * 100 + pl.uni * 10 + pl.hb) {
     case 2114: hipLaunchKernelGGL((lane_qp_kernel<2, true, true, 4>), grid, block, 0, stream, p, nq, maxWSR); break;
     case 2014: hipLaunchKernelGGL((lane_qp_kernel<2, false, true, 4>), grid, block, 0, stream, p, nq, maxWSR); break;

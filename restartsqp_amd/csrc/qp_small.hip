@@ -276,7 +276,7 @@ SmallKnobs rsqp_small_knobs_from_env() {
     SmallKnobs k;
     k.engine = env_int("RSQP_SMALL_ENGINE", -1); k.k_debug_bail = env_int("RSQP_K_DEBUG_BAIL", -1);
     k.lanes = env_int("RSQP_SMALL_LANES", -1); k.waves = env_int("RSQP_SMALL_WAVES", -1);
-    k.lane = env_int("RSQP_LANE", -1); k.lane_hblock = env_int("RSQP_LANE_HBLOCK", -1); k.arena_mapped = env_int("RSQP_ARENA_MAPPED", -1);
+    k.lane = env_int("RSQP_LANE", -1); k.lane_hblock = env_int("RSQP_LANE_HBLOCK", -1); k.lane_shape = env_int("RSQP_LANE_SHAPE", -1); k.arena_mapped = env_int("RSQP_ARENA_MAPPED", -1);
     k.no_spin = getenv("RSQP_NO_SPIN") != nullptr;
     return k;
 }

@@ -60,6 +60,7 @@ struct rsqp_batch {
     // the lane-per-problem kernel's build (qp_lane.hip): lane_hblock = 4 when the batch's one pattern keeps H inside its leading
     // 4 x 4 block (judged once, at create: values change later, patterns never), else 8; last_hblock = what the last launch took
     int lane_hblock = 8, last_hblock = 0; // rsqp_batch_get_lane_hblock
+    int last_lane_shape = 0;              // rsqp_batch_get_lane_shape: SmallPlan::lane_shape of the last launch
     bool hbm = false;                     // images beyond the LDS of a CU: every member on the HBM-resident kernel (qp_small_hbm.hip)
     // the host's record of H's symmetry (judge_h_sym): h_sym = every H symmetric value by value (the tableau kernel of qp_tiny.hip
     // may take the batch); h_symq[q] = member q's is. Kept for batches of at most 8 variables, with the H patterns in the caller's

@@ -282,7 +282,7 @@ int launch_batch(rsqp_batch *b, QPPools &p, int mode, int max_nWSR, bool first, 
     // leaves no mark either: the record here says so
     const int fam = pl.state_family;
     b->state_engine = pl.skip_mark ? -1 : ((p.member_mode && b->sitters && b->state_engine != fam) ? -2 : fam);
-    if (first) { b->last_kernel = pl.family; b->last_hblock = pl.hb; rsqp_plan_words(pl, b->last_plan); }
+    if (first) { b->last_kernel = pl.family; b->last_hblock = pl.hb; b->last_lane_shape = pl.lane_shape; rsqp_plan_words(pl, b->last_plan); }
     hipError_t e = rsqp_launch_small_qp(knobs_of(b, lp), pl, p, b->nq, max_nWSR, b->stream);
     if (e != hipSuccess) return fail(RSQP_ERR_DEVICE, std::string("QP kernel launch: ") + hipGetErrorString(e));
     // rsqp_batch_set_handover: the members a hs071-scale tableau kernel gave up on go to the null-space kernel right behind it, with
@@ -346,6 +346,7 @@ extern "C" int rsqp_batch_solve(rsqp_batch *b, int mode, int max_nWSR) {
 
 extern "C" int rsqp_batch_get_last_kernel(const rsqp_batch *b) { return b ? b->last_kernel : -1; }
 extern "C" int rsqp_batch_get_lane_hblock(const rsqp_batch *b) { return b ? b->last_hblock : 0; }
+extern "C" int rsqp_batch_get_lane_shape(const rsqp_batch *b) { return b ? b->last_lane_shape : 0; }
 extern "C" int rsqp_batch_get_last_plan(const rsqp_batch *b, int *out, int nout) {
     if (!b || !out || nout != RSQP_PLAN_OUT_WORDS) return fail(RSQP_ERR_ARG, "rsqp_batch_get_last_plan");
     if (b->last_kernel < 0) return fail(RSQP_ERR_ARG, "rsqp_batch_get_last_plan: the batch has not launched yet");

@@ -44,7 +44,8 @@ struct SmallKnobs {
     int no_tiny = 0;          // (set by the single-QP rescue, rsqp_api.hip, and by knobs_of, rsqp_batch.hip) 1: no hs071-scale tableau kernel; 2 (the LP launches of a batch): nor the mid-size one
     int lane = -1;            // RSQP_LANE              0: never the lane-per-problem kernel (qp_lane.hip); n > 0: from n members on (default 16 385)
     int lane_hblock = -1;     // RSQP_LANE_HBLOCK       0: the lane-per-problem kernel always keeps the full triangle of H (never its leading-block build)
-    int arena_mapped = -1;    // RSQP_ARENA_MAPPED      single-QP handles: patterns / plans in host-mapped memory, no upload at set_A / set_H (-1: hs071 scale only)
+    int lane_shape = -1;      // RSQP_LANE_SHAPE        0: never the lane-per-problem kernel's full-shape build (nV = 8, nC = 2 as compile-time constants)
+    int arena_mapped = -1;    // RSQP_ARENA_MAPPED     single-QP handles: patterns / plans in host-mapped memory, no upload at set_A / set_H (-1: hs071 scale only)
     int no_spin = 0;          // RSQP_NO_SPIN           single-QP waits block in hipStreamSynchronize instead of spinning on a mapped word
 };
 SmallKnobs rsqp_small_knobs_from_env();      // qp_small.hip

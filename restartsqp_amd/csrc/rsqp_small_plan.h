@@ -32,7 +32,9 @@ struct SmallPlan {
     int waves = 0;        // waves per SIMD asked for (W is what the product build instantiates; tools/small_experiment.sh builds more)
     // tiny_qp_kernel<mc, W>; lane_qp_kernel<mc, keep, uni, hb>
     int mc = 0, keep = 0, uni = 0, hb = 0;
-    int first = 0;        // the mid-size tableau kernel goes first (qp_small_g.h): 1 small_qpg_kernel<3, 1, 9, 4>, 2 <2, 2, 8, 8>; 0 no
+    int lane_shape = 0;   // lane_qp_shape_kernel<mc, keep, uni, hb, NV, NC>: NV * 256 + NC of the lane kernel's full-shape build, else 0 (not
+                          //   among the exported words: the build FAMILY stays (keep, uni, hb); rsqp_batch_get_lane_shape reports it)
+    int first = 0;       // the mid-size tableau kernel goes first (qp_small_g.h): 1 small_qpg_kernel<3, 1, 9, 4>, 2 <2, 2, 8, 8>; 0 no
     unsigned grid = 0, block = 0;       // of the family's kernel (the tableau kernel that goes first: nq blocks of 256)
     long long lds = 0;    // dynamic LDS bytes
     int stride = 0;       // LDS bytes of one problem (null-space kernels)
@@ -120,6 +122,8 @@ inline SmallPlan rsqp_plan_small_launch(const SmallKnobs &kn, const SmallFacts &
         pl.mc = 2; pl.keep = f.keep_state ? 1 : 0;
         pl.hb = (f.uni_pat && f.lane_hblock == 4 && !f.uni_hreg) ? 4 : 8;
         pl.uni = (pl.hb == 4 || f.uni_pat) ? 1 : 0;
+        // the full shape of that kernel, one pattern, H as its block: the build with nV and nC as constants (RSQP_LANE_SHAPE=0: never)
+        if (kn.lane_shape != 0 && f.uniV == 8 && f.uniC == 2 && f.uni_pat && pl.hb == 4) pl.lane_shape = 8 * 256 + 2;
         pl.grid = (unsigned)((nq + kLaneBlock - 1) / kLaneBlock); pl.block = kLaneBlock;
         return pl;
     }

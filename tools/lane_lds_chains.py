@@ -16,7 +16,7 @@ sys.path.insert(0, ROOT)
 from restartsqp_amd import build
 
 FENCE = "sched_barrier mask(0x00000000)"
-KERNEL = re.compile(r"^(_ZN\S*lane_qp_kernelILi(\d+)ELb([01])ELb([01])ELi(\d+)E\S*):")
+KERNEL = re.compile(r"^(_ZN\S*lane_qp_(?:shape_)?kernelILi(\d+)ELb([01])ELb([01])ELi(\d+)E(?:Li(\d+)ELi(\d+)E)?\S*):")
 USAGE = re.compile(r"remark: +(Function Name|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|SGPRs Spill|VGPRs Spill|LDS Size \[bytes/block\]): (\S+)")
 
 
@@ -87,7 +87,8 @@ def main(argv):
             k += 1
             continue
         end = next(j for j in range(k, len(lines)) if lines[j].startswith(".Lfunc_end"))
-        print("lane_qp_kernel<%s, %s, %s, %s>" % (m.group(2), ("false", "true")[int(m.group(3))], ("false", "true")[int(m.group(4))], m.group(5)))
+        print("lane_qp_%skernel<%s, %s, %s, %s%s>" % ("shape_" if m.group(6) else "", m.group(2), ("false", "true")[int(m.group(3))], ("false", "true")[int(m.group(4))],
+                                             m.group(5), ", %s, %s" % (m.group(6), m.group(7)) if m.group(6) else ""))
         if m.group(1) in usage:
             print("    " + "; ".join(usage[m.group(1)]))
         print("    %-4s %-13s %6s %6s %6s %6s %6s   %s" % ("seg", "lines", "reads", "writes", "waits", "trips", "in bb", "reads in flight at a wait: count"))
