@@ -31,9 +31,13 @@ typedef LDS double ldouble;
 #ifdef RSQP_STAMPS
 constexpr int kLaneStamps = 24;
 __device__ unsigned long long g_lane_stamps[kLaneStamps];
+// (fenced on both sides: the scheduler otherwise moves a phase's instructions across the clock read that should bound it -- the
+//  step's 255 instructions once lay below the stamp behind them, and were booked on the working-set change)
 #define LSTAMP(k)                                                                                        \
     do {                                                                                                 \
+        __builtin_amdgcn_sched_barrier(0);                                                               \
         long long t_ = clock64();                                                                        \
+        __builtin_amdgcn_sched_barrier(0);                                                               \
         if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&g_lane_stamps[k], (unsigned long long)(t_ - tlast)); \
         tlast = t_;                                                                                      \
     } while (0)
@@ -99,7 +103,11 @@ template <> struct ShapeWord<-1> {
     __device__ __forceinline__ ShapeWord &operator=(int w) { v = w; return *this; }
     __device__ __forceinline__ operator int() const { return v; }
 };
-template <int MC, int HB, int CH1 = 2, int CH2 = 2, bool ROLES = false, int SHV = -1, int SHC = -1>
+// VOTE: the wave's lanes vote (ballot over the lanes still in the loop) on what happens next, and a wave that agrees runs a text
+// in which that is a constant. Bit 0: the homotopy step by `done` (step); bit K, K = 1 .. 4: change() with every lane's change of
+// kind K. A wave that disagrees runs the text of the builds without the flag; per lane every text performs the same operations
+// on the same operands in the same order (kernel's choice, see lane_qp_body: the full-shape build without kept state)
+template <int MC, int HB, int CH1 = 2, int CH2 = 2, bool ROLES = false, int SHV = -1, int SHC = -1, int VOTE = 0>
 struct LaneT {
     static_assert((SHV < 0) == (SHC < 0) && SHV <= MV && SHC <= MC, "both words of the shape, or neither");
     static_assert(HB == 4 || HB == MV, "leading block of H");
@@ -758,7 +766,11 @@ struct LaneT {
     // (style of the slot passes here and in homotopy(): every arm of a choice is computed first, then selected -- plain selects
     //  between values; a ternary with arithmetic in its arms becomes a tree of divergent branches per slot. The one exception is
     //  measured: the variable slots of homotopy()'s ratio test in the headline build, ROLES)
-    __device__ __forceinline__ int change(int kind, int idx, int side, double tau, bool &treat_done) {
+    // KIND: the kind as a constant (a wave whose lanes agree on it, VOTE), or 0: `kind_` by lane. With the constant, `isc`,
+    // `leaves`, the pivot's sign and `sg` fold and the arms of the other kinds are not in the text; idx, side and q stay by lane,
+    // and so do the arms a lane may take alone: the flip (kinds 1, 2) and the exchange (kinds 3, 4)
+    template <int KIND> __device__ __forceinline__ int change(int kind_, int idx, int side, double tau, bool &treat_done) {
+        const int kind = KIND != 0 ? KIND : kind_;
         const bool isc = (kind == 1) | (kind == 3);
         const int q = isc ? MV + idx : idx;
         double u[N];
@@ -985,33 +997,59 @@ struct LaneT {
             const double tau = bt;
             const bool done = kind == 0;
             const bool cap = iter >= maxit;
-            const bool go = !done & !cap;
-            // ---- homotopy step on my slots
-            SFOR(l, MV, const int s_ = opq(sv[l]); yv[l] += tau * dyv[l];
-                 const double xn = xv[l] + tau * dxv[l];
-                 const double l1 = lo[l] + tau * (loN[l] - lo[l]), u1 = up[l] + tau * (upN[l] - up[l]);
-                 const double gn = g[l] + tau * (gN[l] - g[l]);
-                 const bool hit = go & (kind == 4) & (l == idx);
-                 const double xe1 = s_ == 1 ? upN[l] : xn, xe = s_ == -1 ? loN[l] : xe1;
-                 xv[l] = done ? xe : xn;
-                 g[l] = done ? gN[l] : gn;
-                 gy[l] -= tau * hd[l];
-                 const double l2 = (hit & (side == -1)) ? xn : l1, u2 = (hit & (side == 1)) ? xn : u1;
-                 lo[l] = done ? loN[l] : l2; up[l] = done ? upN[l] : u2;);
-            SFOR(i, MC, yc[i] += tau * dyc[i];
-                 const double an = ax[i] + tau * dax[i];
-                 const double l1 = loA[i] + tau * (cloN[i] - loA[i]), u1 = upA[i] + tau * (cupN[i] - upA[i]);
-                 const bool hit = go & (kind == 3) & (i == idx);
-                 ax[i] = done ? ax[i] : an;
-                 const double l2 = (hit & (side == -1)) ? an : l1, u2 = (hit & (side == 1)) ? an : u1;
-                 loA[i] = done ? cloN[i] : l2; upA[i] = done ? cupN[i] : u2;);
+            const bool go_lane = !done & !cap;
+            // ---- homotopy step on my slots. DM: what the wave agreed on (VOTE) -- 1 no lane is done, 2 every lane is: `done` is that
+            // constant, the selects on it fold, and of the values a done lane discards (the interpolated limits and gradient) nothing
+            // is computed; 0: `done` by lane, the text of the builds without the flag
+            const bool done_lane = done;
+            auto step = [&](auto dm_c) {
+                constexpr int DM = decltype(dm_c)::value;
+                const bool done = DM == 0 ? done_lane : DM == 2;
+                const bool go = DM == 0 ? go_lane : !done & !cap;
+                SFOR(l, MV, const int s_ = opq(sv[l]); yv[l] += tau * dyv[l];
+                     const double xn = xv[l] + tau * dxv[l];
+                     const double l1 = lo[l] + tau * (loN[l] - lo[l]), u1 = up[l] + tau * (upN[l] - up[l]);
+                     const double gn = g[l] + tau * (gN[l] - g[l]);
+                     const bool hit = go & (kind == 4) & (l == idx);
+                     const double xe1 = s_ == 1 ? upN[l] : xn, xe = s_ == -1 ? loN[l] : xe1;
+                     xv[l] = done ? xe : xn;
+                     g[l] = done ? gN[l] : gn;
+                     gy[l] -= tau * hd[l];
+                     const double l2 = (hit & (side == -1)) ? xn : l1, u2 = (hit & (side == 1)) ? xn : u1;
+                     lo[l] = done ? loN[l] : l2; up[l] = done ? upN[l] : u2;);
+                SFOR(i, MC, yc[i] += tau * dyc[i];
+                     const double an = ax[i] + tau * dax[i];
+                     const double l1 = loA[i] + tau * (cloN[i] - loA[i]), u1 = upA[i] + tau * (cupN[i] - upA[i]);
+                     const bool hit = go & (kind == 3) & (i == idx);
+                     ax[i] = done ? ax[i] : an;
+                     const double l2 = (hit & (side == -1)) ? an : l1, u2 = (hit & (side == 1)) ? an : u1;
+                     loA[i] = done ? cloN[i] : l2; upA[i] = done ? cupN[i] : u2;);
+            };
+            LSTAMP_IN(20);
+            if constexpr ((VOTE & 1) != 0) {
+                // (the lanes still in the loop vote; those that have left it are masked off and do not enter the ballot)
+                const unsigned long long in_loop = __builtin_amdgcn_ballot_w64(true), dn = __builtin_amdgcn_ballot_w64(done_lane);
+                if (dn == 0) step(std::integral_constant<int, 1>{});
+                else if (dn == in_loop) step(std::integral_constant<int, 2>{});
+                else step(std::integral_constant<int, 0>{});
+            } else step(std::integral_constant<int, 0>{});
             LSTAMP(8);
             if (done || cap) {
                 if (done) status = QPS_SOLVED; else rcode = RET_MAX_NWSR;
                 break;
             }
             bool treat_done = false;
-            rcode = change(kind, idx, side, tau, treat_done);
+            if constexpr ((VOTE & ~1) != 0) {
+                // every lane here is about to change its working set (done and capped lanes have left): one text per kind the wave
+                // agrees on, the text by lane otherwise
+                const unsigned long long in_loop = __builtin_amdgcn_ballot_w64(true);
+                auto all = [&](int k) { return __builtin_amdgcn_ballot_w64(kind == k) == in_loop; };
+                if ((VOTE & 4) != 0 && all(2)) rcode = change<2>(kind, idx, side, tau, treat_done);
+                else if ((VOTE & 16) != 0 && all(4)) rcode = change<4>(kind, idx, side, tau, treat_done);
+                else if ((VOTE & 8) != 0 && all(3)) rcode = change<3>(kind, idx, side, tau, treat_done);
+                else if ((VOTE & 2) != 0 && all(1)) rcode = change<1>(kind, idx, side, tau, treat_done);
+                else rcode = change<0>(kind, idx, side, tau, treat_done);
+            } else rcode = change<0>(kind, idx, side, tau, treat_done);
             LSTAMP(9);
             if (treat_done) {      // (see change: no exchange partner at the very end of the homotopy)
                 SFOR(l, MV, g[l] = gN[l]; lo[l] = loN[l]; up[l] = upN[l];
@@ -1079,7 +1117,11 @@ __device__ __forceinline__ void lane_qp_body(const QPPools &P, int nq, int maxWS
     // and without scratch memory; the others keep their text, their LDS block and their device code. The results ahead of the
     // objective (below): the headline build only, a kept state keeps its order
     constexpr bool ORDERED = HB < MV;
-    typedef LaneT<MC, HB, CHUNKS ? 14 : 2, CHUNKS ? 6 : 2, ROLES, SHV, SHC> ENG;
+    // the wave's votes (LaneT::VOTE): the full-shape build without kept state -- the step by `done`, and change() by kinds 3 (both
+    // changes of every headline member: a constraint enters by an exchange with a bound) and 2. Kinds 4 and 1 stay on the text by
+    // lane: 14 KB more of it, and the headline batch could not tell the builds apart
+    constexpr int VOTE = (CHUNKS && SHV >= 0) ? (1 | 1 << 2 | 1 << 3) : 0;
+    typedef LaneT<MC, HB, CHUNKS ? 14 : 2, CHUNKS ? 6 : 2, ROLES, SHV, SHC, VOTE> ENG;
     constexpr int N = ENG::N;
     // (+ the staging table: 32 ints; in the ordered build it lies in the first of the spare slots the vectors pass through)
     constexpr int LDSD = (ENG::NT + ENG::NA) * WL + (ORDERED ? ENG::SPV * WL : 16);
