@@ -147,6 +147,11 @@ HANDOVER_SYMBOLS = {
     "rsqp_batch_set_handover": (C.c_int, [C.c_void_p, C.c_int]),
     "rsqp_batch_get_handover": (C.c_int, [C.c_void_p, ip, ip]),
 }
+# ... and of include/rsqp_hip_lane_warm.h (hot starts with new matrices / warm re-initialisations on the lane-per-problem kernel)
+LANE_WARM_SYMBOLS = {
+    "rsqp_batch_set_lane_warm": (C.c_int, [C.c_void_p, C.c_int]),
+    "rsqp_batch_get_lane_warm": (C.c_int, [C.c_void_p]),
+}
 
 
 class OptimalityStatus(C.Structure):
@@ -179,7 +184,8 @@ def lib():
             raise ImportError("%s not built: run `python -c 'import __graft_entry__ as g; g.build()'`" % LIB_PATH)
         _TORCH_FIRST = "torch" in sys.modules
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SYMBOLS.items()) + list(LANE_SYMBOLS.items()) + list(HANDOVER_SYMBOLS.items()):
+        for name, (res, args) in list(SYMBOLS.items()) + list(LANE_SYMBOLS.items()) + list(HANDOVER_SYMBOLS.items()) + \
+                list(LANE_WARM_SYMBOLS.items()):
             f = getattr(L, name)
             f.restype = res
             f.argtypes = args
@@ -734,6 +740,16 @@ class Batch:
         Givens / TQ kernel that takes over the members they give up on at set-up, as a single Solver re-solves such a call
         (rsqp_batch_set_handover); off (the default): those members come back unsolved"""
         check(lib().rsqp_batch_set_handover(self._h, int(bool(on))))
+
+    def set_lane_warm(self, on):
+        """on: a batch the lane-per-problem kernel takes (last_kernel() 2 for its cold start) and that keeps its state also runs its
+        hot starts with new matrices, its warm re-initialisations and the first solve of an optimize_qp() that follows
+        set_matrix_values() on that kernel (rsqp_batch_set_lane_warm); off (the default): on the 8-lane kernel, as before"""
+        check(lib().rsqp_batch_set_lane_warm(self._h, int(bool(on))))
+
+    def lane_warm(self):
+        """the switch of set_lane_warm (rsqp_batch_get_lane_warm)"""
+        return bool(check(lib().rsqp_batch_get_lane_warm(self._h)))
 
     def handover(self, handed=None):
         """(handed, count) of the last solve / optimize call: handed[q] = 1 where member q was handed over to the Givens / TQ kernel

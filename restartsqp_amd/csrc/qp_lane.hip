@@ -1,4 +1,5 @@
-// qp_lane.hip -- hs071-scale QPs of a ONE-SHAPE batch, cold start, ONE LANE PER PROBLEM (round 5).
+// qp_lane.hip -- hs071-scale QPs of a ONE-SHAPE batch, cold start, ONE LANE PER PROBLEM (round 5); in the WARM builds also the hot
+// start with new matrices and the warm re-initialisation (lane_qp_body, rsqp_batch_set_lane_warm).
 //
 // Replaces, for large batches of one shape (one sparsity pattern -- parameter scans, perturbations of one QP: bench.py's
 // headline workload, 65 536 x the hs071 QP through the QPhandler formulation -- or patterns of their own), the qpOASES 3.2.1 SQProblem::init call made
@@ -107,7 +108,9 @@ template <> struct ShapeWord<-1> {
 // in which that is a constant. Bit 0: the homotopy step by `done` (step); bit K, K = 1 .. 4: change() with every lane's change of
 // kind K. A wave that disagrees runs the text of the builds without the flag; per lane every text performs the same operations
 // on the same operands in the same order (kernel's choice, see lane_qp_body: the full-shape build without kept state)
-template <int MC, int HB, int CH1 = 2, int CH2 = 2, bool ROLES = false, int SHV = -1, int SHC = -1, int VOTE = 0>
+// WARM: the build for hot starts with new matrices and warm re-initialisations (lane_qp_body): the set-up from a guess (setup_warm,
+// warm_pivots), the guess's way in (take_guess) and results / state stores that leave out the members a launch does not run
+template <int MC, int HB, int CH1 = 2, int CH2 = 2, bool ROLES = false, int SHV = -1, int SHC = -1, int VOTE = 0, bool WARM = false>
 struct LaneT {
     static_assert((SHV < 0) == (SHC < 0) && SHV <= MV && SHC <= MC, "both words of the shape, or neither");
     static_assert(HB == 4 || HB == MV, "leading block of H");
@@ -356,7 +359,9 @@ struct LaneT {
     // instead of 0.04 for the headline launch with its state kept; instead lane j handles pairs j, j + 64, ... of the wave's run
     // of blocks (two doubles of one problem per instruction, consecutive lanes consecutive pairs): 0.075 ms.
     // The tableau part: both triangles in HBM (what the 8-lane kernel holds), from the upper one in the LDS slots
-    __device__ __forceinline__ void state_put_tableau(double *sbase, long long stride, int nqw, int lane, const ldouble *T) const {
+    // (live, WARM: bit qq = problem qq of the wave is in the launch; the others' blocks stay as they are)
+    __device__ __forceinline__ void state_put_tableau(double *sbase, long long stride, int nqw, int lane, const ldouble *T,
+                                                      unsigned long long live = ~0ull) const {
         static_assert((N & 1) == 0, "pairs of a row");
         constexpr int PAIRS = N * N / 2;
         // (a run-time loop: nothing here indexes a register array, and 50 unrolled trips were hoisted in front of each other until
@@ -368,18 +373,23 @@ struct LaneT {
             const int hi0 = r > k ? r : k, lo0 = r > k ? k : r, hi1 = r > k + 1 ? r : k + 1, lo1 = r > k + 1 ? k + 1 : r;
             double2 v;
             v.x = T[(((hi0 * (hi0 + 1)) >> 1) + lo0) * WL + qq]; v.y = T[(((hi1 * (hi1 + 1)) >> 1) + lo1) * WL + qq];
-            if (qq < nqw) *reinterpret_cast<double2 *>(sbase + (long long)qq * stride + e) = v;
+            bool mine = qq < nqw;
+            if constexpr (WARM) mine = mine && ((live >> (qq & 63)) & 1) != 0;
+            if (mine) *reinterpret_cast<double2 *>(sbase + (long long)qq * stride + e) = v;
         }
     }
     // the slot state + status words behind it: TAILD doubles (the ints as pairs), staged in LDS slots 0 .. in two halves
     static constexpr int TAILD = 96 + 10, THALF = TAILD / 2;
     static_assert(THALF <= NT, "the halves of the slot state pass through the tableau's slots");
-    __device__ __forceinline__ void state_put_tail_half(double *sbase, long long stride, int nqw, int lane, const ldouble *T, int half) const {
+    __device__ __forceinline__ void state_put_tail_half(double *sbase, long long stride, int nqw, int lane, const ldouble *T, int half,
+                                                        unsigned long long live = ~0ull) const {
 #pragma unroll 4
         for (int t = 0; t < THALF; t++) {
             const int m = t * WL + lane;
             const int qq = m / THALF, f = m - qq * THALF;
-            if (qq < nqw) sbase[(long long)qq * stride + N * N + half * THALF + f] = T[f * WL + qq];
+            bool mine = qq < nqw;
+            if constexpr (WARM) mine = mine && ((live >> (qq & 63)) & 1) != 0;
+            if (mine) sbase[(long long)qq * stride + N * N + half * THALF + f] = T[f * WL + qq];
         }
     }
     // my slot state as the TAILD doubles behind the tableau: f < 48 field f / 8 (x g lo up gy y) of variable slot f % 8; f < 80 field
@@ -415,12 +425,15 @@ struct LaneT {
     }
     // the reverse for results: every lane has put its n values into slots s0 .. s0 + n - 1 of its own column; lane j stores
     // elements j, j + 64, ... of the wave's contiguous block (64-bit values, or 32-bit ones kept in the low halves of the slots)
-    template <int CH, class TV> __device__ __forceinline__ void put_block(TV *dst, int n, int cnt, int lane, const ldouble *T, int s0) const {
+    template <int CH, class TV> __device__ __forceinline__ void put_block(TV *dst, int n, int cnt, int lane, const ldouble *T, int s0,
+                                                                          unsigned long long live = ~0ull) const {
         const float rn = 1.0f / (float)n;
         SFOR(t, CH, if (t < n) {
                  const int m = t * WL + lane;
                  const int qq = (int)(((float)m + 0.5f) * rn), e = m - qq * n;
-                 if (m < cnt) {
+                 bool mine = m < cnt;
+                 if constexpr (WARM) mine = mine && ((live >> (qq & 63)) & 1) != 0;
+                 if (mine) {
                      if constexpr (sizeof(TV) == 8) dst[m] = T[(s0 + e) * WL + qq];
                      else dst[m] = ((const __attribute__((address_space(3))) int *)(T + (s0 + e) * WL + qq))[0];
                  }
@@ -761,6 +774,188 @@ struct LaneT {
         return true;
     }
 
+    // ------------------------------------------------------------------ the set-up from a guess (WARM builds)
+    // The guess of the wave's problems (QPPools::guess_x / _y / _sb / _sc: x, y = [bounds; constraints] and the two working sets,
+    // member-major like the results; any of them absent), HBM -> slots 0 .. of the tableau's space -> my registers xv / yv / yc / sv / sc.
+    // The space is free here: setup_warm builds the tableau of the empty working set by itself. A full wave of 16-byte aligned
+    // pools moves 16 bytes per lane (the reverse of put_pairs / put_quads), any other wave element by element. In a hot start
+    // with new matrices the pools ARE the result pools: the wave reads its members' ranges here and writes them at the end
+    template <int CH> __device__ __forceinline__ void get_quads(const int *src, int n, int lane, ldouble *T, int s0) const {
+        typedef __attribute__((address_space(3))) int lint;
+        Walk wk = walk<4>(n, lane);
+        const int4 *s4 = reinterpret_cast<const int4 *>(src) + lane;
+        SFOR(c, (CH + 3) / 4, if (4 * c < n) {
+                 if (c * WL + lane < 16 * n) {
+                     const int4 v4 = s4[c * WL];
+                     const int v[4] = {v4.x, v4.y, v4.z, v4.w};
+                     int qq = wk.qq, e = wk.e;
+                     SFOR(u, 4, ((lint *)(T + (s0 + e) * WL + qq))[0] = v[u];
+                          const bool wrap = e + 1 == n; e = wrap ? 0 : e + 1; qq = wrap ? qq + 1 : qq;);
+                 }
+                 next_group(wk, n);
+             });
+    }
+    template <int CH, class TV> __device__ __forceinline__ void get_block(const TV *src, int n, int cnt, int lane, ldouble *T, int s0) const {
+        typedef __attribute__((address_space(3))) int lint;
+        const float rn = 1.0f / (float)n;
+        TV w[CH];
+        SFOR(t, CH, const int m = t * WL + lane; if (t < n) w[t] = src[m < cnt ? m : cnt - 1];);
+        SFOR(t, CH, if (t < n) {
+                 const int m = t * WL + lane;
+                 const int qq = (int)(((float)m + 0.5f) * rn), e = m - qq * n;
+                 if (m < cnt) {
+                     if constexpr (sizeof(TV) == 8) T[(s0 + e) * WL + qq] = w[t];
+                     else ((lint *)(T + (s0 + e) * WL + qq))[0] = w[t];
+                 }
+             });
+    }
+    __device__ __forceinline__ void take_guess(const QPPools &P, long long q0, int lane, int nqw, ldouble *T) {
+        typedef const __attribute__((address_space(3))) int clint;
+        constexpr int SX = 0, SY = MV, SB = 2 * MV + MC, SW = 3 * MV + MC;
+        static_assert(SW + MC <= NT, "the guess passes through the tableau's slots");
+        const int nY = nV + nC;
+        const bool hx = P.guess_x != nullptr, hy = P.guess_y != nullptr, hb = P.guess_sb != nullptr, hc = P.guess_sc != nullptr && nC > 0;
+        wave_sync();           // (every lane is through with what the staging left in these slots)
+        if (nqw == WL && (((size_t)P.guess_x | (size_t)P.guess_y | (size_t)P.guess_sb | (size_t)P.guess_sc) & 15) == 0) {
+            const int pp = pair_of(lane);
+            double wx[MV], wy[MV + MC];
+            if (hx) BYPARITY(nV, load_pairs<MV, EV>(P.guess_x + q0 * nV, nV, pp, wx););
+            if (hy) BYPARITY(nY, load_pairs<MV + MC, EV>(P.guess_y + q0 * nY, nY, pp, wy););
+            if (hb) get_quads<MV>(P.guess_sb + q0 * nV, nV, lane, T, SB);
+            if (hc) get_quads<MC>(P.guess_sc + q0 * nC, nC, lane, T, SW);
+            if (hx) BYPARITY(nV, drop_pairs<MV, EV>(T, SX, nV, pp, walk<2>(nV, pp), wx););
+            if (hy) BYPARITY(nY, drop_pairs<MV + MC, EV>(T, SY, nY, pp, walk<2>(nY, pp), wy););
+        } else {
+            if (hx) get_block<MV>(P.guess_x + q0 * nV, nV, nqw * nV, lane, T, SX);
+            if (hy) get_block<MV + MC>(P.guess_y + q0 * nY, nY, nqw * nY, lane, T, SY);
+            if (hb) get_block<MV>(P.guess_sb + q0 * nV, nV, nqw * nV, lane, T, SB);
+            if (hc) get_block<MC>(P.guess_sc + q0 * nC, nC, nqw * nC, lane, T, SW);
+        }
+        wave_sync();
+        // (a lane beyond the batch takes the last problem's guess, as it took its data; slots beyond the sizes: neutral values)
+        const ldouble *S = T + (lane < nqw ? lane : nqw - 1);
+        SFOR(l, MV, const bool v = l < nV;
+             const double a0 = S[(SX + l) * WL], a1 = S[(SY + l) * WL]; const int s0 = ((clint *)(S + (SB + l) * WL))[0];
+             xv[l] = (hx && v) ? a0 : 0.0; yv[l] = (hy && v) ? a1 : 0.0; sv[l] = v ? (hb ? s0 : 0) : -1;);
+        SFOR(i, MC, const bool c = i < nC;
+             const double a1 = S[(SY + (c ? nV + i : 0)) * WL]; const int s0 = ((clint *)(S + (SW + i) * WL))[0];
+             yc[i] = (hy && c) ? a1 : 0.0; sc[i] = (hc && c) ? s0 : 0;);
+        wave_sync();           // (every lane has read its slots: the space is the tableau's again)
+    }
+    // sum of u_v^2 over the free variables; sum of a_v^2 over them for row `arow` of A
+    __device__ __forceinline__ void free_norms(const double (&u)[N], int arow, double &pn2, double &na2) const {
+        double s1 = 0.0, s2 = 0.0;
+        SFOR(k, MV, const bool fr = (fmask >> k) & 1; const double a = As(arow, k);
+             const double p1 = fma(u[k], u[k], s1), n1 = fma(a, a, s2);
+             s1 = fr ? p1 : s1; s2 = fr ? n1 : s2;);
+        pn2 = s1; na2 = s2;
+    }
+    // G for a guessed working set, from G = -K: the pending free variables (mask pf) and guessed active constraints (mask pa) enter S
+    // by principal pivots, in the order and with the thresholds of qp_tiny.hip's warm_pivots: single pivots of the right sign first
+    // (a variable with curvature, a constraint independent of S; slot by slot, ONE text for both), then 2 x 2 blocks (variable,
+    // constraint) with an indefinite block. Variables left over: no positive definite reduced Hessian (false). Constraints left
+    // over: dependent on the others, they stay out (pa returns what was skipped). The slot counters are the wave's, the masks a lane's
+    __device__ __forceinline__ bool warm_pivots(int pf, int &pa) {
+        for (int round = 0; round < 2 * N && (pf | pa) != 0; round++) {
+            bool progress = false;
+#pragma unroll 1
+            for (int q = 0; q < MV + MC; q++) {
+                const bool isc = q >= MV;
+                const int i = isc ? q - MV : 0;
+                if (!(((isc ? pa >> i : pf >> q) & 1) != 0)) continue;
+                // (the tests that need no row first: a slot that stays out costs one LDS round trip, or none)
+                if (isc && !(nFR() - nAC() > 0)) continue;
+                const double pi = Gd(q, q);
+                if (!isc && !(-pi > 1e-8 * hscale)) continue;
+                double u[N];
+                fetch_row(q, u);
+                bool take = true;
+                if (isc) {
+                    double pn2, na2;
+                    free_norms(u, i, pn2, na2);
+                    take = na2 > 0.0 && hscale * hscale * pn2 > 1e-18 * na2 && pi * hscale > 1e-10 * na2;
+                }
+                if (take) {
+                    pivot1(u, q, 1.0, pi);
+                    if (isc) { amask |= 1 << i; pa &= ~(1 << i); } else { fmask |= 1 << q; pf &= ~(1 << q); }
+                    progress = true;
+                }
+            }
+            if (!progress && pf != 0 && pa != 0) {
+#pragma unroll 1
+                for (int vi = 0; vi < MV * MC; vi++) {
+                    const int v = vi / MC, i = vi - v * MC;
+                    if (progress || !((pf >> v) & 1) || !((pa >> i) & 1)) continue;
+                    const double pp = Gd(v, v), qq = Gd(MV + i, MV + i), pq = Gd(v, MV + i);
+                    const double det = pp * qq - pq * pq;
+                    if (det < 0.0 && -det > 1e-10 * fmax(fabs(pp * qq), pq * pq) && pq * pq > 1e-16 * hscale * hscale) {
+                        double uv[N], ui[N];
+                        fetch_row(v, uv); fetch_row(MV + i, ui);
+                        const double rd = recip(det);
+                        pivot2(uv, ui, v, 1.0, MV + i, 1.0, qq * rd, -pq * rd, pp * rd);
+                        fmask |= 1 << v; amask |= 1 << i; pf &= ~(1 << v); pa &= ~(1 << i);
+                        progress = true;
+                    }
+                }
+            }
+            if (!progress) break;
+        }
+        return pf == 0;
+    }
+    // EngineT::setup of qp_tiny.hip for a lane that holds all slots: the same decisions in the same order. The guess waits in
+    // xv / yv / yc / sv / sc (take_guess); have_*: the parts of it this lane takes (none of them: the cold start, x = 0, y = 0,
+    // every variable on a finite bound, lower first). false: the guess gives no positive definite reduced Hessian (the caller
+    // falls back to the cold start)
+    __device__ __forceinline__ bool setup_warm(bool have_x0, bool have_y0, bool have_gb, bool have_gc, bool c_from_y0) {
+        status = QPS_PREPARINGAUXILIARYQP;
+        infeasible = unbounded = 0;
+        int pf = 0;
+        SFOR(l, MV, const bool v = l < nV;
+             xv[l] = (have_x0 && v) ? xv[l] : 0.0; yv[l] = (have_y0 && v) ? yv[l] : 0.0;
+             const int sx = xv[l] <= loN[l] + RSQP_BOUND_TOLERANCE ? -1 : (xv[l] >= upN[l] - RSQP_BOUND_TOLERANCE ? 1 : 0);
+             const int sy = yv[l] > RSQP_EPS ? -1 : (yv[l] < -RSQP_EPS ? 1 : 0);
+             int s = have_gb ? sv[l] : (have_x0 ? sx : (have_y0 ? sy : -1));
+             if (s == -1 && loN[l] <= -RSQP_INFTY) s = (upN[l] < RSQP_INFTY && !have_x0 && !have_gb) ? 1 : 0;
+             if (s == 1 && upN[l] >= RSQP_INFTY) s = 0;
+             sv[l] = v ? s : -1;
+             pf |= (v && s == 0) ? 1 << l : 0;);
+        SFOR(i, MC, yc[i] = (have_y0 && i < nC) ? yc[i] : 0.0;);
+        g_from_K();
+        fmask = amask = 0;
+        // A x of the guess and the constraints' sides (qpOASES: from the guess, else from y0, else from A x0)
+        double gyx[MV], axx[MC], hxx[MV];
+        exact_products(gyx, axx, hxx);           // (x = 0, y = 0: every product is +0, what qp_tiny.hip sets without forming them)
+        int pa = 0;
+        SFOR(i, MC, const bool c = i < nC;
+             ax[i] = c ? axx[i] : 0.0;
+             const int sy = yc[i] > RSQP_EPS ? -1 : (yc[i] < -RSQP_EPS ? 1 : 0);
+             const int sx = ax[i] <= cloN[i] + RSQP_BOUND_TOLERANCE ? -1 : (ax[i] >= cupN[i] - RSQP_BOUND_TOLERANCE ? 1 : 0);
+             int sgc = 0;
+             if (have_gc) sgc = sc[i];
+             else if (have_y0 && (!have_x0 || c_from_y0)) sgc = sy;
+             else if (have_x0) sgc = sx;
+             if (sgc == -1 && cloN[i] <= -RSQP_INFTY) sgc = 0;
+             if (sgc == 1 && cupN[i] >= RSQP_INFTY) sgc = 0;
+             if (!c) sgc = 0;
+             sc[i] = sgc;
+             pa |= sgc != 0 ? 1 << i : 0;);
+        if (!warm_pivots(pf, pa)) return false;
+        SFOR(i, MC, sc[i] = ((pa >> i) & 1) ? 0 : sc[i];);          // (what is left in pa was dependent: it stays out)
+        // multipliers: zero when inactive, clipped to the sign their side requires
+        SFOR(l, MV, const bool z = sv[l] == 0 || (sv[l] == -1 && yv[l] < 0.0) || (sv[l] == 1 && yv[l] > 0.0); yv[l] = z ? 0.0 : yv[l];);
+        SFOR(i, MC, const bool z = sc[i] == 0 || (sc[i] == -1 && yc[i] < 0.0) || (sc[i] == 1 && yc[i] > 0.0); yc[i] = z ? 0.0 : yc[i];);
+        // gradient of the auxiliary QP from stationarity, its limits around the iterate
+        exact_products(gyx, axx, hxx);
+        SFOR(l, MV, gy[l] = gyx[l]; g[l] = gyx[l] + yv[l];
+             lo[l] = sv[l] == -1 ? xv[l] : fmin(loN[l], xv[l] - RSQP_BOUND_RELAXATION);
+             up[l] = sv[l] == 1 ? xv[l] : fmax(upN[l], xv[l] + RSQP_BOUND_RELAXATION);
+             if (l >= nV) { lo[l] = 0.0; up[l] = 0.0; });
+        SFOR(i, MC, loA[i] = sc[i] == -1 ? ax[i] : fmin(cloN[i], ax[i] - RSQP_BOUND_RELAXATION);
+             upA[i] = sc[i] == 1 ? ax[i] : fmax(cupN[i], ax[i] + RSQP_BOUND_RELAXATION););
+        status = QPS_AUXILIARYQPSOLVED;
+        return true;
+    }
+
     // ------------------------------------------------------------------ one working-set change
     // kind 1 constraint idx leaves | 2 bound of idx leaves | 3 constraint idx enters at `side` | 4 variable idx gets fixed at `side`
     // (style of the slot passes here and in homotopy(): every arm of a choice is computed first, then selected -- plain selects
@@ -1093,20 +1288,26 @@ struct LaneT {
 };
 
 // persistent state of a problem between solves (hot starts): the layout qp_tiny.hip keeps in the problem's state block. This
-// kernel only WRITES it (KEEP): every hot start of a batch -- new vectors, new matrices, warm re-initialisation -- runs on the 8-lane
-// kernel, which continues from what either kernel left:
+// kernel only WRITES it (KEEP): a hot start on new vectors runs on the 8-lane kernel, which continues from what either kernel left;
+// a hot start with new matrices and a warm re-initialisation read no stored tableau and run there too, or in the WARM builds here:
 // [N x N tableau, both triangles][6 fields x 8 variable slots: x g lo up gy y][4 fields x 8 constraint slots: A x, loA, upA, y][G_ll (8)]
 // [G_{8+l,8+l} (8)][ints: sv (8), sc (8), status, masks, magic, pivots since the tableau was built from the data]
-// (Hot starts were built for this mapping as well -- state block -> LDS -> registers, the guess of a hot start with new matrices
-// turned into a tableau by single and 2 x 2 pivots -- and matched the CPU restatement's hot-start sequences in every test; they were 2-3 x
-// SLOWER than the 8-lane kernel (0.23 / 0.25 ms against 0.097 / 0.13 ms for 65 536 members): 1.6 KB of state per problem each way
-// with one wave per SIMD to hide the round trips, 100-144 KB of code, 340-960 registers spilled to scratch. Removed.)
+// (Hot starts that READ this block were built for this mapping once -- state block -> LDS -> registers, every mode in one kernel --
+// and were 2-3 x slower than the 8-lane kernel (0.23 / 0.25 ms against 0.097 / 0.13 ms for 65 536 members): 1.6 KB of state per
+// problem each way with one wave per SIMD to hide the round trips, 100-144 KB of code, 340-960 registers spilled to scratch. Removed;
+// the WARM builds take 26 values per problem from the result pools instead: DESIGN.md 4.3b.)
 constexpr int LANE_TINY_MAGIC = 0x7a11e;
 
 // the kernel's body; SHV x SHC: the shape as constants (lane_qp_shape_kernel), or -1: run-time words (lane_qp_kernel)
-template <int MC, bool KEEP, bool UNI, int HB, int SHV, int SHC>
+// WARM: the build for hot starts with new matrices (mode 2) and warm re-initialisations (mode 3) of a batch that keeps its state.
+// Neither reads the stored tableau: the guess is x, y and the working sets (mode 2: the batch's own result pools, dense and
+// member-major, 26 values for 8 x 2; mode 3: the warm-start pools), the tableau is built for it from the new matrices by pivots
+// (setup_warm), and the homotopy is the cold start's. The call shape is the launch's (QPPools::guess_mode) or, with
+// QPPools::member_mode, a lane's own word: < 0 the member is not in the launch, 0 cold, 2, 3 (never 1: rsqp_plan_lane_fits)
+template <int MC, bool KEEP, bool UNI, int HB, int SHV, int SHC, bool WARM = false>
 __device__ __forceinline__ void lane_qp_body(const QPPools &P, int nq, int maxWSR) {
     static_assert(UNI || HB == MV, "the block build serves one-pattern batches");
+    static_assert(!WARM || (KEEP && SHV < 0), "a hot start continues a batch that keeps its state; no full-shape build of it");
     // the pivots' chunks (sweep_triangle): 14 entries for pivot1, 6 for pivot2 (which holds 40 doubles of vectors beside them) in
     // the headline build; with the state kept or H in full every chunking tried spilled vector registers, so those go pair by pair
     constexpr bool CHUNKS = !KEEP && HB < MV;
@@ -1121,7 +1322,7 @@ __device__ __forceinline__ void lane_qp_body(const QPPools &P, int nq, int maxWS
     // changes of every headline member: a constraint enters by an exchange with a bound) and 2. Kinds 4 and 1 stay on the text by
     // lane: 14 KB more of it, and the headline batch could not tell the builds apart
     constexpr int VOTE = (CHUNKS && SHV >= 0) ? (1 | 1 << 2 | 1 << 3) : 0;
-    typedef LaneT<MC, HB, CHUNKS ? 14 : 2, CHUNKS ? 6 : 2, ROLES, SHV, SHC, VOTE> ENG;
+    typedef LaneT<MC, HB, CHUNKS ? 14 : 2, CHUNKS ? 6 : 2, ROLES, SHV, SHC, VOTE, WARM> ENG;
     constexpr int N = ENG::N;
     // (+ the staging table: 32 ints; in the ordered build it lies in the first of the spare slots the vectors pass through)
     constexpr int LDSD = (ENG::NT + ENG::NA) * WL + (ORDERED ? ENG::SPV * WL : 16);
@@ -1141,7 +1342,55 @@ __device__ __forceinline__ void lane_qp_body(const QPPools &P, int nq, int maxWS
     long long &tlast = E.tlast;
 #endif
     int rcode = RET_OK, nWSR = 0, setup_pivots = 0;
-    if constexpr (ORDERED) {
+    bool run = true;                       // WARM: my member is in the launch
+    unsigned long long live = ~0ull;       // ... and bit j: the member of lane j is (the wave's stores leave the others' ranges alone)
+    if constexpr (WARM) {
+        // my call shape (a lane beyond the batch runs beside the last member, as everywhere). A member without a solved or stopped
+        // QP behind it has nothing to continue from: cold, as qp_tiny.hip decides from the state word (the status pool holds the same)
+        const int qown = q0 + (lane < nqw ? lane : nqw - 1);
+        int mode = P.member_mode ? P.member_mode[qown] : P.guess_mode;
+        run = mode >= 0;
+        live = __builtin_amdgcn_ballot_w64(run);
+        const int prev = mode == 2 ? P.status[qown] : QPS_SOLVED;       // (asked for here, looked at behind the staging)
+        // staging as in the cold builds; the guess behind it, through the tableau's slots (setup_warm builds the tableau again)
+        typename ENG::Inflight F;
+        bool early = false;
+        if constexpr (ORDERED) early = E.ordered_wave(P, nqw);
+        if constexpr (ORDERED) { if (early) { E.stage_matrices(P, q0, lane, T, F); E.take_bounds(T, lane, F); } }
+        if (!early) E.template stage<UNI>(P, q0, lane, nqw, T);
+        E.take_guess(P, q0, lane, nqw, T);
+        if (mode == 2 && prev % 100 == QPS_NOTINITIALISED) mode = 0;
+        LSTAMP(0);
+        const bool bad = run && E.bounds_inconsistent();
+        if (bad || !run) {
+            // qpOASES areBoundsConsistent: infeasible before any change. A hot start keeps the stored iterate, an init reports the
+            // zero iterate and the empty working set (qp_tiny.hip). A member that sits out: zeros, of which nothing is stored
+            if (bad) { E.infeasible = 1; rcode = RET_INFEASIBLE; }
+            if (mode != 2) {
+                SFOR(l, MV, E.xv[l] = 0.0; E.yv[l] = 0.0; E.sv[l] = 0;);
+                SFOR(i, MC, E.yc[i] = 0.0; E.sc[i] = 0;);
+            }
+            SFOR(l, MV, E.g[l] = E.gy[l] = 0.0; E.lo[l] = E.up[l] = 0.0;);
+            SFOR(i, MC, E.ax[i] = 0.0; E.loA[i] = E.upA[i] = 0.0;);
+            E.g_from_K();
+        } else {
+            // ONE text of the set-up: the guess of the call shape first, the cold start as the fallback when the guess has no positive
+            // definite reduced Hessian (and for the cold members of the launch)
+            bool hx = mode == 2 || (mode == 3 && P.guess_x != nullptr), hy = mode == 2 || (mode == 3 && P.guess_y != nullptr);
+            bool hg = mode == 2 || (mode == 3 && P.guess_sb != nullptr), hc = mode == 2;
+            bool ok = false;
+            for (int attempt = 0; attempt < 2 && !ok; attempt++) {
+                ok = E.setup_warm(hx, hy, hg, hc, P.reinit_from_y0 != 0);
+                hx = hy = hg = hc = false;
+            }
+            setup_pivots = E.nFR() + E.nAC();
+            if (!ok) rcode = RET_SETUP_FAILED;
+        }
+        LSTAMP(1);
+        if constexpr (ORDERED) { if (early) E.take_g(T, lane, F); }
+        if (run && !bad && rcode == RET_OK) rcode = E.homotopy(maxWSR, nWSR);
+        LSTAMP(2);
+    } else if constexpr (ORDERED) {
         // a full wave of aligned pools: the tableau from A and H while the vectors arrive, the set-up from the bounds while g
         // arrives. The passes of the vectors through LDS are the whole wave's work, so the lanes split (inconsistent bounds,
         // free-variable pivots) only between them
@@ -1188,7 +1437,7 @@ __device__ __forceinline__ void lane_qp_body(const QPPools &P, int nq, int maxWS
     }
     // (the refinement step repairs what the update-only tableau accumulates: with at most 4 pivots there is nothing to repair yet)
     const int pivots = setup_pivots + nWSR;
-    const bool refine = rcode == RET_OK && pivots > 4;
+    const bool refine = run && rcode == RET_OK && pivots > 4;
     // no lane of the wave refines (the headline's members make two pivots): finish() then changes neither x, y nor the working
     // sets, and reads A's dense copy, H's registers and the state, not the slots the results pass through -- the results' stores go
     // out first and the products and the objective run under them. One lane that refines keeps the order for its whole wave
@@ -1203,15 +1452,15 @@ __device__ __forceinline__ void lane_qp_body(const QPPools &P, int nq, int maxWS
         double dg[N];
         SFOR(k, N, dg[k] = E.G[tri(k, k) * WL];);
         E.wave_sync();
-        E.state_put_tableau(sbase, P.uni_state, nqw, lane, T);
+        E.state_put_tableau(sbase, P.uni_state, nqw, lane, T, live);
         E.wave_sync();
         E.template tail_put_half<0>(E.G, dg, pivots);
         E.wave_sync();
-        E.state_put_tail_half(sbase, P.uni_state, nqw, lane, T, 0);
+        E.state_put_tail_half(sbase, P.uni_state, nqw, lane, T, 0, live);
         E.wave_sync();
         E.template tail_put_half<1>(E.G, dg, pivots);
         E.wave_sync();
-        E.state_put_tail_half(sbase, P.uni_state, nqw, lane, T, 1);
+        E.state_put_tail_half(sbase, P.uni_state, nqw, lane, T, 1, live);
         LSTAMP(15);
     }
     // ---- results (x, y = [bounds; constraints], working set, status / nWSR / objective): the member-major vectors leave through the
@@ -1225,7 +1474,8 @@ __device__ __forceinline__ void lane_qp_body(const QPPools &P, int nq, int maxWS
         SFOR(l, MV, if (l < nV) E.G[(SY + l) * WL] = E.yv[l];);
         SFOR(i, MC, if (i < nC) E.G[(SY + nV + i) * WL] = E.yc[i]; ((lint *)(E.G + (SW + i) * WL))[0] = E.sc[i];);
         E.wave_sync();
-        if (nqw == WL && (((size_t)P.x | (size_t)P.y | (size_t)P.ws_b | (size_t)P.ws_c) & 15) == 0) {
+        // (WARM: a wave with a member that is not in the launch stores element by element, each element if its member is in)
+        if (nqw == WL && (!WARM || live == ~0ull) && (((size_t)P.x | (size_t)P.y | (size_t)P.ws_b | (size_t)P.ws_c) & 15) == 0) {
             // (a full wave: 16 bytes per lane, as it was staged)
             const int pp = ENG::pair_of(lane);
             BYPARITY(nV, E.template put_pairs<MV, EV>(P.x + (long long)q0 * nV, nV, pp, T, SX););
@@ -1233,17 +1483,17 @@ __device__ __forceinline__ void lane_qp_body(const QPPools &P, int nq, int maxWS
             E.template put_quads<MV>(P.ws_b + (long long)q0 * nV, nV, lane, T, SB);
             if (nC > 0) E.template put_quads<MC>(P.ws_c + (long long)q0 * nC, nC, lane, T, SW);
         } else {
-        E.template put_block<MV>(P.x + (long long)q0 * nV, nV, nqw * nV, lane, T, SX);
-        E.template put_block<MV + MC>(P.y + (long long)q0 * (nV + nC), nV + nC, nqw * (nV + nC), lane, T, SY);
-        E.template put_block<MV>(P.ws_b + (long long)q0 * nV, nV, nqw * nV, lane, T, SB);
-        if (nC > 0) E.template put_block<MC>(P.ws_c + (long long)q0 * nC, nC, nqw * nC, lane, T, SW);
+        E.template put_block<MV>(P.x + (long long)q0 * nV, nV, nqw * nV, lane, T, SX, live);
+        E.template put_block<MV + MC>(P.y + (long long)q0 * (nV + nC), nV + nC, nqw * (nV + nC), lane, T, SY, live);
+        E.template put_block<MV>(P.ws_b + (long long)q0 * nV, nV, nqw * nV, lane, T, SB, live);
+        if (nC > 0) E.template put_block<MC>(P.ws_c + (long long)q0 * nC, nC, nqw * nC, lane, T, SW, live);
         }
     }
     if constexpr (ORDERED) {
         LSTAMP(19);
         if (results_first) obj = E.finish(false);
     }
-    if (q < nq) {
+    if (q < nq && run) {
         const int st = E.status;
         P.status[q] = E.infeasible ? 100 + st : (E.unbounded ? 200 + st : st);
         P.ret[q] = rcode; P.nwsr[q] = nWSR; P.nflips[q] = E.nflips; P.obj[q] = obj;
@@ -1251,9 +1501,9 @@ __device__ __forceinline__ void lane_qp_body(const QPPools &P, int nq, int maxWS
     LSTAMP(4);
 }
 
-template <int MC, bool KEEP, bool UNI, int HB>
+template <int MC, bool KEEP, bool UNI, int HB, bool WARM = false>
 __global__ void __launch_bounds__(WL) lane_qp_kernel(QPPools P, int nq, int maxWSR) {
-    lane_qp_body<MC, KEEP, UNI, HB, -1, -1>(P, nq, maxWSR);
+    lane_qp_body<MC, KEEP, UNI, HB, -1, -1, WARM>(P, nq, maxWSR);
 }
 // the full-shape build: every member NV x NC (the plan's word, SmallPlan::lane_shape); the ragged last wave of such a batch runs it too
 template <int MC, bool KEEP, bool UNI, int HB, int NV, int NC>
@@ -1274,6 +1524,16 @@ hipError_t rsqp_launch_lane_qp(const SmallPlan &pl, const QPPools &p, int nq, in
         return hipGetLastError();
     }
     if (pl.lane_shape != 0) return hipErrorInvalidValue;
+    if (pl.lane_warm) {
+        // hot starts with new matrices / warm re-initialisations (rsqp_plan_lane_fits): the builds that keep the state
+        switch (pl.mc * 1000 + pl.keep * 100 + pl.uni * 10 + pl.hb) {
+        case 2114: hipLaunchKernelGGL((lane_qp_kernel<2, true, true, 4, true>), grid, block, 0, stream, p, nq, maxWSR); break;
+        case 2118: hipLaunchKernelGGL((lane_qp_kernel<2, true, true, 8, true>), grid, block, 0, stream, p, nq, maxWSR); break;
+        case 2108: hipLaunchKernelGGL((lane_qp_kernel<2, true, false, 8, true>), grid, block, 0, stream, p, nq, maxWSR); break;
+        default: return hipErrorInvalidValue;
+        }
+        return hipGetLastError();
+    }
     switch (pl.mc * 1000 + pl.keep * 100 + pl.uni * 10 + pl.hb) {
     case 2114: hipLaunchKernelGGL((lane_qp_kernel<2, true, true, 4>), grid, block, 0, stream, p, nq, maxWSR); break;
     case 2014: hipLaunchKernelGGL((lane_qp_kernel<2, false, true, 4>), grid, block, 0, stream, p, nq, maxWSR); break;

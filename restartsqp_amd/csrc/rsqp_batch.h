@@ -137,6 +137,11 @@ struct rsqp_batch {
     // members that are taken over; handed_valid: the last call was such a call (else rsqp_batch_get_handover reports zeros)
     bool handover = false, handed_valid = false;
     DevBuf<int> handed;
+    // rsqp_batch_set_lane_warm: hot starts with new matrices and warm re-initialisations of a batch the lane-per-problem kernel takes
+    // go to its WARM builds (lane_warm_ok of rsqp_batch.hip says which launches). results_foreign: the result pools may not describe
+    // the members' stored states, which such a hot start assumes -- rsqp_batch_set_results has overwritten them, or a hand-over launch
+    // has run, since the last call whose first launch ran everybody without one (launch_batch)
+    bool lane_warm = false, results_foreign = false;
     int qp_maxiter = 1000;                // rsqp_batch_set_options
     bool mats_updated = false;            // rsqp_batch_set_matrix_values since the last optimize call (Update_A / Update_H of everybody)
     bool opt_started = false;             // an rsqp_batch_optimize_qp has run: members are in different states from here on
@@ -156,7 +161,10 @@ namespace rsqp_batch_units {
 // rsqp_batch.hip
 QPPools pools_of(rsqp_batch *b, bool lp);
 int batch_family(const rsqp_batch *b, const QPPools &p, bool lp);
-int launch_batch(rsqp_batch *b, QPPools &p, int mode, int max_nWSR, bool first, bool lp);
+// warm: the launch may take a WARM build of the lane-per-problem kernel (lane_warm_ok, and what the caller knows of the call)
+int launch_batch(rsqp_batch *b, QPPools &p, int mode, int max_nWSR, bool first, bool lp, bool warm = false);
+// the batch's side of SmallFacts::lane_warm: the switch is on, nothing is handed over, the result pools are the batch's own
+bool lane_warm_ok(const rsqp_batch *b);
 // where a solve / optimize call begins: the hand-over flags and their count cleared (on the stream) when the switch is on
 int begin_handover(rsqp_batch *b);
 int ensure_opt(rsqp_batch *b);

@@ -263,9 +263,10 @@ int ensure_warm_pools(rsqp_batch *b) {
 
 // the plan of a launch on this batch (rsqp_small_plan.h): the batch remembers by itself when a launch keeps no state.
 // handover: the plan of the same launch without the hs071-scale tableau kernels, as rsqp_solve plans its retry on a handle
-static SmallPlan plan_of(const rsqp_batch *b, const QPPools &p, int mode, bool lp, bool handover = false) {
+static SmallPlan plan_of(const rsqp_batch *b, const QPPools &p, int mode, bool lp, bool handover = false, bool warm = false) {
     SmallFacts f = rsqp_small_facts(p, b->hbm, b->state_engine);
     f.skip_mark = 1;
+    f.lane_warm = (warm && !lp && !handover) ? 1 : 0;
     SmallKnobs k = knobs_of(b, lp);
     if (handover && k.no_tiny == 0) k.no_tiny = 1;
     return rsqp_plan_small_launch(k, f, b->nq, b->nVmax, b->nCmax, b->mat_bytes_max, mode);
@@ -274,10 +275,26 @@ static SmallPlan plan_of(const rsqp_batch *b, const QPPools &p, int mode, bool l
 // layout a launch on this batch leaves in the state blocks: 3 HBM-resident, 1 hs071-scale tableau (+ lane-per-problem), 0 LDS-resident
 int batch_family(const rsqp_batch *b, const QPPools &p, bool lp) { return plan_of(b, p, RSQP_MODE_COLD, lp).state_family; }
 
+// a handed member leaves a state block the result pools do not describe, and pools rsqp_batch_set_results has written are not the
+// batch's own answer: either way a hot start with new matrices must read the stored state, which the 8-lane kernel does
+bool lane_warm_ok(const rsqp_batch *b) { return b->lane_warm && !b->handover && !b->results_foreign; }
+
 // one solve launch of the whole batch (p.member_mode: of the members it names). first: the launch rsqp_batch_get_last_kernel reports;
 // lp: a launch of rsqp_batch_optimize_lp (pools_of, knobs_of)
-int launch_batch(rsqp_batch *b, QPPools &p, int mode, int max_nWSR, bool first, bool lp) {
-    const SmallPlan pl = plan_of(b, p, mode, lp);
+int launch_batch(rsqp_batch *b, QPPools &p, int mode, int max_nWSR, bool first, bool lp, bool warm) {
+    const SmallPlan pl = plan_of(b, p, mode, lp, false, warm);
+    if (pl.lane_warm) {
+        // the guess of the WARM builds (QPPools::guess_*). A warm re-initialisation: what the caller gave; a hot start with new
+        // matrices and per-member modes: the result pools -- the plan kernel of rsqp_batch_optimize_qp has copied a mode-3
+        // member's x, y and bound statuses from there into the warm-start pools, so they hold the same values
+        const bool reinit = !p.member_mode && pl.mode == RSQP_MODE_WARM_REINIT;
+        p.guess_x = reinit ? p.x0 : b->x.p; p.guess_y = reinit ? p.y0 : b->y.p; p.guess_sb = reinit ? p.guess_b : b->ws_b.p;
+        p.guess_sc = reinit ? nullptr : b->ws_c.p;
+        p.guess_mode = pl.mode;
+    }
+    // the first launch of a call writes the pools of every member that takes part: with nobody sitting out they are the batch's own
+    // answer again (a hand-over launch behind it says otherwise, below)
+    if (first && !(p.member_mode && b->sitters)) b->results_foreign = false;
     // every member of the launch has a state of this family now; one that sits out keeps what it had. A launch that keeps no state
     // leaves no mark either: the record here says so
     const int fam = pl.state_family;
@@ -291,6 +308,7 @@ int launch_batch(rsqp_batch *b, QPPools &p, int mode, int max_nWSR, bool first, 
     if (b->handover && (pl.family == 1 || pl.family == 2)) {
         e = rsqp_launch_small_handover(knobs_of(b, lp), plan_of(b, p, mode, lp, true), pl, p, b->nq, max_nWSR, b->handed.p, b->stream);
         if (e != hipSuccess) return fail(RSQP_ERR_DEVICE, std::string("hand-over launch: ") + hipGetErrorString(e));
+        b->results_foreign = true;   // (a member taken over: results of the null-space kernel, a state block that says "not initialised")
     }
     return RSQP_OK;
 }
@@ -338,7 +356,9 @@ extern "C" int rsqp_batch_solve(rsqp_batch *b, int mode, int max_nWSR) {
     int rc = begin_handover(b);
     if (rc != RSQP_OK) return rc;
     if (!b->timing) HIPCHK(hipEventRecord(b->ev0, b->stream));
-    if ((rc = launch_batch(b, p, mode, max_nWSR, true, false)) != RSQP_OK) return rc;
+    // (a warm re-initialisation reads the warm-start pools, whoever wrote the result pools)
+    const bool warm = mode == RSQP_MODE_WARM_REINIT ? (b->lane_warm && !b->handover) : lane_warm_ok(b);
+    if ((rc = launch_batch(b, p, mode, max_nWSR, true, false, warm)) != RSQP_OK) return rc;
     b->cert_lp = false;
     if (!b->timing) HIPCHK(hipEventRecord(b->ev1, b->stream));
     return RSQP_OK;
@@ -358,6 +378,16 @@ extern "C" int rsqp_batch_set_keep_state(rsqp_batch *b, int keep) {
     if (!b) return fail(RSQP_ERR_ARG, "null batch");
     b->keep_state = keep != 0;
     return RSQP_OK;
+}
+
+extern "C" int rsqp_batch_set_lane_warm(rsqp_batch *b, int on) {
+    if (!b) return fail(RSQP_ERR_ARG, "null batch");
+    b->lane_warm = on != 0;
+    return RSQP_OK;
+}
+extern "C" int rsqp_batch_get_lane_warm(const rsqp_batch *b) {
+    if (!b) return fail(RSQP_ERR_ARG, "null batch");
+    return b->lane_warm ? 1 : 0;
 }
 
 extern "C" int rsqp_batch_set_handover(rsqp_batch *b, int on) {
@@ -439,6 +469,7 @@ extern "C" int rsqp_batch_set_results(rsqp_batch *b, const double *x, const doub
     if (y) HIPCHK(b->y.upload(y, b->sumV + b->sumC));
     if (ws_b) HIPCHK(b->ws_b.upload(ws_b, b->sumV));
     if (ws_c) HIPCHK(b->ws_c.upload(ws_c, b->sumC));
+    if (x || y || ws_b || ws_c) b->results_foreign = true;
     return RSQP_OK;
 }
 

@@ -142,9 +142,9 @@ int begin_optimize(rsqp_batch *b, int kind) {
 }
 
 // the solve launch behind a plan kernel: every member starts as word `word` of its opt block says (QPPools::member_mode)
-int launch_members(rsqp_batch *b, QPPools &p, int word, int mode, int max_nWSR, bool first, bool lp) {
+int launch_members(rsqp_batch *b, QPPools &p, int word, int mode, int max_nWSR, bool first, bool lp, bool warm = false) {
     p.member_mode = b->opt.p + (size_t)word * b->nq;
-    return launch_batch(b, p, mode, max_nWSR, first, lp);
+    return launch_batch(b, p, mode, max_nWSR, first, lp, warm);
 }
 
 // what both optimize entry points do behind their last launch: the second event, the call's one wait, the members' counts
@@ -294,7 +294,10 @@ extern "C" int rsqp_batch_optimize_qp(rsqp_batch *b, int *nWSR_used) {
                            b->state_engine + 1, batch_family(b, p, false) + 1, b->x.p, b->y.p, b->ws_b.p, b->wx0.p, b->wy0.p, b->wgb.p);
         HIPCHK(hipGetLastError());
         p.x0 = b->wx0.p; p.y0 = b->wy0.p; p.guess_b = b->wgb.p;     // the flip: all three (:204-206)
-        rc = launch_members(b, p, OPT_MODE, RSQP_MODE_COLD, b->qp_maxiter, true, false);
+        // with the batch-wide update mark rsqp_dispatch_mode gives every member 0, 2 or 3, never 1 (updated = true), which the host
+        // knows without a look at the device: the launch may go to the lane-per-problem kernel's WARM build
+        // (rsqp_batch_set_lane_warm). Per-member marks alone, the rescue launch and the LP calls stay where they were
+        rc = launch_members(b, p, OPT_MODE, RSQP_MODE_COLD, b->qp_maxiter, true, false, b->mats_updated && lane_warm_ok(b));
     }
     if (rc != RSQP_OK) return rc;
     // (also behind a call nobody took part in: its plan kernel has written -1 into the mode words, which the uniform cold launch

@@ -87,7 +87,14 @@ struct QPPools {
     const int *member_mode;   // non-null (rsqp_batch_optimize_qp): member q starts as member_mode[q] says (0..3 as the `mode` argument of the
                       //    kernels, which is then ignored); a negative value = the member is not in this launch and nothing of it is
                       //    touched. In one launch every mode-3 member has the same warm-start inputs present (x0 / y0 / guess_b are
-                      //    batch-wide pointers). The lane-per-problem kernel never sees such a launch (rsqp_plan_lane_fits)
+                      //    batch-wide pointers). The lane-per-problem kernel takes such a launch in its WARM builds alone, where the host
+                      //    knows that no member's word is 1 (rsqp_plan_lane_fits; rsqp_batch_set_lane_warm)
+    // the WARM builds of the lane-per-problem kernel (qp_lane.hip; set by launch_batch where the plan says SmallPlan::lane_warm): the
+    // guess a member's set-up starts from -- x, y = [bounds; constraints], bound statuses, constraint statuses, member-major like
+    // the results; any of them null, uniform over the launch. A hot start with new matrices: the batch's own result pools (the
+    // kernel reads a wave's members before it writes them); a warm re-initialisation: the warm-start pools, guess_sc null
+    const double *guess_x, *guess_y; const int *guess_sb, *guess_sc;
+    int guess_mode;   // the call shape of such a launch without member_mode: 2 or 3
 };
 
 // optimizeQP's choice of the call shape (src/qpOASESInterface.cpp:150-208) from get_Matrix_change_status (:817-833), stated ONCE for
@@ -170,7 +177,8 @@ long long rsqp_mat_lds_bytes(int nV, int nC, int annz, int hnnz);
 int rsqp_small_qp_fits(int nVmax, int nCmax);
 // qp_tiny.hip: the register-resident tableau kernel for problems of at most 8 variables and 8 constraints
 hipError_t rsqp_launch_tiny_qp(const SmallPlan &pl, const QPPools &p, int nq, int maxWSR, hipStream_t stream);
-// qp_lane.hip: one lane per problem, for cold starts of large one-shape batches of at most 8 x 2
+// qp_lane.hip: one lane per problem, for cold starts of large one-shape batches of at most 8 x 2 (SmallPlan::lane_warm: their hot
+// starts with new matrices and warm re-initialisations)
 hipError_t rsqp_launch_lane_qp(const SmallPlan &pl, const QPPools &p, int nq, int maxWSR, hipStream_t stream);
 // qp_small_hbm.hip: the null-space engines with their images in HBM, one workgroup per problem, for batches beyond
 // rsqp_small_qp_fits (every member of such a batch, the small ones included); members up to RSQP_HBM_MAX_V x RSQP_HBM_MAX_C

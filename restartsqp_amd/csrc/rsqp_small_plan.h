@@ -14,6 +14,10 @@ struct SmallFacts {
     int lane_hblock, uni_hreg;                                  // uni_hreg: != 0.0 or not
     int hbm;              // the batch is HBM-resident (images beyond the LDS of a CU, qp_small_hbm.hip)
     int state_engine;     // family that wrote the stored hot-start state(s): 0 / 1 / 3 as SmallPlan::state_family, < 0 none or mixed
+    // the CALLER's word (launch_batch of rsqp_batch.hip; 0 from rsqp_small_facts and rsqp_describe_small_launch): this launch may take a
+    // WARM build of the lane-per-problem kernel -- the batch's switch is on (rsqp_batch_set_lane_warm), its result pools hold its
+    // own last answer, nothing is handed over, and a launch with member_mode carries no member whose word is 1
+    int lane_warm;
 };
 inline SmallFacts rsqp_small_facts(const QPPools &p, bool hbm, int state_engine) {
     return SmallFacts{p.tiny_ok, p.uniV, p.uniC, p.uni_pat, p.desc != nullptr, p.keep_state, p.skip_mark, p.member_mode != nullptr,
@@ -32,6 +36,8 @@ struct SmallPlan {
     int waves = 0;        // waves per SIMD asked for (W is what the product build instantiates; tools/small_experiment.sh builds more)
     // tiny_qp_kernel<mc, W>; lane_qp_kernel<mc, keep, uni, hb>
     int mc = 0, keep = 0, uni = 0, hb = 0;
+    int lane_warm = 0;    // lane_qp_kernel<mc, keep, uni, hb, WARM = true>: a hot start with new matrices / a warm re-initialisation (mode 2 / 3, or
+                          //   per-member modes 0 / 2 / 3) on the lane-per-problem kernel; the launcher sets QPPools::guess_* (not among the exported words)
     int lane_shape = 0;   // lane_qp_shape_kernel<mc, keep, uni, hb, NV, NC>: NV * 256 + NC of the lane kernel's full-shape build, else 0 (not
                           //   among the exported words: the build FAMILY stays (keep, uni, hb); rsqp_batch_get_lane_shape reports it)
     int first = 0;       // the mid-size tableau kernel goes first (qp_small_g.h): 1 small_qpg_kernel<3, 1, 9, 4>, 2 <2, 2, 8, 8>; 0 no
@@ -63,16 +69,21 @@ inline int rsqp_plan_is_tiny(const SmallKnobs &kn, const SmallFacts &f, int nVma
 // 1 if a launch that is_tiny is served by the lane-per-problem kernel: a cold start of a one-shape batch of at most 8 x 2 with more members
 // (16 384) than 8 lanes per problem hold at a time; no certificate / doorbell of a single-QP handle, no warm re-initialisation
 // inputs. A batch that keeps its state gets it written in the 8-lane kernel's layout; one that does not leaves no mark either
-// (the handle remembers: QPPools::skip_mark)
+// (the handle remembers: QPPools::skip_mark).
+// 2 (the WARM builds): with the caller's word SmallFacts::lane_warm, a batch that keeps its state also brings its hot starts with new
+// matrices (mode 2), its warm re-initialisations (mode 3, whatever inputs are present) and launches with per-member modes. A hot
+// start on new vectors (mode 1) continues from the stored tableau and stays on the 8-lane kernel
 inline int rsqp_plan_lane_fits(const SmallKnobs &kn, const SmallFacts &f, int skip_mark, int nq, int nVmax, int nCmax, int mode) {
     if (kn.lane == 0) return 0;
     // one shape (every member nV x nC); one sparsity pattern (member 0's arrays serve all) or patterns of their own (each lane walks its own)
     if (!(f.uniV >= 1 && f.uniV <= 8 && f.uniC >= 0 && f.uniC <= 2 && nVmax <= 8 && nCmax <= 2 && (f.uni_pat || f.desc))) return 0;
-    if (mode != 0 || f.member_mode || (!f.keep_state && !skip_mark) || f.cert_out || f.done_flag || !f.tiny_ok || f.x0 || f.y0 || f.guess_b) return 0;
+    const bool warm = f.lane_warm && f.keep_state && (f.member_mode || mode == 2 || mode == 3);
+    if (!warm && (mode != 0 || f.member_mode || f.x0 || f.y0 || f.guess_b)) return 0;
+    if ((!f.keep_state && !skip_mark) || f.cert_out || f.done_flag || !f.tiny_ok) return 0;
     // (measured, tools/lane_vs_tiny_sweep.py: a launch of this kernel takes 36 us up to 16 384 problems and 43 us at 65 536 -- one
     //  round of waves either way; the 8-lane kernel holds 16 384 problems at a time: 21 us up to 8 192, 26 us at 16 384, 40 us at
     //  20 480 (second round), 47 us at 32 768, 90 us at 65 536. With the state kept, 65 536 members: 0.075 against 0.132 ms)
-    return nq >= (kn.lane > 0 ? kn.lane : 16385) ? 1 : 0;
+    return nq >= (kn.lane > 0 ? kn.lane : 16385) ? (warm ? 2 : 1) : 0;
 }
 
 // doubles / 16-bit integers of the LDS image of a formulation, as Engine<L, ML, REGV>::image_doubles (qp_small_engine.h) and
@@ -115,7 +126,7 @@ inline SmallPlan rsqp_plan_small_launch(const SmallKnobs &kn, const SmallFacts &
     if (nq <= 0) { pl.empty = 1; return pl; }
     if (rsqp_align16(rsqp_image_bytes(nVmax, nCmax)) > kSmallMaxLds) { pl.invalid = 1; return pl; }
     // hs071-scale problems: the register-resident tableau kernel (qp_tiny.hip) serves every call shape
-    if (tiny && rsqp_plan_lane_fits(kn, f, pl.skip_mark, nq, nVmax, nCmax, mode)) {
+    if (const int lane_fit = tiny ? rsqp_plan_lane_fits(kn, f, pl.skip_mark, nq, nVmax, nCmax, mode) : 0) {
         // the build: H kept as its leading 4 x 4 block, or the full triangle. The block build needs what only a one-pattern launch
         // without regularisation can promise (QPPools::lane_hblock: the host's word on the pattern)
         pl.family = 2;
@@ -123,7 +134,8 @@ inline SmallPlan rsqp_plan_small_launch(const SmallKnobs &kn, const SmallFacts &
         pl.hb = (f.uni_pat && f.lane_hblock == 4 && !f.uni_hreg) ? 4 : 8;
         pl.uni = (pl.hb == 4 || f.uni_pat) ? 1 : 0;
         // the full shape of that kernel, one pattern, H as its block: the build with nV and nC as constants (RSQP_LANE_SHAPE=0: never)
-        if (kn.lane_shape != 0 && f.uniV == 8 && f.uniC == 2 && f.uni_pat && pl.hb == 4) pl.lane_shape = 8 * 256 + 2;
+        pl.lane_warm = lane_fit == 2 ? 1 : 0;
+        if (!pl.lane_warm && kn.lane_shape != 0 && f.uniV == 8 && f.uniC == 2 && f.uni_pat && pl.hb == 4) pl.lane_shape = 8 * 256 + 2;
         pl.grid = (unsigned)((nq + kLaneBlock - 1) / kLaneBlock); pl.block = kLaneBlock;
         return pl;
     }
