@@ -2,6 +2,9 @@
 least one case each (a 32nd, Engine<64, true> at six waves per SIMD, failed its case here and was taken out of the product): the environment switches, the batch and the build the batch must reach. Shared by tests/test_gpu_small_builds.py (every
 case against the oracle on the GPU) and tests/test_small_launch_plan.py (the golden table names the same 31 builds).
 
+qp_lane.hip holds 11 builds by now. The table covers its six cold run-time-shape builds; the two full-shape builds and the three WARM
+builds are covered in tests/test_gpu_lane_shape.py and tests/test_gpu_lane_warm.py (shared pieces: tests/lane_cases.py).
+
 A build is told from its neighbours by the plan words capi.plan_builds projects: ("qp", engine, L, mat_lds, W, shape),
 ("qpg", first), ("tiny", mc, W), ("lane", keep, uni, hb), ("qph", engine).
 

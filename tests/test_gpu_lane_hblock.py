@@ -4,40 +4,27 @@ A batch of one sparsity pattern whose H has no entry outside the leading 4 x 4 b
 variables have no curvature -- runs the block build (rsqp_batch_get_lane_hblock() == 4); every other batch, and every batch under
 RSQP_LANE_HBLOCK=0, runs the full build (8). The block build leaves out only products with structural zeros, so the two give the same
 BITS: np.array_equal on every result. Beside that the bar of test_gpu_lane.py: status, working sets and nWSR exact against the oracle
-and the 8-lane kernel (RSQP_LANE=0), x / y within 1e-9 relative. Batches of 130-200 members: two full waves and a ragged one."""
+and the 8-lane kernel (RSQP_LANE=0), x / y within 1e-9 relative. Batches of 130-200 members: two full waves and a ragged one. The
+launch and the comparisons are tests/lane_cases.py's."""
 import numpy as np
 import pytest
 
 from conftest import oracle_cold
+from lane_cases import (assert_eight_lane_agreement, assert_same_bits, assert_same_solution, continue_hot, hs071_path_batch, lane_cold,
+                        oracle_handles, perturbations, with_H)
 from restartsqp_amd import problems
 from restartsqp_amd.qpdump import QPData, dense_to_csc
-from test_gpu_parity import assert_same_solution
 
 pytestmark = pytest.mark.gpu
 
-FIELDS = ("x", "y", "ws_b", "ws_c", "status", "nWSR", "obj")
 
-
-def cold(capi, monkeypatch, probs, lane="1", hblock=None, keep=False):
-    """one cold start of a fresh batch -> (results, kernel, block size)"""
-    monkeypatch.setenv("RSQP_LANE", lane)
-    if hblock is None:
-        monkeypatch.delenv("RSQP_LANE_HBLOCK", raising=False)
-    else:
-        monkeypatch.setenv("RSQP_LANE_HBLOCK", hblock)
-    b = capi.Batch(probs)
-    b.set_keep_state(keep)
-    b.solve(capi.MODE_COLD, 1000)
-    out = b.results(), b.last_kernel(), b.lane_hblock()
+def cold_closed(capi, monkeypatch, probs, want, **how):
+    """lane_cold on the build `want` (0: the 8-lane kernel), the batch closed -> results"""
+    b, res = lane_cold(capi, monkeypatch, probs, **how)
+    hb = b.lane_hblock()
     b.close()
-    return out
-
-
-def assert_same_bits(ra, rb):
-    assert len(ra) == len(rb)
-    for k, (a, c) in enumerate(zip(ra, rb)):
-        for f in FIELDS:
-            assert np.array_equal(np.asarray(a[f]), np.asarray(c[f])), (k, f, a[f], c[f])
+    assert hb == want, (hb, want)
+    return res
 
 
 def assert_oracle_and_eight_lane(oracle, probs, res, tiny, need_solved=True):
@@ -48,29 +35,19 @@ def assert_oracle_and_eight_lane(oracle, probs, res, tiny, need_solved=True):
         if rc == 0:
             solved += 1
             assert_same_solution(qp, r, n)
-            assert r["nWSR"] == t["nWSR"] and np.array_equal(r["ws_b"], t["ws_b"]) and np.array_equal(r["ws_c"], t["ws_c"])
-            assert np.abs(r["x"] - t["x"]).max() <= 1e-9 * max(1.0, np.abs(t["x"]).max())
-            assert np.abs(r["y"] - t["y"]).max() <= 1e-9 * max(1.0, np.abs(t["y"]).max())
+            assert_eight_lane_agreement(r, t)
     assert not need_solved or solved == len(probs)
     return solved
 
 
-def check_build(capi, oracle, monkeypatch, probs, want, keep=False, need_solved=True):
+def check_build(capi, oracle, monkeypatch, probs, want, keep=False):
     """the batch on the lane kernel (build `want`), against the oracle, the 8-lane kernel and -- block build -- the full build's bits"""
-    res, kern, hb = cold(capi, monkeypatch, probs, keep=keep)
-    assert kern == 2 and hb == want, (kern, hb)
-    tiny, kern0, hb0 = cold(capi, monkeypatch, probs, lane="0", keep=keep)
-    assert kern0 == 1 and hb0 == 0
-    assert_oracle_and_eight_lane(oracle, probs, res, tiny, need_solved)
+    res = cold_closed(capi, monkeypatch, probs, want, keep=keep)
+    tiny = cold_closed(capi, monkeypatch, probs, 0, keep=keep, lane="0")
+    assert_oracle_and_eight_lane(oracle, probs, res, tiny)
     if want == 4:
-        full, kern8, hb8 = cold(capi, monkeypatch, probs, hblock="0", keep=keep)
-        assert kern8 == 2 and hb8 == 8
-        assert_same_bits(res, full)
+        assert_same_bits(res, cold_closed(capi, monkeypatch, probs, 8, keep=keep, full_H=True))
     return res
-
-
-def with_H(q, H):
-    return QPData(q.nV, q.nC, *dense_to_csc(H), q.A_jc, q.A_ir, q.A_val, q.g, q.lb, q.ub, q.lbA, q.ubA, name=q.name)
 
 
 def block_batch(rng, nV, nC, n, free=False, rel=0.05):
@@ -83,12 +60,7 @@ def block_batch(rng, nV, nC, n, free=False, rel=0.05):
     base = with_H(base, H)
     if free:
         base.lb[1] = -np.inf; base.ub[1] = np.inf
-    out = []
-    for _ in range(n):
-        q = problems.perturb(rng, base, rel)
-        q.A_val = q.A_val * (1.0 + rel * rng.normal(size=q.A_val.shape))
-        out.append(q)
-    return out
+    return perturbations(rng, base, n, rel)
 
 
 @pytest.mark.parametrize("keep", [False, True])
@@ -139,15 +111,9 @@ def test_a_batch_without_H(capi, oracle, monkeypatch):
     zero = np.zeros(6 + 1, np.int32)
     for q in probs:
         q.H_jc = q.H_ir = q.H_val = None
-    monkeypatch.setenv("RSQP_LANE", "1")
-    monkeypatch.delenv("RSQP_LANE_HBLOCK", raising=False)
-    res, kern, hb = cold(capi, monkeypatch, probs)
-    assert kern == 2 and hb == 4, (kern, hb)
-    full, kern8, hb8 = cold(capi, monkeypatch, probs, hblock="0")
-    assert kern8 == 2 and hb8 == 8
-    assert_same_bits(res, full)
-    tiny, kern0, _ = cold(capi, monkeypatch, probs, lane="0")
-    assert kern0 == 1
+    res = cold_closed(capi, monkeypatch, probs, 4)
+    assert_same_bits(res, cold_closed(capi, monkeypatch, probs, 8, full_H=True))
+    tiny = cold_closed(capi, monkeypatch, probs, 0, lane="0")
     oq = [QPData(q.nV, q.nC, zero, np.zeros(0, np.int32), np.zeros(0), q.A_jc, q.A_ir, q.A_val, q.g, q.lb, q.ub, q.lbA, q.ubA) for q in probs]
     assert assert_oracle_and_eight_lane(oracle, oq, res, tiny, need_solved=False) > 0
 
@@ -156,42 +122,12 @@ def test_a_batch_without_H(capi, oracle, monkeypatch):
 def test_hot_starts_continue_from_the_state_the_block_build_wrote(capi, oracle, monkeypatch, shape):
     """the sequence of test_gpu_lane.py's hot-start test on a batch that runs the block build: the state block it writes is the full
     tableau in the 8-lane kernel's layout, and the hot starts (new vectors, new matrices, new vectors) continue from it there"""
-    monkeypatch.setenv("RSQP_LANE", "1")
-    monkeypatch.delenv("RSQP_LANE_HBLOCK", raising=False)
     nV, nC = shape
     rng = np.random.default_rng(5300 + 10 * nV + nC)
     probs = block_batch(rng, nV, nC, 150)
-    b = capi.Batch(probs)
-    b.solve(capi.MODE_COLD, 1000)
-    assert b.last_kernel() == 2 and b.lane_hblock() == 4
-    orcs = []
-    for q, r in zip(probs, b.results()):
-        qp, rc, n = oracle_cold(oracle, q)
-        assert_same_solution(qp, r, n)
-        orcs.append(qp)
-    cur = probs
-    hot_changes = 0
-    for step in range(3):
-        nxt = [problems.perturb(rng, q, 0.3) for q in cur]
-        new_matrices = step == 1
-        if new_matrices:
-            for q in nxt:
-                q.A_val = q.A_val * (1.0 + 0.02 * rng.normal(size=q.A_val.shape))
-        b.set_vectors_from(nxt)
-        if new_matrices:
-            b.set_matrix_values(np.concatenate([q.A_val for q in nxt]), np.concatenate([q.H_val for q in nxt]))
-        b.solve(capi.MODE_HOT_MATRICES if new_matrices else capi.MODE_HOT_VECTORS, 1000)
-        assert b.last_kernel() == 1 and b.lane_hblock() == 0
-        for q, qp, r in zip(nxt, orcs, b.results()):
-            if new_matrices:
-                qp.set_A_csc(q.A_jc, q.A_ir, q.A_val); qp.set_H_csc(q.H_jc, q.H_ir, q.H_val)
-                rc, n = qp.hotstart_matrices(q.g, q.lb, q.ub, q.lbA, q.ubA, 1000)
-            else:
-                rc, n = qp.hotstart(q.g, q.lb, q.ub, q.lbA, q.ubA, 1000)
-            assert_same_solution(qp, r, n)
-            hot_changes += r["nWSR"]
-        cur = nxt
-    assert hot_changes > 0
+    b, res = lane_cold(capi, monkeypatch, probs, keep=True)
+    assert b.lane_hblock() == 4
+    continue_hot(capi, b, probs, oracle_handles(oracle, probs, res), rng, ("vectors", "matrices", "vectors"))
     b.close()
 
 
@@ -203,20 +139,9 @@ def test_an_odd_member_count_and_an_odd_width(capi, oracle, monkeypatch):
 
 
 def test_members_that_take_different_paths_on_the_block_build(capi, oracle, monkeypatch):
-    """the iterates of the hs071 SQP trajectory that share one pattern, perturbed and interleaved (test_gpu_lane.py): neighbouring
-    lanes take different paths of 5 changes each, exchanges among them"""
-    import json, os
-    from collections import Counter
-    from conftest import GOLDEN
-    tr = json.load(open(os.path.join(GOLDEN, "sqp_traces.json")))["hs071"]["qps"]
-    base = [problems.handler_qp(problems.hs071_nlp(np.array(g["x"]), np.array(g["lam"])), delta=g["delta"], rho=g["rho"]) for g in tr]
-    key = lambda q: (tuple(q.A_jc), tuple(q.A_ir), tuple(q.H_jc), tuple(q.H_ir))
-    best = Counter(key(q) for q in base).most_common(1)[0][0]
-    base = [q for q in base if key(q) == best]
-    assert len(base) >= 3
-    rng = np.random.default_rng(20260104)
-    probs = [problems.perturb(rng, base[k % len(base)]) for k in range(192)]
-    res = check_build(capi, oracle, monkeypatch, probs, 4)
+    """the iterates of the hs071 SQP trajectory that share one pattern, perturbed and interleaved (lane_cases.hs071_path_batch):
+    neighbouring lanes take different paths of 5 changes each, exchanges among them"""
+    res = check_build(capi, oracle, monkeypatch, hs071_path_batch(192), 4)
     assert len({(r["nWSR"], tuple(r["ws_b"]), tuple(r["ws_c"])) for r in res}) >= 2
 
 

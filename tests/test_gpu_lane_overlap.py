@@ -18,17 +18,14 @@ first wave). The shapes, each for the path it takes:
   free             members that lack a finite bound on some variables: the free-variable pivots of the set-up, between the passes
   inconsistent     one member of a full wave with lb > ub: the exit before any change, taken by one lane while the others set up
   mixed            members with more than four pivots beside members with none in EVERY wave: the vote keeps the earlier order
-The `mixed` and `hs071` claims are asserted from the oracle's own counts in a test that needs no GPU."""
+The `mixed` and `hs071` claims are asserted from the oracle's own counts in a test that needs no GPU. The launch, the comparisons
+and the families that other files use as well (hs071, outside_block, own_patterns, free) are tests/lane_cases.py's."""
 import numpy as np
 import pytest
 
-from conftest import oracle_cold
-from restartsqp_amd import problems
+import lane_cases as LC
+from lane_cases import assert_oracle_answer, assert_same_bits, continue_hot, lane_cold, oracle_handles
 from restartsqp_amd.qpdump import QPData, dense_to_csc
-import test_gpu_lane_io as io
-import test_gpu_lane_roles as roles
-from test_gpu_lane_io import FIELDS, _path
-from test_gpu_parity import assert_same_solution
 
 SIZES = (64, 65, 128, 129)
 DISTINCT, TWIN = 128, 5          # the distinct members of a shape; the one whose copy is the ragged wave of an odd-sized batch
@@ -69,26 +66,28 @@ def _inconsistent():
     return out
 
 
-# name -> (the distinct members, the build that serves them: H as its leading block (4) or in full (8))
+# the families of this file alone
+LC.FAMILIES.update({"overlap 7x2": lambda: block_members(7, 2, 9401), "overlap 5x1": lambda: block_members(5, 1, 9402),
+                    "overlap 4x0": lambda: block_members(4, 0, 9403), "overlap mixed": lambda: block_members(8, 2, 9404, quiet=3),
+                    "overlap inconsistent": _inconsistent})
+# name -> (the family of lane_cases whose first DISTINCT members the shape takes, the build that serves them: H as its leading
+# block (4) or in full (8))
 SHAPES = {
-    "hs071": (lambda: problems.hs071_scale_batch(DISTINCT), 4),
-    "7x2": (lambda: block_members(7, 2, 9401), 4),
-    "5x1": (lambda: block_members(5, 1, 9402), 4),
-    "4x0": (lambda: block_members(4, 0, 9403), 4),
-    "outside_block": (lambda: io.members("hs071_outside_block")[:DISTINCT], 8),
-    "own_patterns": (lambda: io.members("own_patterns")[:DISTINCT], 8),
-    "free": (lambda: roles.distinct_members()[:DISTINCT], 4),
-    "mixed": (lambda: block_members(8, 2, 9404, quiet=3), 4),
-    "inconsistent": (_inconsistent, 4),
+    "hs071": ("hs071", 4),
+    "7x2": ("overlap 7x2", 4),
+    "5x1": ("overlap 5x1", 4),
+    "4x0": ("overlap 4x0", 4),
+    "outside_block": ("hs071_outside_block", 8),
+    "own_patterns": ("own_patterns", 8),
+    "free": ("roles", 4),
+    "mixed": ("overlap mixed", 4),
+    "inconsistent": ("overlap inconsistent", 4),
 }
 _cache = {}
 
 
 def members(name):
-    if ("members", name) not in _cache:
-        _cache[("members", name)] = SHAPES[name][0]()
-        assert len(_cache[("members", name)]) == DISTINCT
-    return _cache[("members", name)]
+    return LC.members(SHAPES[name][0])[:DISTINCT]
 
 
 def batch(name, size):
@@ -99,10 +98,7 @@ def batch(name, size):
 
 
 def oracle_of(oracle, name, k):
-    """the oracle's cold start of distinct member k, computed once, left as it is"""
-    if ("oracle", name, k) not in _cache:
-        _cache[("oracle", name, k)] = oracle_cold(oracle, members(name)[k])
-    return _cache[("oracle", name, k)]
+    return LC.oracle_of(oracle, SHAPES[name][0], k)
 
 
 def pivots_of(oracle, name, k):
@@ -117,7 +113,7 @@ def test_the_shapes_take_the_paths_they_are_named_for(oracle):
     """(no GPU) the build each shape is served by; the entry counts; which members have free variables; the one inconsistent member;
     per wave of every batch, whether a lane refines"""
     for name, (_, hb) in SHAPES.items():
-        assert io.expected_block(members(name)) == hb, name
+        assert len(members(name)) == DISTINCT and LC.expected_block(members(name)) == hb, name
     q = members("hs071")[0]
     assert (q.nV, q.nC, int(q.A_jc[8]), int(q.H_jc[8])) == (8, 2, 12, 11)
     assert [int(members(n)[0].A_jc[-1]) for n in ("7x2", "5x1", "4x0")] == [14, 5, 0]
@@ -140,46 +136,20 @@ def test_the_shapes_take_the_paths_they_are_named_for(oracle):
 
 @pytest.mark.parametrize("name", ["7x2", "5x1", "4x0", "mixed"])
 def test_the_oracle_answers_are_unambiguous(oracle, name):
-    """(no GPU) test_gpu_lane_io.py's margins on the members generated here: solved; strict complementarity; no ratio test ties -- the
+    """(no GPU) lane_cases.assert_unambiguous on the members generated here: solved; strict complementarity; no ratio test ties -- the
     path does not move with the vectors"""
-    rng = np.random.default_rng(1)
-    for k, q in enumerate(members(name)):
-        qp, rc, n = oracle_of(oracle, name, k)
-        assert rc == 0 and qp.exitflag() == 20, (name, k, rc)
-        x, y = qp.x, qp.y
-        ax = q.dense_A() @ x if q.nC else np.zeros(0)
-        val = np.concatenate([x, ax]); lo = np.concatenate([q.lb, q.lbA]); hi = np.concatenate([q.ub, q.ubA])
-        ws = np.concatenate([qp.ws_bounds, qp.ws_constraints])
-        assert np.all(np.abs(y[ws != 0]) > 1e-6), (name, k)
-        assert np.all((val - lo)[ws == 0] > 1e-6) and np.all((hi - val)[ws == 0] > 1e-6), (name, k)
-        d = [1e-10 * rng.normal(size=v.shape) for v in (q.g, q.lb, q.ub, q.lbA, q.ubA)]
-        ref = _path(oracle, q, n)
-        assert ref[-1][0] == n
-        assert _path(oracle, q, n, d, 1.0) == ref and _path(oracle, q, n, d, -1.0) == ref, (name, k)
-
-
-def lane_cold(capi, monkeypatch, probs, full_H=False, keep=False):
-    monkeypatch.setenv("RSQP_LANE", "1")
-    if full_H:
-        monkeypatch.setenv("RSQP_LANE_HBLOCK", "0")
-    else:
-        monkeypatch.delenv("RSQP_LANE_HBLOCK", raising=False)
-    b = capi.Batch(probs)
-    b.set_keep_state(keep)
-    b.solve(capi.MODE_COLD, 1000)
-    assert b.last_kernel() == 2
-    return b, b.results(), b.lane_hblock()
+    LC.assert_family_unambiguous(oracle, SHAPES[name][0])
 
 
 def results(capi, monkeypatch, name, size):
     """the batch's cold start on the build its shape is served by, solved once"""
-    if ("results", name, size) not in _cache:
-        b, res, hb = lane_cold(capi, monkeypatch, batch(name, size)[0])
+    if (name, size) not in _cache:
+        b, res = lane_cold(capi, monkeypatch, batch(name, size)[0])
+        assert b.lane_hblock() == SHAPES[name][1], (name, b.lane_hblock())
         b.close()
-        assert hb == SHAPES[name][1], (name, hb)
         assert len(res) == size
-        _cache[("results", name, size)] = res
-    return _cache[("results", name, size)]
+        _cache[(name, size)] = res
+    return _cache[(name, size)]
 
 
 @pytest.mark.gpu
@@ -194,9 +164,7 @@ def test_every_member_gets_the_oracles_answer(capi, oracle, monkeypatch, name, s
             # (infeasible before any change: no solution to compare)
             assert r["status"] == qp.exitflag() != 20 and r["nWSR"] == n == 0
             continue
-        assert r["status"] == qp.exitflag() == 20
-        assert_same_solution(qp, r, n)                  # (status, nWSR, working sets exact; x, y within 1e-9)
-        assert abs(r["obj"] - qp.objective) <= 1e-9 * max(1.0, abs(qp.objective))
+        assert_oracle_answer(qp, r, n, (name, k))       # (status 20, nWSR, working sets exact; x, y, objective within 1e-9)
 
 
 @pytest.mark.gpu
@@ -207,12 +175,11 @@ def test_the_ordered_staging_gives_the_bits_of_the_earlier_one(capi, monkeypatch
     results, inside one library"""
     probs, idx = batch(name, size)
     res = results(capi, monkeypatch, name, size)
-    b, full, hb = lane_cold(capi, monkeypatch, probs, full_H=True)
+    b, full = lane_cold(capi, monkeypatch, probs, full_H=True)
+    assert b.lane_hblock() == 8
     b.close()
-    assert hb == 8 and len(full) == len(res) == size
-    for i, (a, c) in enumerate(zip(res, full)):
-        for f in FIELDS:
-            assert np.array_equal(np.asarray(a[f]), np.asarray(c[f])), (name, size, i, f, a[f], c[f])
+    assert len(res) == size
+    assert_same_bits(res, full, (name, size))
 
 
 @pytest.mark.gpu
@@ -221,8 +188,7 @@ def test_a_member_answers_the_same_bits_in_a_full_wave_and_in_the_ragged_one(cap
     r65, r129, r128 = results(capi, monkeypatch, name, 65), results(capi, monkeypatch, name, 129), results(capi, monkeypatch, name, 128)
     # (ragged wave, full wave): the twin within each odd batch and across the batches; a member of the second wave across 128 / 129
     for rag, ful in ((r65[64], r65[TWIN]), (r129[128], r129[TWIN]), (r65[64], r128[TWIN]), (r129[100], r128[100])):
-        for f in FIELDS:
-            assert np.array_equal(np.asarray(rag[f]), np.asarray(ful[f])), (name, f, rag[f], ful[f])
+        assert_same_bits(rag, ful, name)
 
 
 @pytest.mark.gpu
@@ -232,23 +198,7 @@ def test_a_hot_start_continues_from_the_kept_state(capi, oracle, monkeypatch, na
     start on new vectors (8-lane kernel, from the block the lane kernel wrote) take the oracle's number of changes exactly, member by
     member; a full wave and a ragged one"""
     probs, idx = batch(name, 65)
-    b, res, hb = lane_cold(capi, monkeypatch, probs, keep=True)
-    assert hb == 4
-    orcs = []
-    for q, r in zip(probs, res):
-        qp, rc, n = oracle_cold(oracle, q)              # (a handle of its own: the hot start moves it)
-        assert_same_solution(qp, r, n)
-        orcs.append(qp)
-    rng = np.random.default_rng(9410)
-    nxt = [problems.perturb(rng, q, 0.3) for q in probs]
-    b.set_vectors_from(nxt)
-    b.solve(capi.MODE_HOT_VECTORS, 1000)
-    assert b.last_kernel() == 1
-    changes = 0
-    for q, qp, r in zip(nxt, orcs, b.results()):
-        rc, n = qp.hotstart(q.g, q.lb, q.ub, q.lbA, q.ubA, 1000)
-        assert r["nWSR"] == n
-        assert_same_solution(qp, r, n)
-        changes += n
-    assert changes > 0
+    b, res = lane_cold(capi, monkeypatch, probs, keep=True)
+    assert b.lane_hblock() == 4
+    continue_hot(capi, b, probs, oracle_handles(oracle, probs, res), np.random.default_rng(9410))
     b.close()

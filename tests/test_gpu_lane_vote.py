@@ -16,21 +16,16 @@ plain, a flip to the opposite side or an exchange):
   (f) the headline's own members (two changes each, both of kind 3 by an exchange with a bound, in every lane);
   (g) a member with inconsistent bounds and a member that ends infeasible inside a full wave.
 A test without a GPU asserts, from the same record, that each situation occurs in the waves built. One shape (8 x 2), one pattern, H
-in its leading 4 x 4 block; the members are those of test_gpu_lane_roles.py and test_gpu_lane_pivots.py (two patterns: a batch
-takes its waves from one), whose own tests assert that no answer is ambiguous. Batches of 64, 65, 128 and 129: a full wave, a full
-wave beside a ragged wave of one lane, two full waves, and the ragged wave behind them; the ragged wave's member also sits in the
-full wave in front of it."""
+in its leading 4 x 4 block; the members are lane_cases' families "roles" and "pivots" (two patterns: a batch takes its waves from
+one; test_gpu_lane_roles.py and test_gpu_lane_pivots.py assert that no answer of theirs is ambiguous), "odd" and "hs071". Batches
+of 64, 65, 128 and 129: a full wave, a full wave beside a ragged wave of one lane, two full waves, and the ragged wave behind them;
+the ragged wave's member also sits in the full wave in front of it."""
 import numpy as np
 import pytest
 
-import test_gpu_lane_pivots as LP
-import test_gpu_lane_roles as LR
-import test_gpu_lane_shape as LS
-from conftest import oracle_cold
-from test_gpu_lane_io import FIELDS, _path
-from test_gpu_parity import assert_same_solution
+import lane_cases as LC
+from lane_cases import FULL, ODD_INCONSISTENT, ODD_INFEASIBLE, assert_same_bits, assert_same_solution, lane_cold, pattern, working_sets
 
-FULL = 8 * 256 + 2
 KINDS = {1: "constraint leaves", 2: "bound leaves", 3: "constraint enters", 4: "variable fixed"}
 TWIN = 5                                     # the lane of a batch's last full wave whose member the ragged wave repeats
 _cache = {}
@@ -40,19 +35,12 @@ _cache = {}
 # the members and the oracle's record of their changes
 # ------------------------------------------------------------------------------------
 def member(key):
-    pool, k = key
-    if pool == "odd":
-        return LS.odd_batch()[k]
-    if pool == "hs071":
-        return LS.batch_of("hs071")[k]
-    return (LR if pool == "roles" else LP).distinct_members()[k]
+    """key: (family of lane_cases, index in it)"""
+    return LC.members(key[0])[key[1]]
 
 
 def oracle_of(oracle, key):
-    """the oracle's cold start of a member, computed once, left as it is"""
-    if ("oracle", key) not in _cache:
-        _cache[("oracle", key)] = oracle_cold(oracle, member(key))
-    return _cache[("oracle", key)]
+    return LC.oracle_of(oracle, *key)
 
 
 def changes_of(oracle, key):
@@ -62,7 +50,7 @@ def changes_of(oracle, key):
     if ("changes", key) not in _cache:
         qp, rc, n = oracle_of(oracle, key)
         assert rc == 0 and qp.exitflag() == 20, key
-        ws = [np.array(b + c) for _, b, c in _path(oracle, member(key), n)]
+        ws = working_sets(oracle, member(key), n)
         ev = []
         for a, b in zip(ws[:-1], ws[1:]):
             moved = np.nonzero(a != b)[0]
@@ -190,12 +178,11 @@ def passes(oracle, keys):
 # ------------------------------------------------------------------------------------
 def test_the_batches_have_the_four_sizes_and_one_pattern_each(oracle):
     sizes = set()
-    key = lambda q: (tuple(q.A_jc), tuple(q.A_ir), tuple(q.H_jc), tuple(q.H_ir))
     for name in BATCHES:
         probs = [member(k) for k in batch_keys(oracle, name)]
         sizes.add(len(probs))
         assert len(probs) == int(name.split()[0])
-        assert len({key(q) for q in probs}) == 1 and all(q.nV == 8 and q.nC == 2 and q.H_ir.max() < 4 for q in probs), name
+        assert len({pattern(q) for q in probs}) == 1 and all(q.nV == 8 and q.nC == 2 and q.H_ir.max() < 4 for q in probs), name
     assert sizes == {64, 65, 128, 129}
     named = {w for names, _ in BATCHES.values() for w in names}
     assert named == set(waves(oracle)) | {"g odd", "hs071 0", "hs071 1"}              # (every wave built is in a batch)
@@ -239,10 +226,10 @@ def test_every_situation_occurs_in_the_waves_built(oracle):
         assert [(t, kinds) for t, kinds, _ in p] == [(1, {3}), (1, {3}), (2, set())]
         assert all(c[2] == "exchange" for _, _, ch in p for c in ch)
     # (g) inside a full wave: inconsistent bounds (infeasible before any change), infeasible after some changes
-    assert LS.ODD_INCONSISTENT < 64 and LS.ODD_INFEASIBLE < 64
-    qp, rc, n0 = oracle_of(oracle, ("odd", LS.ODD_INCONSISTENT))
+    assert ODD_INCONSISTENT < 64 and ODD_INFEASIBLE < 64
+    qp, rc, n0 = oracle_of(oracle, ("odd", ODD_INCONSISTENT))
     assert rc != 0 and qp.exitflag() != 20 and n0 == 0
-    qp, rc, n1 = oracle_of(oracle, ("odd", LS.ODD_INFEASIBLE))
+    qp, rc, n1 = oracle_of(oracle, ("odd", ODD_INFEASIBLE))
     assert rc != 0 and qp.exitflag() != 20 and n1 > 0
 
 
@@ -253,7 +240,7 @@ def results(capi, oracle, monkeypatch, name, shape):
     """the batch's cold start on the full-shape build (the votes) or on the run-time-shape build (none), solved once"""
     key = ("results", name, shape)
     if key not in _cache:
-        b, res = LS.lane_cold(capi, monkeypatch, [member(k) for k in batch_keys(oracle, name)], shape=shape)
+        b, res = lane_cold(capi, monkeypatch, [member(k) for k in batch_keys(oracle, name)], shape=shape)
         assert b.lane_hblock() == 4 and b.lane_shape() == (FULL if shape else 0)
         b.close()
         _cache[key] = res
@@ -274,7 +261,7 @@ def test_the_voted_texts_give_the_oracles_answers(capi, oracle, monkeypatch, nam
             assert_same_solution(qp, r, n)              # (status, nWSR, working sets exact; x, y within 1e-9)
             solved += 1
     # (the odd wave's two members that cannot be solved; its ragged wave repeats lane TWIN, the one with inconsistent bounds)
-    odd = (("odd", LS.ODD_INCONSISTENT), ("odd", LS.ODD_INFEASIBLE))
+    odd = (("odd", ODD_INCONSISTENT), ("odd", ODD_INFEASIBLE))
     assert solved == len(res) - sum(key in odd for key in keys) and (name != "65 odd" or len(res) - solved == 3)
 
 
@@ -282,10 +269,8 @@ def test_the_voted_texts_give_the_oracles_answers(capi, oracle, monkeypatch, nam
 @pytest.mark.parametrize("name", list(BATCHES))
 def test_the_voted_texts_give_the_bits_of_the_build_without_votes(capi, oracle, monkeypatch, name):
     new, old = results(capi, oracle, monkeypatch, name, True), results(capi, oracle, monkeypatch, name, False)
-    assert len(new) == len(old) == len(batch_keys(oracle, name))
-    for i, (a, c) in enumerate(zip(new, old)):
-        for f in FIELDS:
-            assert np.array_equal(np.asarray(a[f]), np.asarray(c[f])), (name, i, f, a[f], c[f])
+    assert len(new) == len(batch_keys(oracle, name))
+    assert_same_bits(new, old, name)
 
 
 @pytest.mark.gpu
@@ -293,6 +278,4 @@ def test_the_voted_texts_give_the_bits_of_the_build_without_votes(capi, oracle, 
 def test_a_member_answers_the_same_bits_in_a_full_wave_and_in_the_ragged_one(capi, oracle, monkeypatch, name):
     """the ragged wave's lanes all hold its one member: whatever the full wave in front of it voted, that wave agrees on everything"""
     res = results(capi, oracle, monkeypatch, name, True)
-    rag, ful = res[-1], res[-65 + TWIN]
-    for f in FIELDS:
-        assert np.array_equal(np.asarray(rag[f]), np.asarray(ful[f])), (name, f, rag[f], ful[f])
+    assert_same_bits(res[-1], res[-65 + TWIN], name)

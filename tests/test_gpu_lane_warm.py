@@ -4,21 +4,17 @@
 
 Bar as everywhere: status, nWSR and both working sets exact, x / y / objective within 1e-9 relative, against the oracle's
 init(.., x0, y0, guess_b) / hotstart / hotstart_matrices; against the switch-off run status, nWSR and working sets equal. Batches have
-131-200 members (two or three full waves and a ragged tail) under RSQP_LANE=1; the inputs are the generators of tests/test_gpu_lane.py.
+131-200 members (two or three full waves and a ragged tail) under RSQP_LANE=1; the inputs are the generators of tests/lane_cases.py.
 """
 import numpy as np
 import pytest
 
 from conftest import oracle_cold
+from lane_cases import RTOL, assert_same_solution, one_pattern_batch, own_pattern_batch
 from restartsqp_amd import problems
-from restartsqp_amd.qpdump import dense_to_csc
 from test_gpu_batch_optimize import Ref, assert_member, MODES, RESCUES, newmats
-from test_gpu_lane import one_pattern_batch
-from test_gpu_parity import assert_same_solution
 
 pytestmark = pytest.mark.gpu
-
-RTOL = 1e-9
 
 
 def batch(capi, monkeypatch, probs, warm):
@@ -67,7 +63,7 @@ def assert_against_oracle(tag, qp, r, n):
         assert_same_solution(qp, r, n)
     except AssertionError as e:
         raise AssertionError("%r: status %d (oracle %d) nWSR %d (oracle %d): %s" % (tag, r["status"], qp.exitflag(), r["nWSR"], n, e))
-    if qp.is_solved():
+    if qp.is_solved():              # (status 20 or 22, where assert_oracle_answer is for 20 alone)
         assert abs(r["obj"] - qp.objective) <= RTOL * max(1.0, abs(qp.objective)), tag
 
 
@@ -230,24 +226,6 @@ def test_members_that_end_differently(capi, oracle, monkeypatch):
         else:
             assert all(second[m]["status"] not in (20, capi.QPERROR_INFEASIBLE) and second[m]["nWSR"] == 3 for m in infeasible)
             assert sum(r["status"] == 20 for r in others) > 0 and sum(r["status"] != 20 and r["nWSR"] == 3 for r in others) > 0
-
-
-def own_pattern_batch(rng, nV, nC, n):
-    """three base problems of different density, interleaved member by member (test_one_shape_with_patterns_of_their_own)"""
-    bases = [problems.random_qp(rng, nV, nC, density=d) for d in (0.3, 0.6, 1.0)]
-    for k, b0 in enumerate(bases[:2]):
-        H = b0.dense_H()
-        M = np.triu(rng.random((nV, nV)) < (0.3 + 0.3 * k), 1)
-        H = H * (M | M.T | np.eye(nV, dtype=bool))
-        H += np.diag(np.abs(H).sum(axis=1))                      # (stays positive definite)
-        b0.H_jc, b0.H_ir, b0.H_val = dense_to_csc(H)
-    probs = []
-    for k in range(n):
-        q = problems.perturb(rng, bases[k % 3], 0.05)
-        q.A_val = q.A_val * (1.0 + 0.05 * rng.normal(size=q.A_val.shape))
-        probs.append(q)
-    assert len({(len(q.A_val), len(q.H_val)) for q in probs}) >= 2
-    return probs
 
 
 @pytest.mark.parametrize("shape", [(8, 2), (5, 1)])
