@@ -325,7 +325,8 @@ int rsqp_batch_get_dispatch(const rsqp_batch *b, int *mode, int *rescue);
  *     whose stored state is another family's starts cold at its next hot start and is reported as mode 0, as the whole batch is.
  *   - the first optimize call of a batch is the uniform cold launch only when everybody takes part; otherwise the members that take
  *     part come out cold through the per-member dispatch (on the 8-lane kernel: the lane-per-problem kernel carries per-member
- *     modes only in the builds of rsqp_batch_set_lane_warm, for calls that follow rsqp_batch_set_matrix_values).
+ *     modes only in the builds of rsqp_batch_set_lane_warm, for calls that follow rsqp_batch_set_matrix_values, or for every call
+ *     with rsqp_batch_set_lane_hot on as well).
  * Unchanged on purpose: rsqp_batch_solve, rsqp_batch_test_optimality, rsqp_batch_get_results and the record packers ignore the mask
  * (rsqp_batch_solve runs and rewrites the state of every member); the first optimize call of the other kind (QP <-> LP) still starts
  * every member over, those that sit out included -- a lock-step driver keeps an LP batch beside its QP batch, as the reference
@@ -561,4 +562,6 @@ int rsqp_dense_chol_inverse(int n, double *G, double *Ginv, double pd_rel, doubl
 #include "rsqp_hip_lane.h"
 /* hot starts with new matrices and warm re-initialisations on the lane-per-problem kernel (set / get of the switch): the same way */
 #include "rsqp_hip_lane_warm.h"
+/* hot starts on new vectors on that kernel (set / get of the switch): the same way */
+#include "rsqp_hip_lane_hot.h"
 #endif

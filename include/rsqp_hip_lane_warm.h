@@ -21,9 +21,10 @@ extern "C" {
  * equal, x, y and the objective to rounding; rsqp_batch_get_dispatch, nWSR_used and the stored state's layout do not change, and a
  * later hot start on new vectors continues from the state on the 8-lane kernel. rsqp_batch_get_last_plan reports family 2 with the
  * mode of the launch.
- * These calls stay on the 8-lane kernel with the switch on: a hot start on new vectors; the rescue solve of an optimize call, an
- * optimize call without rsqp_batch_set_matrix_values before it (marks of rsqp_batch_set_matrix_values_of and
- * rsqp_batch_handler_set_matrices alone included) and rsqp_batch_optimize_lp; a hot start whose result pools
+ * These calls stay on the 8-lane kernel with the switch on: a hot start on new vectors and an optimize call without
+ * rsqp_batch_set_matrix_values before it (marks of rsqp_batch_set_matrix_values_of and rsqp_batch_handler_set_matrices alone
+ * included) -- both unless rsqp_batch_set_lane_hot of rsqp_hip_lane_hot.h is on as well --; the rescue solve of an optimize call
+ * and rsqp_batch_optimize_lp; a hot start whose result pools
  * rsqp_batch_set_results has written since the last solve; every call while the hand-over is on (rsqp_batch_set_handover), and the
  * call after it. on == 0 (default): every entry point launches what it launched before there was a switch. */
 int rsqp_batch_set_lane_warm(rsqp_batch *b, int on);

@@ -152,6 +152,11 @@ LANE_WARM_SYMBOLS = {
     "rsqp_batch_set_lane_warm": (C.c_int, [C.c_void_p, C.c_int]),
     "rsqp_batch_get_lane_warm": (C.c_int, [C.c_void_p]),
 }
+# ... and of include/rsqp_hip_lane_hot.h (hot starts on new vectors on the lane-per-problem kernel)
+LANE_HOT_SYMBOLS = {
+    "rsqp_batch_set_lane_hot": (C.c_int, [C.c_void_p, C.c_int]),
+    "rsqp_batch_get_lane_hot": (C.c_int, [C.c_void_p]),
+}
 
 
 class OptimalityStatus(C.Structure):
@@ -185,7 +190,7 @@ def lib():
         _TORCH_FIRST = "torch" in sys.modules
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SYMBOLS.items()) + list(LANE_SYMBOLS.items()) + list(HANDOVER_SYMBOLS.items()) + \
-                list(LANE_WARM_SYMBOLS.items()):
+                list(LANE_WARM_SYMBOLS.items()) + list(LANE_HOT_SYMBOLS.items()):
             f = getattr(L, name)
             f.restype = res
             f.argtypes = args
@@ -750,6 +755,17 @@ class Batch:
     def lane_warm(self):
         """the switch of set_lane_warm (rsqp_batch_get_lane_warm)"""
         return bool(check(lib().rsqp_batch_get_lane_warm(self._h)))
+
+    def set_lane_hot(self, on):
+        """on: while set_lane_warm is on as well (alone this switch changes nothing), a batch the lane-per-problem kernel serves and
+        that keeps its state also runs its hot starts on new vectors (solve(MODE_HOT_VECTORS)) and the first solve of every
+        optimize_qp() call behind the first -- update marks batch-wide, per member or absent -- on that kernel
+        (rsqp_batch_set_lane_hot); off (the default): as before"""
+        check(lib().rsqp_batch_set_lane_hot(self._h, int(bool(on))))
+
+    def lane_hot(self):
+        """the switch of set_lane_hot (rsqp_batch_get_lane_hot)"""
+        return bool(check(lib().rsqp_batch_get_lane_hot(self._h)))
 
     def handover(self, handed=None):
         """(handed, count) of the last solve / optimize call: handed[q] = 1 where member q was handed over to the Givens / TQ kernel

@@ -1,5 +1,6 @@
 // qp_lane.hip -- hs071-scale QPs of a ONE-SHAPE batch, cold start, ONE LANE PER PROBLEM (round 5); in the WARM builds also the hot
-// start with new matrices and the warm re-initialisation (lane_qp_body, rsqp_batch_set_lane_warm).
+// start with new matrices and the warm re-initialisation (lane_qp_body, rsqp_batch_set_lane_warm), at level 2 also the hot start on new
+// vectors (rsqp_batch_set_lane_hot).
 //
 // Replaces, for large batches of one shape (one sparsity pattern -- parameter scans, perturbations of one QP: bench.py's
 // headline workload, 65 536 x the hs071 QP through the QPhandler formulation -- or patterns of their own), the qpOASES 3.2.1 SQProblem::init call made
@@ -109,8 +110,9 @@ template <> struct ShapeWord<-1> {
 // kind K. A wave that disagrees runs the text of the builds without the flag; per lane every text performs the same operations
 // on the same operands in the same order (kernel's choice, see lane_qp_body: the full-shape build without kept state)
 // WARM: the build for hot starts with new matrices and warm re-initialisations (lane_qp_body): the set-up from a guess (setup_warm,
-// warm_pivots), the guess's way in (take_guess) and results / state stores that leave out the members a launch does not run
-template <int MC, int HB, int CH1 = 2, int CH2 = 2, bool ROLES = false, int SHV = -1, int SHC = -1, int VOTE = 0, bool WARM = false>
+// warm_pivots), the guess's way in (take_guess) and results / state stores that leave out the members a launch does not run. A
+// level: 0 no, 1 those two call shapes, 2 also the hot start on new vectors (take_limits, setup_warm's `hot`)
+template <int MC, int HB, int CH1 = 2, int CH2 = 2, bool ROLES = false, int SHV = -1, int SHC = -1, int VOTE = 0, int WARM = 0>
 struct LaneT {
     static_assert((SHV < 0) == (SHC < 0) && SHV <= MV && SHC <= MC, "both words of the shape, or neither");
     static_assert(HB == 4 || HB == MV, "leading block of H");
@@ -374,7 +376,7 @@ struct LaneT {
             double2 v;
             v.x = T[(((hi0 * (hi0 + 1)) >> 1) + lo0) * WL + qq]; v.y = T[(((hi1 * (hi1 + 1)) >> 1) + lo1) * WL + qq];
             bool mine = qq < nqw;
-            if constexpr (WARM) mine = mine && ((live >> (qq & 63)) & 1) != 0;
+            if constexpr (WARM != 0) mine = mine && ((live >> (qq & 63)) & 1) != 0;
             if (mine) *reinterpret_cast<double2 *>(sbase + (long long)qq * stride + e) = v;
         }
     }
@@ -388,7 +390,7 @@ struct LaneT {
             const int m = t * WL + lane;
             const int qq = m / THALF, f = m - qq * THALF;
             bool mine = qq < nqw;
-            if constexpr (WARM) mine = mine && ((live >> (qq & 63)) & 1) != 0;
+            if constexpr (WARM != 0) mine = mine && ((live >> (qq & 63)) & 1) != 0;
             if (mine) sbase[(long long)qq * stride + N * N + half * THALF + f] = T[f * WL + qq];
         }
     }
@@ -432,7 +434,7 @@ struct LaneT {
                  const int m = t * WL + lane;
                  const int qq = (int)(((float)m + 0.5f) * rn), e = m - qq * n;
                  bool mine = m < cnt;
-                 if constexpr (WARM) mine = mine && ((live >> (qq & 63)) & 1) != 0;
+                 if constexpr (WARM != 0) mine = mine && ((live >> (qq & 63)) & 1) != 0;
                  if (mine) {
                      if constexpr (sizeof(TV) == 8) dst[m] = T[(s0 + e) * WL + qq];
                      else dst[m] = ((const __attribute__((address_space(3))) int *)(T + (s0 + e) * WL + qq))[0];
@@ -842,6 +844,32 @@ struct LaneT {
              yc[i] = (hy && c) ? a1 : 0.0; sc[i] = (hc && c) ? s0 : 0;);
         wave_sync();           // (every lane has read its slots: the space is the tableau's again)
     }
+    // WARM level 2, a hot start on new vectors: the limits the members' last homotopy ended on -- lo, up (fields 2, 3 of the variable
+    // slots: 16 consecutive doubles of a state block's tail) and loA, upA (fields 1, 2 of the constraint slots, MC of each) --, HBM ->
+    // slots of the tableau's space -> my registers lo / up / loA / upA. They are all a hot start needs of the block beyond the guess:
+    // g, gy and A x are exact products of the homotopy's first iteration, the tableau is built by setup_warm, and the tableau half
+    // of the block is not read. Four lanes share a member's 32-byte piece, and a member's 128-byte run is used up by four
+    // instructions in a row (a lane walking its own block: 64 lines per instruction for 8 bytes of each); in LDS the 16 lanes
+    // of a store group then hold 4 owners (4-way conflicts on 20 stores; a member's run per 16 lanes would be 16-way)
+    __device__ __forceinline__ void take_limits(const double *sbase, long long stride, int lane, int nqw, ldouble *T) {
+        constexpr int SL = 0, SA = 2 * MV, PV = 2 * MV, PC = 2 * MC;
+        static_assert(SA + PC <= NT && WL % PC == 0 && PV % 4 == 0, "the limits pass through the tableau's slots");
+        const double *tail = sbase + N * N;
+        double wv[PV], wc[PC];
+        SFOR(t, PV, const int qq = (lane >> 2) + (WL / 4) * (t >> 2), f = (lane & 3) + 4 * (t & 3);
+             wv[t] = tail[(long long)(qq < nqw ? qq : nqw - 1) * stride + 2 * MV + f];);
+        SFOR(t, PC, const int qq = lane / PC + (WL / PC) * t, f = lane % PC;
+             wc[t] = tail[(long long)(qq < nqw ? qq : nqw - 1) * stride + 6 * MV + (1 + f / MC) * 8 + f % MC];);
+        SFOR(t, PV, const int qq = (lane >> 2) + (WL / 4) * (t >> 2), f = (lane & 3) + 4 * (t & 3);
+             T[(SL + f) * WL + qq] = wv[t];);
+        SFOR(t, PC, const int qq = lane / PC + (WL / PC) * t, f = lane % PC;
+             T[(SA + f) * WL + qq] = wc[t];);
+        wave_sync();
+        const ldouble *S = T + (lane < nqw ? lane : nqw - 1);
+        SFOR(l, MV, lo[l] = S[(SL + l) * WL]; up[l] = S[(SL + MV + l) * WL];);
+        SFOR(i, MC, loA[i] = S[(SA + i) * WL]; upA[i] = S[(SA + MC + i) * WL];);
+        wave_sync();           // (every lane has read its slots: the space is the tableau's again)
+    }
     // sum of u_v^2 over the free variables; sum of a_v^2 over them for row `arow` of A
     __device__ __forceinline__ void free_norms(const double (&u)[N], int arow, double &pn2, double &na2) const {
         double s1 = 0.0, s2 = 0.0;
@@ -906,7 +934,10 @@ struct LaneT {
     // xv / yv / yc / sv / sc (take_guess); have_*: the parts of it this lane takes (none of them: the cold start, x = 0, y = 0,
     // every variable on a finite bound, lower first). false: the guess gives no positive definite reduced Hessian (the caller
     // falls back to the cold start)
-    __device__ __forceinline__ bool setup_warm(bool have_x0, bool have_y0, bool have_gb, bool have_gc, bool c_from_y0) {
+    // hot (WARM level 2, a hot start on new vectors): the guess is the stored iterate, and lo / up / loA / upA hold the limits it was
+    // reached under (take_limits). The working set was valid under THOSE limits, so the targets, which are new, take no side away,
+    // no multiplier is clipped, and the limits stay: the homotopy runs from them to the targets, as qp_tiny.hip's mode 1 does
+    __device__ __forceinline__ bool setup_warm(bool have_x0, bool have_y0, bool have_gb, bool have_gc, bool c_from_y0, bool hot = false) {
         status = QPS_PREPARINGAUXILIARYQP;
         infeasible = unbounded = 0;
         int pf = 0;
@@ -915,8 +946,8 @@ struct LaneT {
              const int sx = xv[l] <= loN[l] + RSQP_BOUND_TOLERANCE ? -1 : (xv[l] >= upN[l] - RSQP_BOUND_TOLERANCE ? 1 : 0);
              const int sy = yv[l] > RSQP_EPS ? -1 : (yv[l] < -RSQP_EPS ? 1 : 0);
              int s = have_gb ? sv[l] : (have_x0 ? sx : (have_y0 ? sy : -1));
-             if (s == -1 && loN[l] <= -RSQP_INFTY) s = (upN[l] < RSQP_INFTY && !have_x0 && !have_gb) ? 1 : 0;
-             if (s == 1 && upN[l] >= RSQP_INFTY) s = 0;
+             if (!hot && s == -1 && loN[l] <= -RSQP_INFTY) s = (upN[l] < RSQP_INFTY && !have_x0 && !have_gb) ? 1 : 0;
+             if (!hot && s == 1 && upN[l] >= RSQP_INFTY) s = 0;
              sv[l] = v ? s : -1;
              pf |= (v && s == 0) ? 1 << l : 0;);
         SFOR(i, MC, yc[i] = (have_y0 && i < nC) ? yc[i] : 0.0;);
@@ -934,24 +965,35 @@ struct LaneT {
              if (have_gc) sgc = sc[i];
              else if (have_y0 && (!have_x0 || c_from_y0)) sgc = sy;
              else if (have_x0) sgc = sx;
-             if (sgc == -1 && cloN[i] <= -RSQP_INFTY) sgc = 0;
-             if (sgc == 1 && cupN[i] >= RSQP_INFTY) sgc = 0;
+             if (!hot && sgc == -1 && cloN[i] <= -RSQP_INFTY) sgc = 0;
+             if (!hot && sgc == 1 && cupN[i] >= RSQP_INFTY) sgc = 0;
              if (!c) sgc = 0;
              sc[i] = sgc;
              pa |= sgc != 0 ? 1 << i : 0;);
         if (!warm_pivots(pf, pa)) return false;
         SFOR(i, MC, sc[i] = ((pa >> i) & 1) ? 0 : sc[i];);          // (what is left in pa was dependent: it stays out)
         // multipliers: zero when inactive, clipped to the sign their side requires
-        SFOR(l, MV, const bool z = sv[l] == 0 || (sv[l] == -1 && yv[l] < 0.0) || (sv[l] == 1 && yv[l] > 0.0); yv[l] = z ? 0.0 : yv[l];);
-        SFOR(i, MC, const bool z = sc[i] == 0 || (sc[i] == -1 && yc[i] < 0.0) || (sc[i] == 1 && yc[i] > 0.0); yc[i] = z ? 0.0 : yc[i];);
+        SFOR(l, MV, const bool z = sv[l] == 0 || (!hot && ((sv[l] == -1 && yv[l] < 0.0) || (sv[l] == 1 && yv[l] > 0.0))); yv[l] = z ? 0.0 : yv[l];);
+        SFOR(i, MC, const bool z = sc[i] == 0 || (!hot && ((sc[i] == -1 && yc[i] < 0.0) || (sc[i] == 1 && yc[i] > 0.0))); yc[i] = z ? 0.0 : yc[i];);
         // gradient of the auxiliary QP from stationarity, its limits around the iterate
         exact_products(gyx, axx, hxx);
+        if constexpr (WARM >= 2) {
+        SFOR(l, MV, gy[l] = gyx[l]; g[l] = gyx[l] + yv[l];
+             const double l1 = sv[l] == -1 ? xv[l] : fmin(loN[l], xv[l] - RSQP_BOUND_RELAXATION);
+             const double u1 = sv[l] == 1 ? xv[l] : fmax(upN[l], xv[l] + RSQP_BOUND_RELAXATION);
+             lo[l] = hot ? lo[l] : l1; up[l] = hot ? up[l] : u1;
+             if (l >= nV) { lo[l] = 0.0; up[l] = 0.0; });
+        SFOR(i, MC, const double l1 = sc[i] == -1 ? ax[i] : fmin(cloN[i], ax[i] - RSQP_BOUND_RELAXATION);
+             const double u1 = sc[i] == 1 ? ax[i] : fmax(cupN[i], ax[i] + RSQP_BOUND_RELAXATION);
+             loA[i] = (hot && i < nC) ? loA[i] : l1; upA[i] = (hot && i < nC) ? upA[i] : u1;);
+        } else {
         SFOR(l, MV, gy[l] = gyx[l]; g[l] = gyx[l] + yv[l];
              lo[l] = sv[l] == -1 ? xv[l] : fmin(loN[l], xv[l] - RSQP_BOUND_RELAXATION);
              up[l] = sv[l] == 1 ? xv[l] : fmax(upN[l], xv[l] + RSQP_BOUND_RELAXATION);
              if (l >= nV) { lo[l] = 0.0; up[l] = 0.0; });
         SFOR(i, MC, loA[i] = sc[i] == -1 ? ax[i] : fmin(cloN[i], ax[i] - RSQP_BOUND_RELAXATION);
              upA[i] = sc[i] == 1 ? ax[i] : fmax(cupN[i], ax[i] + RSQP_BOUND_RELAXATION););
+        }
         status = QPS_AUXILIARYQPSOLVED;
         return true;
     }
@@ -1288,7 +1330,8 @@ struct LaneT {
 };
 
 // persistent state of a problem between solves (hot starts): the layout qp_tiny.hip keeps in the problem's state block. This
-// kernel only WRITES it (KEEP): a hot start on new vectors runs on the 8-lane kernel, which continues from what either kernel left;
+// kernel WRITES it (KEEP): a hot start on new vectors runs on the 8-lane kernel, which continues from what either kernel left, or in
+// the WARM builds of level 2 here, which read 20 doubles of its tail (take_limits) and never its tableau;
 // a hot start with new matrices and a warm re-initialisation read no stored tableau and run there too, or in the WARM builds here:
 // [N x N tableau, both triangles][6 fields x 8 variable slots: x g lo up gy y][4 fields x 8 constraint slots: A x, loA, upA, y][G_ll (8)]
 // [G_{8+l,8+l} (8)][ints: sv (8), sc (8), status, masks, magic, pivots since the tableau was built from the data]
@@ -1303,8 +1346,13 @@ constexpr int LANE_TINY_MAGIC = 0x7a11e;
 // Neither reads the stored tableau: the guess is x, y and the working sets (mode 2: the batch's own result pools, dense and
 // member-major, 26 values for 8 x 2; mode 3: the warm-start pools), the tableau is built for it from the new matrices by pivots
 // (setup_warm), and the homotopy is the cold start's. The call shape is the launch's (QPPools::guess_mode) or, with
-// QPPools::member_mode, a lane's own word: < 0 the member is not in the launch, 0 cold, 2, 3 (never 1: rsqp_plan_lane_fits)
-template <int MC, bool KEEP, bool UNI, int HB, int SHV, int SHC, bool WARM = false>
+// QPPools::member_mode, a lane's own word: < 0 the member is not in the launch, 0 cold, 2, 3 (level 1: never 1, rsqp_plan_lane_fits).
+// WARM == 2 also carries the word 1, the hot start on new vectors: the guess of mode 2 plus the limits the member's last homotopy
+// ended on, from the tail of its state block (take_limits); the tableau is built by pivots for the stored working set from the
+// unchanged matrices, the auxiliary limits are the stored ones, and the homotopy runs from them to the new targets (its relaxation
+// pass for a side that was infinite and is finite now included). The state write is the one of every call shape: the tableau it
+// built goes out with the working set it belongs to, whether or not the member changed it
+template <int MC, bool KEEP, bool UNI, int HB, int SHV, int SHC, int WARM = 0>
 __device__ __forceinline__ void lane_qp_body(const QPPools &P, int nq, int maxWSR) {
     static_assert(UNI || HB == MV, "the block build serves one-pattern batches");
     static_assert(!WARM || (KEEP && SHV < 0), "a hot start continues a batch that keeps its state; no full-shape build of it");
@@ -1344,14 +1392,15 @@ __device__ __forceinline__ void lane_qp_body(const QPPools &P, int nq, int maxWS
     int rcode = RET_OK, nWSR = 0, setup_pivots = 0;
     bool run = true;                       // WARM: my member is in the launch
     unsigned long long live = ~0ull;       // ... and bit j: the member of lane j is (the wave's stores leave the others' ranges alone)
-    if constexpr (WARM) {
+    unsigned long long live_state = ~0ull; // ... and writes its state block (WARM level 2: not a hot start that found its new bounds inconsistent)
+    if constexpr (WARM != 0) {
         // my call shape (a lane beyond the batch runs beside the last member, as everywhere). A member without a solved or stopped
         // QP behind it has nothing to continue from: cold, as qp_tiny.hip decides from the state word (the status pool holds the same)
         const int qown = q0 + (lane < nqw ? lane : nqw - 1);
         int mode = P.member_mode ? P.member_mode[qown] : P.guess_mode;
         run = mode >= 0;
-        live = __builtin_amdgcn_ballot_w64(run);
-        const int prev = mode == 2 ? P.status[qown] : QPS_SOLVED;       // (asked for here, looked at behind the staging)
+        live = live_state = __builtin_amdgcn_ballot_w64(run);
+        const int prev = (mode == 2 || (WARM >= 2 && mode == 1)) ? P.status[qown] : QPS_SOLVED;       // (asked for here, looked at behind the staging)
         // staging as in the cold builds; the guess behind it, through the tableau's slots (setup_warm builds the tableau again)
         typename ENG::Inflight F;
         bool early = false;
@@ -1359,29 +1408,37 @@ __device__ __forceinline__ void lane_qp_body(const QPPools &P, int nq, int maxWS
         if constexpr (ORDERED) { if (early) { E.stage_matrices(P, q0, lane, T, F); E.take_bounds(T, lane, F); } }
         if (!early) E.template stage<UNI>(P, q0, lane, nqw, T);
         E.take_guess(P, q0, lane, nqw, T);
-        if (mode == 2 && prev % 100 == QPS_NOTINITIALISED) mode = 0;
+        // level 2, a wave with a hot start on new vectors among its members: the stored limits behind the guess (take_limits)
+        if constexpr (WARM >= 2) {
+            if (__builtin_amdgcn_ballot_w64(mode == 1) != 0) E.take_limits(P.state + (long long)q0 * P.uni_state, P.uni_state, lane, nqw, T);
+        }
+        if ((mode == 2 || (WARM >= 2 && mode == 1)) && prev % 100 == QPS_NOTINITIALISED) mode = 0;
+        const bool hot = WARM >= 2 && mode == 1;
         LSTAMP(0);
         const bool bad = run && E.bounds_inconsistent();
+        if constexpr (WARM >= 2) live_state = live & ~__builtin_amdgcn_ballot_w64(bad && hot);
         if (bad || !run) {
             // qpOASES areBoundsConsistent: infeasible before any change. A hot start keeps the stored iterate, an init reports the
             // zero iterate and the empty working set (qp_tiny.hip). A member that sits out: zeros, of which nothing is stored
+            // (a hot start on new vectors keeps its state block as well, byte for byte, and the status word it holds: live_state)
             if (bad) { E.infeasible = 1; rcode = RET_INFEASIBLE; }
-            if (mode != 2) {
+            if (mode != 2 && !hot) {
                 SFOR(l, MV, E.xv[l] = 0.0; E.yv[l] = 0.0; E.sv[l] = 0;);
                 SFOR(i, MC, E.yc[i] = 0.0; E.sc[i] = 0;);
             }
+            if (hot) E.status = prev % 100;
             SFOR(l, MV, E.g[l] = E.gy[l] = 0.0; E.lo[l] = E.up[l] = 0.0;);
             SFOR(i, MC, E.ax[i] = 0.0; E.loA[i] = E.upA[i] = 0.0;);
             E.g_from_K();
         } else {
             // ONE text of the set-up: the guess of the call shape first, the cold start as the fallback when the guess has no positive
             // definite reduced Hessian (and for the cold members of the launch)
-            bool hx = mode == 2 || (mode == 3 && P.guess_x != nullptr), hy = mode == 2 || (mode == 3 && P.guess_y != nullptr);
-            bool hg = mode == 2 || (mode == 3 && P.guess_sb != nullptr), hc = mode == 2;
+            bool hx = mode == 2 || hot || (mode == 3 && P.guess_x != nullptr), hy = mode == 2 || hot || (mode == 3 && P.guess_y != nullptr);
+            bool hg = mode == 2 || hot || (mode == 3 && P.guess_sb != nullptr), hc = mode == 2 || hot, ht = hot;
             bool ok = false;
             for (int attempt = 0; attempt < 2 && !ok; attempt++) {
-                ok = E.setup_warm(hx, hy, hg, hc, P.reinit_from_y0 != 0);
-                hx = hy = hg = hc = false;
+                ok = E.setup_warm(hx, hy, hg, hc, P.reinit_from_y0 != 0, ht);
+                hx = hy = hg = hc = ht = false;
             }
             setup_pivots = E.nFR() + E.nAC();
             if (!ok) rcode = RET_SETUP_FAILED;
@@ -1452,15 +1509,15 @@ __device__ __forceinline__ void lane_qp_body(const QPPools &P, int nq, int maxWS
         double dg[N];
         SFOR(k, N, dg[k] = E.G[tri(k, k) * WL];);
         E.wave_sync();
-        E.state_put_tableau(sbase, P.uni_state, nqw, lane, T, live);
+        E.state_put_tableau(sbase, P.uni_state, nqw, lane, T, live_state);
         E.wave_sync();
         E.template tail_put_half<0>(E.G, dg, pivots);
         E.wave_sync();
-        E.state_put_tail_half(sbase, P.uni_state, nqw, lane, T, 0, live);
+        E.state_put_tail_half(sbase, P.uni_state, nqw, lane, T, 0, live_state);
         E.wave_sync();
         E.template tail_put_half<1>(E.G, dg, pivots);
         E.wave_sync();
-        E.state_put_tail_half(sbase, P.uni_state, nqw, lane, T, 1, live);
+        E.state_put_tail_half(sbase, P.uni_state, nqw, lane, T, 1, live_state);
         LSTAMP(15);
     }
     // ---- results (x, y = [bounds; constraints], working set, status / nWSR / objective): the member-major vectors leave through the
@@ -1501,7 +1558,7 @@ __device__ __forceinline__ void lane_qp_body(const QPPools &P, int nq, int maxWS
     LSTAMP(4);
 }
 
-template <int MC, bool KEEP, bool UNI, int HB, bool WARM = false>
+template <int MC, bool KEEP, bool UNI, int HB, int WARM = 0>
 __global__ void __launch_bounds__(WL) lane_qp_kernel(QPPools P, int nq, int maxWSR) {
     lane_qp_body<MC, KEEP, UNI, HB, -1, -1, WARM>(P, nq, maxWSR);
 }
@@ -1524,12 +1581,23 @@ hipError_t rsqp_launch_lane_qp(const SmallPlan &pl, const QPPools &p, int nq, in
         return hipGetLastError();
     }
     if (pl.lane_shape != 0) return hipErrorInvalidValue;
+    if (pl.lane_warm && pl.lane_hot) {
+        // ... and hot starts on new vectors, alone or among the members' own words (rsqp_plan_lane_fits; rsqp_batch_set_lane_hot)
+        switch (pl.mc * 1000 + pl.keep * 100 + pl.uni * 10 + pl.hb) {
+        case 2114: hipLaunchKernelGGL((lane_qp_kernel<2, true, true, 4, 2>), grid, block, 0, stream, p, nq, maxWSR); break;
+        case 2118: hipLaunchKernelGGL((lane_qp_kernel<2, true, true, 8, 2>), grid, block, 0, stream, p, nq, maxWSR); break;
+        case 2108: hipLaunchKernelGGL((lane_qp_kernel<2, true, false, 8, 2>), grid, block, 0, stream, p, nq, maxWSR); break;
+        default: return hipErrorInvalidValue;
+        }
+        return hipGetLastError();
+    }
+    if (pl.lane_hot) return hipErrorInvalidValue;
     if (pl.lane_warm) {
         // hot starts with new matrices / warm re-initialisations (rsqp_plan_lane_fits): the builds that keep the state
         switch (pl.mc * 1000 + pl.keep * 100 + pl.uni * 10 + pl.hb) {
-        case 2114: hipLaunchKernelGGL((lane_qp_kernel<2, true, true, 4, true>), grid, block, 0, stream, p, nq, maxWSR); break;
-        case 2118: hipLaunchKernelGGL((lane_qp_kernel<2, true, true, 8, true>), grid, block, 0, stream, p, nq, maxWSR); break;
-        case 2108: hipLaunchKernelGGL((lane_qp_kernel<2, true, false, 8, true>), grid, block, 0, stream, p, nq, maxWSR); break;
+        case 2114: hipLaunchKernelGGL((lane_qp_kernel<2, true, true, 4, 1>), grid, block, 0, stream, p, nq, maxWSR); break;
+        case 2118: hipLaunchKernelGGL((lane_qp_kernel<2, true, true, 8, 1>), grid, block, 0, stream, p, nq, maxWSR); break;
+        case 2108: hipLaunchKernelGGL((lane_qp_kernel<2, true, false, 8, 1>), grid, block, 0, stream, p, nq, maxWSR); break;
         default: return hipErrorInvalidValue;
         }
         return hipGetLastError();

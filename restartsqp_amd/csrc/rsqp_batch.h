@@ -142,6 +142,9 @@ struct rsqp_batch {
     // the members' stored states, which such a hot start assumes -- rsqp_batch_set_results has overwritten them, or a hand-over launch
     // has run, since the last call whose first launch ran everybody without one (launch_batch)
     bool lane_warm = false, results_foreign = false;
+    // rsqp_batch_set_lane_hot: where lane_warm_ok holds, hot starts on new vectors and optimize calls whose update marks are per
+    // member go to the WARM builds of level 2 as well. Alone it changes nothing
+    bool lane_hot = false;
     int qp_maxiter = 1000;                // rsqp_batch_set_options
     bool mats_updated = false;            // rsqp_batch_set_matrix_values since the last optimize call (Update_A / Update_H of everybody)
     bool opt_started = false;             // an rsqp_batch_optimize_qp has run: members are in different states from here on
@@ -161,10 +164,12 @@ namespace rsqp_batch_units {
 // rsqp_batch.hip
 QPPools pools_of(rsqp_batch *b, bool lp);
 int batch_family(const rsqp_batch *b, const QPPools &p, bool lp);
-// warm: the launch may take a WARM build of the lane-per-problem kernel (lane_warm_ok, and what the caller knows of the call)
-int launch_batch(rsqp_batch *b, QPPools &p, int mode, int max_nWSR, bool first, bool lp, bool warm = false);
+// warm: the launch may take a WARM build of the lane-per-problem kernel (lane_warm_ok, and what the caller knows of the call): 1, or
+// 2 = one that carries hot starts on new vectors as well (lane_warm_level)
+int launch_batch(rsqp_batch *b, QPPools &p, int mode, int max_nWSR, bool first, bool lp, int warm = 0);
 // the batch's side of SmallFacts::lane_warm: the switch is on, nothing is handed over, the result pools are the batch's own
 bool lane_warm_ok(const rsqp_batch *b);
+int lane_warm_level(const rsqp_batch *b);
 // where a solve / optimize call begins: the hand-over flags and their count cleared (on the stream) when the switch is on
 int begin_handover(rsqp_batch *b);
 int ensure_opt(rsqp_batch *b);

@@ -263,10 +263,11 @@ int ensure_warm_pools(rsqp_batch *b) {
 
 // the plan of a launch on this batch (rsqp_small_plan.h): the batch remembers by itself when a launch keeps no state.
 // handover: the plan of the same launch without the hs071-scale tableau kernels, as rsqp_solve plans its retry on a handle
-static SmallPlan plan_of(const rsqp_batch *b, const QPPools &p, int mode, bool lp, bool handover = false, bool warm = false) {
+static SmallPlan plan_of(const rsqp_batch *b, const QPPools &p, int mode, bool lp, bool handover = false, int warm = 0) {
     SmallFacts f = rsqp_small_facts(p, b->hbm, b->state_engine);
     f.skip_mark = 1;
-    f.lane_warm = (warm && !lp && !handover) ? 1 : 0;
+    f.lane_warm = (warm >= 1 && !lp && !handover) ? 1 : 0;
+    f.lane_hot = (warm >= 2 && !lp && !handover) ? 1 : 0;
     SmallKnobs k = knobs_of(b, lp);
     if (handover && k.no_tiny == 0) k.no_tiny = 1;
     return rsqp_plan_small_launch(k, f, b->nq, b->nVmax, b->nCmax, b->mat_bytes_max, mode);
@@ -278,14 +279,16 @@ int batch_family(const rsqp_batch *b, const QPPools &p, bool lp) { return plan_o
 // a handed member leaves a state block the result pools do not describe, and pools rsqp_batch_set_results has written are not the
 // batch's own answer: either way a hot start with new matrices must read the stored state, which the 8-lane kernel does
 bool lane_warm_ok(const rsqp_batch *b) { return b->lane_warm && !b->handover && !b->results_foreign; }
+// the `warm` word of launch_batch for a call the WARM builds may take: 2 with rsqp_batch_set_lane_hot on as well, else 1
+int lane_warm_level(const rsqp_batch *b) { return b->lane_hot ? 2 : 1; }
 
 // one solve launch of the whole batch (p.member_mode: of the members it names). first: the launch rsqp_batch_get_last_kernel reports;
 // lp: a launch of rsqp_batch_optimize_lp (pools_of, knobs_of)
-int launch_batch(rsqp_batch *b, QPPools &p, int mode, int max_nWSR, bool first, bool lp, bool warm) {
+int launch_batch(rsqp_batch *b, QPPools &p, int mode, int max_nWSR, bool first, bool lp, int warm) {
     const SmallPlan pl = plan_of(b, p, mode, lp, false, warm);
     if (pl.lane_warm) {
         // the guess of the WARM builds (QPPools::guess_*). A warm re-initialisation: what the caller gave; a hot start with new
-        // matrices and per-member modes: the result pools -- the plan kernel of rsqp_batch_optimize_qp has copied a mode-3
+        // matrices or on new vectors and per-member modes: the result pools -- the plan kernel of rsqp_batch_optimize_qp has copied a mode-3
         // member's x, y and bound statuses from there into the warm-start pools, so they hold the same values
         const bool reinit = !p.member_mode && pl.mode == RSQP_MODE_WARM_REINIT;
         p.guess_x = reinit ? p.x0 : b->x.p; p.guess_y = reinit ? p.y0 : b->y.p; p.guess_sb = reinit ? p.guess_b : b->ws_b.p;
@@ -357,8 +360,9 @@ extern "C" int rsqp_batch_solve(rsqp_batch *b, int mode, int max_nWSR) {
     if (rc != RSQP_OK) return rc;
     if (!b->timing) HIPCHK(hipEventRecord(b->ev0, b->stream));
     // (a warm re-initialisation reads the warm-start pools, whoever wrote the result pools)
+    // (a hot start on new vectors goes there with rsqp_batch_set_lane_hot on as well: the plan reads the level)
     const bool warm = mode == RSQP_MODE_WARM_REINIT ? (b->lane_warm && !b->handover) : lane_warm_ok(b);
-    if ((rc = launch_batch(b, p, mode, max_nWSR, true, false, warm)) != RSQP_OK) return rc;
+    if ((rc = launch_batch(b, p, mode, max_nWSR, true, false, warm ? lane_warm_level(b) : 0)) != RSQP_OK) return rc;
     b->cert_lp = false;
     if (!b->timing) HIPCHK(hipEventRecord(b->ev1, b->stream));
     return RSQP_OK;
@@ -388,6 +392,16 @@ extern "C" int rsqp_batch_set_lane_warm(rsqp_batch *b, int on) {
 extern "C" int rsqp_batch_get_lane_warm(const rsqp_batch *b) {
     if (!b) return fail(RSQP_ERR_ARG, "null batch");
     return b->lane_warm ? 1 : 0;
+}
+
+extern "C" int rsqp_batch_set_lane_hot(rsqp_batch *b, int on) {
+    if (!b) return fail(RSQP_ERR_ARG, "null batch");
+    b->lane_hot = on != 0;
+    return RSQP_OK;
+}
+extern "C" int rsqp_batch_get_lane_hot(const rsqp_batch *b) {
+    if (!b) return fail(RSQP_ERR_ARG, "null batch");
+    return b->lane_hot ? 1 : 0;
 }
 
 extern "C" int rsqp_batch_set_handover(rsqp_batch *b, int on) {

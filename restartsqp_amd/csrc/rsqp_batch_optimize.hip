@@ -142,7 +142,7 @@ int begin_optimize(rsqp_batch *b, int kind) {
 }
 
 // the solve launch behind a plan kernel: every member starts as word `word` of its opt block says (QPPools::member_mode)
-int launch_members(rsqp_batch *b, QPPools &p, int word, int mode, int max_nWSR, bool first, bool lp, bool warm = false) {
+int launch_members(rsqp_batch *b, QPPools &p, int word, int mode, int max_nWSR, bool first, bool lp, int warm = 0) {
     p.member_mode = b->opt.p + (size_t)word * b->nq;
     return launch_batch(b, p, mode, max_nWSR, first, lp, warm);
 }
@@ -296,8 +296,10 @@ extern "C" int rsqp_batch_optimize_qp(rsqp_batch *b, int *nWSR_used) {
         p.x0 = b->wx0.p; p.y0 = b->wy0.p; p.guess_b = b->wgb.p;     // the flip: all three (:204-206)
         // with the batch-wide update mark rsqp_dispatch_mode gives every member 0, 2 or 3, never 1 (updated = true), which the host
         // knows without a look at the device: the launch may go to the lane-per-problem kernel's WARM build
-        // (rsqp_batch_set_lane_warm). Per-member marks alone, the rescue launch and the LP calls stay where they were
-        rc = launch_members(b, p, OPT_MODE, RSQP_MODE_COLD, b->qp_maxiter, true, false, b->mats_updated && lane_warm_ok(b));
+        // (rsqp_batch_set_lane_warm). With rsqp_batch_set_lane_hot on as well the build carries the word 1 too, and the marks no longer
+        // matter: batch-wide, per member or absent. The rescue launch and the LP calls stay where they were
+        rc = launch_members(b, p, OPT_MODE, RSQP_MODE_COLD, b->qp_maxiter, true, false,
+                            (lane_warm_ok(b) && (b->mats_updated || b->lane_hot)) ? lane_warm_level(b) : 0);
     }
     if (rc != RSQP_OK) return rc;
     // (also behind a call nobody took part in: its plan kernel has written -1 into the mode words, which the uniform cold launch

@@ -88,13 +88,15 @@ struct QPPools {
                       //    kernels, which is then ignored); a negative value = the member is not in this launch and nothing of it is
                       //    touched. In one launch every mode-3 member has the same warm-start inputs present (x0 / y0 / guess_b are
                       //    batch-wide pointers). The lane-per-problem kernel takes such a launch in its WARM builds alone, where the host
-                      //    knows that no member's word is 1 (rsqp_plan_lane_fits; rsqp_batch_set_lane_warm)
+                      //    knows that no member's word is 1 (rsqp_plan_lane_fits; rsqp_batch_set_lane_warm), or in those of level 2,
+                      //    which carry the word 1 as well (rsqp_batch_set_lane_hot)
     // the WARM builds of the lane-per-problem kernel (qp_lane.hip; set by launch_batch where the plan says SmallPlan::lane_warm): the
     // guess a member's set-up starts from -- x, y = [bounds; constraints], bound statuses, constraint statuses, member-major like
     // the results; any of them null, uniform over the launch. A hot start with new matrices: the batch's own result pools (the
     // kernel reads a wave's members before it writes them); a warm re-initialisation: the warm-start pools, guess_sc null
     const double *guess_x, *guess_y; const int *guess_sb, *guess_sc;
-    int guess_mode;   // the call shape of such a launch without member_mode: 2 or 3
+    int guess_mode;   // the call shape of such a launch without member_mode: 2 or 3; level 2 also 1, a hot start on new vectors, whose
+                      //    guess is the one of mode 2 plus the limits in the tails of the members' state blocks (`state`, `uni_state`)
 };
 
 // optimizeQP's choice of the call shape (src/qpOASESInterface.cpp:150-208) from get_Matrix_change_status (:817-833), stated ONCE for

@@ -18,6 +18,9 @@ struct SmallFacts {
     // WARM build of the lane-per-problem kernel -- the batch's switch is on (rsqp_batch_set_lane_warm), its result pools hold its
     // own last answer, nothing is handed over, and a launch with member_mode carries no member whose word is 1
     int lane_warm;
+    // the CALLER's word beside it (rsqp_batch_set_lane_hot; read only where lane_warm is set): a hot start on new vectors (mode 1), and
+    // a launch with member_mode whatever its members' words say, may take the builds that carry the word 1 as well
+    int lane_hot;
 };
 inline SmallFacts rsqp_small_facts(const QPPools &p, bool hbm, int state_engine) {
     return SmallFacts{p.tiny_ok, p.uniV, p.uniC, p.uni_pat, p.desc != nullptr, p.keep_state, p.skip_mark, p.member_mode != nullptr,
@@ -38,6 +41,8 @@ struct SmallPlan {
     int mc = 0, keep = 0, uni = 0, hb = 0;
     int lane_warm = 0;    // lane_qp_kernel<mc, keep, uni, hb, WARM = true>: a hot start with new matrices / a warm re-initialisation (mode 2 / 3, or
                           //   per-member modes 0 / 2 / 3) on the lane-per-problem kernel; the launcher sets QPPools::guess_* (not among the exported words)
+    int lane_hot = 0;     // beside lane_warm: lane_qp_kernel<mc, keep, uni, hb, WARM = 2>, which also carries a hot start on new vectors (mode 1, or a
+                          //   member's word 1): the guess plus the stored limits of the state blocks' tails (not among the exported words)
     int lane_shape = 0;   // lane_qp_shape_kernel<mc, keep, uni, hb, NV, NC>: NV * 256 + NC of the lane kernel's full-shape build, else 0 (not
                           //   among the exported words: the build FAMILY stays (keep, uni, hb); rsqp_batch_get_lane_shape reports it)
     int first = 0;       // the mid-size tableau kernel goes first (qp_small_g.h): 1 small_qpg_kernel<3, 1, 9, 4>, 2 <2, 2, 8, 8>; 0 no
@@ -72,18 +77,21 @@ inline int rsqp_plan_is_tiny(const SmallKnobs &kn, const SmallFacts &f, int nVma
 // (the handle remembers: QPPools::skip_mark).
 // 2 (the WARM builds): with the caller's word SmallFacts::lane_warm, a batch that keeps its state also brings its hot starts with new
 // matrices (mode 2), its warm re-initialisations (mode 3, whatever inputs are present) and launches with per-member modes. A hot
-// start on new vectors (mode 1) continues from the stored tableau and stays on the 8-lane kernel
+// start on new vectors (mode 1) continues from the stored tableau and stays on the 8-lane kernel, unless the caller says
+// SmallFacts::lane_hot as well:
+// 3 (the WARM builds of level 2): a hot start on new vectors, or a launch with per-member modes one of whose words may be 1
 inline int rsqp_plan_lane_fits(const SmallKnobs &kn, const SmallFacts &f, int skip_mark, int nq, int nVmax, int nCmax, int mode) {
     if (kn.lane == 0) return 0;
     // one shape (every member nV x nC); one sparsity pattern (member 0's arrays serve all) or patterns of their own (each lane walks its own)
     if (!(f.uniV >= 1 && f.uniV <= 8 && f.uniC >= 0 && f.uniC <= 2 && nVmax <= 8 && nCmax <= 2 && (f.uni_pat || f.desc))) return 0;
-    const bool warm = f.lane_warm && f.keep_state && (f.member_mode || mode == 2 || mode == 3);
+    const bool hot = f.lane_warm && f.lane_hot && f.keep_state && (f.member_mode || mode == 1);
+    const bool warm = hot || (f.lane_warm && f.keep_state && (f.member_mode || mode == 2 || mode == 3));
     if (!warm && (mode != 0 || f.member_mode || f.x0 || f.y0 || f.guess_b)) return 0;
     if ((!f.keep_state && !skip_mark) || f.cert_out || f.done_flag || !f.tiny_ok) return 0;
     // (measured, tools/lane_vs_tiny_sweep.py: a launch of this kernel takes 36 us up to 16 384 problems and 43 us at 65 536 -- one
     //  round of waves either way; the 8-lane kernel holds 16 384 problems at a time: 21 us up to 8 192, 26 us at 16 384, 40 us at
     //  20 480 (second round), 47 us at 32 768, 90 us at 65 536. With the state kept, 65 536 members: 0.075 against 0.132 ms)
-    return nq >= (kn.lane > 0 ? kn.lane : 16385) ? (warm ? 2 : 1) : 0;
+    return nq >= (kn.lane > 0 ? kn.lane : 16385) ? (hot ? 3 : (warm ? 2 : 1)) : 0;
 }
 
 // doubles / 16-bit integers of the LDS image of a formulation, as Engine<L, ML, REGV>::image_doubles (qp_small_engine.h) and
@@ -134,7 +142,7 @@ inline SmallPlan rsqp_plan_small_launch(const SmallKnobs &kn, const SmallFacts &
         pl.hb = (f.uni_pat && f.lane_hblock == 4 && !f.uni_hreg) ? 4 : 8;
         pl.uni = (pl.hb == 4 || f.uni_pat) ? 1 : 0;
         // the full shape of that kernel, one pattern, H as its block: the build with nV and nC as constants (RSQP_LANE_SHAPE=0: never)
-        pl.lane_warm = lane_fit == 2 ? 1 : 0;
+        pl.lane_warm = lane_fit >= 2 ? 1 : 0; pl.lane_hot = lane_fit == 3 ? 1 : 0;
         if (!pl.lane_warm && kn.lane_shape != 0 && f.uniV == 8 && f.uniC == 2 && f.uni_pat && pl.hb == 4) pl.lane_shape = 8 * 256 + 2;
         pl.grid = (unsigned)((nq + kLaneBlock - 1) / kLaneBlock); pl.block = kLaneBlock;
         return pl;

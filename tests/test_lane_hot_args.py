@@ -1,0 +1,58 @@
+"""CPU-side checks of the switch that sends a batch's hot starts on new vectors to the lane-per-problem kernel
+(include/rsqp_hip_lane_hot.h, which include/rsqp_hip.h includes: rsqp_batch_set_lane_hot, rsqp_batch_get_lane_hot): declared,
+exported, bound through a table of their own, and a null batch is an argument error before any device call. The behaviour itself
+needs a GPU: tests/test_gpu_lane_hot.py. (That rsqp_describe_small_launch still reproduces every golden plan -- the switch is a word
+its callers leave at 0 -- is tests/test_small_launch_plan.py's.)"""
+import os
+import re
+
+from conftest import ROOT
+
+NEW = ("rsqp_batch_set_lane_hot", "rsqp_batch_get_lane_hot")
+
+
+def test_entry_points_are_declared_exported_and_bound(capi):
+    main = open(os.path.join(ROOT, "include", "rsqp_hip.h")).read()
+    assert re.search(r'^#include "rsqp_hip_lane_hot.h"', main, flags=re.M)
+    header = open(os.path.join(ROOT, "include", "rsqp_hip_lane_hot.h")).read()
+    L = capi.lib()
+    for name in NEW:
+        assert re.search(r"\bint\s+%s\s*\(" % name, header), name
+        assert name in capi.LANE_HOT_SYMBOLS and hasattr(L, name), name
+        assert getattr(L, name).argtypes == capi.LANE_HOT_SYMBOLS[name][1]
+    declared = set(re.findall(r"^\s*int\s+(rsqp_\w+)\s*\(", header, flags=re.M))
+    assert declared == set(capi.LANE_HOT_SYMBOLS) == set(NEW)
+    # ... and in no other table or header: rsqp_hip.h's own declarations and the three older extensions stay what they were
+    for table in (capi.SYMBOLS, capi.LANE_SYMBOLS, capi.HANDOVER_SYMBOLS, capi.LANE_WARM_SYMBOLS):
+        assert not declared & set(table)
+    for other in ("rsqp_hip.h", "rsqp_hip_lane.h", "rsqp_hip_handover.h", "rsqp_hip_lane_warm.h"):
+        text = open(os.path.join(ROOT, "include", other)).read()
+        for name in NEW:
+            assert not re.search(r"\b%s\s*\(" % name, text), (other, name)
+    assert callable(capi.Batch.set_lane_hot) and callable(capi.Batch.lane_hot)
+    # the header says that the switch does nothing alone
+    assert "rsqp_batch_set_lane_warm" in header and "alone it changes nothing" in header
+
+
+def test_null_batch_is_an_argument_error(capi):
+    L = capi.lib()
+    assert L.rsqp_batch_set_lane_hot(None, 1) == capi.ERR_ARG
+    assert L.rsqp_batch_set_lane_hot(None, 0) == capi.ERR_ARG
+    assert L.rsqp_batch_get_lane_hot(None) == capi.ERR_ARG
+    assert L.rsqp_last_error()
+
+
+def test_the_launch_plan_words_do_not_name_the_switch(capi):
+    """the switch is a batch's own: no word of rsqp_describe_small_launch carries it, and a plan described through that entry point
+    never takes the build for hot starts on new vectors -- such a start, and a launch with per-member modes, of a batch the lane
+    kernel takes stays on the 8-lane kernel there"""
+    assert len(capi.SMALL_LAUNCH_IN) == 27 and len(capi.SMALL_LAUNCH_OUT) == 20
+    assert not any("hot" in w for w in capi.SMALL_LAUNCH_IN + capi.SMALL_LAUNCH_OUT)
+    words = dict(engine=-1, lanes=-1, waves=-1, no_tiny=0, lane=1, nq=200, nVmax=8, nCmax=2, mat_bytes_max=1024, mode=0, hbm=0,
+                 state_engine=1, tiny_ok=1, uniV=8, uniC=2, uni_pat=1, desc=1, keep_state=1, skip_mark=1, member_mode=0, done_flag=0,
+                 cert_out=0, x0=0, y0=0, guess_b=0, lane_hblock=8, uni_hreg=0)
+    assert capi.describe_small_launch(**words)["family"] == 2
+    plan = capi.describe_small_launch(**dict(words, mode=capi.MODE_HOT_VECTORS))
+    assert plan["family"] == 1 and plan["mode"] == capi.MODE_HOT_VECTORS
+    assert capi.describe_small_launch(**dict(words, member_mode=1))["family"] == 1
+    assert capi.describe_small_launch(**dict(words, member_mode=1, mode=capi.MODE_HOT_VECTORS))["family"] == 1
