@@ -564,4 +564,6 @@ int rsqp_dense_chol_inverse(int n, double *G, double *Ginv, double pd_rel, doubl
 #include "rsqp_hip_lane_warm.h"
 /* hot starts on new vectors on that kernel (set / get of the switch): the same way */
 #include "rsqp_hip_lane_hot.h"
+/* the dense building blocks called the way the engine calls them, and the GEMM's launch plan (verification): the same way */
+#include "rsqp_hip_dense_check.h"
 #endif

@@ -157,6 +157,20 @@ LANE_HOT_SYMBOLS = {
     "rsqp_batch_set_lane_hot": (C.c_int, [C.c_void_p, C.c_int]),
     "rsqp_batch_get_lane_hot": (C.c_int, [C.c_void_p]),
 }
+# ... and of include/rsqp_hip_dense_check.h (the dense building blocks called the way the engine calls them; the GEMM's launch plan)
+_ll = C.c_longlong
+_buf = [dp, _ll, _ll, _ll]      # a whole host buffer: pointer, length, offset and leading dimension of the operand inside it
+DENSE_CHECK_SYMBOLS = {
+    "rsqp_dense_describe_gemm": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ll, ip, C.c_int]),
+    "rsqp_dense_check_gemm": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double] + 3 * _buf + [_ll]),
+    "rsqp_dense_check_work_create": (C.c_int, [_ll, C.POINTER(C.c_void_p)]),
+    "rsqp_dense_check_work_destroy": (C.c_int, [C.c_void_p]),
+    "rsqp_dense_check_qr": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double] + 3 * _buf + [ip, ip]),
+    "rsqp_dense_check_chol": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double] + 3 * _buf + [ip]),
+}
+DENSE_GEMM_PLAIN, DENSE_GEMM_UPPER, DENSE_GEMM_KTRI1, DENSE_GEMM_KTRI2, DENSE_GEMM_KTRI3 = range(5)      # RSQP_DENSE_GEMM_*
+DENSE_INV_UPPER, DENSE_INV_MIRROR, DENSE_INV_TRI2 = range(3)                                            # RSQP_DENSE_INV_*
+DENSE_PLAN_OUT = ("TM", "TN", "splits", "kc", "skinny")                                                 # the words of rsqp_dense_describe_gemm
 
 
 class OptimalityStatus(C.Structure):
@@ -190,7 +204,7 @@ def lib():
         _TORCH_FIRST = "torch" in sys.modules
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SYMBOLS.items()) + list(LANE_SYMBOLS.items()) + list(HANDOVER_SYMBOLS.items()) + \
-                list(LANE_WARM_SYMBOLS.items()) + list(LANE_HOT_SYMBOLS.items()):
+                list(LANE_WARM_SYMBOLS.items()) + list(LANE_HOT_SYMBOLS.items()) + list(DENSE_CHECK_SYMBOLS.items()):
             f = getattr(L, name)
             f.restype = res
             f.argtypes = args
@@ -214,6 +228,14 @@ def describe_small_launch(**words):
     out = np.zeros(len(SMALL_LAUNCH_OUT), np.int32)
     check(lib().rsqp_describe_small_launch(_ip(a), len(a), _ip(out), len(out)))
     return dict(zip(SMALL_LAUNCH_OUT, out.tolist()))
+
+
+def describe_dense_gemm(m, n, k, batch=1, ws_cap=None):
+    """the launch plan of the dense GEMM for an m x n result with inner dimension k as a dict over DENSE_PLAN_OUT; ws_cap: the
+    doubles of the split-K workspace the launcher is given (None: none). Needs no GPU (rsqp_dense_describe_gemm)"""
+    out = np.zeros(len(DENSE_PLAN_OUT), np.int32)
+    check(lib().rsqp_dense_describe_gemm(m, n, k, batch, int(ws_cap is not None), ws_cap or 0, _ip(out), len(out)))
+    return dict(zip(DENSE_PLAN_OUT, out.tolist()))
 
 
 def plan_builds(plan):

@@ -1,7 +1,7 @@
 // dense_la.hip -- dense f64 building blocks for gfx950 (see rsqp_dense.h).
 //
 //   * k_dgemm: LDS-tiled GEMM on v_mfma_f64_16x16x4_f64. Workgroup = 8 waves (2 x 4) on a 128 x 128
-//     tile or 4 waves (2 x 2) on 64-wide tiles, K step 16. Both operand tiles are staged in LDS as [k][index] so that the
+//     tile or 4 waves (2 x 2) on a 128 x 64 or 64 x 64 tile (three builds: dgemm_plan), K step 16. Both operand tiles are staged in LDS as [k][index] so that the
 //     fragment of an MFMA (lane l: index l & 15, k = l >> 4) is one ds_read_b64 with 16 consecutive
 //     lanes on consecutive words; the next K tile is fetched into registers while the current one
 //     is multiplied. The roles of the two MFMA operands are swapped (D = B_frag x A_frag) so that
@@ -12,6 +12,8 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <limits>
+#include <vector>
 
 #include "rsqp_dense.h"
 #include "rsqp_internal.h"
@@ -218,12 +220,14 @@ __global__ void k_splitk_reduce(int m, int n, int splits, const double *__restri
 
 }  // namespace
 
-static hipError_t dgemm_ws(bool transA, bool transB, int m, int n, int k, double alpha, const double *A, long long lda,
-                           const double *B, long long ldb, double beta, double *C, long long ldc, double *ws,
-                           long long ws_cap, hipStream_t st, int upper = 0, int ktri = 0, int batch = 1, long long sA = 0,
-                           long long sB = 0, long long sC = 0) {
-    if (m <= 0 || n <= 0) return hipSuccess;
-    const int ta = transA ? 1 : 0, tb = transB ? 1 : 0;
+// The launch plan of one product (m, n >= 1): which build of k_dgemm (its tile TM x TN), into how many slices of kc the inner
+// dimension is split (splits == 1: kc == k), and whether the forced 128 x 128 "skinny" case applies. The ONE place where this is
+// decided: dgemm_ws launches what it says, rsqp_dense_describe_gemm (rsqp_hip_dense_check.h) shows it without a GPU.
+// The build <64, 128> does not exist: TM = 64 needs m <= 64 (then ceil(m/64) = ceil(m/128) = 1) or ceil(m/64) ceil(n/128) batch
+// < 512; TN = 128 behind it needs that same product >= 512 -- so m <= 64, and the product equals `big`, which is < 512 here
+// (tests/test_dense_plan.py enumerates it).
+struct DgemmPlan { int TM, TN, splits, kc, skinny; };
+static DgemmPlan dgemm_plan(int m, int n, int k, int batch, bool have_ws, long long ws_cap) {
     // large tiles when they still give every CU work, small ones otherwise
     const long long big = (long long)((m + 127) / 128) * ((n + 127) / 128) * std::max(batch, 1);
     int TM = 128, TN = 128;
@@ -233,18 +237,30 @@ static hipError_t dgemm_ws(bool transA, bool transB, int m, int n, int k, double
     }
     // a block of reflectors against a wide matrix (W = V'C: 256 x n with an inner dimension of thousands): the large tile,
     // and K split so that the chip has work -- 64 x 64 tiles ran these at 29-35 TFLOP/s
-    const bool skinny_case = ws && m <= 512 && m >= 128 && n >= 1024 && k >= 2048 && ws_cap >= 2LL * m * n;
+    const bool skinny_case = have_ws && m <= 512 && m >= 128 && n >= 1024 && k >= 2048 && ws_cap >= 2LL * m * n;
     if (skinny_case) { TM = 128; TN = 128; }
     const int bx = (m + TM - 1) / TM, by = (n + TN - 1) / TN;
     // a long inner dimension over few output tiles: split K so that the chip has work
     int splits = 1;
-    if (ws && ((long long)bx * by < 200 || skinny_case) && k >= 1024) {
+    if (have_ws && ((long long)bx * by < 200 || skinny_case) && k >= 1024) {
         splits = (int)std::min<long long>(std::min<long long>((511 + (long long)bx * by) / ((long long)bx * by), k / 256), ws_cap / ((long long)m * n));
         if (splits < 2) splits = 1;
     }
     int kc = k;
     if (splits > 1) { kc = ((k + splits - 1) / splits + 31) / 32 * 32; splits = (k + kc - 1) / kc; }
     if (batch > 1) splits = 1;
+    return DgemmPlan{TM, TN, splits, kc, skinny_case ? 1 : 0};
+}
+
+static hipError_t dgemm_ws(bool transA, bool transB, int m, int n, int k, double alpha, const double *A, long long lda,
+                           const double *B, long long ldb, double beta, double *C, long long ldc, double *ws,
+                           long long ws_cap, hipStream_t st, int upper = 0, int ktri = 0, int batch = 1, long long sA = 0,
+                           long long sB = 0, long long sC = 0) {
+    if (m <= 0 || n <= 0) return hipSuccess;
+    const int ta = transA ? 1 : 0, tb = transB ? 1 : 0;
+    const DgemmPlan pl = dgemm_plan(m, n, k, batch, ws != nullptr, ws_cap);
+    const int TM = pl.TM, TN = pl.TN, splits = pl.splits, kc = pl.kc;
+    const int bx = (m + TM - 1) / TM, by = (n + TN - 1) / TN;
     dim3 grid(bx, by, batch > 1 ? batch : splits);
     double *Cout = splits > 1 ? ws : C;
     const long long ldo = splits > 1 ? m : ldc;
@@ -261,9 +277,9 @@ static hipError_t dgemm_ws(bool transA, bool transB, int m, int n, int k, double
     // measured on 4096^3: 8 waves (4 resident per SIMD, 122 VGPRs) 53.5 TFLOP/s; 4 waves x 2 resident
     // 51.5; 4 waves x 1 resident (the compiler's default allocation) 37.8; K step 32 is slower (spills)
     if (TM == 128 && TN == 128) GEMM_LAUNCH(128, 128, 8, 4, RSQP_GEMM_GK);
-    else if (TM == 64 && TN == 128) GEMM_LAUNCH(64, 128, 4, 3, 16);
     else if (TM == 128 && TN == 64) GEMM_LAUNCH(128, 64, 4, 3, 16);
-    else GEMM_LAUNCH(64, 64, 4, 4, 16);
+    else if (TM == 64 && TN == 64) GEMM_LAUNCH(64, 64, 4, 4, 16);
+    else return hipErrorInvalidValue;      // (a plan no build serves: dgemm_plan yields none)
 #undef GEMM_LAUNCH
     if (splits > 1) {
         const long long tot = (long long)m * n;
@@ -860,23 +876,35 @@ __global__ void k_get_diag(int n, const double *__restrict__ G, long long ldg, d
 
 }  // namespace
 
+// every double array of a workspace for mmax rows and how many doubles it holds (rsqp_dense_work_alloc allocates these; the check
+// entry points at the end of this file fill them)
+constexpr int DW_ARRAYS = 11;
+static void dense_work_layout(RsqpDenseWork *w, long long mmax, double **(&p)[DW_ARRAYS], long long (&sz)[DW_ARRAYS]) {
+    const long long np = (mmax + NB - 1) / NB;
+    int a = 0;
+    p[a] = &w->V; sz[a++] = mmax * OB;
+    p[a] = &w->T; sz[a++] = np * NB * NB;
+    p[a] = &w->W; sz[a++] = mmax * OB;
+    p[a] = &w->W2; sz[a++] = mmax * OB;
+    p[a] = &w->T2; sz[a++] = 2LL * OB * OB + (long long)OB * NB;      // T2, S2, tmp
+    p[a] = &w->Tout; sz[a++] = ((mmax + OB - 1) / OB) * OB * OB;
+    p[a] = &w->tau; sz[a++] = 2 * mmax;                                // tau, rdiag
+    p[a] = &w->norm2; sz[a++] = mmax;
+    p[a] = &w->dblk; sz[a++] = 66LL * NB * NB;                         // S, Uinv + split-K slabs
+    p[a] = &w->ws; sz[a++] = 4LL * OB * mmax;                          // = ws_cap
+    p[a] = &w->hr; sz[a++] = 3LL * NB * NB;
+}
+
 hipError_t rsqp_dense_work_alloc(RsqpDenseWork *w, long long mmax) {
     rsqp_dense_work_free(w);
     if (mmax < 1) mmax = 1;
-    const long long np = (mmax + NB - 1) / NB;
     hipError_t e;
-    if ((e = hipMalloc((void **)&w->V, sizeof(double) * mmax * OB)) != hipSuccess) return e;
-    if ((e = hipMalloc((void **)&w->T, sizeof(double) * np * NB * NB)) != hipSuccess) return e;
-    if ((e = hipMalloc((void **)&w->W, sizeof(double) * mmax * OB)) != hipSuccess) return e;
-    if ((e = hipMalloc((void **)&w->W2, sizeof(double) * mmax * OB)) != hipSuccess) return e;
-    if ((e = hipMalloc((void **)&w->T2, sizeof(double) * (2LL * OB * OB + (long long)OB * NB))) != hipSuccess) return e;   // T2, S2, tmp
-    if ((e = hipMalloc((void **)&w->Tout, sizeof(double) * ((mmax + OB - 1) / OB) * OB * OB)) != hipSuccess) return e;
-    if ((e = hipMalloc((void **)&w->tau, sizeof(double) * 2 * mmax)) != hipSuccess) return e;   // tau, rdiag
-    if ((e = hipMalloc((void **)&w->norm2, sizeof(double) * mmax)) != hipSuccess) return e;
-    if ((e = hipMalloc((void **)&w->dblk, sizeof(double) * 66 * NB * NB)) != hipSuccess) return e;   // S, Uinv + split-K slabs
+    double **p[DW_ARRAYS];
+    long long sz[DW_ARRAYS];
+    dense_work_layout(w, mmax, p, sz);
+    for (int a = 0; a < DW_ARRAYS; a++)
+        if ((e = hipMalloc((void **)p[a], sizeof(double) * sz[a])) != hipSuccess) return e;
     w->ws_cap = 4LL * OB * mmax;
-    if ((e = hipMalloc((void **)&w->ws, sizeof(double) * w->ws_cap)) != hipSuccess) return e;
-    if ((e = hipMalloc((void **)&w->hr, sizeof(double) * 3 * NB * NB)) != hipSuccess) return e;
     if ((e = hipMalloc((void **)&w->flag, sizeof(int) * 4)) != hipSuccess) return e;
     if ((e = hipMemset(w->flag, 0, sizeof(int) * 4)) != hipSuccess) return e;
     w->mmax = mmax;
@@ -1170,4 +1198,155 @@ extern "C" int rsqp_dense_chol_inverse(int n, double *G, double *Ginv, double pd
     rsqp_dense_work_free(&w);
     if (not_pd) *not_pd = flags[1];
     return e == hipSuccess ? 0 : -2;
+}
+
+// =====================================================================================
+// check entry points (include/rsqp_hip_dense_check.h): the kernels called the way the engine calls them -- operands at an
+// offset inside larger buffers, leading dimensions that differ between them, one workspace over several factorisations
+// =====================================================================================
+#include "../../include/rsqp_hip_dense_check.h"
+
+extern "C" int rsqp_dense_describe_gemm(int m, int n, int k, int batch, int have_ws, long long ws_cap, int *out, int n_out) {
+    if (m < 1 || n < 1 || k < 0 || batch < 1 || ws_cap < 0 || !out || n_out != RSQP_DENSE_PLAN_WORDS) return -1;
+    const DgemmPlan pl = dgemm_plan(m, n, k, batch, have_ws != 0, have_ws ? ws_cap : 0);
+    out[0] = pl.TM; out[1] = pl.TN; out[2] = pl.splits; out[3] = pl.kc; out[4] = pl.skinny;
+    return 0;
+}
+
+struct rsqp_dense_check_work { RsqpDenseWork w; };
+
+namespace {
+// a rows x cols operand at `off` with leading dimension ld inside a buffer of len doubles: every element it addresses lies inside
+bool window_ok(const double *buf, long long len, long long off, long long ld, long long rows, long long cols) {
+    if (!buf || len < 1 || off < 0 || off > len || rows < 0 || cols < 0 || ld < std::max(1LL, rows)) return false;
+    if (rows == 0 || cols == 0) return true;
+    return (cols - 1) <= (len - off - rows) / ld && off + (cols - 1) * ld + rows <= len;
+}
+hipError_t fill_device(double *d, long long n, double v) {
+    std::vector<double> h((size_t)n, v);
+    return hipMemcpy(d, h.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice);
+}
+// every array of the workspace (not flag) := v
+hipError_t dense_work_fill(RsqpDenseWork *w, double v) {
+    double **p[DW_ARRAYS];
+    long long sz[DW_ARRAYS];
+    dense_work_layout(w, w->mmax, p, sz);
+    for (int a = 0; a < DW_ARRAYS; a++) DCHK(fill_device(*p[a], sz[a], v));
+    return hipSuccess;
+}
+struct HostBuf {      // a whole host buffer on the device: uploaded whole, downloaded whole
+    double *host; long long len; DevMem d;
+    hipError_t up() { hipError_t e = d.alloc((size_t)len); return e != hipSuccess ? e : hipMemcpy(d.p, host, sizeof(double) * (size_t)len, hipMemcpyHostToDevice); }
+    hipError_t down() { return hipMemcpy(host, d.p, sizeof(double) * (size_t)len, hipMemcpyDeviceToHost); }
+};
+}  // namespace
+
+extern "C" int rsqp_dense_check_work_create(long long mmax, rsqp_dense_check_work **out) {
+    if (!out || mmax < 1 || mmax > (1LL << 20)) return -1;
+    rsqp_dense_check_work *h = new rsqp_dense_check_work();
+    if (rsqp_dense_work_alloc(&h->w, mmax) != hipSuccess || dense_work_fill(&h->w, 0.0) != hipSuccess) {
+        rsqp_dense_work_free(&h->w);
+        delete h;
+        return -2;
+    }
+    *out = h;
+    return 0;
+}
+
+extern "C" int rsqp_dense_check_work_destroy(rsqp_dense_check_work *h) {
+    if (!h) return -1;
+    rsqp_dense_work_free(&h->w);
+    delete h;
+    return 0;
+}
+
+extern "C" int rsqp_dense_check_gemm(int variant, int transA, int transB, int m, int n, int k, double alpha, double beta, double *A,
+                                     long long lenA, long long offA, long long lda, double *B, long long lenB, long long offB,
+                                     long long ldb, double *C, long long lenC, long long offC, long long ldc, long long ws_cap) {
+    if (variant < RSQP_DENSE_GEMM_PLAIN || variant > RSQP_DENSE_GEMM_KTRI3 || m < 0 || n < 0 || k < 0 || ws_cap < 0) return -1;
+    if (ws_cap > 0 && (variant != RSQP_DENSE_GEMM_PLAIN || ws_cap > (1LL << 28))) return -1;      // split-K belongs to the plain product
+    if (variant == RSQP_DENSE_GEMM_UPPER && m != n) return -1;
+    if (variant == RSQP_DENSE_GEMM_KTRI1 && (m != n || k != n || transA || !transB)) return -1;      // C = alpha A A'
+    if (variant == RSQP_DENSE_GEMM_KTRI2 && transA) return -1;
+    if (variant == RSQP_DENSE_GEMM_KTRI3 && !transA) return -1;
+    if (!window_ok(A, lenA, offA, lda, transA ? k : m, transA ? m : k)) return -1;
+    if (variant != RSQP_DENSE_GEMM_KTRI1 && !window_ok(B, lenB, offB, ldb, transB ? n : k, transB ? k : n)) return -1;
+    if (!window_ok(C, lenC, offC, ldc, m, n)) return -1;
+    const bool haveB = variant != RSQP_DENSE_GEMM_KTRI1;
+    HostBuf a{A, lenA}, b{B, lenB}, c{C, lenC};
+    DevMem ws;
+    HCHK(a.up()); if (haveB) HCHK(b.up()); HCHK(c.up());
+    if (ws_cap > 0) { HCHK(ws.alloc((size_t)ws_cap)); HCHK(fill_device(ws.p, ws_cap, std::numeric_limits<double>::quiet_NaN())); }
+    const double *dA = a.d.p + offA, *dB = haveB ? b.d.p + offB : nullptr;
+    double *dC = c.d.p + offC;
+    const bool ta = transA != 0, tb = transB != 0;
+    hipError_t e = hipSuccess;
+    switch (variant) {
+    case RSQP_DENSE_GEMM_PLAIN:
+        e = ws_cap > 0 ? dgemm_ws(ta, tb, m, n, k, alpha, dA, lda, dB, ldb, beta, dC, ldc, ws.p, ws_cap, nullptr)
+                       : rsqp_dgemm(ta, tb, m, n, k, alpha, dA, lda, dB, ldb, beta, dC, ldc, nullptr);
+        break;
+    case RSQP_DENSE_GEMM_UPPER: e = rsqp_dgemm_upper(ta, tb, n, k, alpha, dA, lda, dB, ldb, beta, dC, ldc, nullptr); break;
+    case RSQP_DENSE_GEMM_KTRI1: e = rsqp_dtrmmt_upper(n, alpha, dA, lda, dC, ldc, nullptr); break;
+    case RSQP_DENSE_GEMM_KTRI2: e = rsqp_dgemm_tri(ta, tb, m, n, k, alpha, dA, lda, dB, ldb, beta, dC, ldc, 2, nullptr); break;
+    default: e = rsqp_dgemm_tri(ta, tb, m, n, k, alpha, dA, lda, dB, ldb, beta, dC, ldc, 3, nullptr); break;
+    }
+    HCHK(e);
+    HCHK(hipDeviceSynchronize());
+    HCHK(a.down()); if (haveB) HCHK(b.down()); HCHK(c.down());
+    return 0;
+}
+
+extern "C" int rsqp_dense_check_qr(rsqp_dense_check_work *h, int m, int n, int panel_cholqr, int poison, double eps_li, double *B,
+                                   long long lenB, long long offB, long long ldb, double *Q, long long lenQ, long long offQ,
+                                   long long ldq, double *X, long long lenX, long long offX, long long ldx, int *flags, int *retried) {
+    if (!h || !flags || !retried || n < 1 || m < n || m > h->w.mmax) return -1;
+    if (!window_ok(B, lenB, offB, ldb, m, n) || !window_ok(Q, lenQ, offQ, ldq, m, m) || !window_ok(X, lenX, offX, ldx, n, n)) return -1;
+    RsqpDenseWork &w = h->w;
+    HostBuf b{B, lenB}, q{Q, lenQ}, x{X, lenX};
+    HCHK(b.up()); HCHK(q.up()); HCHK(x.up());
+    if (poison) HCHK(dense_work_fill(&w, std::numeric_limits<double>::quiet_NaN()));
+    *retried = 0;
+    w.panel_cholqr = panel_cholqr != 0;
+    hipError_t e = hipSuccess;
+    for (int attempt = 0; attempt < 2 && e == hipSuccess; attempt++) {      // (setup_tq_blocked of qp_large.hip)
+        e = hipMemset(w.flag, 0, sizeof(int) * 4);
+        if (e == hipSuccess && attempt) e = b.up();
+        if (e == hipSuccess) e = rsqp_dgeqrf(m, n, b.d.p + offB, ldb, eps_li, &w, nullptr);
+        if (e == hipSuccess) e = hipMemcpy(flags, w.flag, sizeof(int) * 4, hipMemcpyDeviceToHost);
+        if (e != hipSuccess || flags[2] == 0 || !w.panel_cholqr) break;
+        w.panel_cholqr = false;
+        *retried = 1;
+    }
+    w.panel_cholqr = true;
+    if (e == hipSuccess) e = rsqp_dtrtri_upper(n, b.d.p + offB, ldb, x.d.p + offX, ldx, &w, nullptr);
+    if (e == hipSuccess) e = rsqp_dorgqr(m, n, b.d.p + offB, ldb, q.d.p + offQ, ldq, &w, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    HCHK(e);
+    HCHK(b.down()); HCHK(q.down()); HCHK(x.down());
+    return 0;
+}
+
+extern "C" int rsqp_dense_check_chol(rsqp_dense_check_work *h, int n, int form, int poison, double pd_rel, double pd_abs, double *G,
+                                     long long lenG, long long offG, long long ldg, double *X, long long lenX, long long offX,
+                                     long long ldx, double *Gi, long long lenI, long long offI, long long ldi, int *flags) {
+    if (!h || !flags || n < 1 || n > h->w.mmax || form < RSQP_DENSE_INV_UPPER || form > RSQP_DENSE_INV_TRI2) return -1;
+    if (!window_ok(G, lenG, offG, ldg, n, n) || !window_ok(X, lenX, offX, ldx, n, n) || !window_ok(Gi, lenI, offI, ldi, n, n)) return -1;
+    RsqpDenseWork &w = h->w;
+    HostBuf g{G, lenG}, x{X, lenX}, gi{Gi, lenI};
+    HCHK(g.up()); HCHK(x.up()); HCHK(gi.up());
+    if (poison) HCHK(dense_work_fill(&w, std::numeric_limits<double>::quiet_NaN()));
+    HCHK(hipMemset(w.flag, 0, sizeof(int) * 4));
+    HCHK(rsqp_dpotrf_upper(n, g.d.p + offG, ldg, pd_rel, pd_abs, &w, nullptr));
+    HCHK(hipMemcpy(flags, w.flag, sizeof(int) * 4, hipMemcpyDeviceToHost));
+    if (flags[1] == 0) {      // (not positive definite: the engine stops here as well)
+        double *dX = x.d.p + offX, *dI = gi.d.p + offI;
+        HCHK(rsqp_dtrtri_upper(n, g.d.p + offG, ldg, dX, ldx, &w, nullptr));
+        if (form == RSQP_DENSE_INV_TRI2) HCHK(rsqp_dgemm_tri(false, true, n, n, n, 1.0, dX, ldx, dX, ldx, 0.0, dI, ldi, 2, nullptr));
+        else HCHK(rsqp_dtrmmt_upper(n, 1.0, dX, ldx, dI, ldi, nullptr));
+        if (form == RSQP_DENSE_INV_MIRROR) HCHK(rsqp_mirror_upper(n, dI, ldi, nullptr));
+    }
+    HCHK(hipDeviceSynchronize());
+    HCHK(g.down()); HCHK(x.down()); HCHK(gi.down());
+    return 0;
 }
