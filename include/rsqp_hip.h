@@ -566,4 +566,6 @@ int rsqp_dense_chol_inverse(int n, double *G, double *Ginv, double pd_rel, doubl
 #include "rsqp_hip_lane_hot.h"
 /* the dense building blocks called the way the engine calls them, and the GEMM's launch plan (verification): the same way */
 #include "rsqp_hip_dense_check.h"
+/* the decisions of a lock-step SQP loop per member of a batch (infeasibility, ratio test + radius, NLP KKT check): the same way */
+#include "rsqp_hip_nlp_step.h"
 #endif

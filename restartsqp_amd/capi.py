@@ -168,6 +168,15 @@ DENSE_CHECK_SYMBOLS = {
     "rsqp_dense_check_qr": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double] + 3 * _buf + [ip, ip]),
     "rsqp_dense_check_chol": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double] + 3 * _buf + [ip]),
 }
+# ... and of include/rsqp_hip_nlp_step.h (the decisions of a lock-step SQP loop per member: infeasibility, ratio test, NLP KKT check)
+NLP_STEP_SYMBOLS = {
+    "rsqp_nlp_step_default_options": (C.c_int, [C.c_void_p]),
+    "rsqp_batch_handler_infeasibility": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "rsqp_batch_handler_ratio_test": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "rsqp_batch_handler_check_optimality": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+}
+EXIT_UNKNOWN, EXIT_TRUST_REGION_TOO_SMALL = -99, 4                                                      # RSQP_EXIT_*
+KKT_PRIMAL, KKT_DUAL, KKT_COMPL, KKT_STAT, KKT_FIRST_ORDER_OPT = 1, 2, 4, 8, 16                         # RSQP_KKT_*: the verdict bits
 DENSE_GEMM_PLAIN, DENSE_GEMM_UPPER, DENSE_GEMM_KTRI1, DENSE_GEMM_KTRI2, DENSE_GEMM_KTRI3 = range(5)      # RSQP_DENSE_GEMM_*
 DENSE_INV_UPPER, DENSE_INV_MIRROR, DENSE_INV_TRI2 = range(3)                                            # RSQP_DENSE_INV_*
 DENSE_PLAN_OUT = ("TM", "TN", "splits", "kc", "skinny")                                                 # the words of rsqp_dense_describe_gemm
@@ -183,6 +192,39 @@ class HandlerIterate(C.Structure):
     """rsqp_handler_iterate: host or device addresses, as handler_update's on_device says"""
     _fields_ = [("what", C.c_void_p), ("delta", C.c_void_p), ("rho", C.c_void_p), ("x_k", C.c_void_p), ("grad", C.c_void_p),
                 ("c_k", C.c_void_p)]
+
+
+class NlpStepOptions(C.Structure):
+    """rsqp_nlp_step_options; a new one holds the defaults of src/Options.cpp:28-42 (rsqp_nlp_step_default_options), keyword
+    arguments override fields"""
+    _fields_ = [(k, C.c_double) for k in ("active_set_tol", "opt_prim_fea_tol", "opt_dual_fea_tol", "opt_compl_tol", "opt_stat_tol",
+                                          "eta_s", "eta_c", "eta_e", "gamma_c", "gamma_e", "delta_min", "delta_max", "tol")] + \
+               [("refresh_ubA", C.c_int)]
+
+    def __init__(self, **fields):
+        super().__init__()
+        check(lib().rsqp_nlp_step_default_options(C.addressof(self)))
+        for k, v in fields.items():
+            if k not in dict(self._fields_):
+                raise TypeError("rsqp_nlp_step_options has no field %r" % k)
+            setattr(self, k, v)
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class NlpTrial(C.Structure):
+    """rsqp_nlp_trial: host or device addresses, as handler_ratio_test's on_device says"""
+    IN = ("what", "rho", "f_trial", "c_trial")
+    INOUT = ("x_k", "c_k", "f_k", "infea_k", "delta")
+    OUT = ("actual_reduction", "pred_reduction", "infea_trial", "accept", "hu_word", "hm_word", "exitflag")
+    INTS = ("what", "accept", "hu_word", "hm_word", "exitflag")
+    _fields_ = [(k, C.c_void_p) for k in IN + INOUT + OUT]
+
+
+class NlpPoint(C.Structure):
+    """rsqp_nlp_point: host or device addresses, as handler_check_optimality's on_device says"""
+    _fields_ = [(k, C.c_void_p) for k in ("what", "x_k", "grad", "c_k", "infea")]
 
 
 class RsqpError(RuntimeError):
@@ -204,7 +246,8 @@ def lib():
         _TORCH_FIRST = "torch" in sys.modules
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SYMBOLS.items()) + list(LANE_SYMBOLS.items()) + list(HANDOVER_SYMBOLS.items()) + \
-                list(LANE_WARM_SYMBOLS.items()) + list(LANE_HOT_SYMBOLS.items()) + list(DENSE_CHECK_SYMBOLS.items()):
+                list(LANE_WARM_SYMBOLS.items()) + list(LANE_HOT_SYMBOLS.items()) + list(DENSE_CHECK_SYMBOLS.items()) + \
+                list(NLP_STEP_SYMBOLS.items()):
             f = getattr(L, name)
             f.restype = res
             f.argtypes = args
@@ -679,6 +722,96 @@ class Batch:
             addr = [out[k].ctypes.data for k, n in sizes]
         check(lib().rsqp_batch_handler_get_step(self._h, *addr, int(bool(on_device))))
         return out
+
+    # ---- the decisions of the SQP loop per member (include/rsqp_hip_nlp_step.h) ----
+    def _addr(self, a, n, name, on_device, ints=False, writable=False):
+        """the address of a pooled argument of n entries: a device tensor, or a host array -- which is converted unless the call
+        writes it (then it must be a contiguous ndarray of the right type: it is written in place); (address, what keeps it alive)"""
+        if a is None:
+            return None, None
+        if on_device:
+            return self._dev_addr(a, n, name, "int32" if ints else "float64"), a
+        dt = np.int32 if ints else np.float64
+        if not writable:
+            a = self._sized(a, n, name, dt)
+        elif not (isinstance(a, np.ndarray) and a.dtype == dt and a.flags.c_contiguous and a.flags.writeable):
+            raise ValueError("%s is written in place: a contiguous %s ndarray is needed" % (name, np.dtype(dt).name))
+        elif a.size != n:
+            raise ValueError("%s has %d entries, the batch needs %d" % (name, a.size, n))
+        return a.ctypes.data, a
+
+    def _new_out(self, n, on_device, ints=False, cols=None):
+        shape = n if cols is None else (n, cols)
+        if on_device:
+            torch = device_torch()
+            dev = "cuda" if getattr(self, "device", -1) < 0 else "cuda:%d" % self.device
+            return torch.zeros(shape, dtype=torch.int32 if ints else torch.float64, device=dev)
+        return np.zeros(shape, np.int32 if ints else np.float64)
+
+    def handler_infeasibility(self, c, on_device=False, out=None):
+        """cal_infea(c, c_l, c_u) of every member (rsqp_batch_handler_infeasibility): c in the layout of lbA, the result nq entries
+        -- `out`, else a new array (on_device: tensors on the batch's device)"""
+        sN, sC = self._handler_sizes()
+        if out is None:
+            out = self._new_out(self.nq, on_device)
+        ca, keep = self._addr(c, sC, "c", on_device)
+        oa, _ = self._addr(out, self.nq, "out", on_device, writable=True)
+        check(lib().rsqp_batch_handler_infeasibility(self._h, ca, oa, int(bool(on_device))))
+        del keep
+        return out
+
+    def handler_ratio_test(self, what, rho, f_trial, c_trial, x_k, c_k, f_k, infea_k, delta, options=None, on_device=False, out=None):
+        """ratio_test + update_radius for every member with what[q] != 0 (rsqp_batch_handler_ratio_test), on the step of the last
+        solve. what (int32), rho, f_trial: nq; c_trial: the layout of lbA. x_k (NLP layout), c_k, f_k, infea_k, delta are the
+        members' iterates and are WRITTEN IN PLACE: contiguous float64 ndarrays, or with on_device tensors on the batch's device,
+        complete before the call. Returns the outputs as a dict over NlpTrial.OUT (accept, hu_word, hm_word, exitflag: int32) --
+        the arrays of `out` where it has them (a member with word 0 keeps their bytes), else new zero-filled ones"""
+        sN, sC = self._handler_sizes()
+        nq = self.nq
+        size = dict(what=nq, rho=nq, f_trial=nq, c_trial=sC, x_k=sN, c_k=sC, f_k=nq, infea_k=nq, delta=nq)
+        given = dict(what=what, rho=rho, f_trial=f_trial, c_trial=c_trial, x_k=x_k, c_k=c_k, f_k=f_k, infea_k=infea_k, delta=delta)
+        out = dict(out or {})
+        for k in NlpTrial.OUT:
+            if out.get(k) is None:
+                out[k] = self._new_out(nq, on_device, ints=k in NlpTrial.INTS)
+        t, keep = NlpTrial(), []
+        for k in NlpTrial.IN + NlpTrial.INOUT:
+            if given[k] is None and size[k] > 0:
+                raise ValueError("%s is required" % k)
+            addr, a = self._addr(given[k], size[k], k, on_device, ints=k in NlpTrial.INTS, writable=k in NlpTrial.INOUT)
+            setattr(t, k, addr); keep.append(a)
+        for k in NlpTrial.OUT:
+            addr, a = self._addr(out[k], nq, k, on_device, ints=k in NlpTrial.INTS, writable=True)
+            setattr(t, k, addr)
+        o = options or NlpStepOptions()
+        check(lib().rsqp_batch_handler_ratio_test(self._h, C.addressof(t), C.addressof(o), int(bool(on_device))))
+        del keep
+        return out
+
+    def handler_check_optimality(self, what, x_k, grad, c_k, infea, options=None, on_device=False, out=None, verdict=None):
+        """check_optimality for every member with what[q] != 0 (rsqp_batch_handler_check_optimality), with the multipliers of the
+        last solve and the Jacobian as it stands in the batch's A pool (handler_set_matrices with the point's J comes first).
+        x_k, grad: NLP layout; c_k: the layout of lbA; infea: nq. Returns (status, verdict): status [nq, 5] over CERTIFICATE_FIELDS,
+        verdict int32 with the KKT_* bits -- `out` / `verdict` where given (a member with word 0 keeps their bytes), else new
+        zero-filled ones; on_device: tensors on the batch's device"""
+        sN, sC = self._handler_sizes()
+        nq = self.nq
+        if out is None:
+            out = self._new_out(nq, on_device, cols=5)
+        if verdict is None:
+            verdict = self._new_out(nq, on_device, ints=True)
+        p, keep = NlpPoint(), []
+        for k, a, n in (("what", what, nq), ("x_k", x_k, sN), ("grad", grad, sN), ("c_k", c_k, sC), ("infea", infea, nq)):
+            if a is None and n > 0:
+                raise ValueError("%s is required" % k)
+            addr, a = self._addr(a, n, k, on_device, ints=k == "what")
+            setattr(p, k, addr); keep.append(a)
+        oa, _ = self._addr(out, 5 * nq, "out", on_device, writable=True)
+        va, _ = self._addr(verdict, nq, "verdict", on_device, ints=True, writable=True)
+        o = options or NlpStepOptions()
+        check(lib().rsqp_batch_handler_check_optimality(self._h, C.addressof(p), C.addressof(o), oa, va, int(bool(on_device))))
+        del keep
+        return out, verdict
 
     def get_vectors(self):
         """(g, lb, ub, lbA, ubA) as the pools hold them on the device, in the layout of set_vectors"""

@@ -1,8 +1,9 @@
 // rsqp_batch.h -- struct rsqp_batch and what more than one of its translation units uses. Private to them: rsqp_batch.hip (the batch
 // itself: create, whole-batch setters, solve, results, certificate, records), rsqp_batch_optimize.hip (optimizeQP / optimizeLP per
-// member and their plan kernels) and rsqp_batch_handler.hip (everything that writes the pools member by member). Device code does not
-// cross a unit: the __device__ helpers here are inline. Everything but the struct itself (the opaque type of the C ABI) is in namespace
-// rsqp_batch_units, which the three units open.
+// member and their plan kernels), rsqp_batch_handler.hip (everything that writes the pools member by member) and rsqp_batch_nlp.hip
+// (the decisions of the SQP loop, which read the pools member by member). Device code does not cross a unit: the __device__ helpers
+// here are inline. Everything but the struct itself (the opaque type of the C ABI) is in namespace rsqp_batch_units, which the units
+// open.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -181,4 +182,6 @@ void judge_h_sym(rsqp_batch *b, const int *members, const double *Hval);
 // after values have been written: the sums of a folded layout into the canonical pool, and (A) the CSR copy from that pool
 int settle_A(rsqp_batch *b);
 int settle_H(rsqp_batch *b);
+// rsqp_batch_handler.hip: the pinned block and the scratch block of at least `words` doubles each (rsqp_batch::scratch)
+int ensure_staging(rsqp_batch *b, size_t words);
 }  // namespace rsqp_batch_units

@@ -247,14 +247,14 @@ batch_handler_step_kernel(int nq, const QPDesc *__restrict__ desc, const double 
         if (infea) infea[q] = sm;
     }
 }
+}  // namespace
 
 // a host-pointer call packs its arrays into `words` doubles of the pinned block, which cross in one copy to or from the same
 // words of the scratch block (rsqp_batch::scratch: both are free)
-int ensure_staging(rsqp_batch *b, size_t words) {
+int rsqp_batch_units::ensure_staging(rsqp_batch *b, size_t words) {
     if (b->pin.n < words) HIPCHK(b->pin.alloc(words, false));
     return ensure_scratch(b, words);
 }
-}  // namespace
 
 extern "C" int rsqp_batch_handler_set_problem(rsqp_batch *b, const double *x_l, const double *x_u, const double *c_l, const double *c_u) {
     if (!b || !x_l || !x_u || (b->sumC > 0 && (!c_l || !c_u))) return fail(RSQP_ERR_ARG, "rsqp_batch_handler_set_problem");

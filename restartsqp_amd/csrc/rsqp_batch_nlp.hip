@@ -1,0 +1,353 @@
+// rsqp_batch_nlp.hip -- the decisions of a lock-step SQP loop for every member of a batch (rsqp_batch_handler_infeasibility /
+// _ratio_test / _check_optimality of include/rsqp_hip_nlp_step.h): cal_infea, ratio_test + update_radius and check_optimality of
+// src/Algorithm.cpp, read from the result pools of the last solve and from the canonical A pool, with their kernels.
+#include "rsqp_batch.h"
+
+// Every scalar formula here must give the bits the same C expression gives on the host without contraction: hipcc would contract
+// a + b*c into an FMA by default, so contraction is OFF for this whole unit (the build flags of the other units stay as they are).
+#pragma clang fp contract(off)
+
+namespace {
+constexpr double NLP_INF = 1.0e18;   // INF of the reference (Utils.hpp:35)
+
+// the shape of member q: a one-shape batch (uniV > 0) multiplies, else the descriptor says
+struct MemberShape { int nV, nC, offV, offC; };
+__device__ inline MemberShape shape_of(const QPDesc *__restrict__ desc, int uniV, int uniC, int q) {
+    if (uniV > 0) return MemberShape{uniV, uniC, q * uniV, q * uniC};
+    return MemberShape{desc[q].nV, desc[q].nC, desc[q].offV, desc[q].offC};
+}
+
+// the sum of v over the G lanes of a sub-group, the same bits in every lane: partners G/2, G/4, ..., 1 lanes apart
+template <int G>
+__device__ inline double group_sum(double v) {
+    for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, G);
+    return v;
+}
+
+// lane `lane`'s share of cal_infea(c, c_l, c_u) (src/Algorithm.cpp:584-589) over m constraints: entries lane, lane + G, ...
+template <int G>
+__device__ inline double infea_share(const double *__restrict__ c, const double *__restrict__ c_l, const double *__restrict__ c_u,
+                                     int m, int lane) {
+    double s = 0.0;
+    for (int i = lane; i < m; i += G) {
+        const double v = c[i];
+        if (v < c_l[i]) s += (c_l[i] - v);
+        else if (v > c_u[i]) s += (v - c_u[i]);
+    }
+    return s;
+}
+
+// G lanes per member, as batch_handler_step_kernel: lanes past the last member, and those of a member that sits out, skip the loops
+// and stay in the shuffles
+template <int G>
+__global__ void __launch_bounds__(256)
+batch_nlp_infea_kernel(int nq, int uniV, int uniC, const QPDesc *__restrict__ desc, const double *__restrict__ c,
+                       const double *__restrict__ c_l, const double *__restrict__ c_u, double *__restrict__ infea) {
+    const int q = (int)(((long long)blockIdx.x * blockDim.x + threadIdx.x) / G), lane = (int)threadIdx.x % G;
+    double s = 0.0;
+    if (q < nq) {
+        const MemberShape sh = shape_of(desc, uniV, uniC, q);
+        s = infea_share<G>(c + sh.offC, c_l + sh.offC, c_u + sh.offC, sh.nC, lane);
+    }
+    s = group_sum<G>(s);
+    if (q < nq && lane == 0) infea[q] = s;
+}
+
+// ratio_test + update_radius (src/Algorithm.cpp:722-801, 820-849). The sub-group's lane 0 computes the member's scalars behind the
+// reduction; the verdict goes to the other lanes by a shuffle, and the copies of an accepted step walk the member's entries G at a time
+struct NlpRatio {
+    int nq, uniV, uniC;
+    const QPDesc *desc;
+    rsqp_nlp_trial t;
+    rsqp_nlp_step_options o;
+    const double *c_l, *c_u;        // rsqp_batch_handler_set_problem
+    const double *x, *obj;          // the result pools of the last solve
+};
+template <int G>
+__global__ void __launch_bounds__(256) batch_nlp_ratio_kernel(NlpRatio a) {
+    const int q = (int)(((long long)blockIdx.x * blockDim.x + threadIdx.x) / G), lane = (int)threadIdx.x % G;
+    const bool act = q < a.nq && a.t.what[q] != 0;
+    MemberShape sh{0, 0, 0, 0};
+    int n = 0, offN = 0;
+    double s = 0.0, mx = 0.0;
+    if (act) {
+        sh = shape_of(a.desc, a.uniV, a.uniC, q);
+        n = sh.nV - 2 * sh.nC; offN = sh.offV - 2 * sh.offC;
+        s = infea_share<G>(a.t.c_trial + sh.offC, a.c_l + sh.offC, a.c_u + sh.offC, sh.nC, lane);
+        for (int i = lane; i < n; i += G) mx = fmax(mx, fabs(a.x[sh.offV + i]));    // getInfNorm of p: exact in any order
+    }
+    s = group_sum<G>(s);
+    for (int o = G / 2; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, G));
+    int acc = 0;
+    if (act && lane == 0) {
+        const rsqp_nlp_step_options &o = a.o;
+        const double rho = a.t.rho[q], f_k = a.t.f_k[q], infea_k = a.t.infea_k[q], f_t = a.t.f_trial[q];
+        const double P1_x = f_k + rho * infea_k;
+        const double P1_x_trial = f_t + rho * s;
+        const double actual = P1_x - P1_x_trial;
+        const double pred = rho * infea_k - a.obj[q];
+        acc = (actual >= (o.eta_s * pred) && actual >= -o.tol) ? 1 : 0;
+        double delta = a.t.delta[q];
+        bool radius = false;
+        if (actual < o.eta_c * pred) {
+            delta = o.gamma_c * delta;
+            radius = true;
+        } else if (actual > o.eta_e * pred && (o.tol > fabs(delta - mx))) {
+            const double grown = o.gamma_e * delta;
+            delta = (o.delta_max < grown) ? o.delta_max : grown;      // std::min(gamma_e * delta_, delta_max)
+            radius = true;
+        }
+        if (radius) a.t.delta[q] = delta;
+        if (acc) { a.t.f_k[q] = f_t; a.t.infea_k[q] = s; }
+        if (a.t.actual_reduction) a.t.actual_reduction[q] = actual;
+        if (a.t.pred_reduction) a.t.pred_reduction[q] = pred;
+        if (a.t.infea_trial) a.t.infea_trial[q] = s;
+        if (a.t.accept) a.t.accept[q] = acc;
+        if (a.t.hu_word)
+            a.t.hu_word[q] = acc ? (RSQP_HU_BOUNDS | RSQP_HU_GRAD | (o.refresh_ubA ? RSQP_HU_UBA : 0)) : (radius ? RSQP_HU_DELTA : 0);
+        if (a.t.hm_word) a.t.hm_word[q] = acc ? (RSQP_HM_JAC | RSQP_HM_HESS) : 0;
+        if (a.t.exitflag) a.t.exitflag[q] = delta < o.delta_min ? RSQP_EXIT_TRUST_REGION_TOO_SMALL : RSQP_EXIT_UNKNOWN;
+    }
+    acc = __shfl(acc, 0, G);
+    if (acc) {      // (only lanes of an active member hold 1)
+        for (int i = lane; i < n; i += G) a.t.x_k[offN + i] = a.t.x_k[offN + i] + a.x[sh.offV + i];
+        for (int i = lane; i < sh.nC; i += G) a.t.c_k[sh.offC + i] = a.t.c_trial[sh.offC + i];
+    }
+}
+
+// classify_single_constraint (src/Utils.cpp:29-45), exactly as written
+enum { T_EQUAL, T_BOUNDED, T_BOUNDED_BELOW, T_BOUNDED_ABOVE, T_UNBOUNDED };
+__device__ inline int classify(double lower_bound, double upper_bound) {
+    if (lower_bound > -NLP_INF && upper_bound < NLP_INF) return (upper_bound - lower_bound) < 1.0e-8 ? T_EQUAL : T_BOUNDED;
+    else if (lower_bound > -NLP_INF && upper_bound > NLP_INF) return T_BOUNDED_BELOW;
+    else if (upper_bound < NLP_INF && lower_bound < -NLP_INF) return T_BOUNDED_ABOVE;
+    return T_UNBOUNDED;
+}
+// one bound pair's terms of the dual and the complementarity sums (src/Algorithm.cpp:251-306); max / min as std::max / std::min
+__device__ inline void kkt_terms(double l, double u, double v, double lam, double &dual, double &compl_) {
+    switch (classify(l, u)) {
+    case T_BOUNDED_ABOVE: dual += (lam < 0.0) ? 0.0 : lam; compl_ += fabs(lam * (u - v)); break;
+    case T_BOUNDED_BELOW: dual += -((0.0 < lam) ? 0.0 : lam); compl_ += fabs(lam * (v - l)); break;
+    case T_UNBOUNDED: compl_ += fabs(lam); break;
+    default: break;
+    }
+}
+
+// check_optimality (src/Algorithm.cpp:170-364). A lane owns the variables lane, lane + G, ... and with each its column of J: it
+// walks the column's entries of the canonical CSC pool in index order (no atomics), adds lam_x, subtracts grad and contributes the
+// absolute value. A one-shape, one-pattern batch (uni_pat) reads member 0's pattern arrays, as the solve kernels do
+struct NlpKkt {
+    int nq, uniV, uniC, uni_pat, uni_annz;
+    const QPDesc *desc;
+    rsqp_nlp_point pt;
+    rsqp_nlp_step_options o;
+    const double *x_l, *x_u, *c_l, *c_u;
+    const double *y;                          // the multiplier pool of the last solve
+    const int *Ajc, *Air; const double *Aval; // the canonical CSC pool of A
+    rsqp_optimality_status *out;
+    int *verdict;
+};
+template <int G>
+__global__ void __launch_bounds__(256) batch_nlp_kkt_kernel(NlpKkt a) {
+    const int q = (int)(((long long)blockIdx.x * blockDim.x + threadIdx.x) / G), lane = (int)threadIdx.x % G;
+    const bool act = q < a.nq && a.pt.what[q] != 0;
+    double dual_v = 0.0, dual_c = 0.0, compl_v = 0.0, compl_c = 0.0, stat = 0.0;
+    if (act) {
+        const MemberShape sh = shape_of(a.desc, a.uniV, a.uniC, q);
+        const int n = sh.nV - 2 * sh.nC, m = sh.nC, offN = sh.offV - 2 * sh.offC;
+        const double *const lam_x = a.y + sh.offV + sh.offC, *const lam_c = lam_x + sh.nV;
+        const int *const jc = a.Ajc + (a.uni_pat ? 0 : a.desc[q].offAjc), *const ir = a.Air + (a.uni_pat ? 0 : a.desc[q].offAnz);
+        const double *const val = a.Aval + (a.uni_pat ? (long long)q * a.uni_annz : (long long)a.desc[q].offAnz);
+        for (int i = lane; i < n; i += G) {
+            const double lam = lam_x[i];
+            kkt_terms(a.x_l[offN + i], a.x_u[offN + i], a.pt.x_k[offN + i], lam, dual_v, compl_v);
+            double d = 0.0;
+            for (int k = jc[i]; k < jc[i + 1]; k++) d += val[k] * lam_c[ir[k]];
+            d = d + lam;
+            d = d - a.pt.grad[offN + i];
+            stat += fabs(d);
+        }
+        for (int i = lane; i < m; i += G)
+            kkt_terms(a.c_l[sh.offC + i], a.c_u[sh.offC + i], a.pt.c_k[sh.offC + i], lam_c[i], dual_c, compl_c);
+    }
+    // variables then constraints in the dual sum, constraints then variables in the complementarity sum (:251-269, 277-306)
+    const double dual = group_sum<G>(dual_v + dual_c), compl_ = group_sum<G>(compl_c + compl_v);
+    stat = group_sum<G>(stat);
+    if (act && lane == 0) {
+        const double primal = a.pt.infea[q];
+        if (a.out) {
+            rsqp_optimality_status s;
+            s.primal_violation = primal; s.dual_violation = dual; s.compl_violation = compl_; s.stationarity_violation = stat;
+            s.KKT_error = dual + primal + compl_ + stat;
+            a.out[q] = s;
+        }
+        if (a.verdict) {
+            int v = (primal < a.o.opt_prim_fea_tol ? RSQP_KKT_PRIMAL : 0) | (dual < a.o.opt_dual_fea_tol ? RSQP_KKT_DUAL : 0) |
+                    (compl_ < a.o.opt_compl_tol ? RSQP_KKT_COMPL : 0) | (stat < a.o.opt_stat_tol ? RSQP_KKT_STAT : 0);
+            if (v == (RSQP_KKT_PRIMAL | RSQP_KKT_DUAL | RSQP_KKT_COMPL | RSQP_KKT_STAT)) v |= RSQP_KKT_FIRST_ORDER_OPT;
+            a.verdict[q] = v;
+        }
+    }
+}
+
+// hs071-scale members: 8 lanes each, eight members per wavefront; else a wavefront per member (rsqp_batch_handler_get_step)
+inline int lanes_per_member(const rsqp_batch *b) { return (b->nVmax + b->nCmax <= 16) ? 8 : 64; }
+inline dim3 grid_of(const rsqp_batch *b, int G) { return dim3((unsigned)(((long long)b->nq * G + 255) / 256)); }
+inline int uni_shape(const rsqp_batch *b) { return (b->uniV > 0 && b->uniC >= 0) ? b->uniV : 0; }
+// `ints` ints in doubles of the staging block
+inline size_t int_words(size_t ints) { return (ints + 1) / 2; }
+}  // namespace
+
+extern "C" int rsqp_nlp_step_default_options(rsqp_nlp_step_options *o) {
+    if (!o) return fail(RSQP_ERR_ARG, "rsqp_nlp_step_default_options: null pointer");
+    o->active_set_tol = 1.0e-5;
+    o->opt_prim_fea_tol = 1.0e-4; o->opt_dual_fea_tol = 1.0e-4; o->opt_compl_tol = 1.0e-4; o->opt_stat_tol = 1.0e-4;
+    o->eta_s = 1.0e-8; o->eta_c = 0.25; o->eta_e = 0.75;
+    o->gamma_c = 0.5; o->gamma_e = 2;
+    o->delta_min = 1.0e-16; o->delta_max = 1.0e8;
+    o->tol = 1.0e-8;
+    o->refresh_ubA = 0;
+    return RSQP_OK;
+}
+
+extern "C" int rsqp_batch_handler_infeasibility(rsqp_batch *b, const double *c, double *infea, int on_device) {
+    if (!b || !infea || (b->sumC > 0 && !c)) return fail(RSQP_ERR_ARG, "rsqp_batch_handler_infeasibility: the batch, infea (and c) are required");
+    if (!b->have_problem) return fail(RSQP_ERR_ARG, "rsqp_batch_handler_infeasibility: rsqp_batch_handler_set_problem has not been called");
+    HIPCHK(hipSetDevice(b->device));
+    const size_t nq = (size_t)b->nq, sC = (size_t)b->sumC, words = sC + nq;      // c | infea
+    const double *dc = c;
+    double *di = infea;
+    if (!on_device) {
+        const int rc = ensure_staging(b, words);
+        if (rc != RSQP_OK) return rc;
+        if (sC > 0) {
+            std::memcpy(b->pin.p, c, sizeof(double) * sC);
+            HIPCHK(hipMemcpyAsync(b->scratch.p, b->pin.p, sizeof(double) * sC, hipMemcpyHostToDevice, b->stream));
+        }
+        dc = b->scratch.p; di = b->scratch.p + sC;
+    }
+    const int G = lanes_per_member(b), uniV = uni_shape(b), uniC = uniV > 0 ? b->uniC : 0;
+    if (G == 8)
+        hipLaunchKernelGGL(batch_nlp_infea_kernel<8>, grid_of(b, G), dim3(256), 0, b->stream, b->nq, uniV, uniC, b->d_desc.p, dc, b->h_cl.p, b->h_cu.p, di);
+    else
+        hipLaunchKernelGGL(batch_nlp_infea_kernel<64>, grid_of(b, G), dim3(256), 0, b->stream, b->nq, uniV, uniC, b->d_desc.p, dc, b->h_cl.p, b->h_cu.p, di);
+    HIPCHK(hipGetLastError());
+    if (!on_device) HIPCHK(hipMemcpyAsync(b->pin.p + sC, b->scratch.p + sC, sizeof(double) * nq, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    if (!on_device) std::memcpy(infea, b->pin.p + sC, sizeof(double) * nq);
+    return RSQP_OK;
+}
+
+extern "C" int rsqp_batch_handler_ratio_test(rsqp_batch *b, const rsqp_nlp_trial *t, const rsqp_nlp_step_options *o, int on_device) {
+    if (!b || !t || !o || !t->what || !t->rho || !t->f_trial || !t->x_k || !t->f_k || !t->infea_k || !t->delta ||
+        (b->sumC > 0 && (!t->c_trial || !t->c_k)))
+        return fail(RSQP_ERR_ARG, "rsqp_batch_handler_ratio_test: what, rho, f_trial, x_k, f_k, infea_k, delta (and c_trial, c_k) and the options are required");
+    if (!b->have_problem) return fail(RSQP_ERR_ARG, "rsqp_batch_handler_ratio_test: rsqp_batch_handler_set_problem has not been called");
+    HIPCHK(hipSetDevice(b->device));
+    NlpRatio a;
+    std::memset(&a, 0, sizeof(a));
+    a.t = *t; a.o = *o;
+    const size_t nq = (size_t)b->nq, sN = (size_t)b->sumN, sC = (size_t)b->sumC;
+    // up only: what (ints) | rho | f_trial | c_trial; both ways: x_k | c_k | f_k | infea_k | delta | actual | pred | infea_trial |
+    // accept, hu_word, hm_word, exitflag (ints). The outputs go up as well: a member that sits out keeps their bytes
+    const size_t o_rho = int_words(nq), o_ft = o_rho + nq, o_ct = o_ft + nq, o_x = o_ct + sC, o_c = o_x + sN, o_f = o_c + sC, o_in = o_f + nq,
+                 o_d = o_in + nq, o_ar = o_d + nq, o_pr = o_ar + nq, o_it = o_pr + nq, o_w = o_it + nq, words = o_w + int_words(4 * nq);
+    if (!on_device) {
+        const int rc = ensure_staging(b, words);
+        if (rc != RSQP_OK) return rc;
+        double *const h = b->pin.p, *const d = b->scratch.p;
+        int *const hw = reinterpret_cast<int *>(h + o_w), *const dw = reinterpret_cast<int *>(d + o_w);
+        std::memcpy(h, t->what, sizeof(int) * nq);
+        std::memcpy(h + o_rho, t->rho, sizeof(double) * nq); std::memcpy(h + o_ft, t->f_trial, sizeof(double) * nq);
+        std::memcpy(h + o_x, t->x_k, sizeof(double) * sN);
+        if (sC > 0) { std::memcpy(h + o_ct, t->c_trial, sizeof(double) * sC); std::memcpy(h + o_c, t->c_k, sizeof(double) * sC); }
+        std::memcpy(h + o_f, t->f_k, sizeof(double) * nq); std::memcpy(h + o_in, t->infea_k, sizeof(double) * nq);
+        std::memcpy(h + o_d, t->delta, sizeof(double) * nq);
+        if (t->actual_reduction) std::memcpy(h + o_ar, t->actual_reduction, sizeof(double) * nq);
+        if (t->pred_reduction) std::memcpy(h + o_pr, t->pred_reduction, sizeof(double) * nq);
+        if (t->infea_trial) std::memcpy(h + o_it, t->infea_trial, sizeof(double) * nq);
+        if (t->accept) std::memcpy(hw, t->accept, sizeof(int) * nq);
+        if (t->hu_word) std::memcpy(hw + nq, t->hu_word, sizeof(int) * nq);
+        if (t->hm_word) std::memcpy(hw + 2 * nq, t->hm_word, sizeof(int) * nq);
+        if (t->exitflag) std::memcpy(hw + 3 * nq, t->exitflag, sizeof(int) * nq);
+        HIPCHK(hipMemcpyAsync(d, h, sizeof(double) * words, hipMemcpyHostToDevice, b->stream));
+        a.t.what = reinterpret_cast<const int *>(d); a.t.rho = d + o_rho; a.t.f_trial = d + o_ft; a.t.c_trial = d + o_ct;
+        a.t.x_k = d + o_x; a.t.c_k = d + o_c; a.t.f_k = d + o_f; a.t.infea_k = d + o_in; a.t.delta = d + o_d;
+        a.t.actual_reduction = t->actual_reduction ? d + o_ar : nullptr; a.t.pred_reduction = t->pred_reduction ? d + o_pr : nullptr;
+        a.t.infea_trial = t->infea_trial ? d + o_it : nullptr;
+        a.t.accept = t->accept ? dw : nullptr; a.t.hu_word = t->hu_word ? dw + nq : nullptr;
+        a.t.hm_word = t->hm_word ? dw + 2 * nq : nullptr; a.t.exitflag = t->exitflag ? dw + 3 * nq : nullptr;
+    }
+    a.nq = b->nq; a.uniV = uni_shape(b); a.uniC = a.uniV > 0 ? b->uniC : 0; a.desc = b->d_desc.p;
+    a.c_l = b->h_cl.p; a.c_u = b->h_cu.p; a.x = b->x.p; a.obj = b->obj.p;
+    const int G = lanes_per_member(b);
+    if (G == 8) hipLaunchKernelGGL(batch_nlp_ratio_kernel<8>, grid_of(b, G), dim3(256), 0, b->stream, a);
+    else hipLaunchKernelGGL(batch_nlp_ratio_kernel<64>, grid_of(b, G), dim3(256), 0, b->stream, a);
+    HIPCHK(hipGetLastError());
+    if (!on_device)
+        HIPCHK(hipMemcpyAsync(b->pin.p + o_x, b->scratch.p + o_x, sizeof(double) * (words - o_x), hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    if (!on_device) {
+        const double *const h = b->pin.p;
+        const int *const hw = reinterpret_cast<const int *>(h + o_w);
+        std::memcpy(t->x_k, h + o_x, sizeof(double) * sN);
+        if (sC > 0) std::memcpy(t->c_k, h + o_c, sizeof(double) * sC);
+        std::memcpy(t->f_k, h + o_f, sizeof(double) * nq); std::memcpy(t->infea_k, h + o_in, sizeof(double) * nq);
+        std::memcpy(t->delta, h + o_d, sizeof(double) * nq);
+        if (t->actual_reduction) std::memcpy(t->actual_reduction, h + o_ar, sizeof(double) * nq);
+        if (t->pred_reduction) std::memcpy(t->pred_reduction, h + o_pr, sizeof(double) * nq);
+        if (t->infea_trial) std::memcpy(t->infea_trial, h + o_it, sizeof(double) * nq);
+        if (t->accept) std::memcpy(t->accept, hw, sizeof(int) * nq);
+        if (t->hu_word) std::memcpy(t->hu_word, hw + nq, sizeof(int) * nq);
+        if (t->hm_word) std::memcpy(t->hm_word, hw + 2 * nq, sizeof(int) * nq);
+        if (t->exitflag) std::memcpy(t->exitflag, hw + 3 * nq, sizeof(int) * nq);
+    }
+    return RSQP_OK;
+}
+
+extern "C" int rsqp_batch_handler_check_optimality(rsqp_batch *b, const rsqp_nlp_point *pt, const rsqp_nlp_step_options *o,
+                                                   rsqp_optimality_status *out, int *verdict, int on_device) {
+    if (!b || !pt || !o || !pt->what || !pt->x_k || !pt->grad || !pt->infea || (b->sumC > 0 && !pt->c_k))
+        return fail(RSQP_ERR_ARG, "rsqp_batch_handler_check_optimality: what, x_k, grad, infea (and c_k) and the options are required");
+    if (!b->have_problem) return fail(RSQP_ERR_ARG, "rsqp_batch_handler_check_optimality: rsqp_batch_handler_set_problem has not been called");
+    HIPCHK(hipSetDevice(b->device));
+    NlpKkt a;
+    std::memset(&a, 0, sizeof(a));
+    a.pt = *pt; a.o = *o; a.out = out; a.verdict = verdict;
+    const size_t nq = (size_t)b->nq, sN = (size_t)b->sumN, sC = (size_t)b->sumC;
+    // up only: what (ints) | x_k | grad | c_k | infea; both ways (a member that sits out keeps the bytes): out (5 nq) | verdict (ints)
+    const size_t o_x = int_words(nq), o_g = o_x + sN, o_c = o_g + sN, o_in = o_c + sC, o_out = o_in + nq, o_v = o_out + 5 * nq,
+                 words = o_v + int_words(nq);
+    static_assert(sizeof(rsqp_optimality_status) == 5 * sizeof(double), "the records are packed as five doubles");
+    if (!on_device) {
+        const int rc = ensure_staging(b, words);
+        if (rc != RSQP_OK) return rc;
+        double *const h = b->pin.p, *const d = b->scratch.p;
+        std::memcpy(h, pt->what, sizeof(int) * nq);
+        std::memcpy(h + o_x, pt->x_k, sizeof(double) * sN); std::memcpy(h + o_g, pt->grad, sizeof(double) * sN);
+        if (sC > 0) std::memcpy(h + o_c, pt->c_k, sizeof(double) * sC);
+        std::memcpy(h + o_in, pt->infea, sizeof(double) * nq);
+        if (out) std::memcpy(h + o_out, out, sizeof(double) * 5 * nq);
+        if (verdict) std::memcpy(h + o_v, verdict, sizeof(int) * nq);
+        HIPCHK(hipMemcpyAsync(d, h, sizeof(double) * words, hipMemcpyHostToDevice, b->stream));
+        a.pt.what = reinterpret_cast<const int *>(d); a.pt.x_k = d + o_x; a.pt.grad = d + o_g; a.pt.c_k = d + o_c; a.pt.infea = d + o_in;
+        a.out = out ? reinterpret_cast<rsqp_optimality_status *>(d + o_out) : nullptr;
+        a.verdict = verdict ? reinterpret_cast<int *>(d + o_v) : nullptr;
+    }
+    a.nq = b->nq; a.uniV = uni_shape(b); a.uniC = a.uniV > 0 ? b->uniC : 0; a.desc = b->d_desc.p;
+    a.uni_pat = b->uni_pat ? 1 : 0; a.uni_annz = b->uni_annz;
+    a.x_l = b->h_xl.p; a.x_u = b->h_xu.p; a.c_l = b->h_cl.p; a.c_u = b->h_cu.p;
+    a.y = b->y.p; a.Ajc = b->Ajc.p; a.Air = b->Air.p; a.Aval = b->Aval.p;
+    const int G = lanes_per_member(b);
+    if (G == 8) hipLaunchKernelGGL(batch_nlp_kkt_kernel<8>, grid_of(b, G), dim3(256), 0, b->stream, a);
+    else hipLaunchKernelGGL(batch_nlp_kkt_kernel<64>, grid_of(b, G), dim3(256), 0, b->stream, a);
+    HIPCHK(hipGetLastError());
+    if (!on_device && (out || verdict))
+        HIPCHK(hipMemcpyAsync(b->pin.p + o_out, b->scratch.p + o_out, sizeof(double) * (words - o_out), hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    if (!on_device) {
+        if (out) std::memcpy(out, b->pin.p + o_out, sizeof(double) * 5 * nq);
+        if (verdict) std::memcpy(verdict, b->pin.p + o_v, sizeof(int) * nq);
+    }
+    return RSQP_OK;
+}

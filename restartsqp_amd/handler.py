@@ -176,6 +176,150 @@ def batch_matrices_reference(Aval, Hval, what, jac, hess, nV, nC, Ajc_per_member
     return A, H
 
 
+def nlp_step_lanes(n, m):
+    """G of include/rsqp_hip_nlp_step.h: lanes per member in the kernels of the NLP step, from the batch's largest QP"""
+    nV = np.asarray(n, dtype=np.int64) + 2 * np.asarray(m, dtype=np.int64)
+    return 8 if int(nV.max()) + int(np.max(m)) <= 16 else 64
+
+
+def tree_sum(terms, G):
+    """the sum of float64 terms in the order the header fixes: lane l adds the terms l, l + G, ... in index order, starting from
+    0.0; the partial sums are then added pairwise, partners G/2, G/4, ..., 1 lanes apart. Every step is one float64 addition"""
+    terms = np.asarray(terms, dtype=np.float64)
+    v = np.zeros(G)
+    for i, t in enumerate(terms):
+        v[i % G] = v[i % G] + t
+    lane, o = np.arange(G), G // 2
+    while o > 0:
+        v = v + v[lane ^ o]
+        o //= 2
+    return np.float64(v[0])
+
+
+def cal_infea_reference(c, c_l, c_u, G):
+    """cal_infea of one member (src/Algorithm.cpp:577-602, the call without x) with the terms added as tree_sum adds them"""
+    c, c_l, c_u = (np.asarray(a, dtype=np.float64) for a in (c, c_l, c_u))
+    with np.errstate(invalid="ignore"):
+        terms = np.where(c < c_l, c_l - c, np.where(c > c_u, c - c_u, 0.0))
+    return tree_sum(terms, G)
+
+
+def batch_ratio_test_reference(options, what, rho, f_trial, c_trial, x_k, c_k, f_k, infea_k, delta, p, norm_p, qp_obj, n, m, c_l, c_u):
+    """ratio_test + update_radius (src/Algorithm.cpp:722-801, 820-849) as rsqp_batch_handler_ratio_test states them, in numpy
+    float64 scalars (which do not contract): the expected value of every test.
+
+    options: a mapping with eta_s, eta_c, eta_e, gamma_c, gamma_e, delta_min, delta_max, tol, refresh_ubA. p (NLP layout), norm_p and
+    qp_obj (one entry per member) are those of the last solve; the other arguments are the call's. Returns a dict: the in/out
+    arrays x_k, c_k, f_k, infea_k, delta as new arrays and the seven outputs; a member with word 0 keeps its in/out entries and has
+    NaN (doubles) / 0 (ints) in the outputs, where the call leaves what it found."""
+    f8 = np.float64
+    o = {k: (int(options[k]) if k == "refresh_ubA" else f8(options[k])) for k in
+         ("eta_s", "eta_c", "eta_e", "gamma_c", "gamma_e", "delta_min", "delta_max", "tol", "refresh_ubA")}
+    nq, G = len(n), nlp_step_lanes(n, m)
+    r = {k: np.array(a, dtype=np.float64) for k, a in (("x_k", x_k), ("c_k", c_k), ("f_k", f_k), ("infea_k", infea_k), ("delta", delta))}
+    for k in ("actual_reduction", "pred_reduction", "infea_trial"):
+        r[k] = np.full(nq, np.nan)
+    for k in ("accept", "hu_word", "hm_word", "exitflag"):
+        r[k] = np.zeros(nq, np.int32)
+    c_trial, p = np.asarray(c_trial, dtype=np.float64), np.asarray(p, dtype=np.float64)
+    oN = oC = 0
+    for q in range(nq):
+        N, Cc = slice(oN, oN + int(n[q])), slice(oC, oC + int(m[q]))
+        oN, oC = oN + int(n[q]), oC + int(m[q])
+        if int(what[q]) == 0:
+            continue
+        rho_q, fk, ik, ft = f8(rho[q]), f8(r["f_k"][q]), f8(r["infea_k"][q]), f8(f_trial[q])
+        with np.errstate(all="ignore"):
+            it = cal_infea_reference(c_trial[Cc], c_l[Cc], c_u[Cc], G)
+            actual = (fk + rho_q * ik) - (ft + rho_q * it)
+            pred = rho_q * ik - f8(qp_obj[q])
+            accept = bool(actual >= o["eta_s"] * pred and actual >= -o["tol"])
+            d, radius = f8(r["delta"][q]), False
+            if actual < o["eta_c"] * pred:
+                d, radius = o["gamma_c"] * d, True
+            elif actual > o["eta_e"] * pred and o["tol"] > abs(d - f8(norm_p[q])):
+                grown = o["gamma_e"] * d
+                d, radius = (o["delta_max"] if o["delta_max"] < grown else grown), True
+        if accept:
+            r["x_k"][N] = r["x_k"][N] + p[N]
+            r["c_k"][Cc] = c_trial[Cc]
+            r["f_k"][q], r["infea_k"][q] = ft, it
+        r["delta"][q] = d
+        r["actual_reduction"][q], r["pred_reduction"][q], r["infea_trial"][q], r["accept"][q] = actual, pred, it, int(accept)
+        if accept:
+            r["hu_word"][q] = capi.HU_BOUNDS | capi.HU_GRAD | (capi.HU_UBA if o["refresh_ubA"] else 0)
+            r["hm_word"][q] = capi.HM_JAC | capi.HM_HESS
+        elif radius:
+            r["hu_word"][q] = capi.HU_DELTA
+        r["exitflag"][q] = capi.EXIT_TRUST_REGION_TOO_SMALL if d < o["delta_min"] else capi.EXIT_UNKNOWN
+    return r
+
+
+EQUAL, BOUNDED, BOUNDED_BELOW, BOUNDED_ABOVE, UNBOUNDED = "EQUAL", "BOUNDED", "BOUNDED_BELOW", "BOUNDED_ABOVE", "UNBOUNDED"
+
+
+def classify_single_constraint(lower_bound, upper_bound):
+    """src/Utils.cpp:29-45 exactly as written: the second branch tests upper_bound > INF, so (finite, exactly 1e18) is UNBOUNDED"""
+    if lower_bound > -INF and upper_bound < INF:
+        return EQUAL if (upper_bound - lower_bound) < 1.0e-8 else BOUNDED
+    elif lower_bound > -INF and upper_bound > INF:
+        return BOUNDED_BELOW
+    elif upper_bound < INF and lower_bound < -INF:
+        return BOUNDED_ABOVE
+    return UNBOUNDED
+
+
+def batch_check_optimality_reference(options, what, x_k, grad, c_k, infea, lam_x, lam_c, J, n, m, x_l, x_u, c_l, c_u):
+    """check_optimality (src/Algorithm.cpp:170-364) as rsqp_batch_handler_check_optimality states it: the expected value of every
+    test. Products and differences are float64, as the C expressions are; the four sums are taken in np.longdouble.
+
+    lam_x (NLP layout) and lam_c (constraint layout) are the multipliers of the last solve; J[q]: member q's Jacobian as a dense
+    m x n array. Returns (status, verdict, scale): status [nq, 5] float64 over (primal, dual, compl, stationarity, KKT_error) --
+    NaN for a member with word 0 --, verdict the bits, and scale [nq, 3, 2] = per sum (dual, compl, stationarity) the number of
+    terms that enter it and the sum of the absolute values of all products that enter it (stationarity: every |J_ij lam_i|, |lam_x|
+    and |grad|), from which a test derives its rounding bound."""
+    L = np.longdouble
+    tol = [np.float64(options[k]) for k in ("opt_prim_fea_tol", "opt_dual_fea_tol", "opt_compl_tol", "opt_stat_tol")]
+    nq = len(n)
+    status, verdict, scale = np.full((nq, 5), np.nan), np.zeros(nq, np.int32), np.zeros((nq, 3, 2))
+    arrs = [np.asarray(a, dtype=np.float64) for a in (x_k, grad, c_k, lam_x, lam_c, x_l, x_u, c_l, c_u)]
+    x_k, grad, c_k, lam_x, lam_c, x_l, x_u, c_l, c_u = arrs
+    oN = oC = 0
+    for q in range(nq):
+        N, Cc = slice(oN, oN + int(n[q])), slice(oC, oC + int(m[q]))
+        oN, oC = oN + int(n[q]), oC + int(m[q])
+        if int(what[q]) == 0:
+            continue
+        dual, compl, kd, kc, sd, sc = L(0), L(0), 0, 0, L(0), L(0)
+        with np.errstate(all="ignore"):
+            for lo, up, v, lam in list(zip(x_l[N], x_u[N], x_k[N], lam_x[N])) + list(zip(c_l[Cc], c_u[Cc], c_k[Cc], lam_c[Cc])):
+                t = classify_single_constraint(lo, up)
+                if t == BOUNDED_ABOVE:
+                    d, c = (np.float64(0.0) if lam < 0.0 else lam), abs(lam * (up - v))
+                elif t == BOUNDED_BELOW:
+                    d, c = -(np.float64(0.0) if 0.0 < lam else lam), abs(lam * (v - lo))
+                elif t == UNBOUNDED:
+                    d, c = None, abs(lam)
+                else:
+                    continue
+                if d is not None:
+                    dual, kd, sd = dual + L(d), kd + 1, sd + L(abs(d))
+                compl, kc, sc = compl + L(c), kc + 1, sc + L(c)
+            Jq = np.asarray(J[q], dtype=np.float64).reshape(int(m[q]), int(n[q]))
+            prod = Jq * lam_c[Cc][:, None]                                    # float64 products, as the device forms them
+            col = prod.astype(L).sum(axis=0) + lam_x[N].astype(L) - grad[N].astype(L)
+            stat = np.abs(col).sum()
+            ks = Jq.size + 2 * int(n[q])
+            ss = np.abs(prod).astype(L).sum() + np.abs(lam_x[N]).astype(L).sum() + np.abs(grad[N]).astype(L).sum()
+        primal = np.float64(infea[q])
+        dual, compl, stat = np.float64(dual), np.float64(compl), np.float64(stat)
+        status[q] = (primal, dual, compl, stat, dual + primal + compl + stat)
+        bits = [primal < tol[0], dual < tol[1], compl < tol[2], stat < tol[3]]
+        verdict[q] = sum(1 << k for k, b in enumerate(bits) if b) | (16 if all(bits) else 0)
+        scale[q] = ((kd, float(sd)), (kc, float(sc)), (ks, float(ss)))
+    return status, verdict, scale
+
+
 class BatchQPhandler:
     """QPhandler for every member of a ``capi.Batch`` whose members have the (p, u, v) shape: the reference's method names, each with
     a member mask first. A call notes its arguments for the named members and ORs bits into a pending word per member;
