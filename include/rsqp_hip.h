@@ -568,4 +568,6 @@ int rsqp_dense_chol_inverse(int n, double *G, double *Ginv, double pd_rel, doubl
 #include "rsqp_hip_dense_check.h"
 /* the decisions of a lock-step SQP loop per member of a batch (infeasibility, ratio test + radius, NLP KKT check): the same way */
 #include "rsqp_hip_nlp_step.h"
+/* update_penalty_parameter per member of a QP batch and the LP batch paired with it, decided on the device: the same way */
+#include "rsqp_hip_penalty.h"
 #endif

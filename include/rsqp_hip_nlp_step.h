@@ -77,7 +77,8 @@ typedef struct {
  *   rejected, a radius branch taken: hu_word = RSQP_HU_DELTA, hm_word = 0
  *   otherwise:                both 0 -- the reference's "QP is not changed" state (:652-671), which the caller sees as two zero
  *                             words beside a non-zero `what`.
- * The penalty bit stays with the caller, who ORs it in: update_penalty_parameter solves QPs and LPs and is not part of this call.
+ * The penalty bit stays with the caller, who ORs it in: update_penalty_parameter solves QPs and LPs and is not part of this call but
+ * of rsqp_hip_penalty.h's rsqp_batch_handler_update_penalty, which runs before it and returns that bit as its own hu_word.
  * Required: t, o, what, rho, f_trial, x_k, f_k, infea_k, delta (and c_trial, c_k when the batch has constraints). */
 int rsqp_batch_handler_ratio_test(rsqp_batch *b, const rsqp_nlp_trial *t, const rsqp_nlp_step_options *o, int on_device);
 

@@ -175,6 +175,12 @@ NLP_STEP_SYMBOLS = {
     "rsqp_batch_handler_ratio_test": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "rsqp_batch_handler_check_optimality": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
 }
+# ... and of include/rsqp_hip_penalty.h (update_penalty_parameter per member of a QP batch and the LP batch paired with it)
+PENALTY_SYMBOLS = {
+    "rsqp_penalty_default_options": (C.c_int, [C.c_void_p]),
+    "rsqp_batch_handler_pair_lp": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rsqp_batch_handler_update_penalty": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+}
 EXIT_UNKNOWN, EXIT_TRUST_REGION_TOO_SMALL = -99, 4                                                      # RSQP_EXIT_*
 KKT_PRIMAL, KKT_DUAL, KKT_COMPL, KKT_STAT, KKT_FIRST_ORDER_OPT = 1, 2, 4, 8, 16                         # RSQP_KKT_*: the verdict bits
 DENSE_GEMM_PLAIN, DENSE_GEMM_UPPER, DENSE_GEMM_KTRI1, DENSE_GEMM_KTRI2, DENSE_GEMM_KTRI3 = range(5)      # RSQP_DENSE_GEMM_*
@@ -227,6 +233,33 @@ class NlpPoint(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("what", "x_k", "grad", "c_k", "infea")]
 
 
+class PenaltyOptions(C.Structure):
+    """rsqp_penalty_options; a new one holds the defaults of src/Options.cpp:43-52 (rsqp_penalty_default_options), keyword arguments
+    override fields"""
+    _fields_ = [("penalty_update_tol", C.c_double), ("increase_parm", C.c_double), ("rho_max", C.c_double), ("penalty_iter_max", C.c_int),
+                ("eps1_change_parm", C.c_double), ("eps2", C.c_double)]
+
+    def __init__(self, **fields):
+        super().__init__()
+        check(lib().rsqp_penalty_default_options(C.addressof(self)))
+        for k, v in fields.items():
+            if k not in dict(self._fields_):
+                raise TypeError("rsqp_penalty_options has no field %r" % k)
+            setattr(self, k, v)
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class PenaltyState(C.Structure):
+    """rsqp_penalty_state: host or device addresses, as handler_update_penalty's on_device says"""
+    IN = ("what", "infea_k", "delta", "x_k", "c_k")
+    INOUT = ("rho", "eps1", "trial", "succ", "fail")
+    OUT = ("infea_model", "infea_infty", "hu_word", "exitflag", "nwsr_qp", "nwsr_lp", "rounds")
+    INTS = ("what", "trial", "succ", "fail", "hu_word", "exitflag", "nwsr_qp", "nwsr_lp", "rounds")
+    _fields_ = [(k, C.c_void_p) for k in IN + INOUT + OUT]
+
+
 class RsqpError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("rsqp error %d: %s" % (code, msg))
@@ -247,7 +280,7 @@ def lib():
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SYMBOLS.items()) + list(LANE_SYMBOLS.items()) + list(HANDOVER_SYMBOLS.items()) + \
                 list(LANE_WARM_SYMBOLS.items()) + list(LANE_HOT_SYMBOLS.items()) + list(DENSE_CHECK_SYMBOLS.items()) + \
-                list(NLP_STEP_SYMBOLS.items()):
+                list(NLP_STEP_SYMBOLS.items()) + list(PENALTY_SYMBOLS.items()):
             f = getattr(L, name)
             f.restype = res
             f.argtypes = args
@@ -812,6 +845,43 @@ class Batch:
         check(lib().rsqp_batch_handler_check_optimality(self._h, C.addressof(p), C.addressof(o), oa, va, int(bool(on_device))))
         del keep
         return out, verdict
+
+    # ---- update_penalty_parameter per member, across this batch and its LP batch (include/rsqp_hip_penalty.h) ----
+    def handler_pair_lp(self, lp):
+        """`lp` becomes the LP handler of this batch (myLP_ beside myQP_, rsqp_batch_handler_pair_lp): another Batch of the same
+        members -- sizes and canonical A pattern member by member --, on the same device, with handler_set_problem called on both;
+        None unpairs. The pair keeps `lp` alive"""
+        check(lib().rsqp_batch_handler_pair_lp(self._h, None if lp is None else lp._h))
+        self._lp_pair = lp
+
+    def handler_update_penalty(self, what, infea_k, delta, x_k, c_k, rho, eps1, trial, succ, fail, options=None, on_device=False, out=None):
+        """update_penalty_parameter for every member with what[q] != 0 (rsqp_batch_handler_update_penalty), between the QP solve and
+        the ratio test: on the results of this batch's last solve, with the LP batch of handler_pair_lp. what (int32), infea_k,
+        delta: nq; x_k: NLP layout; c_k: the layout of lbA. rho, eps1 (float64) and trial, succ, fail (int32) are the members' state
+        and are WRITTEN IN PLACE: contiguous ndarrays, or with on_device tensors on the batch's device, complete before the call.
+        Returns the outputs as a dict over PenaltyState.OUT (infea_model, infea_infty: float64, the others int32) -- the arrays of
+        `out` where it has them (a member with word 0 keeps their bytes), else new zero-filled ones"""
+        sN, sC = self._handler_sizes()
+        nq = self.nq
+        size = dict(what=nq, infea_k=nq, delta=nq, x_k=sN, c_k=sC, rho=nq, eps1=nq, trial=nq, succ=nq, fail=nq)
+        given = dict(what=what, infea_k=infea_k, delta=delta, x_k=x_k, c_k=c_k, rho=rho, eps1=eps1, trial=trial, succ=succ, fail=fail)
+        out = dict(out or {})
+        for k in PenaltyState.OUT:
+            if out.get(k) is None:
+                out[k] = self._new_out(nq, on_device, ints=k in PenaltyState.INTS)
+        s, keep = PenaltyState(), []
+        for k in PenaltyState.IN + PenaltyState.INOUT:
+            if given[k] is None and size[k] > 0:
+                raise ValueError("%s is required" % k)
+            addr, a = self._addr(given[k], size[k], k, on_device, ints=k in PenaltyState.INTS, writable=k in PenaltyState.INOUT)
+            setattr(s, k, addr); keep.append(a)
+        for k in PenaltyState.OUT:
+            addr, a = self._addr(out[k], nq, k, on_device, ints=k in PenaltyState.INTS, writable=True)
+            setattr(s, k, addr)
+        o = options or PenaltyOptions()
+        check(lib().rsqp_batch_handler_update_penalty(self._h, C.addressof(s), C.addressof(o), int(bool(on_device))))
+        del keep
+        return out
 
     def get_vectors(self):
         """(g, lb, ub, lbA, ubA) as the pools hold them on the device, in the layout of set_vectors"""

@@ -1,7 +1,8 @@
 // rsqp_batch.h -- struct rsqp_batch and what more than one of its translation units uses. Private to them: rsqp_batch.hip (the batch
 // itself: create, whole-batch setters, solve, results, certificate, records), rsqp_batch_optimize.hip (optimizeQP / optimizeLP per
 // member and their plan kernels), rsqp_batch_handler.hip (everything that writes the pools member by member) and rsqp_batch_nlp.hip
-// (the decisions of the SQP loop, which read the pools member by member). Device code does not cross a unit: the __device__ helpers
+// (the decisions of the SQP loop, which read the pools member by member) and rsqp_batch_penalty.hip (update_penalty_parameter across
+// a QP batch and its LP batch). Device code does not cross a unit: the __device__ helpers
 // here are inline. Everything but the struct itself (the opaque type of the C ABI) is in namespace rsqp_batch_units, which the units
 // open.
 #pragma once
@@ -151,6 +152,15 @@ struct rsqp_batch {
     bool opt_started = false;             // an rsqp_batch_optimize_qp has run: members are in different states from here on
     float last_ms = 0.f;
     bool keep_state = true;
+    // rsqp_batch_handler_pair_lp / rsqp_batch_handler_update_penalty (rsqp_batch_penalty.hip): the host's copy of the canonical A
+    // pattern (what the pairing compares), the LP batch paired with this one, and the call's per-member work on the device, allocated
+    // at its first use: pen_i = PEN_INTS x nq ints, pen_d = PEN_DOUBLES x nq doubles, the x of the first solve (sumV), the block
+    // counters of the decision kernels, and the host-mapped word they report through
+    std::vector<int> h_Ajc, h_Air;
+    rsqp_batch *lp_pair = nullptr;
+    DevBuf<int> pen_i, pen_cnt;
+    DevBuf<double> pen_d, pen_x;
+    HostBuf<int> pen_live;
     bool timing = false;   // between timer_start and timer_stop: no per-launch events (they cost ~10 us of stream time each)
     ~rsqp_batch() {
         if (ev0) (void)hipEventDestroy(ev0);
@@ -184,4 +194,6 @@ int settle_A(rsqp_batch *b);
 int settle_H(rsqp_batch *b);
 // rsqp_batch_handler.hip: the pinned block and the scratch block of at least `words` doubles each (rsqp_batch::scratch)
 int ensure_staging(rsqp_batch *b, size_t words);
+// what rsqp_batch_handler_set_matrices builds at its first call: hm_joff, and hm_inv, the inverse of perm (CSC slot -> CSR slot)
+int ensure_handler_matrices(rsqp_batch *b);
 }  // namespace rsqp_batch_units

@@ -152,6 +152,7 @@ extern "C" int rsqp_batch_create(int nq, const int *nV, const int *nC, const int
         judge_h_sym(b, nullptr, Hval_in);   // (on the caller's arrays: repeated positions are summed in the caller's order on both)
     } else if (b->haveH) b->h_sym = false;
     b->sumV = offV; b->sumC = offC; b->sumAnz = offAnz; b->sumHnz = offHnz;
+    b->h_Ajc.assign(Ajc, Ajc + offAjc); b->h_Air.assign(Air, Air + offAnz);   // (rsqp_batch_handler_pair_lp compares them)
     // uniform batch: every member has the sizes and the patterns of member 0 (QPPools::uni_pat)
     b->uni_pat = b->uniV > 0 && b->uniC >= 0;
     if (b->uni_pat) {

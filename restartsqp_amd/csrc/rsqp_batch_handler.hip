@@ -431,8 +431,10 @@ batch_hess_symmetry_kernel(int nq, const QPDesc *__restrict__ desc, const int *_
     if (symq[q] != s) { symq[q] = s; *changed = 1; }
 }
 
+}  // namespace
+
 // what the first call builds: where the members' entries start in jac, and the inverse of perm
-int ensure_handler_matrices(rsqp_batch *b) {
+int rsqp_batch_units::ensure_handler_matrices(rsqp_batch *b) {
     if (b->hm_ready) return RSQP_OK;
     std::vector<long long> joff((size_t)b->nq + 1, 0);
     for (int q = 0; q < b->nq; q++) joff[q + 1] = joff[q] + b->h_jn[q];
@@ -446,7 +448,6 @@ int ensure_handler_matrices(rsqp_batch *b) {
     b->hm_ready = true;
     return RSQP_OK;
 }
-}  // namespace
 
 extern "C" int rsqp_batch_handler_set_matrices(rsqp_batch *b, const int *what, const double *jac, const double *hess, int on_device) {
     if (!b || !what) return fail(RSQP_ERR_ARG, "rsqp_batch_handler_set_matrices: the batch and what are required");

@@ -495,3 +495,119 @@ class BatchQPhandler:
     def step(self, on_device=None, out=None):
         """p, lam_c, lam_x, infea_model (get_infea_measure_model, :592-594) and norm_p of the last solve (Batch.handler_step)"""
         return self.batch.handler_step(self.on_device if on_device is None else on_device, out=out)
+
+
+# ------------------------------------------------------------------------------------
+# update_penalty_parameter per member (rsqp_batch_handler_update_penalty of include/rsqp_hip_penalty.h)
+# ------------------------------------------------------------------------------------
+def penalty_lp_data(st, qp):
+    """setupLP (src/Algorithm.cpp:700-704) for one member: the data of its LP from the data `qp` of the QP just solved -- set_bounds
+    from the iterate, set_g(rho) (zeros, then rho on the slacks), set_A with the QP's J. H stays what `qp` has: an LP solve ignores it"""
+    import copy
+    n, m = int(st["n"]), int(st["m"])
+    d = copy.copy(qp)
+    d.g = np.concatenate([np.zeros(n), np.full(2 * m, np.float64(st["rho"]))])
+    d.lb = np.concatenate([np.maximum(st["x_l"] - st["x_k"], -st["delta"]), np.zeros(2 * m)])
+    d.ub = np.concatenate([np.minimum(st["x_u"] - st["x_k"], st["delta"]), np.full(2 * m, INF)])
+    d.lbA, d.ubA = st["c_l"] - st["c_k"], st["c_u"] - st["c_k"]
+    return d
+
+
+def batch_update_penalty_reference(qp_members, lp_members, state, options, G=8):
+    """Algorithm::update_penalty_parameter (src/Algorithm.cpp:886-1028) per member, in plain Python with numpy float64 scalars (which
+    do not contract), as rsqp_batch_handler_update_penalty states it: the expected value of every test.
+
+    qp_members[q] / lp_members[q]: the member's two solver objects. Each has optimize(data, new_matrices=False) -> nWSR_used of the
+    call (optimizeQP / optimizeLP on the QPData-like `data`; new_matrices: set_A comes first), and x, objective, status (the exit
+    flag, capi.QP_OPTIMAL when solved) of its last solve; the QP member has just solved state[q]["qp"]. state[q]: a dict with what,
+    qp (the data of that solve), n, m, infea_k, delta, x_k, c_k, x_l, x_u, c_l, c_u, rho, eps1, trial, succ, fail. options: a mapping
+    over the fields of rsqp_penalty_options. G: lanes of the tree sums (nlp_step_lanes over the batch).
+
+    Returns one dict per member: the state as the call leaves it (rho, eps1, trial, succ, fail), the outputs (infea_model,
+    infea_infty -- None where no LP solved --, hu_word, exitflag, nwsr_qp, nwsr_lp, rounds), x and obj as the result pools hold them
+    afterwards (the first solve's on the failure path), and for the tests' own checks: branch (None sat out, "qp_unsolved", "none",
+    "lp_unsolved", "A", "B"), outcome (None, "success", "failure"), broke (left the loop on an unsolved QP), capped (left it at
+    rho_max) and margins, the relative distance |a - b| / max(|a|, |b|) of every float comparison that decided something."""
+    import copy
+    f8 = np.float64
+    o = {k: (int(options[k]) if k == "penalty_iter_max" else f8(options[k])) for k in
+         ("penalty_update_tol", "increase_parm", "rho_max", "penalty_iter_max", "eps1_change_parm", "eps2")}
+    out = []
+
+    def slack_sum(x, n):
+        return tree_sum(np.abs(np.asarray(x, dtype=np.float64)[n:]), G)
+
+    for q, st in enumerate(state):
+        r = dict(rho=f8(st["rho"]), eps1=f8(st["eps1"]), trial=int(st["trial"]), succ=int(st["succ"]), fail=int(st["fail"]),
+                 infea_model=None, infea_infty=None, hu_word=0, exitflag=None, nwsr_qp=0, nwsr_lp=0, rounds=0, branch=None, outcome=None,
+                 broke=False, capped=False, margins=[], x=None, obj=None)
+        out.append(r)
+        if int(st["what"]) == 0:
+            continue
+        Q, L = qp_members[q], lp_members[q]
+        margins = r["margins"]
+
+        def cmp(a, b):
+            with np.errstate(all="ignore"):
+                scale = max(abs(a), abs(b))
+                margins.append(float(abs(a - b) / scale) if scale > 0 and np.isfinite(scale) else 1.0)
+
+        if Q.status != capi.QP_OPTIMAL:
+            r.update(branch="qp_unsolved", exitflag=int(Q.status))
+            continue
+        n, m = int(st["n"]), int(st["m"])
+        infea_k, rho = f8(st["infea_k"]), f8(st["rho"])
+        r["exitflag"] = capi.EXIT_UNKNOWN
+        model = slack_sum(Q.x, n)
+        r.update(x=np.array(Q.x), obj=f8(Q.objective), infea_model=model)
+        cmp(model, o["penalty_update_tol"])
+        if not model > o["penalty_update_tol"]:                                          # :893
+            r["branch"] = "none"
+            continue
+        model0, rho_trial, x0, obj0 = model, rho, np.array(Q.x), f8(Q.objective)
+        r["nwsr_lp"] = int(L.optimize(penalty_lp_data(st, st["qp"]), new_matrices=True))  # setupLP + solveLP (:896-899)
+        if L.status != capi.QP_OPTIMAL:                                                  # :901-904
+            r.update(branch="lp_unsolved", exitflag=int(L.status))
+            continue
+        infty = slack_sum(L.x, n)
+        r["infea_infty"] = infty
+        cmp(infty, o["penalty_update_tol"])
+        r["branch"] = "A" if infty <= o["penalty_update_tol"] else "B"                  # :909
+        data = copy.copy(st["qp"])
+        while True:
+            if r["branch"] == "A":                                                       # :914
+                cmp(model, o["penalty_update_tol"])
+                if not model > o["penalty_update_tol"]:
+                    break
+            else:                                                                        # :941-944
+                lhs, rhs = infea_k - model, r["eps1"] * (infea_k - infty)
+                cmp(lhs, rhs)
+                if not (lhs < rhs and r["trial"] < o["penalty_iter_max"]):
+                    break
+            if rho_trial >= o["rho_max"]:                                                # :915, :947
+                r["capped"] = True
+                break
+            nxt = rho_trial * o["increase_parm"]
+            rho_trial = nxt if nxt < o["rho_max"] else o["rho_max"]                     # min(rho_max, rho_trial * increase_parm)
+            r["trial"] += 1
+            data.g = np.concatenate([np.asarray(st["qp"].g, dtype=np.float64)[:n], np.full(2 * m, rho_trial)])   # update_penalty
+            r["nwsr_qp"] += int(Q.optimize(data))
+            r["rounds"] += 1
+            if Q.status != capi.QP_OPTIMAL:                                              # :929-932, :963-966
+                r.update(broke=True, exitflag=int(Q.status))
+                break
+            model = slack_sum(Q.x, n)
+        r["infea_model"] = model
+        if rho_trial > rho:                                                              # :975
+            if not r["broke"]:
+                lhs, rhs = rho_trial * infea_k - f8(Q.objective), o["eps2"] * rho_trial * (infea_k - model)
+                cmp(lhs, rhs)
+            if not r["broke"] and lhs >= rhs:                                            # :979-981
+                r["succ"] += 1
+                r["eps1"] = r["eps1"] + (1 - r["eps1"]) * o["eps1_change_parm"]
+                r["rho"] = rho_trial
+                r.update(outcome="success", x=np.array(Q.x), obj=f8(Q.objective))
+            else:
+                r["fail"] += 1
+                r.update(outcome="failure", infea_model=model0, hu_word=capi.HU_PENALTY, x=x0, obj=obj0)
+    return out
