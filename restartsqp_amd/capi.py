@@ -181,6 +181,17 @@ PENALTY_SYMBOLS = {
     "rsqp_batch_handler_pair_lp": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rsqp_batch_handler_update_penalty": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
 }
+# ... and of include/rsqp_hip_band_check.h (the banded H^-1 operator of the HBM-resident engine called the way the engine calls it)
+_vec = [dp, _ll, _ll]           # a whole host buffer holding one vector (or the columns of a matrix): pointer, length, offset
+BAND_CHECK_SYMBOLS = {
+    "rsqp_band_check_factor": (C.c_int, [C.c_int, dp, dp, dp, ip, ip, ip, dp, dp, _ll, dp, _ll, dp, _ll]),
+    "rsqp_band_check_create": (C.c_int, [C.c_int, dp, dp, dp, C.POINTER(C.c_void_p)]),
+    "rsqp_band_check_destroy": (C.c_int, [C.c_void_p]),
+    "rsqp_band_check_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ll, C.c_int] + 3 * _vec + [ip, C.POINTER(_ll)]),
+    "rsqp_band_check_apply_q": (C.c_int, [C.c_void_p, C.c_int, ip, dp, dp, dp, dp] + 2 * _vec + [ip, C.POINTER(_ll)]),
+}
+BAND_KERNEL_ENGINE, BAND_KERNEL_1WG = 0, 1                                                              # RSQP_BAND_KERNEL_*
+BAND_MAX_N, BAND_THREADS = 16384, 1024                                                                  # RSQP_BAND_MAX_N, _THREADS
 EXIT_UNKNOWN, EXIT_TRUST_REGION_TOO_SMALL = -99, 4                                                      # RSQP_EXIT_*
 KKT_PRIMAL, KKT_DUAL, KKT_COMPL, KKT_STAT, KKT_FIRST_ORDER_OPT = 1, 2, 4, 8, 16                         # RSQP_KKT_*: the verdict bits
 DENSE_GEMM_PLAIN, DENSE_GEMM_UPPER, DENSE_GEMM_KTRI1, DENSE_GEMM_KTRI2, DENSE_GEMM_KTRI3 = range(5)      # RSQP_DENSE_GEMM_*
@@ -280,7 +291,7 @@ def lib():
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SYMBOLS.items()) + list(LANE_SYMBOLS.items()) + list(HANDOVER_SYMBOLS.items()) + \
                 list(LANE_WARM_SYMBOLS.items()) + list(LANE_HOT_SYMBOLS.items()) + list(DENSE_CHECK_SYMBOLS.items()) + \
-                list(NLP_STEP_SYMBOLS.items()) + list(PENALTY_SYMBOLS.items()):
+                list(NLP_STEP_SYMBOLS.items()) + list(PENALTY_SYMBOLS.items()) + list(BAND_CHECK_SYMBOLS.items()):
             f = getattr(L, name)
             f.restype = res
             f.argtypes = args
@@ -312,6 +323,76 @@ def describe_dense_gemm(m, n, k, batch=1, ws_cap=None):
     out = np.zeros(len(DENSE_PLAN_OUT), np.int32)
     check(lib().rsqp_dense_describe_gemm(m, n, k, batch, int(ws_cap is not None), ws_cap or 0, _ip(out), len(out)))
     return dict(zip(DENSE_PLAN_OUT, out.tolist()))
+
+
+def band_factor(d0, e1, e2):
+    """the host side of the banded H^-1 operator for the bands d0 = H[i][i], e1 = H[i][i-1], e2 = H[i][i-2] as a dict: built, c (rows
+    per chunk), build (the C of the kernels), growth, and -- when built -- the chunk-interleaved m1i, m2i and sinv exactly as they are
+    uploaded (else None). Needs no GPU (rsqp_band_check_factor)"""
+    d0, e1, e2 = _d(d0), _d(e1), _d(e2)
+    n = len(d0)
+    c = (n + BAND_THREADS - 1) // BAND_THREADS
+    m1i, m2i, sinv = np.zeros(BAND_THREADS * (c + 1)), np.zeros(BAND_THREADS * (c + 2)), np.zeros(max(n, 1))
+    w = [C.c_int(0) for _ in range(3)]
+    growth = C.c_double(0.0)
+    check(lib().rsqp_band_check_factor(n, _dp(d0), _dp(e1), _dp(e2), *[C.byref(v) for v in w], C.byref(growth), _dp(m1i), len(m1i),
+                                       _dp(m2i), len(m2i), _dp(sinv), len(sinv)))
+    built = bool(w[0].value)
+    return dict(built=built, c=w[1].value, build=w[2].value, growth=growth.value, m1i=m1i if built else None,
+                m2i=m2i if built else None, sinv=sinv[:n] if built else None)
+
+
+class BandCheck:
+    """the uploaded banded factor of one Hessian (rsqp_band_check): apply / apply_q launch the engine's kernels on whole host
+    buffers, which are float64 ndarrays WRITTEN IN PLACE (every double of them comes back from the device)"""
+
+    def __init__(self, d0, e1, e2):
+        d0, e1, e2 = _d(d0), _d(e1), _d(e2)
+        self.n = len(d0)
+        h = C.c_void_p()
+        check(lib().rsqp_band_check_create(self.n, _dp(d0), _dp(e1), _dp(e2), C.byref(h)))
+        self._h = h
+        self.seq = 0        # the tag of the last multi-workgroup product
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().rsqp_band_check_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    @staticmethod
+    def _whole(a, name):
+        if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.ndim == 1 and a.flags.c_contiguous and a.flags.writeable):
+            raise ValueError("%s is written in place: a contiguous one-dimensional float64 ndarray is needed" % name)
+        return a
+
+    def apply(self, buf_in, off_in=0, ncols=1, ld=None, sub=None, off_sub=0, buf_out=None, off_out=0, kernel=BAND_KERNEL_ENGINE):
+        """out(:, j) = H^-1 (in(:, j) - sub), j < ncols; buf_out None: in place (the result replaces the operand in buf_in).
+        Returns the err word"""
+        a = self._whole(buf_in, "buf_in")
+        o = None if buf_out is None else self._whole(buf_out, "buf_out")
+        s = _d(sub)
+        err, seq = C.c_int(0), C.c_longlong(0)
+        check(lib().rsqp_band_check_apply(self._h, kernel, ncols, self.n if ld is None else ld, int(o is None), _dp(a), len(a), off_in,
+                                          _dp(s), 0 if s is None else len(s), off_sub, _dp(o), 0 if o is None else len(o), off_out,
+                                          C.byref(err), C.byref(seq)))
+        self.seq = seq.value
+        return err.value
+
+    def apply_q(self, Sb, ATdy, dy, gN, g, buf_Hdx, off_h, buf_dx, off_x, kernel=BAND_KERNEL_ENGINE):
+        """the step direction's form of one vector: Hdx = (ATdy + (Sb ? dy : 0)) - (gN - g) on every row, dx = H^-1 Hdx on the rows
+        with Sb == 0. Returns the err word"""
+        Sb = _i(Sb)
+        v = [_d(x) for x in (ATdy, dy, gN, g)]
+        if len(Sb) != self.n or any(len(x) != self.n for x in v):
+            raise ValueError("Sb, ATdy, dy, gN, g have %d entries each" % self.n)
+        hb, xb = self._whole(buf_Hdx, "buf_Hdx"), self._whole(buf_dx, "buf_dx")
+        err, seq = C.c_int(0), C.c_longlong(0)
+        check(lib().rsqp_band_check_apply_q(self._h, kernel, _ip(Sb), *[_dp(x) for x in v], _dp(hb), len(hb), off_h, _dp(xb), len(xb),
+                                            off_x, C.byref(err), C.byref(seq)))
+        self.seq = seq.value
+        return err.value
 
 
 def plan_builds(plan):

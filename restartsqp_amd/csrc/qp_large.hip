@@ -3524,3 +3524,5 @@ double RsqpLargeEngine::objective() {
     P.read_scal(20, 3, r);
     return 0.5 * (r[0] - P.M.hreg * r[2]) + r[1];
 }
+
+#include "qp_band_check.h"

@@ -10,19 +10,25 @@
 using Impl = RsqpLargeEngine::Impl;
 
 // ---- the H^-1 operator -------------------------------------------------------------------------------------------------------------
-// banded: LDL' on the host (O(n) work, the values come over once per set-up), homogeneous solutions per chunk, nine arrays up
-int Impl::rs_build_band(const std::vector<double> &hv, bool *ok) {
-    *ok = false;
-    const int n = nV;
-    std::vector<double> d0(n, 0.0), e1(n, 0.0), e2(n, 0.0);      // H[i][i], H[i][i-1], H[i][i-2]
-    for (int c = 0; c < n; c++)
-        for (int k = M.h_Hjc[c]; k < M.h_Hjc[c + 1]; k++) {
-            const int r = M.h_Hir[k];
-            if (r == c) d0[c] += hv[k];
-            else if (r == c + 1) e1[r] += hv[k];
-            else if (r == c + 2) e2[r] += hv[k];
-        }
-    for (int i = 0; i < n; i++) d0[i] += M.hreg;
+// banded: LDL' on the host (O(n) work, the values come over once per set-up), homogeneous solutions per chunk, nine arrays up.
+// The host side is stated ONCE, in three free functions that the engine (rs_build_band / band_launch below) and the check entry
+// points of include/rsqp_hip_band_check.h (qp_band_check.h) share: the factor and its chunk-interleaved image (band_factor_host),
+// the rule "rows per chunk -> build of the kernels" (band_build_of, through BAND_BUILDS) and the launch itself (band_dispatch).
+struct BandFactor {
+    bool built = false;
+    int n = 0, c = 0;                 // rows, rows per chunk
+    double growth = -1.0;             // largest entry of a homogeneous solution over a 64-row window (-1: a pivot failed first)
+    std::vector<double> buf;          // m1i [T (c + 1)] | m2i [T (c + 2)] | sinv [n] | agg [2 * BAND_MW * 8], as uploaded
+    size_t off_m2i() const { return (size_t)BAND_TH * (c + 1); }
+    size_t off_sinv() const { return (size_t)BAND_TH * (2 * c + 3); }
+    size_t off_agg() const { return off_sinv() + (size_t)n; }
+};
+// d0 = H[i][i] (hreg included), e1 = H[i][i-1], e2 = H[i][i-2]; not built: n outside 1..BAND_MAX_N, a pivot that is not positive
+// (enough), or a factor whose homogeneous solutions grow
+static void band_factor_host(int n, const double *d0, const double *e1, const double *e2, BandFactor *f) {
+    *f = BandFactor();
+    if (n < 1 || n > BAND_MAX_N) return;
+    f->n = n; f->c = (n + BAND_TH - 1) / BAND_TH;
     std::vector<double> d(n), l1(n, 0.0), l2(n, 0.0);
     for (int i = 0; i < n; i++) {
         if (i >= 2) l2[i] = e2[i] / d[i - 2];
@@ -30,7 +36,7 @@ int Impl::rs_build_band(const std::vector<double> &hv, bool *ok) {
         double di = d0[i];
         if (i >= 1) di -= l1[i] * l1[i] * d[i - 1];
         if (i >= 2) di -= l2[i] * l2[i] * d[i - 2];
-        if (!(di > 1e-12 * std::fabs(d0[i])) || !(di > 0.0)) return RET_OK;      // not positive definite (enough): not this path
+        if (!(di > 1e-12 * std::fabs(d0[i])) || !(di > 0.0)) return;      // not positive definite (enough): not this path
         d[i] = di;
     }
     // (a factor whose homogeneous solutions grow along the rows -- H far from diagonal dominance -- would lose digits in the scan
@@ -45,11 +51,13 @@ int Impl::rs_build_band(const std::vector<double> &hv, bool *ok) {
                 growth = std::max(growth, std::max(std::fabs(na), std::fabs(nb)));
             }
         }
-        if (!(growth <= 1e3)) return RET_OK;
+        f->growth = growth;
+        if (!(growth <= 1e3)) return;
     }
-    const int T = BAND_TH, c = (n + T - 1) / T;
+    const int T = BAND_TH, c = f->c;
     const size_t nagg = 2 * BAND_MW * 8;
-    std::vector<double> buf((size_t)T * (2 * c + 3) + (size_t)n + nagg, 0.0);
+    std::vector<double> &buf = f->buf;
+    buf.assign((size_t)T * (2 * c + 3) + (size_t)n + nagg, 0.0);
     double *m1i = buf.data(), *m2i = m1i + (size_t)T * (c + 1), *sinv = m2i + (size_t)T * (c + 2);
     std::vector<double> sq(n);
     for (int i = 0; i < n; i++) { sq[i] = std::sqrt(d[i]); sinv[i] = 1.0 / sq[i]; }
@@ -60,22 +68,60 @@ int Impl::rs_build_band(const std::vector<double> &hv, bool *ok) {
             m2i[(size_t)k * T + t] = (i < n && i >= 2) ? l2[i] * sq[i - 2] / sq[i] : 0.0;
         }
     }
-    if (!band_buf) LCHK(hipMalloc(reinterpret_cast<void **>(&band_buf), sizeof(double) * buf.size()));
-    LCHK(hipMemcpy(band_buf, buf.data(), sizeof(double) * buf.size(), hipMemcpyHostToDevice));
-    band.n = n; band.c = c;
-    band.m1i = band_buf; band.m2i = band.m1i + (size_t)T * (c + 1); band.sinv = band.m2i + (size_t)T * (c + 2);
-    band.agg = band_buf + (size_t)T * (2 * c + 3) + (size_t)n;
+    f->built = true;
+}
+// the build of k_band_apply / k_band_apply_mw that serves chunks of c rows (C >= c: a chunk lives in C registers per array)
+static inline int band_build_of(int c) { return c <= 4 ? 4 : (c <= 8 ? 8 : (c <= 10 ? 10 : (c <= 12 ? 12 : 16))); }
+#define BAND_BUILDS(X, c) \
+    switch (band_build_of(c)) { case 4: X(4); break; case 8: X(8); break; case 10: X(10); break; case 12: X(12); break; default: X(16); break; }
+// the one-workgroup kernel keeps a whole vector in dynamic LDS (per handle: a function attribute belongs to the device it lives on)
+static hipError_t band_set_attributes() {
+    hipError_t e = hipSuccess;
+#define RS_ATTR(CC) if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_band_apply<CC>), hipFuncAttributeMaxDynamicSharedMemorySize, BAND_MAX_N * 8)
+    RS_ATTR(4); RS_ATTR(8); RS_ATTR(10); RS_ATTR(12); RS_ATTR(16);
+#undef RS_ATTR
+    return e;
+}
+// out = H^-1 (in - sub) for ncols columns, or the step direction's form (q.Sb set). One vector goes to the 16 single-wave
+// workgroups unless one_wg says otherwise, and takes the next tag of *seq; several go to a grid of the one-workgroup kernel
+static void band_dispatch(const BandOp &band, double *seq, bool one_wg, int ncols, const double *in, const double *sub, double *out,
+                          long long ldc, const BandQ &q, hipStream_t st) {
+    if (ncols == 1 && !one_wg) {       // one vector: 16 single-wave workgroups
+        const double tag = (*seq += 1.0);
+#define RS_MW(CC) hipLaunchKernelGGL(k_band_apply_mw<CC>, dim3(BAND_MW), dim3(64), 0, st, band, in, sub, out, q, tag)
+        BAND_BUILDS(RS_MW, band.c)
+#undef RS_MW
+        return;
+    }
+    const size_t lds = sizeof(double) * (size_t)band.n;
+#define RS_1W(CC) hipLaunchKernelGGL(k_band_apply<CC>, dim3(ncols), dim3(BAND_TH), lds, st, band, in, sub, out, ldc, q)
+    BAND_BUILDS(RS_1W, band.c)
+#undef RS_1W
+}
+int Impl::rs_build_band(const std::vector<double> &hv, bool *ok) {
+    *ok = false;
+    const int n = nV;
+    std::vector<double> d0(n, 0.0), e1(n, 0.0), e2(n, 0.0);      // H[i][i], H[i][i-1], H[i][i-2]
+    for (int c = 0; c < n; c++)
+        for (int k = M.h_Hjc[c]; k < M.h_Hjc[c + 1]; k++) {
+            const int r = M.h_Hir[k];
+            if (r == c) d0[c] += hv[k];
+            else if (r == c + 1) e1[r] += hv[k];
+            else if (r == c + 2) e2[r] += hv[k];
+        }
+    for (int i = 0; i < n; i++) d0[i] += M.hreg;
+    BandFactor f;
+    band_factor_host(n, d0.data(), e1.data(), e2.data(), &f);
+    if (!f.built) return RET_OK;
+    if (!band_buf) LCHK(hipMalloc(reinterpret_cast<void **>(&band_buf), sizeof(double) * f.buf.size()));
+    LCHK(hipMemcpy(band_buf, f.buf.data(), sizeof(double) * f.buf.size(), hipMemcpyHostToDevice));
+    band.n = n; band.c = f.c;
+    band.m1i = band_buf; band.m2i = band_buf + f.off_m2i(); band.sinv = band_buf + f.off_sinv();
+    band.agg = band_buf + f.off_agg();
     band.err = dflag + 1;
     band_seq = 0.0;
     LCHK(hipMemsetAsync(dflag + 1, 0, sizeof(int), st));
-    if (!band_attr_set) {      // (per handle: a function attribute belongs to the device the handle lives on)
-        LCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_band_apply<4>), hipFuncAttributeMaxDynamicSharedMemorySize, BAND_MAX_N * 8));
-        LCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_band_apply<8>), hipFuncAttributeMaxDynamicSharedMemorySize, BAND_MAX_N * 8));
-        LCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_band_apply<10>), hipFuncAttributeMaxDynamicSharedMemorySize, BAND_MAX_N * 8));
-        LCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_band_apply<12>), hipFuncAttributeMaxDynamicSharedMemorySize, BAND_MAX_N * 8));
-        LCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_band_apply<16>), hipFuncAttributeMaxDynamicSharedMemorySize, BAND_MAX_N * 8));
-        band_attr_set = true;
-    }
+    if (!band_attr_set) { LCHK(band_set_attributes()); band_attr_set = true; }
     // the explicit inverse as well (in Z: n^2 doubles, 0.8 GB at n = 10 000): H^-1 c' of an incoming row -- a unit vector or a few
     // entries -- is then a combination of a few of its columns (k_rs_hinv_row, every lane busy) instead of a banded product whose
     // two scans and two cross-workgroup hand-offs take 20 us whatever the vector holds. One banded product per column, all at once.
@@ -152,18 +198,7 @@ int Impl::rs_prepare(bool *ok) {
 void Impl::band_launch(int ncols, const double *in, const double *sub, double *out, long long ldc, bool qmode) {
     BandQ q{};
     if (qmode) { q.Sb = Sb; q.ATdy = ATdy; q.dy = dy; q.gN = gN; q.g = g; q.Hdx = Hdx; }
-    const int c = band.c;
-    if (ncols == 1 && !kn.band_1wg) {       // one vector: 16 single-wave workgroups
-        const double seq = (band_seq += 1.0);
-#define RS_MW(CC) hipLaunchKernelGGL(k_band_apply_mw<CC>, dim3(BAND_MW), dim3(64), 0, st, band, in, sub, out, q, seq)
-        if (c <= 4) RS_MW(4); else if (c <= 8) RS_MW(8); else if (c <= 10) RS_MW(10); else if (c <= 12) RS_MW(12); else RS_MW(16);
-#undef RS_MW
-        return;
-    }
-    const size_t lds = sizeof(double) * (size_t)nV;
-#define RS_1W(CC) hipLaunchKernelGGL(k_band_apply<CC>, dim3(ncols), dim3(BAND_TH), lds, st, band, in, sub, out, ldc, q)
-    if (c <= 4) RS_1W(4); else if (c <= 8) RS_1W(8); else if (c <= 10) RS_1W(10); else if (c <= 12) RS_1W(12); else RS_1W(16);
-#undef RS_1W
+    band_dispatch(band, &band_seq, kn.band_1wg, ncols, in, sub, out, ldc, q, st);
 }
 // out = H^-1 (in - sub); fix_dx: the step direction's product -- in = q - (gN - g) formed on the way (into Hdx), out = dx written on
 // the free variables only (in / sub are ignored)

@@ -107,6 +107,39 @@ def test_indefinite_or_unsymmetric_hessian_keeps_the_null_space_path(capi, oracl
         assert s.large_path() == 0
 
 
+def _path_of(capi, q, H):
+    q2 = QPData(q.nV, q.nC, *dense_to_csc(H), q.A_jc, q.A_ir, q.A_val, q.g, q.lb, q.ub, q.lbA, q.ubA)
+    s = load(capi, q2)
+    s.solve(capi.MODE_COLD, 5000)
+    return s.large_path()
+
+
+@pytest.mark.parametrize("nV", [5, 40])
+def test_path_selection_at_the_edges_of_the_symmetry_and_band_check(capi, nV):
+    """k_rs_sym_check decides the path from two words: the half bandwidth (<= 2: the banded operator, path 2; above: a dense H^-1, path 3
+    or 4) and whether every entry has a mirror image of the same value (else the null-space path). Each edge is set by ONE pair of
+    entries, in the first column and in the last one: what a wrong column range, a reduction that drops a wave or a mirror search
+    that misses the ends of a column would get wrong"""
+    rng = np.random.default_rng(505)
+    q = banded_qp(rng, nV, 6, hb=1)
+    H = np.zeros((nV, nV))
+    for c in range(nV):
+        H[q.H_ir[q.H_jc[c]:q.H_jc[c + 1]], c] = q.H_val[q.H_jc[c]:q.H_jc[c + 1]]
+    assert np.array_equal(H, H.T) and _path_of(capi, q, H) == 2           # (tridiagonal: the banded operator)
+    for col in (0, nV - 1):
+        far = lambda d: col + d if col == 0 else col - d                  # the row at distance d from the column, inside the matrix
+        for d, want in ((2, (2,)), (3, (3, 4))):
+            Hd = H.copy(); Hd[far(d), col] = Hd[col, far(d)] = 0.05
+            assert _path_of(capi, q, Hd) in want, (col, d)
+        for d in (1, 2):
+            Hm = H.copy(); Hm[far(d), col] = 0.05; Hm[col, far(d)] = 0.0   # the entry of column `col` has no mirror image
+            assert _path_of(capi, q, Hm) == 0, (col, d, "missing")
+            Hv = H.copy(); Hv[far(d), col] = 0.05; Hv[col, far(d)] = 0.05 * (1 + 1e-9)      # ... or one of another value
+            assert _path_of(capi, q, Hv) == 0, (col, d, "value")
+            Hs = H.copy(); Hs[far(d), col] = 0.05; Hs[col, far(d)] = 0.05 * (1 + 1e-14)     # (within the check's 1e-12: symmetric)
+            assert _path_of(capi, q, Hs) == 2, (col, d, "same")
+
+
 def test_degenerate_inputs_on_the_general_path(capi, oracle):
     """duplicate rows, constraints parallel to bounds, dependent equalities: the exchange rule on the general path"""
     rng = np.random.default_rng(504)
