@@ -61,6 +61,14 @@ extern "C" void rsqp_debug_lane_stamps(unsigned long long *out, int reset) {
 #define LSTAMP_IN(k)
 #endif
 
+// the exchange's votes of the headline build (LaneT::VOTE >> 5, see change_exchange()): 1 the sums and li, 2 / 4 the partner's kind
+// 2 / 1, 8 the ranges of the slots. Shipped: the sums and li alone -- with the partner's kind, the ranges or both the headline batch
+// ran 1 to 2.5 % SLOWER than with bit 0 alone, in every round (5 to 7 KB more text). A tuning build screens them
+// bit by bit (tools/lane_experiment.sh -DRSQP_LANE_XVOTE=<bits>)
+#ifndef RSQP_LANE_XVOTE
+#define RSQP_LANE_XVOTE 1
+#endif
+
 namespace {
 
 constexpr int MV = 8, WL = 64;
@@ -107,7 +115,8 @@ template <> struct ShapeWord<-1> {
 };
 // VOTE: the wave's lanes vote (ballot over the lanes still in the loop) on what happens next, and a wave that agrees runs a text
 // in which that is a constant. Bit 0: the homotopy step by `done` (step); bit K, K = 1 .. 4: change() with every lane's change of
-// kind K. A wave that disagrees runs the text of the builds without the flag; per lane every text performs the same operations
+// kind K; bits 5 .. 8: the votes inside a wave's kind-3 change (change_exchange: the sums and li, the partner's kind, the slots' ranges).
+// A wave that disagrees runs the text of the builds without the flag; per lane every text performs the same operations
 // on the same operands in the same order (kernel's choice, see lane_qp_body: the full-shape build without kept state)
 // WARM: the build for hot starts with new matrices and warm re-initialisations (lane_qp_body): the set-up from a guess (setup_warm,
 // warm_pivots), the guess's way in (take_guess) and results / state stores that leave out the members a launch does not run. A
@@ -1003,6 +1012,108 @@ struct LaneT {
     // (style of the slot passes here and in homotopy(): every arm of a choice is computed first, then selected -- plain selects
     //  between values; a ternary with arithmetic in its arms becomes a tree of divergent branches per slot. The one exception is
     //  measured: the variable slots of homotopy()'s ratio test in the headline build, ROLES)
+    // The parts of a change that both of its texts below hold -- change<KIND>() and change_exchange() --, each stated once. They are
+    // macros, expanded in place with the partner's kind by lane (`pk`) or as a literal: change<KIND>() must stay, token for token,
+    // the text it was, because every build of the kernel holds it and the builds without the exchange's votes keep their device
+    // code. (As lambdas or member templates, inlined in full either way, each of the parts changed the register allocation of every
+    // build; so did a pair of braces around one of them.) They declare their locals in the scope that expands them.
+    // CHANGE_SUMS: the sum of u_v^2 over the free variables and of a_v^2 over them for the incoming row (row idx of A, or e_idx), and
+    // from them li: 1 the row is independent of the active ones (plain entry), 0 it depends on them (exchange); in the band between
+    // the two thresholds the residual of the row's representation by the active rows decides (qp_small_g.h)
+#define CHANGE_SUMS                                                                                                                  \
+            double arow[MV];                                                                                                         \
+            double pn2 = 0.0, na2 = 0.0;                                                                                             \
+            const int ia = kind == 3 ? idx : 0;                                                                                      \
+            SFOR(k, MV, const bool fr = (fmask >> k) & 1;                                                                            \
+                 const double aA = As(ia, k), aE = k == idx ? 1.0 : 0.0;                                                             \
+                 arow[k] = kind == 3 ? aA : aE;                                                                                      \
+                 const double p1 = fma(u[k], u[k], pn2), n1 = fma(arow[k], arow[k], na2);                                            \
+                 pn2 = fr ? p1 : pn2; na2 = fr ? n1 : na2;);                                                                         \
+            int li;                                                                                                                  \
+            if (nFR() - nAC() <= 0 || !(na2 > 0.0)) li = 0;                                                                          \
+            else {                                                                                                                   \
+                const double p2 = hscale * hscale * pn2;                                                                             \
+                li = p2 > 1e-12 * na2 ? 1 : (p2 < 1e-24 * na2 ? 0 : -1);                                                             \
+            }                                                                                                                        \
+            if (li < 0) {                                                                                                            \
+                double rn2 = 0.0;                                                                                                    \
+                SFOR(l, MV, double r = l < nV ? arow[l] : 0.0;                                                                       \
+                     SFOR(i, MC, const double r1 = fma(-As(i, l), sg * u[MV + i], r); r = ((amask >> i) & 1) ? r1 : r;);             \
+                     rn2 += ((l < nV) & (sv[l] == 0)) ? r * r : 0.0;);                                                               \
+                li = rn2 > 9e-16 * na2 ? 1 : 0;                 /* |r| / |a_FR| > 3e-8 */                                            \
+            }                                                                                                                        \
+            LSTAMP_IN(21);
+    // CHANGE_PARTNER: the exchange's first half -- shift the multipliers along the dependency until one of them reaches zero; that
+    // one leaves (pk, pidx). No partner: infeasible beyond this point of the homotopy -- unless that point IS its end to rounding
+#define CHANGE_PARTNER                                                                                                               \
+                const double sgn = side == 1 ? -1.0 : 1.0, ss = sgn * sg;                                                            \
+                double xiv[MV], xic[MC];                                                                                             \
+                double bt = RSQP_INFTY;                                                                                              \
+                int bid = 0x7fffffff;                                                                                                \
+                SFOR(i, MC, const bool on = (i < nC) & (sc[i] != 0), wl = sc[i] == -1;                                               \
+                     const double xu = ss * u[MV + i];                                                                               \
+                     xic[i] = on ? xu : 0.0;                                                                                         \
+                     const double num = wl ? yc[i] : -yc[i], den = wl ? xic[i] : -xic[i];                                            \
+                     if (on & (den > RSQP_EPS_DEN)) {                                                                                \
+                         const double t = (num > 0.0 ? num : 0.0) / den;                                                             \
+                         const bool better = (t < bt) | ((t == bt) & (i < bid));                                                     \
+                         bt = better ? t : bt; bid = better ? i : bid;                                                               \
+                     });                                                                                                             \
+                SFOR(l, MV, const bool on = (l < nV) & (sv[l] != 0), wl = sv[l] == -1;                                               \
+                     const double xu = ss * u[l];                                                                                    \
+                     xiv[l] = on ? xu : 0.0;                                                                                         \
+                     const double num = wl ? yv[l] : -yv[l], den = wl ? xiv[l] : -xiv[l];                                            \
+                     if (on & (den > RSQP_EPS_DEN)) {                                                                                \
+                         const double t = (num > 0.0 ? num : 0.0) / den;                                                             \
+                         const bool better = (t < bt) | ((t == bt) & (nC + l < bid));                                                \
+                         bt = better ? t : bt; bid = better ? nC + l : bid;                                                          \
+                     });                                                                                                             \
+                if (bid == 0x7fffffff) {                                                                                             \
+                    if (tau >= 1.0 - 1e-9) { treat_done = true; return RET_OK; }                                                     \
+                    return RET_INFEASIBLE;                                                                                           \
+                }                                                                                                                    \
+                if (bid < nC) { pk = 1; pidx = bid; } else { pk = 2; pidx = bid - nC; }                                              \
+                SFOR(l, MV, yv[l] -= bt * xiv[l];);                                                                                  \
+                SFOR(i, MC, yc[i] -= bt * xic[i];);                                                                                  \
+                ynew = sgn * bt;                                                                                                     \
+                LSTAMP_IN(22);
+    // CHANGE_BLOCK_PIVOT(PK): the exchange's second half, the 2 x 2 block pivot on (partner, incoming). PK: `pk`, or the kind of the
+    // partner as a literal (a wave whose lanes agree on it): p and the pivot's signs fold
+#define CHANGE_BLOCK_PIVOT(PK)                                                                                                       \
+                const int p = PK == 1 ? MV + pidx : pidx;                                                                            \
+                double u2[N];                                                                                                        \
+                fetch_row(p, u2);                                                                                                    \
+                const double pp = Gd(p, p), qq = pi, pq = Gd(p, q);                                                                  \
+                const double det = pp * qq - pq * pq;                                                                                \
+                if (!(det < 0.0) || !(-det > 1e-10 * fmax(fabs(pp * qq), pq * pq))) return RET_SETUP_FAILED;                         \
+                const double rd = recip(det);                                                                                        \
+                LSTAMP_IN(23);                                                                                                       \
+                pivot2(u2, u, p, PK == 1 ? -1.0 : 1.0, q, kind == 3 ? 1.0 : -1.0, qq * rd, -pq * rd, pp * rd);                       \
+                LSTAMP_IN(16);                                                                                                       \
+                since_refresh = REFRESH;
+    // CHANGE_ENTRY_TEST: the set-up test of a plain entry
+#define CHANGE_ENTRY_TEST                                                                                                            \
+                if (kind == 3) { if (!(pi * hscale > 1e-10 * na2)) return RET_SETUP_FAILED; }                                        \
+                else if (!(pi * hscale > 1e-10)) return RET_SETUP_FAILED;
+    // CHANGE_FINISH(PK): the pivot on q alone where no partner leaves, and the working set. PK as above, or the literal 0: no lane
+    // has a partner
+#define CHANGE_FINISH(PK)                                                                                                            \
+        LSTAMP_IN(14);                                                                                                               \
+        if (PK == 0) pivot1(u, q, (kind == 2 || kind == 3) ? 1.0 : -1.0, pi);                                                        \
+        LSTAMP_IN(16);                                                                                                               \
+        const bool leaves = (kind == 1) | (kind == 2);                                                                               \
+        const int snew = leaves ? 0 : side;                                                                                          \
+        const double ynw = leaves ? 0.0 : ynew;                                                                                      \
+        SFOR(l, MV, const bool my = !isc & (l == idx), pr = (PK == 2) & (l == pidx);                                                 \
+             const int s1 = pr ? 0 : sv[l]; const double y1 = pr ? 0.0 : yv[l];                                                      \
+             sv[l] = my ? snew : s1; yv[l] = my ? ynw : y1;);                                                                        \
+        SFOR(i, MC, const bool my = isc & (i == idx), pr = (PK == 1) & (i == pidx);                                                  \
+             const int s1 = pr ? 0 : sc[i]; const double y1 = pr ? 0.0 : yc[i];                                                      \
+             sc[i] = my ? snew : s1; yc[i] = my ? ynw : y1;);                                                                        \
+        if (kind == 1) amask &= ~(1 << idx); else if (kind == 2) fmask |= 1 << idx; else if (kind == 3) amask |= 1 << idx; else fmask &= ~(1 << idx); \
+        if (PK == 1) amask &= ~(1 << pidx); else if (PK == 2) fmask |= 1 << pidx;                                                    \
+        return RET_OK;
+
     // KIND: the kind as a constant (a wave whose lanes agree on it, VOTE), or 0: `kind_` by lane. With the constant, `isc`,
     // `leaves`, the pivot's sign and `sg` fold and the arms of the other kinds are not in the text; idx, side and q stay by lane,
     // and so do the arms a lane may take alone: the flip (kinds 1, 2) and the exchange (kinds 3, 4)
@@ -1039,95 +1150,79 @@ struct LaneT {
         double ynew = 0.0;
         if (kind >= 3) {
             const double sg = kind == 3 ? -1.0 : 1.0;
-            // sum of u_v^2 over the free variables; sum of a_v^2 over them for the incoming row (row idx of A, or e_idx)
-            double arow[MV];
-            double pn2 = 0.0, na2 = 0.0;
-            const int ia = kind == 3 ? idx : 0;
-            SFOR(k, MV, const bool fr = (fmask >> k) & 1;
-                 const double aA = As(ia, k), aE = k == idx ? 1.0 : 0.0;
-                 arow[k] = kind == 3 ? aA : aE;
-                 const double p1 = fma(u[k], u[k], pn2), n1 = fma(arow[k], arow[k], na2);
-                 pn2 = fr ? p1 : pn2; na2 = fr ? n1 : na2;);
-            int li;
-            if (nFR() - nAC() <= 0 || !(na2 > 0.0)) li = 0;
-            else {
-                const double p2 = hscale * hscale * pn2;
-                li = p2 > 1e-12 * na2 ? 1 : (p2 < 1e-24 * na2 ? 0 : -1);
-            }
-            if (li < 0) {
-                // the band: the residual of the row's representation by the active rows decides (qp_small_g.h)
-                double rn2 = 0.0;
-                SFOR(l, MV, double r = l < nV ? arow[l] : 0.0;
-                     SFOR(i, MC, const double r1 = fma(-As(i, l), sg * u[MV + i], r); r = ((amask >> i) & 1) ? r1 : r;);
-                     rn2 += ((l < nV) & (sv[l] == 0)) ? r * r : 0.0;);
-                li = rn2 > 9e-16 * na2 ? 1 : 0;                 // |r| / |a_FR| > 3e-8
-            }
+            LSTAMP_IN(14);
+            CHANGE_SUMS
             if (li == 0) {
-                // ---- exchange: shift the multipliers along the dependency until one of them reaches zero; that one leaves
-                const double sgn = side == 1 ? -1.0 : 1.0, ss = sgn * sg;
-                double xiv[MV], xic[MC];
-                double bt = RSQP_INFTY;
-                int bid = 0x7fffffff;
-                SFOR(i, MC, const bool on = (i < nC) & (sc[i] != 0), wl = sc[i] == -1;
-                     const double xu = ss * u[MV + i];
-                     xic[i] = on ? xu : 0.0;
-                     const double num = wl ? yc[i] : -yc[i], den = wl ? xic[i] : -xic[i];
-                     if (on & (den > RSQP_EPS_DEN)) {
-                         const double t = (num > 0.0 ? num : 0.0) / den;
-                         const bool better = (t < bt) | ((t == bt) & (i < bid));
-                         bt = better ? t : bt; bid = better ? i : bid;
-                     });
-                SFOR(l, MV, const bool on = (l < nV) & (sv[l] != 0), wl = sv[l] == -1;
-                     const double xu = ss * u[l];
-                     xiv[l] = on ? xu : 0.0;
-                     const double num = wl ? yv[l] : -yv[l], den = wl ? xiv[l] : -xiv[l];
-                     if (on & (den > RSQP_EPS_DEN)) {
-                         const double t = (num > 0.0 ? num : 0.0) / den;
-                         const bool better = (t < bt) | ((t == bt) & (nC + l < bid));
-                         bt = better ? t : bt; bid = better ? nC + l : bid;
-                     });
-                if (bid == 0x7fffffff) {
-                    // no partner: infeasible beyond this point of the homotopy -- unless that point IS its end to rounding
-                    if (tau >= 1.0 - 1e-9) { treat_done = true; return RET_OK; }
-                    return RET_INFEASIBLE;
-                }
-                if (bid < nC) { pk = 1; pidx = bid; } else { pk = 2; pidx = bid - nC; }
-                SFOR(l, MV, yv[l] -= bt * xiv[l];);
-                SFOR(i, MC, yc[i] -= bt * xic[i];);
-                ynew = sgn * bt;
-                const int p = pk == 1 ? MV + pidx : pidx;
-                double u2[N];
-                fetch_row(p, u2);
-                const double pp = Gd(p, p), qq = pi, pq = Gd(p, q);
-                const double det = pp * qq - pq * pq;
-                if (!(det < 0.0) || !(-det > 1e-10 * fmax(fabs(pp * qq), pq * pq))) return RET_SETUP_FAILED;
-                const double rd = recip(det);
-                LSTAMP_IN(14);
-                pivot2(u2, u, p, pk == 1 ? -1.0 : 1.0, q, kind == 3 ? 1.0 : -1.0, qq * rd, -pq * rd, pp * rd);
-                LSTAMP_IN(16);
-                since_refresh = REFRESH;
+                CHANGE_PARTNER
+                CHANGE_BLOCK_PIVOT(pk)
             } else {
-                if (kind == 3) { if (!(pi * hscale > 1e-10 * na2)) return RET_SETUP_FAILED; }
-                else if (!(pi * hscale > 1e-10)) return RET_SETUP_FAILED;
+                CHANGE_ENTRY_TEST
             }
         }
-        LSTAMP_IN(14);
-        if (pk == 0) pivot1(u, q, (kind == 2 || kind == 3) ? 1.0 : -1.0, pi);
-        LSTAMP_IN(16);
-        // ---- the working set
-        const bool leaves = (kind == 1) | (kind == 2);
-        const int snew = leaves ? 0 : side;
-        const double ynw = leaves ? 0.0 : ynew;
-        SFOR(l, MV, const bool my = !isc & (l == idx), pr = (pk == 2) & (l == pidx);
-             const int s1 = pr ? 0 : sv[l]; const double y1 = pr ? 0.0 : yv[l];
-             sv[l] = my ? snew : s1; yv[l] = my ? ynw : y1;);
-        SFOR(i, MC, const bool my = isc & (i == idx), pr = (pk == 1) & (i == pidx);
-             const int s1 = pr ? 0 : sc[i]; const double y1 = pr ? 0.0 : yc[i];
-             sc[i] = my ? snew : s1; yc[i] = my ? ynw : y1;);
-        if (kind == 1) amask &= ~(1 << idx); else if (kind == 2) fmask |= 1 << idx; else if (kind == 3) amask |= 1 << idx; else fmask &= ~(1 << idx);
-        if (pk == 1) amask &= ~(1 << pidx); else if (pk == 2) fmask |= 1 << pidx;
-        return RET_OK;
+        CHANGE_FINISH(pk)
     }
+    // change<3>() with the exchange's votes, XV (VOTE, bits 5 .. 8): the lanes still in the function vote once more on what that text
+    // leaves by lane, and a wave that agrees runs a text in which it is a constant.
+    // Bit 0: whether any lane needs the sums at all -- nFR - nAC <= 0 in every lane: li is 0 whatever they say, and neither they
+    // nor the band are on that path (both changes of every headline member) --, and, behind the sums, li: all 0 the exchange, all
+    // 1 the plain entry with pivot1 unmasked, else the text by lane. Bit 1 / bit 2: the partner's kind behind the exchange's ratio
+    // test, all bounds / all constraints: p, pivot2's signs, the `pr` selects of the working-set pass and the mask updates fold.
+    // Bit 3: the ranges of idx and, with the partner's kind, of pidx are stated, so that the `k <= q` of the row helpers and
+    // pivot2's slot compares fold where the range decides them (q = MV + idx >= every variable slot; a bound's p < every
+    // constraint slot). Per lane every path performs the operations of change<3>() on the same operands in the same order
+    template <int XV> __device__ __forceinline__ int change_exchange(int idx, int side, double tau, bool &treat_done) {
+        static_assert((XV & 1) != 0, "the votes on the partner and the ranges ride on the vote on the sums");
+        constexpr int kind = 3;
+        constexpr bool isc = true;
+        if constexpr ((XV & 8) != 0) { __builtin_assume(idx >= 0); __builtin_assume(idx < MC); }
+        const int q = MV + idx;
+        double u[N];
+        fetch_row(q, u);
+        const double pi = Gd(q, q);
+        int pk = 0, pidx = -1;
+        double ynew = 0.0;
+        const double sg = -1.0;
+        LSTAMP_IN(14);
+        const unsigned long long here = __builtin_amdgcn_ballot_w64(true);
+        if (__builtin_amdgcn_ballot_w64(nFR() - nAC() <= 0) != here) {
+            CHANGE_SUMS
+            const unsigned long long l0 = __builtin_amdgcn_ballot_w64(li == 0);
+            if (l0 != here) {
+                if (l0 == 0) {
+                    CHANGE_ENTRY_TEST
+                    CHANGE_FINISH(0)
+                }
+                if (li == 0) {
+                    CHANGE_PARTNER
+                    CHANGE_BLOCK_PIVOT(pk)
+                } else {
+                    CHANGE_ENTRY_TEST
+                }
+                CHANGE_FINISH(pk)
+            }
+        }
+        // every lane exchanges
+        CHANGE_PARTNER
+        // (the lanes without a partner have returned)
+        const unsigned long long left = __builtin_amdgcn_ballot_w64(true);
+        if ((XV & 2) != 0 && __builtin_amdgcn_ballot_w64(pk == 2) == left) {
+            if constexpr ((XV & 8) != 0) { __builtin_assume(pidx >= 0); __builtin_assume(pidx < MV); }
+            CHANGE_BLOCK_PIVOT(2)
+            CHANGE_FINISH(2)
+        }
+        if ((XV & 4) != 0 && __builtin_amdgcn_ballot_w64(pk == 1) == left) {
+            if constexpr ((XV & 8) != 0) { __builtin_assume(pidx >= 0); __builtin_assume(pidx < MC); }
+            CHANGE_BLOCK_PIVOT(1)
+            CHANGE_FINISH(1)
+        }
+        CHANGE_BLOCK_PIVOT(pk)
+        CHANGE_FINISH(pk)
+    }
+#undef CHANGE_SUMS
+#undef CHANGE_PARTNER
+#undef CHANGE_BLOCK_PIVOT
+#undef CHANGE_ENTRY_TEST
+#undef CHANGE_FINISH
 
     __device__ __forceinline__ int homotopy(int maxit, int &nWSR) {
         int iter = 0, rcode = RET_OK;
@@ -1283,7 +1378,10 @@ struct LaneT {
                 auto all = [&](int k) { return __builtin_amdgcn_ballot_w64(kind == k) == in_loop; };
                 if ((VOTE & 4) != 0 && all(2)) rcode = change<2>(kind, idx, side, tau, treat_done);
                 else if ((VOTE & 16) != 0 && all(4)) rcode = change<4>(kind, idx, side, tau, treat_done);
-                else if ((VOTE & 8) != 0 && all(3)) rcode = change<3>(kind, idx, side, tau, treat_done);
+                else if ((VOTE & 8) != 0 && all(3)) {
+                    if constexpr (((VOTE >> 5) & 15) != 0) rcode = change_exchange<(VOTE >> 5) & 15>(idx, side, tau, treat_done);
+                    else rcode = change<3>(kind, idx, side, tau, treat_done);
+                }
                 else if ((VOTE & 2) != 0 && all(1)) rcode = change<1>(kind, idx, side, tau, treat_done);
                 else rcode = change<0>(kind, idx, side, tau, treat_done);
             } else rcode = change<0>(kind, idx, side, tau, treat_done);
@@ -1369,7 +1467,8 @@ __device__ __forceinline__ void lane_qp_body(const QPPools &P, int nq, int maxWS
     // the wave's votes (LaneT::VOTE): the full-shape build without kept state -- the step by `done`, and change() by kinds 3 (both
     // changes of every headline member: a constraint enters by an exchange with a bound) and 2. Kinds 4 and 1 stay on the text by
     // lane: 14 KB more of it, and the headline batch could not tell the builds apart
-    constexpr int VOTE = (CHUNKS && SHV >= 0) ? (1 | 1 << 2 | 1 << 3) : 0;
+    // The exchange's votes (bits 5 .. 8, change_exchange() in place of change<3>()): RSQP_LANE_XVOTE, the sums and li
+    constexpr int VOTE = (CHUNKS && SHV >= 0) ? (1 | 1 << 2 | 1 << 3 | RSQP_LANE_XVOTE << 5) : 0;
     typedef LaneT<MC, HB, CHUNKS ? 14 : 2, CHUNKS ? 6 : 2, ROLES, SHV, SHC, VOTE, WARM> ENG;
     constexpr int N = ENG::N;
     // (+ the staging table: 32 ints; in the ordered build it lies in the first of the spare slots the vectors pass through)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Quick-turnaround tuning build of the lane-per-problem kernel (qp_lane.hip) into restartsqp_amd/lib/librsqp_exp.so;
-# select it with RSQP_LIB=<path>. Extra compiler flags as arguments (e.g. -DRSQP_STAMPS).
+# select it with RSQP_LIB=<path>. Extra compiler flags as arguments (e.g. -DRSQP_STAMPS, -DRSQP_LANE_XVOTE=<bits>).
 set -e
 cd "$(dirname "$0")/.."
 OBJ=restartsqp_amd/lib/obj

@@ -28,7 +28,9 @@ L.rsqp_debug_lane_stamps(buf, 0)
 names = {10: "staging: loads issued, pattern pointers", 11: "staging: loads arrived, dropped into LDS", 12: "staging: own vectors, A scattered",
          13: "staging: H scattered and read", 17: "staging in dependency order: H read, tableau built", 0: "staging: rest", 1: "set-up (auxiliary QP)", 18: "staging in dependency order: g arrived, taken", 2: "homotopy: tail of the last pass",
          5: "homotopy: x on bounds, refresh, drift, input", 6: "homotopy: out = G in", 7: "homotopy: dx / dy, candidates (divisions)",
-         20: "homotopy: decode (kind, slot, side)", 8: "homotopy: step", 14: "homotopy: change: row fetch, tests", 16: "homotopy: change: pivot (pivot1 / pivot2, row store)",
+         20: "homotopy: decode (kind, slot, side)", 8: "homotopy: step", 14: "homotopy: change: row fetch, tests",
+         21: "homotopy: change: entry's sums and li (kinds 3, 4)", 22: "homotopy: change: exchange: partner ratio test",
+         23: "homotopy: change: exchange: second row fetch, determinant", 16: "homotopy: change: pivot (pivot1 / pivot2, row store)",
          9: "homotopy: change: working set",
          3: "refinement step + exact products + objective", 15: "state block written back", 19: "results: x, y, working sets issued",
          4: "results to HBM (results first: objective, status words)"}
