@@ -570,6 +570,8 @@ int rsqp_dense_chol_inverse(int n, double *G, double *Ginv, double pd_rel, doubl
 #include "rsqp_hip_nlp_step.h"
 /* update_penalty_parameter per member of a QP batch and the LP batch paired with it, decided on the device: the same way */
 #include "rsqp_hip_penalty.h"
+/* second_order_correction per member of a batch, decided on the device, and the setter of the objective pool: the same way */
+#include "rsqp_hip_soc.h"
 /* the banded H^-1 operator of the HBM-resident engine called the way the engine calls it (verification): the same way */
 #include "rsqp_hip_band_check.h"
 #endif

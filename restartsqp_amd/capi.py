@@ -192,6 +192,14 @@ BAND_CHECK_SYMBOLS = {
 }
 BAND_KERNEL_ENGINE, BAND_KERNEL_1WG = 0, 1                                                              # RSQP_BAND_KERNEL_*
 BAND_MAX_N, BAND_THREADS = 16384, 1024                                                                  # RSQP_BAND_MAX_N, _THREADS
+# ... and of include/rsqp_hip_soc.h (second_order_correction per member of a batch, and the setter of the objective pool)
+SOC_SYMBOLS = {
+    "rsqp_soc_default_options": (C.c_int, [C.c_void_p]),
+    "rsqp_batch_handler_soc_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "rsqp_batch_handler_soc_end": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "rsqp_batch_set_objective": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+SOC_TEST, SOC_CORRECT = 1, 2                                                                             # RSQP_SOC_*: bits of what[q]
 EXIT_UNKNOWN, EXIT_TRUST_REGION_TOO_SMALL = -99, 4                                                      # RSQP_EXIT_*
 KKT_PRIMAL, KKT_DUAL, KKT_COMPL, KKT_STAT, KKT_FIRST_ORDER_OPT = 1, 2, 4, 8, 16                         # RSQP_KKT_*: the verdict bits
 DENSE_GEMM_PLAIN, DENSE_GEMM_UPPER, DENSE_GEMM_KTRI1, DENSE_GEMM_KTRI2, DENSE_GEMM_KTRI3 = range(5)      # RSQP_DENSE_GEMM_*
@@ -271,6 +279,36 @@ class PenaltyState(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in IN + INOUT + OUT]
 
 
+class SocOptions(C.Structure):
+    """rsqp_soc_options; a new one holds the defaults (rsqp_soc_default_options: composite_pred = 0, the reference as found),
+    keyword arguments override fields"""
+    _fields_ = [("composite_pred", C.c_int)]
+
+    def __init__(self, **fields):
+        super().__init__()
+        check(lib().rsqp_soc_default_options(C.addressof(self)))
+        for k, v in fields.items():
+            if k not in dict(self._fields_):
+                raise TypeError("rsqp_soc_options has no field %r" % k)
+            setattr(self, k, v)
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class SocTrial(C.Structure):
+    """rsqp_soc_trial: host or device addresses, as handler_soc_begin's / handler_soc_end's on_device says. The fields of NlpTrial,
+    then grad, infea_model, x_trial, soc, qp_obj, nwsr_soc"""
+    IN = ("what", "rho", "f_trial", "c_trial", "grad", "infea_model")
+    INOUT = ("x_k", "c_k", "f_k", "infea_k", "delta")
+    OUT = ("actual_reduction", "pred_reduction", "infea_trial", "accept", "hu_word", "hm_word", "exitflag", "x_trial", "soc", "qp_obj",
+           "nwsr_soc")
+    INTS = ("what", "accept", "hu_word", "hm_word", "exitflag", "soc", "nwsr_soc")
+    _fields_ = [(k, C.c_void_p) for k in ("what", "rho", "f_trial", "c_trial", "x_k", "c_k", "f_k", "infea_k", "delta",
+                                          "actual_reduction", "pred_reduction", "infea_trial", "accept", "hu_word", "hm_word", "exitflag",
+                                          "grad", "infea_model", "x_trial", "soc", "qp_obj", "nwsr_soc")]
+
+
 class RsqpError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("rsqp error %d: %s" % (code, msg))
@@ -291,7 +329,8 @@ def lib():
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SYMBOLS.items()) + list(LANE_SYMBOLS.items()) + list(HANDOVER_SYMBOLS.items()) + \
                 list(LANE_WARM_SYMBOLS.items()) + list(LANE_HOT_SYMBOLS.items()) + list(DENSE_CHECK_SYMBOLS.items()) + \
-                list(NLP_STEP_SYMBOLS.items()) + list(PENALTY_SYMBOLS.items()) + list(BAND_CHECK_SYMBOLS.items()):
+                list(NLP_STEP_SYMBOLS.items()) + list(PENALTY_SYMBOLS.items()) + list(BAND_CHECK_SYMBOLS.items()) + \
+                list(SOC_SYMBOLS.items()):
             f = getattr(L, name)
             f.restype = res
             f.argtypes = args
@@ -963,6 +1002,63 @@ class Batch:
         check(lib().rsqp_batch_handler_update_penalty(self._h, C.addressof(s), C.addressof(o), int(bool(on_device))))
         del keep
         return out
+
+    # ---- second_order_correction per member (include/rsqp_hip_soc.h) ----
+    def _soc_call(self, fn, begin, what, rho, f_trial, c_trial, x_k, c_k, f_k, infea_k, delta, grad, infea_model, options, soc_options,
+                  on_device, out):
+        sN, sC = self._handler_sizes()
+        nq = self.nq
+        size = dict(what=nq, rho=nq, f_trial=nq, c_trial=sC, grad=sN, infea_model=nq, x_k=sN, c_k=sC, f_k=nq, infea_k=nq, delta=nq)
+        given = dict(what=what, rho=rho, f_trial=f_trial, c_trial=c_trial, grad=grad, infea_model=infea_model, x_k=x_k, c_k=c_k, f_k=f_k,
+                     infea_k=infea_k, delta=delta)
+        optional = ("grad", "infea_model") if begin else ("what", "grad", "infea_model")
+        out = dict(out or {})
+        if not begin and out.get("soc") is None:
+            raise ValueError("soc is required: the array handler_soc_begin wrote")
+        for k in SocTrial.OUT:
+            if out.get(k) is None:
+                out[k] = self._new_out(sN if k == "x_trial" else nq, on_device, ints=k in SocTrial.INTS)
+        t, keep = SocTrial(), []
+        for k in SocTrial.IN + SocTrial.INOUT:
+            if given[k] is None and size[k] > 0 and k not in optional:
+                raise ValueError("%s is required" % k)
+            addr, a = self._addr(given[k], size[k], k, on_device, ints=k in SocTrial.INTS, writable=k in SocTrial.INOUT)
+            setattr(t, k, addr); keep.append(a)
+        for k in SocTrial.OUT:
+            addr, a = self._addr(out[k], sN if k == "x_trial" else nq, k, on_device, ints=k in SocTrial.INTS, writable=True)
+            setattr(t, k, addr)
+        o, so = options or NlpStepOptions(), soc_options or SocOptions()
+        check(fn(self._h, C.addressof(t), C.addressof(o), C.addressof(so), int(bool(on_device))))
+        del keep
+        return out
+
+    def handler_soc_begin(self, what, rho, f_trial, c_trial, x_k, c_k, f_k, infea_k, delta, grad=None, infea_model=None, options=None,
+                          soc_options=None, on_device=False, out=None):
+        """the ratio test with second_order_correction for every member with what[q] != 0 (rsqp_batch_handler_soc_begin), called
+        INSTEAD OF handler_ratio_test: what[q] = SOC_TEST | SOC_CORRECT bits; the other arguments as handler_ratio_test takes them,
+        plus grad (NLP layout: grad_f at x_k, required when a word has SOC_CORRECT) and infea_model (nq, optional: as the penalty
+        call left it). x_k, c_k, f_k, infea_k, delta are WRITTEN IN PLACE. Returns the outputs as a dict over SocTrial.OUT (x_trial:
+        NLP layout; accept, hu_word, hm_word, exitflag, soc, nwsr_soc: int32) -- the arrays of `out` where it has them (a member
+        with word 0 keeps their bytes), else new zero-filled ones. The members with soc == 1 await f and c at x_trial and
+        handler_soc_end"""
+        return self._soc_call(lib().rsqp_batch_handler_soc_begin, True, what, rho, f_trial, c_trial, x_k, c_k, f_k, infea_k, delta, grad,
+                              infea_model, options, soc_options, on_device, out)
+
+    def handler_soc_end(self, rho, f_trial, c_trial, x_k, c_k, f_k, infea_k, delta, out, options=None, soc_options=None,
+                        on_device=False):
+        """the second ratio test, the restore of a rejected correction and update_radius for every member with out["soc"][q] != 0
+        that the last handler_soc_begin set going (rsqp_batch_handler_soc_end): f_trial, c_trial at the x_trial of that call; `out`
+        is the dict that call returned (soc is required) and is returned with this call's outputs"""
+        return self._soc_call(lib().rsqp_batch_handler_soc_end, False, None, rho, f_trial, c_trial, x_k, c_k, f_k, infea_k, delta, None,
+                              None, options, soc_options, on_device, out)
+
+    def set_objective(self, obj, members=None):
+        """the objective pool of the named members (a mask; None: everybody) := obj (nq entries); nothing else is touched
+        (rsqp_batch_set_objective)"""
+        obj = self._sized(obj, self.nq, "obj")
+        if obj is None:
+            raise ValueError("obj is required")
+        check(lib().rsqp_batch_set_objective(self._h, _ip(self._mask(members)), _dp(obj)))
 
     def get_vectors(self):
         """(g, lb, ub, lbA, ubA) as the pools hold them on the device, in the layout of set_vectors"""

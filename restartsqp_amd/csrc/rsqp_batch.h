@@ -1,8 +1,8 @@
 // rsqp_batch.h -- struct rsqp_batch and what more than one of its translation units uses. Private to them: rsqp_batch.hip (the batch
 // itself: create, whole-batch setters, solve, results, certificate, records), rsqp_batch_optimize.hip (optimizeQP / optimizeLP per
 // member and their plan kernels), rsqp_batch_handler.hip (everything that writes the pools member by member) and rsqp_batch_nlp.hip
-// (the decisions of the SQP loop, which read the pools member by member) and rsqp_batch_penalty.hip (update_penalty_parameter across
-// a QP batch and its LP batch). Device code does not cross a unit: the __device__ helpers
+// (the decisions of the SQP loop, which read the pools member by member), rsqp_batch_penalty.hip (update_penalty_parameter across
+// a QP batch and its LP batch) and rsqp_batch_soc.hip (second_order_correction; the last three share rsqp_batch_decide.h). Device code does not cross a unit: the __device__ helpers
 // here are inline. Everything but the struct itself (the opaque type of the C ABI) is in namespace rsqp_batch_units, which the units
 // open.
 #pragma once
@@ -45,6 +45,13 @@ enum { OPT_FIRST = 0, OPT_OLD, OPT_NEW, OPT_MODE, OPT_RMODE, OPT_RESCUE, OPT_N1,
 // word `word` of member q
 __device__ inline int &opt_word(int *opt, int nq, int word, int q) { return opt[word * nq + q]; }
 __device__ inline const int &opt_word(const int *opt, int nq, int word, int q) { return opt[word * nq + q]; }
+
+// the bound formulas of QPhandler (src/QPhandler.cpp:167-201, 342-368, 533-567), one subtraction and one fmax / fmin each: what
+// batch_handler_update_kernel writes for RSQP_HU_SET / _BOUNDS / _DELTA, and second_order_correction's update_bounds at x_k + p
+__device__ inline double hu_lb(double x_l, double x_k, double delta) { return fmax(x_l - x_k, -delta); }
+__device__ inline double hu_ub(double x_u, double x_k, double delta) { return fmin(x_u - x_k, delta); }
+__device__ inline double hu_lbA(double c_l, double c_k) { return c_l - c_k; }
+__device__ inline double hu_ubA(double c_u, double c_k) { return c_u - c_k; }
 }  // namespace rsqp_batch_units
 using namespace rsqp_batch_units;
 
@@ -161,6 +168,13 @@ struct rsqp_batch {
     DevBuf<int> pen_i, pen_cnt;
     DevBuf<double> pen_d, pen_x;
     HostBuf<int> pen_live;
+    // rsqp_batch_handler_soc_begin / _soc_end (rsqp_batch_soc.hip): the call's per-member work on the device, allocated at its first
+    // use as the penalty call's: soc_i = SOC_INTS x nq ints, soc_d = SOC_DOUBLES x nq doubles, the x of the first solve (sumV), the
+    // block counters of the decision kernels and the host-mapped word they report through. soc_begun: a soc_begin has run
+    DevBuf<int> soc_i, soc_cnt;
+    DevBuf<double> soc_d, soc_x;
+    HostBuf<int> soc_live;
+    bool soc_begun = false;
     bool timing = false;   // between timer_start and timer_stop: no per-launch events (they cost ~10 us of stream time each)
     ~rsqp_batch() {
         if (ev0) (void)hipEventDestroy(ev0);

@@ -196,8 +196,8 @@ __global__ void __launch_bounds__(256) batch_handler_update_kernel(HandlerUpdate
     if (W == 0) return;
     const bool set = (W & RSQP_HU_SET) != 0;
     if (!isV) {
-        if (s == 3) { if (set || (W & RSQP_HU_BOUNDS)) a.lbA[k] = a.c_l[k] - a.c_k[k]; }
-        else if (set || ((W & RSQP_HU_BOUNDS) && (W & RSQP_HU_UBA))) a.ubA[k] = a.c_u[k] - a.c_k[k];
+        if (s == 3) { if (set || (W & RSQP_HU_BOUNDS)) a.lbA[k] = hu_lbA(a.c_l[k], a.c_k[k]); }
+        else if (set || ((W & RSQP_HU_BOUNDS) && (W & RSQP_HU_UBA))) a.ubA[k] = hu_ubA(a.c_u[k], a.c_k[k]);
         return;
     }
     const int i = k - offV, n = nV - 2 * nC, j = offV - 2 * offC + i;   // j: the entry in the NLP layout (i < n)
@@ -210,8 +210,8 @@ __global__ void __launch_bounds__(256) batch_handler_update_kernel(HandlerUpdate
         if (set) a.g[k] = a.grad ? a.grad[j] : 0.0;
         else if ((W & RSQP_HU_GRAD) && a.grad) a.g[k] = a.grad[j];
     } else if (set || (W & (RSQP_HU_BOUNDS | RSQP_HU_DELTA))) {
-        if (s == 1) a.lb[k] = fmax(a.x_l[j] - a.x_k[j], -a.delta[q]);
-        else a.ub[k] = fmin(a.x_u[j] - a.x_k[j], a.delta[q]);
+        if (s == 1) a.lb[k] = hu_lb(a.x_l[j], a.x_k[j], a.delta[q]);
+        else a.ub[k] = hu_ub(a.x_u[j], a.x_k[j], a.delta[q]);
     }
 }
 

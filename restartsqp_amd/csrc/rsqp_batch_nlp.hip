@@ -1,42 +1,17 @@
 // rsqp_batch_nlp.hip -- the decisions of a lock-step SQP loop for every member of a batch (rsqp_batch_handler_infeasibility /
 // _ratio_test / _check_optimality of include/rsqp_hip_nlp_step.h): cal_infea, ratio_test + update_radius and check_optimality of
 // src/Algorithm.cpp, read from the result pools of the last solve and from the canonical A pool, with their kernels.
-#include "rsqp_batch.h"
+#include "rsqp_batch_decide.h"
 
 // Every scalar formula here must give the bits the same C expression gives on the host without contraction: hipcc would contract
-// a + b*c into an FMA by default, so contraction is OFF for this whole unit (the build flags of the other units stay as they are).
+// a + b*c into an FMA by default, so contraction is OFF for this whole unit (rsqp_batch_decide.h says so as well; the build flags of
+// the other units stay as they are).
 #pragma clang fp contract(off)
 
 namespace {
 constexpr double NLP_INF = 1.0e18;   // INF of the reference (Utils.hpp:35)
 
-// the shape of member q: a one-shape batch (uniV > 0) multiplies, else the descriptor says
-struct MemberShape { int nV, nC, offV, offC; };
-__device__ inline MemberShape shape_of(const QPDesc *__restrict__ desc, int uniV, int uniC, int q) {
-    if (uniV > 0) return MemberShape{uniV, uniC, q * uniV, q * uniC};
-    return MemberShape{desc[q].nV, desc[q].nC, desc[q].offV, desc[q].offC};
-}
-
-// the sum of v over the G lanes of a sub-group, the same bits in every lane: partners G/2, G/4, ..., 1 lanes apart
-template <int G>
-__device__ inline double group_sum(double v) {
-    for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, G);
-    return v;
-}
-
-// lane `lane`'s share of cal_infea(c, c_l, c_u) (src/Algorithm.cpp:584-589) over m constraints: entries lane, lane + G, ...
-template <int G>
-__device__ inline double infea_share(const double *__restrict__ c, const double *__restrict__ c_l, const double *__restrict__ c_u,
-                                     int m, int lane) {
-    double s = 0.0;
-    for (int i = lane; i < m; i += G) {
-        const double v = c[i];
-        if (v < c_l[i]) s += (c_l[i] - v);
-        else if (v > c_u[i]) s += (v - c_u[i]);
-    }
-    return s;
-}
-
+// the member's shape, the tree sums and cal_infea's share of a lane: rsqp_batch_decide.h
 // G lanes per member, as batch_handler_step_kernel: lanes past the last member, and those of a member that sits out, skip the loops
 // and stay in the shuffles
 template <int G>
@@ -77,26 +52,16 @@ __global__ void __launch_bounds__(256) batch_nlp_ratio_kernel(NlpRatio a) {
         for (int i = lane; i < n; i += G) mx = fmax(mx, fabs(a.x[sh.offV + i]));    // getInfNorm of p: exact in any order
     }
     s = group_sum<G>(s);
-    for (int o = G / 2; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, G));
+    mx = group_max<G>(mx);
     int acc = 0;
     if (act && lane == 0) {
         const rsqp_nlp_step_options &o = a.o;
-        const double rho = a.t.rho[q], f_k = a.t.f_k[q], infea_k = a.t.infea_k[q], f_t = a.t.f_trial[q];
-        const double P1_x = f_k + rho * infea_k;
-        const double P1_x_trial = f_t + rho * s;
-        const double actual = P1_x - P1_x_trial;
-        const double pred = rho * infea_k - a.obj[q];
-        acc = (actual >= (o.eta_s * pred) && actual >= -o.tol) ? 1 : 0;
+        const double f_t = a.t.f_trial[q];
+        const RatioTest r = ratio_test_of(o, a.t.rho[q], a.t.f_k[q], a.t.infea_k[q], f_t, s, a.obj[q]);
+        const double actual = r.actual, pred = r.pred;
+        acc = r.acc;
         double delta = a.t.delta[q];
-        bool radius = false;
-        if (actual < o.eta_c * pred) {
-            delta = o.gamma_c * delta;
-            radius = true;
-        } else if (actual > o.eta_e * pred && (o.tol > fabs(delta - mx))) {
-            const double grown = o.gamma_e * delta;
-            delta = (o.delta_max < grown) ? o.delta_max : grown;      // std::min(gamma_e * delta_, delta_max)
-            radius = true;
-        }
+        const bool radius = radius_update(o, actual, pred, mx, delta);
         if (radius) a.t.delta[q] = delta;
         if (acc) { a.t.f_k[q] = f_t; a.t.infea_k[q] = s; }
         if (a.t.actual_reduction) a.t.actual_reduction[q] = actual;
@@ -104,9 +69,9 @@ __global__ void __launch_bounds__(256) batch_nlp_ratio_kernel(NlpRatio a) {
         if (a.t.infea_trial) a.t.infea_trial[q] = s;
         if (a.t.accept) a.t.accept[q] = acc;
         if (a.t.hu_word)
-            a.t.hu_word[q] = acc ? (RSQP_HU_BOUNDS | RSQP_HU_GRAD | (o.refresh_ubA ? RSQP_HU_UBA : 0)) : (radius ? RSQP_HU_DELTA : 0);
+            a.t.hu_word[q] = acc ? accepted_hu_word(o) : (radius ? RSQP_HU_DELTA : 0);
         if (a.t.hm_word) a.t.hm_word[q] = acc ? (RSQP_HM_JAC | RSQP_HM_HESS) : 0;
-        if (a.t.exitflag) a.t.exitflag[q] = delta < o.delta_min ? RSQP_EXIT_TRUST_REGION_TOO_SMALL : RSQP_EXIT_UNKNOWN;
+        if (a.t.exitflag) a.t.exitflag[q] = radius_exitflag(o, delta);
     }
     acc = __shfl(acc, 0, G);
     if (acc) {      // (only lanes of an active member hold 1)
@@ -190,12 +155,6 @@ __global__ void __launch_bounds__(256) batch_nlp_kkt_kernel(NlpKkt a) {
     }
 }
 
-// hs071-scale members: 8 lanes each, eight members per wavefront; else a wavefront per member (rsqp_batch_handler_get_step)
-inline int lanes_per_member(const rsqp_batch *b) { return (b->nVmax + b->nCmax <= 16) ? 8 : 64; }
-inline dim3 grid_of(const rsqp_batch *b, int G) { return dim3((unsigned)(((long long)b->nq * G + 255) / 256)); }
-inline int uni_shape(const rsqp_batch *b) { return (b->uniV > 0 && b->uniC >= 0) ? b->uniV : 0; }
-// `ints` ints in doubles of the staging block
-inline size_t int_words(size_t ints) { return (ints + 1) / 2; }
 }  // namespace
 
 extern "C" int rsqp_nlp_step_default_options(rsqp_nlp_step_options *o) {

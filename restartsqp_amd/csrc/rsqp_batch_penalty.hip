@@ -2,9 +2,9 @@
 // LP batch paired with it (rsqp_batch_handler_pair_lp / rsqp_batch_handler_update_penalty of include/rsqp_hip_penalty.h): the
 // decision kernels between the inner optimize calls, the launch that carries J from the QP batch's A pool into the LP batch's, and
 // the host side that strings them together and learns one number per round.
-#include "rsqp_batch.h"
+#include "rsqp_batch_decide.h"
 
-// Every scalar formula here must give the bits the same C expression gives on the host without contraction (rsqp_batch_nlp.hip)
+// Every scalar formula here must give the bits the same C expression gives on the host without contraction (rsqp_batch_decide.h)
 #pragma clang fp contract(off)
 
 namespace {
@@ -16,25 +16,7 @@ enum { PH_DONE = 0, PH_LP, PH_LOOP_A, PH_LOOP_B };
 // what lane 0 of a member's group tells the other lanes to do behind the decision
 enum { ACT_ROUND = 1, ACT_SAVE = 2, ACT_RESTORE = 4 };
 
-struct MemberShape { int nV, nC, offV, offC; };
-__device__ inline MemberShape shape_of(const QPDesc *__restrict__ desc, int uniV, int uniC, int q) {
-    if (uniV > 0) return MemberShape{uniV, uniC, q * uniV, q * uniC};
-    return MemberShape{desc[q].nV, desc[q].nC, desc[q].offV, desc[q].offC};
-}
-// the sum of v over the G lanes of a sub-group, the same bits in every lane: partners G/2, G/4, ..., 1 lanes apart
-template <int G>
-__device__ inline double group_sum(double v) {
-    for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, G);
-    return v;
-}
-// exitflag_of (rsqp_host.h) on the device: qpOASESInterface::get_status (src/qpOASESInterface.cpp:332-357)
-__device__ inline int dev_exitflag(int sw) {
-    if (sw >= 200) return RSQP_QPERROR_UNBOUNDED;
-    if (sw >= 100) return RSQP_QPERROR_INFEASIBLE;
-    if (sw == QPS_SOLVED) return RSQP_QP_OPTIMAL;
-    if (sw >= QPS_NOTINITIALISED && sw <= QPS_HOMOTOPYQPSOLVED) return RSQP_QPERROR_NOTINITIALISED + sw;
-    return RSQP_QPERROR_UNKNOWN;
-}
+// the member's shape, the tree sum and the exit flag of an unsolved solve: rsqp_batch_decide.h
 
 struct PenaltyArgs {
     int nq, uniV, uniC;
@@ -204,16 +186,7 @@ __global__ void __launch_bounds__(256) batch_penalty_kernel(PenaltyArgs a) {
     if (todo & ACT_RESTORE)
         for (int i = lane; i < sh.nV; i += G) a.x[sh.offV + i] = a.x0[sh.offV + i];
     // how many go on: added per member, reported by the block that finishes last
-    if (goes_on) atomicAdd(&a.cnt[0], 1);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __threadfence();
-        if (atomicAdd(&a.cnt[1], 1) == (int)gridDim.x - 1) {
-            __threadfence();
-            *a.live = atomicExch(&a.cnt[0], 0);
-            atomicExch(&a.cnt[1], 0);
-        }
-    }
+    report_live(goes_on, a.cnt, a.live);
 }
 
 // set_A of setupLP (:703) for the members penalty_begin named: the entries of columns [0, n) of the member's A, slot by slot from the
@@ -238,10 +211,6 @@ batch_penalty_jacobian_kernel(int nq, int uni_pat, int uni_annz, const QPDesc *_
     if (lane == 0 && first[q] != 0) mark[q] = 1;
 }
 
-inline int lanes_per_member(const rsqp_batch *b) { return (b->nVmax + b->nCmax <= 16) ? 8 : 64; }
-inline dim3 grid_of(const rsqp_batch *b, int G) { return dim3((unsigned)(((long long)b->nq * G + 255) / 256)); }
-inline size_t int_words(size_t ints) { return (ints + 1) / 2; }
-
 template <int STAGE>
 int launch_decision(rsqp_batch *b, const PenaltyArgs &a, int *live) {
     const int G = lanes_per_member(b);
@@ -254,22 +223,15 @@ int launch_decision(rsqp_batch *b, const PenaltyArgs &a, int *live) {
 }
 
 // while the call runs: the LP batch launches on the QP batch's stream, and an inner optimize call of either batch reads the mask a
-// decision kernel wrote where it reads the mask of rsqp_batch_set_members. Both are put back when the call ends, however it ends
+// decision kernel wrote where it reads the mask of rsqp_batch_set_members (MaskLoan). Both are put back when the call ends, however
+// it ends
 struct Loan {
-    rsqp_batch *qp, *lp;
+    MaskLoan qp_mask, lp_mask;
+    rsqp_batch *lp;
     hipStream_t lp_stream;
-    int *take[2]; size_t take_n[2]; bool sitters[2];
-    Loan(rsqp_batch *q, rsqp_batch *l) : qp(q), lp(l), lp_stream(l->stream) {
-        rsqp_batch *const both[2] = {qp, lp};
-        for (int k = 0; k < 2; k++) { take[k] = both[k]->take.p; take_n[k] = both[k]->take.n; sitters[k] = both[k]->sitters; }
-        lp->stream = qp->stream;
-    }
-    static void lend(rsqp_batch *b, int *mask, int live) { b->take.p = mask; b->take.n = (size_t)b->nq; b->sitters = live < b->nq; }
-    ~Loan() {
-        rsqp_batch *const both[2] = {qp, lp};
-        for (int k = 0; k < 2; k++) { both[k]->take.p = take[k]; both[k]->take.n = take_n[k]; both[k]->sitters = sitters[k]; }
-        lp->stream = lp_stream;
-    }
+    Loan(rsqp_batch *q, rsqp_batch *l) : qp_mask(q), lp_mask(l), lp(l), lp_stream(l->stream) { lp->stream = q->stream; }
+    static void lend(rsqp_batch *b, int *mask, int live) { MaskLoan::lend(b, mask, live); }
+    ~Loan() { lp->stream = lp_stream; }
 };
 }  // namespace
 

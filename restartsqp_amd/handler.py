@@ -611,3 +611,150 @@ def batch_update_penalty_reference(qp_members, lp_members, state, options, G=8):
                 r["fail"] += 1
                 r.update(outcome="failure", infea_model=model0, hu_word=capi.HU_PENALTY, x=x0, obj=obj0)
     return out
+
+
+# ------------------------------------------------------------------------------------
+# second_order_correction per member (rsqp_batch_handler_soc_begin / _soc_end of include/rsqp_hip_soc.h)
+# ------------------------------------------------------------------------------------
+def hess_times_reference(qp, n, p):
+    """(H_k p)_i, i < n, as rsqp_batch_handler_soc_begin forms it: from 0.0, + H_ij * p_j (one multiplication, one addition) over the
+    entries of row i of the leading n x n block of qp's H (CSC, a row at most once per column) in increasing j"""
+    jc, ir, val = np.asarray(qp.H_jc), np.asarray(qp.H_ir), np.asarray(qp.H_val, dtype=np.float64)
+    out = np.zeros(n)
+    for j in range(n):
+        for k in range(int(jc[j]), int(jc[j + 1])):
+            i = int(ir[k])
+            if i < n:
+                out[i] = out[i] + val[k] * np.float64(p[j])
+    return out
+
+
+def soc_qp_data(st, qp, p, c_trial, refresh_ubA=False):
+    """the correction QP of one member (src/Algorithm.cpp:1181-1184) from the data `qp` of the QP just solved: update_grad(H_k p +
+    grad_f), update_bounds at x_k + p with c_trial (ubA only with refresh_ubA); the slack part of g and the matrices stay"""
+    import copy
+    n = int(st["n"])
+    d = copy.copy(qp)
+    g = np.array(qp.g, dtype=np.float64)
+    g[:n] = hess_times_reference(qp, n, p) + np.asarray(st["grad"], dtype=np.float64)
+    xt = np.asarray(st["x_k"], dtype=np.float64) + np.asarray(p, dtype=np.float64)
+    lb, ub = np.array(qp.lb, dtype=np.float64), np.array(qp.ub, dtype=np.float64)
+    lb[:n] = np.maximum(st["x_l"] - xt, -np.float64(st["delta"])); ub[:n] = np.minimum(st["x_u"] - xt, np.float64(st["delta"]))
+    d.g, d.lb, d.ub = g, lb, ub
+    d.lbA = np.asarray(st["c_l"], dtype=np.float64) - c_trial
+    d.ubA = (np.asarray(st["c_u"], dtype=np.float64) - c_trial) if refresh_ubA else np.array(qp.ubA, dtype=np.float64)
+    return d
+
+
+def batch_soc_reference(qp_members, state, options, soc_options, trial, G=8):
+    """ratio_test, second_order_correction and update_radius of one SQP iteration (src/Algorithm.cpp:722-801, 1144-1211, 820-849) per
+    member, in plain Python with numpy float64 scalars (which do not contract), as rsqp_batch_handler_soc_begin followed by
+    rsqp_batch_handler_soc_end state them: the expected value of every test.
+
+    qp_members[q]: the member's solver object with the optimize / x / objective / status interface of
+    batch_update_penalty_reference; it has just solved state[q]["qp"]. state[q]: a dict with what (SOC_* bits), qp, n, m, x_k, c_k,
+    f_k, infea_k, delta, rho, grad, x_l, x_u, c_l, c_u and optionally infea_model. options: a mapping over the fields of
+    rsqp_nlp_step_options the calls read; soc_options: over rsqp_soc_options. trial(q, step) -> (f, c) at x_k + step: the caller's
+    evaluators. G: lanes of the tree sums (nlp_step_lanes over the batch).
+
+    Returns one dict per member: the iterate as the calls leave it (x_k, c_k, f_k, infea_k, delta), the outputs (actual_reduction,
+    pred_reduction, infea_trial, accept, hu_word, hm_word, exitflag, x_trial, soc -- as soc_begin returns it --, qp_obj, nwsr_soc;
+    None where nothing is written), x and obj as the result pools hold them afterwards, and for the tests' own checks: branch (None
+    sat out, "no_correct" the word lacks CORRECT, "accepted" at once, "soc_unsolved", "soc_accepted", "soc_rejected"), radius
+    ("shrunk", "grown", "unchanged"; None where update_radius did not run), too_small, and margins, the relative distance
+    |a - b| / max(|a|, |b|) of every float comparison that decided something."""
+    f8 = np.float64
+    o = {k: (int(options[k]) if k == "refresh_ubA" else f8(options[k])) for k in
+         ("eta_s", "eta_c", "eta_e", "gamma_c", "gamma_e", "delta_min", "delta_max", "tol", "refresh_ubA")}
+    composite = int(soc_options.get("composite_pred", 0)) != 0
+    accepted_hu = capi.HU_BOUNDS | capi.HU_GRAD | (capi.HU_UBA if o["refresh_ubA"] else 0)
+    out = []
+    for q, st in enumerate(state):
+        n, m = int(st["n"]), int(st["m"])
+        r = dict(x_k=np.array(st["x_k"], dtype=np.float64), c_k=np.array(st["c_k"], dtype=np.float64), f_k=f8(st["f_k"]),
+                 infea_k=f8(st["infea_k"]), delta=f8(st["delta"]), actual_reduction=None, pred_reduction=None, infea_trial=None,
+                 accept=None, hu_word=None, hm_word=None, exitflag=None, x_trial=None, soc=None, qp_obj=None, nwsr_soc=None, x=None,
+                 obj=None, branch=None, radius=None, too_small=False, margins=[])
+        out.append(r)
+        W = int(st["what"])
+        if W == 0:
+            continue
+        Q = qp_members[q]
+        margins = r["margins"]
+        rho = f8(st["rho"])
+        c_l, c_u = np.asarray(st["c_l"], dtype=np.float64), np.asarray(st["c_u"], dtype=np.float64)
+
+        def cmp(a, b):
+            with np.errstate(all="ignore"):
+                scale = max(abs(a), abs(b))
+                margins.append(float(abs(a - b) / scale) if scale > 0 and np.isfinite(scale) else 1.0)
+
+        def test(f_t, c_t, qp_obj):
+            it = cal_infea_reference(c_t, c_l, c_u, G)
+            actual = (r["f_k"] + rho * r["infea_k"]) - (f8(f_t) + rho * it)
+            pred = rho * r["infea_k"] - f8(qp_obj)
+            cmp(actual, o["eta_s"] * pred); cmp(actual, -o["tol"])
+            return it, actual, pred, bool(actual >= o["eta_s"] * pred and actual >= -o["tol"])
+
+        def radius(actual, pred, norm_p):
+            d = r["delta"]
+            cmp(actual, o["eta_c"] * pred)
+            if actual < o["eta_c"] * pred:
+                d, r["radius"] = o["gamma_c"] * d, "shrunk"
+            else:
+                cmp(actual, o["eta_e"] * pred)
+                if actual > o["eta_e"] * pred:
+                    cmp(o["tol"], abs(d - norm_p))
+                if actual > o["eta_e"] * pred and o["tol"] > abs(d - norm_p):
+                    grown = o["gamma_e"] * d
+                    d, r["radius"] = (o["delta_max"] if o["delta_max"] < grown else grown), "grown"
+                else:
+                    r["radius"] = "unchanged"
+            r["delta"] = d
+            cmp(d, o["delta_min"])
+            r["too_small"] = bool(d < o["delta_min"])
+            r["exitflag"] = capi.EXIT_TRUST_REGION_TOO_SMALL if r["too_small"] else capi.EXIT_UNKNOWN
+
+        def accept_step(step, f_t, c_t, it):
+            r["x_k"] = r["x_k"] + step
+            r["c_k"], r["f_k"], r["infea_k"] = np.array(c_t, dtype=np.float64), f8(f_t), it
+
+        x0, obj0 = np.array(Q.x, dtype=np.float64), f8(Q.objective)
+        p = x0[:n]
+        f_t, c_t = trial(q, p)
+        c_t = np.asarray(c_t, dtype=np.float64)
+        it, actual, pred, acc = test(f_t, c_t, obj0)
+        r.update(x=x0, obj=obj0)
+        if acc or not (W & capi.SOC_CORRECT):
+            r["branch"] = "accepted" if (W & capi.SOC_CORRECT) else "no_correct"
+            radius(actual, pred, f8(np.abs(p).max()) if n else f8(0.0))
+            if acc:
+                accept_step(p, f_t, c_t, it)
+            r.update(actual_reduction=actual, pred_reduction=pred, infea_trial=it, accept=int(acc), soc=0, nwsr_soc=0, qp_obj=obj0,
+                     hu_word=accepted_hu if acc else (capi.HU_DELTA if r["radius"] != "unchanged" else 0),
+                     hm_word=(capi.HM_JAC | capi.HM_HESS) if acc else 0)
+            continue
+        data = soc_qp_data(st, st["qp"], p, c_t, bool(o["refresh_ubA"]))
+        r["nwsr_soc"] = int(Q.optimize(data))
+        if Q.status != capi.QP_OPTIMAL:                                                  # :1190-1193
+            r.update(branch="soc_unsolved", exitflag=int(Q.status), soc=0, x=None, obj=None)
+            continue
+        xs, obj_soc = np.array(Q.x, dtype=np.float64), f8(Q.objective)
+        model = f8(st["infea_model"]) if st.get("infea_model") is not None else tree_sum(np.abs(x0[n:]), G)
+        qp_obj = obj_soc + (obj0 - rho * model)                                          # :1198
+        step = p + xs[:n]
+        x_pool = xs.copy(); x_pool[:n] = step
+        r.update(soc=1, x_trial=r["x_k"] + step)
+        f_t, c_t = trial(q, step)
+        c_t = np.asarray(c_t, dtype=np.float64)
+        it, actual, pred, acc = test(f_t, c_t, qp_obj if composite else obj_soc)        # :1200-1201: get_obj_QP() is the correction's
+        if acc:
+            r.update(branch="soc_accepted", x=x_pool, obj=obj_soc, qp_obj=qp_obj, hm_word=capi.HM_JAC | capi.HM_HESS)
+            norm_p = f8(np.abs(step).max())
+            accept_step(step, f_t, c_t, it)
+        else:                                                                            # :1202-1208
+            r.update(branch="soc_rejected", x=x0, obj=obj0, qp_obj=obj0, hm_word=0)
+            norm_p = f8(np.abs(p).max())
+        radius(actual, pred, norm_p)
+        r.update(actual_reduction=actual, pred_reduction=pred, infea_trial=it, accept=int(acc), hu_word=accepted_hu)
+    return out
