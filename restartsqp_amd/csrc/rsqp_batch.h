@@ -1,16 +1,22 @@
-// rsqp_batch.h -- struct rsqp_batch and what more than one of its translation units uses. Private to them: rsqp_batch.hip (the batch
-// itself: create, whole-batch setters, solve, results, certificate, records), rsqp_batch_optimize.hip (optimizeQP / optimizeLP per
-// member and their plan kernels), rsqp_batch_handler.hip (everything that writes the pools member by member) and rsqp_batch_nlp.hip
-// (the decisions of the SQP loop, which read the pools member by member), rsqp_batch_penalty.hip (update_penalty_parameter across
-// a QP batch and its LP batch) and rsqp_batch_soc.hip (second_order_correction; the last three share rsqp_batch_decide.h). Device code does not cross a unit: the __device__ helpers
-// here are inline. Everything but the struct itself (the opaque type of the C ABI) is in namespace rsqp_batch_units, which the units
-// open.
+// rsqp_batch.h -- struct rsqp_batch and what more than one of its translation units uses. Private to the units:
+//   rsqp_batch.hip           the batch itself: create, whole-batch setters, solve, results, certificate, records
+//   rsqp_batch_optimize.hip  optimizeQP / optimizeLP per member and their plan kernels
+//   rsqp_batch_handler.hip   everything that writes the pools member by member
+//   rsqp_batch_nlp.hip       the decisions of the SQP loop, which read the pools member by member
+//   rsqp_batch_penalty.hip   update_penalty_parameter across a QP batch and its LP batch
+//   rsqp_batch_soc.hip       second_order_correction
+// and the two shared headers: rsqp_batch_staging.h (the staging block of a host-pointer call, plain C++; included here) and
+// rsqp_batch_decide.h (the arithmetic of the decisions, with FP contraction off; the last three units include it).
+// Device code does not cross a unit: the __device__ helpers here are inline. Everything but the struct itself (the opaque type
+// of the C ABI) is in namespace rsqp_batch_units, which the units open.
 #pragma once
 #include <algorithm>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
+#include "rsqp_batch_staging.h"
 #include "rsqp_host.h"
 #include "rsqp_matrix.h"
 
@@ -52,6 +58,29 @@ __device__ inline double hu_lb(double x_l, double x_k, double delta) { return fm
 __device__ inline double hu_ub(double x_u, double x_k, double delta) { return fmin(x_u - x_k, delta); }
 __device__ inline double hu_lbA(double c_l, double c_k) { return c_l - c_k; }
 __device__ inline double hu_ubA(double c_u, double c_k) { return c_u - c_k; }
+// the per-member work of a call whose decisions are taken on the device, allocated at its first use: `ints` ints and `doubles`
+// doubles, nq of each per word (word w of member q at [w * nq + q]), the x of the first solve (sumV), the block counters of the
+// decision kernels (report_live) and the host-mapped word they report through. DecisionView: what the kernels get of it
+struct DecisionView {
+    int nq;
+    int *i; double *d;
+    double *x0;                               // pooled like x
+    int *cnt;                                 // [0] members that go on, [1] blocks that have finished
+    int *live;                                // host-mapped: [0] of the finished launch
+    __device__ int &wi(int w, int q) const { return i[(size_t)w * nq + q]; }
+    __device__ double &wd(int w, int q) const { return d[(size_t)w * nq + q]; }
+};
+struct DecisionWork {
+    DevBuf<int> i, cnt;
+    DevBuf<double> d, x0;
+    HostBuf<int> live;
+    int ensure(size_t ints, size_t doubles, size_t sumV) {
+        if (i.p) return RSQP_OK;
+        HIPCHK(i.alloc(ints)); HIPCHK(d.alloc(doubles)); HIPCHK(x0.alloc(sumV)); HIPCHK(cnt.alloc(2)); HIPCHK(live.alloc(1, true));
+        return RSQP_OK;
+    }
+    DecisionView view(int nq) const { return DecisionView{nq, i.p, d.p, x0.p, cnt.p, live.dev}; }
+};
 }  // namespace rsqp_batch_units
 using namespace rsqp_batch_units;
 
@@ -160,20 +189,13 @@ struct rsqp_batch {
     float last_ms = 0.f;
     bool keep_state = true;
     // rsqp_batch_handler_pair_lp / rsqp_batch_handler_update_penalty (rsqp_batch_penalty.hip): the host's copy of the canonical A
-    // pattern (what the pairing compares), the LP batch paired with this one, and the call's per-member work on the device, allocated
-    // at its first use: pen_i = PEN_INTS x nq ints, pen_d = PEN_DOUBLES x nq doubles, the x of the first solve (sumV), the block
-    // counters of the decision kernels, and the host-mapped word they report through
+    // pattern (what the pairing compares), the LP batch paired with this one, and the call's work on the device
     std::vector<int> h_Ajc, h_Air;
     rsqp_batch *lp_pair = nullptr;
-    DevBuf<int> pen_i, pen_cnt;
-    DevBuf<double> pen_d, pen_x;
-    HostBuf<int> pen_live;
-    // rsqp_batch_handler_soc_begin / _soc_end (rsqp_batch_soc.hip): the call's per-member work on the device, allocated at its first
-    // use as the penalty call's: soc_i = SOC_INTS x nq ints, soc_d = SOC_DOUBLES x nq doubles, the x of the first solve (sumV), the
-    // block counters of the decision kernels and the host-mapped word they report through. soc_begun: a soc_begin has run
-    DevBuf<int> soc_i, soc_cnt;
-    DevBuf<double> soc_d, soc_x;
-    HostBuf<int> soc_live;
+    DecisionWork pen;
+    // rsqp_batch_handler_soc_begin / _soc_end (rsqp_batch_soc.hip): the calls' work on the device, which lives from soc_begin to
+    // soc_end (so it is not the penalty call's). soc_begun: a soc_begin has run
+    DecisionWork soc;
     bool soc_begun = false;
     bool timing = false;   // between timer_start and timer_stop: no per-launch events (they cost ~10 us of stream time each)
     ~rsqp_batch() {
@@ -210,4 +232,103 @@ int settle_H(rsqp_batch *b);
 int ensure_staging(rsqp_batch *b, size_t words);
 // what rsqp_batch_handler_set_matrices builds at its first call: hm_joff, and hm_inv, the inverse of perm (CSC slot -> CSR slot)
 int ensure_handler_matrices(rsqp_batch *b);
+
+// ---- what the member-by-member kernels and their calls share; no floating-point formula (those: rsqp_batch_decide.h) ----
+// the shape of member q: a one-shape batch (uniV > 0) multiplies, else the descriptor says
+struct MemberShape { int nV, nC, offV, offC; };
+__device__ inline MemberShape shape_of(const QPDesc *__restrict__ desc, int uniV, int uniC, int q) {
+    if (uniV > 0) return MemberShape{uniV, uniC, q * uniV, q * uniC};
+    return MemberShape{desc[q].nV, desc[q].nC, desc[q].offV, desc[q].offC};
+}
+// the sum of v over the G lanes of a sub-group, the same bits in every lane: partners G/2, G/4, ..., 1 lanes apart
+template <int G>
+__device__ inline double group_sum(double v) {
+    for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, G);
+    return v;
+}
+// the maximum over the sub-group (exact in any order)
+template <int G>
+__device__ inline double group_max(double v) {
+    for (int o = G / 2; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, G));
+    return v;
+}
+// how many members go on behind a decision kernel: added per member into cnt[0], reported through the host-mapped word by the block
+// that finishes last (cnt[1] counts the blocks), which clears both for the next launch. Every thread of the block calls it
+__device__ inline void report_live(int goes_on, int *cnt, int *live) {
+    if (goes_on) atomicAdd(&cnt[0], 1);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __threadfence();
+        if (atomicAdd(&cnt[1], 1) == (int)gridDim.x - 1) {
+            __threadfence();
+            *live = atomicExch(&cnt[0], 0);
+            atomicExch(&cnt[1], 0);
+        }
+    }
+}
+
+// hs071-scale members: 8 lanes each, eight members per wavefront; else a wavefront per member
+inline int lanes_per_member(const rsqp_batch *b) { return (b->nVmax + b->nCmax <= 16) ? 8 : 64; }
+inline dim3 grid_of(const rsqp_batch *b, int G) { return dim3((unsigned)(((long long)b->nq * G + 255) / 256)); }
+inline int uni_shape(const rsqp_batch *b) { return (b->uniV > 0 && b->uniC >= 0) ? b->uniV : 0; }
+inline StageSizes stage_sizes(const rsqp_batch *b) { return StageSizes{(size_t)b->nq, (size_t)b->sumN, (size_t)b->sumC}; }
+
+// the one launch of a kernel with G lanes per member: kernel(g) is its instance for g = std::integral_constant<int, G>, e.g.
+// [](auto g) { return batch_nlp_ratio_kernel<decltype(g)::value>; }. On the batch's stream, grid_of(b, G) x 256
+template <class Kernel, class... Args>
+int launch_groups(rsqp_batch *b, Kernel kernel, const Args &... args) {
+    const int G = lanes_per_member(b);
+    if (G == 8) hipLaunchKernelGGL(kernel(std::integral_constant<int, 8>()), grid_of(b, G), dim3(256), 0, b->stream, args...);
+    else hipLaunchKernelGGL(kernel(std::integral_constant<int, 64>()), grid_of(b, G), dim3(256), 0, b->stream, args...);
+    HIPCHK(hipGetLastError());
+    return RSQP_OK;
+}
+// ... of a decision kernel (report_live): waits for it; *live = how many members go on
+template <class Kernel, class... Args>
+int launch_decision(rsqp_batch *b, const DecisionWork &w, int *live, Kernel kernel, const Args &... args) {
+    const int rc = launch_groups(b, kernel, args...);
+    if (rc != RSQP_OK) return rc;
+    HIPCHK(hipStreamSynchronize(b->stream));
+    *live = *w.live.p;
+    return RSQP_OK;
+}
+
+// The HIP side of a call's staging block (StagingLayout): the fields are declared while `active` (a host-pointer call); with
+// on_device the caller's pointers pass through and only down()'s wait remains. up(): the caller's arrays into the pinned block,
+// what goes up in one copy to the same words of the scratch block, the declared fields to their device addresses. down(): the
+// tail that comes down in one copy (`copy`: somebody takes it), the wait for the stream, the tail into the caller's arrays
+struct Staging : StagingLayout {
+    rsqp_batch *b;
+    bool active;
+    Staging(rsqp_batch *batch, int on_device) : b(batch), active(on_device == 0) {}
+    int up() {
+        if (!active) return RSQP_OK;
+        if (!ok()) return fail(RSQP_ERR_ARG, "staging block: more fields than the table holds, or an up-only field behind the tail");
+        const int rc = ensure_staging(b, words());
+        if (rc != RSQP_OK) return rc;
+        pack(b->pin.p);
+        if (up_words() > 0) HIPCHK(hipMemcpyAsync(b->scratch.p, b->pin.p, sizeof(double) * up_words(), hipMemcpyHostToDevice, b->stream));
+        address(b->scratch.p);
+        return RSQP_OK;
+    }
+    int down(bool copy = true) {
+        if (active && copy && words() > tail())
+            HIPCHK(hipMemcpyAsync(b->pin.p + tail(), b->scratch.p + tail(), sizeof(double) * (words() - tail()), hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+        if (active) unpack(b->pin.p);
+        return RSQP_OK;
+    }
+};
+
+// while a call runs an inner optimize call, that call reads the mask a decision kernel wrote where it reads the mask of
+// rsqp_batch_set_members, which is put back when the loan ends, however the call ends
+struct MaskLoan {
+    rsqp_batch *b;
+    int *take; size_t take_n; bool sitters;
+    explicit MaskLoan(rsqp_batch *batch) : b(batch), take(batch->take.p), take_n(batch->take.n), sitters(batch->sitters) {}
+    MaskLoan(const MaskLoan &) = delete;
+    MaskLoan &operator=(const MaskLoan &) = delete;
+    static void lend(rsqp_batch *b, int *mask, int live) { b->take.p = mask; b->take.n = (size_t)b->nq; b->sitters = live < b->nq; }
+    ~MaskLoan() { b->take.p = take; b->take.n = take_n; b->sitters = sitters; }
+};
 }  // namespace rsqp_batch_units

@@ -1,8 +1,8 @@
 // rsqp_batch_decide.h -- what the decision units of a batch share (rsqp_batch_nlp.hip, rsqp_batch_penalty.hip, rsqp_batch_soc.hip):
-// the member's shape, the G-lane groups and their tree sums, cal_infea, the arithmetic of ratio_test and update_radius
-// (src/Algorithm.cpp:722-801, 820-849), the exit flag of an unsolved QP, the launch shape, the report of how many members go on and
-// the loan of the members' mask to an inner optimize call. Private to those units; device code does not cross a unit, so everything
-// here is inline.
+// cal_infea, the arithmetic of ratio_test and update_radius (src/Algorithm.cpp:722-801, 820-849), what a ratio test writes for a
+// member, the accepted step and the exit flag of an unsolved QP. What carries no floating-point formula (the member's shape, the
+// G-lane groups, the launches, the staging block) is in rsqp_batch.h. Private to those units; device code does not cross a unit, so
+// everything here is inline.
 #pragma once
 #include "rsqp_batch.h"
 
@@ -11,26 +11,6 @@
 #pragma clang fp contract(off)
 
 namespace rsqp_batch_units {
-// the shape of member q: a one-shape batch (uniV > 0) multiplies, else the descriptor says
-struct MemberShape { int nV, nC, offV, offC; };
-__device__ inline MemberShape shape_of(const QPDesc *__restrict__ desc, int uniV, int uniC, int q) {
-    if (uniV > 0) return MemberShape{uniV, uniC, q * uniV, q * uniC};
-    return MemberShape{desc[q].nV, desc[q].nC, desc[q].offV, desc[q].offC};
-}
-
-// the sum of v over the G lanes of a sub-group, the same bits in every lane: partners G/2, G/4, ..., 1 lanes apart
-template <int G>
-__device__ inline double group_sum(double v) {
-    for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, G);
-    return v;
-}
-// the maximum over the sub-group (exact in any order)
-template <int G>
-__device__ inline double group_max(double v) {
-    for (int o = G / 2; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, G));
-    return v;
-}
-
 // lane `lane`'s share of cal_infea(c, c_l, c_u) (src/Algorithm.cpp:584-589) over m constraints: entries lane, lane + G, ...
 template <int G>
 __device__ inline double infea_share(const double *__restrict__ c, const double *__restrict__ c_l, const double *__restrict__ c_u,
@@ -85,37 +65,36 @@ __device__ inline int dev_exitflag(int sw) {
     return RSQP_QPERROR_UNKNOWN;
 }
 
-// hs071-scale members: 8 lanes each, eight members per wavefront; else a wavefront per member (rsqp_batch_handler_get_step)
-inline int lanes_per_member(const rsqp_batch *b) { return (b->nVmax + b->nCmax <= 16) ? 8 : 64; }
-inline dim3 grid_of(const rsqp_batch *b, int G) { return dim3((unsigned)(((long long)b->nq * G + 255) / 256)); }
-inline int uni_shape(const rsqp_batch *b) { return (b->uniV > 0 && b->uniC >= 0) ? b->uniV : 0; }
-// `ints` ints in doubles of the staging block
-inline size_t int_words(size_t ints) { return (ints + 1) / 2; }
-
-// how many members go on behind a decision kernel: added per member into cnt[0], reported through the host-mapped word by the block
-// that finishes last (cnt[1] counts the blocks), which clears both for the next launch. Every thread of the block calls it
-__device__ inline void report_live(int goes_on, int *cnt, int *live) {
-    if (goes_on) atomicAdd(&cnt[0], 1);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __threadfence();
-        if (atomicAdd(&cnt[1], 1) == (int)gridDim.x - 1) {
-            __threadfence();
-            *live = atomicExch(&cnt[0], 0);
-            atomicExch(&cnt[1], 0);
-        }
+// What a ratio test writes for member q (lane 0 of its group), update_radius included: r from ratio_test_of on f_t and infea_t,
+// delta as the member brought it, norm_p the norm the radius is judged by. Trial: rsqp_nlp_trial, or rsqp_soc_trial, which has its
+// fields. TEST_PLAIN: rsqp_batch_handler_ratio_test. TEST_SOC_FIRST: soc_begin's, for a member that ends there -- it also clears
+// soc and nwsr_soc and reports qp_obj. TEST_SOC_SECOND: soc_end's -- the words of an accepted step either way (rejected:
+// update_grad + update_bounds at x_k, :1206-1207); norm_p is that of p + s, or of the restored p
+enum { TEST_PLAIN, TEST_SOC_FIRST, TEST_SOC_SECOND };
+template <int TEST, class Trial>
+__device__ inline void write_verdict(const Trial &t, const rsqp_nlp_step_options &o, int q, const RatioTest &r, double f_t,
+                                     double infea_t, double delta, double norm_p, double qp_obj = 0.0) {
+    const bool radius = radius_update(o, r.actual, r.pred, norm_p, delta);
+    if (radius) t.delta[q] = delta;
+    if (r.acc) { t.f_k[q] = f_t; t.infea_k[q] = infea_t; }
+    if (t.actual_reduction) t.actual_reduction[q] = r.actual;
+    if (t.pred_reduction) t.pred_reduction[q] = r.pred;
+    if (t.infea_trial) t.infea_trial[q] = infea_t;
+    if (t.accept) t.accept[q] = r.acc;
+    if (t.hu_word) t.hu_word[q] = (r.acc || TEST == TEST_SOC_SECOND) ? accepted_hu_word(o) : (radius ? RSQP_HU_DELTA : 0);
+    if (t.hm_word) t.hm_word[q] = r.acc ? (RSQP_HM_JAC | RSQP_HM_HESS) : 0;
+    if (t.exitflag) t.exitflag[q] = radius_exitflag(o, delta);
+    if constexpr (TEST == TEST_SOC_FIRST) {
+        t.soc[q] = 0;
+        if (t.nwsr_soc) t.nwsr_soc[q] = 0;
+        if (t.qp_obj) t.qp_obj[q] = qp_obj;
     }
 }
-
-// while a call runs an inner optimize call, that call reads the mask a decision kernel wrote where it reads the mask of
-// rsqp_batch_set_members, which is put back when the loan ends, however the call ends
-struct MaskLoan {
-    rsqp_batch *b;
-    int *take; size_t take_n; bool sitters;
-    explicit MaskLoan(rsqp_batch *batch) : b(batch), take(batch->take.p), take_n(batch->take.n), sitters(batch->sitters) {}
-    MaskLoan(const MaskLoan &) = delete;
-    MaskLoan &operator=(const MaskLoan &) = delete;
-    static void lend(rsqp_batch *b, int *mask, int live) { b->take.p = mask; b->take.n = (size_t)b->nq; b->sitters = live < b->nq; }
-    ~MaskLoan() { b->take.p = take; b->take.n = take_n; b->sitters = sitters; }
-};
+// the accepted step (:792-795) by the G lanes of the member's group: x_k += p, the leading entries of the member's x; c_k = c_trial
+template <int G, class Trial>
+__device__ inline void accept_step(const Trial &t, const double *x, const MemberShape &sh, int lane) {
+    const int n = sh.nV - 2 * sh.nC, offN = sh.offV - 2 * sh.offC;
+    for (int i = lane; i < n; i += G) t.x_k[offN + i] = t.x_k[offN + i] + x[sh.offV + i];
+    for (int i = lane; i < sh.nC; i += G) t.c_k[sh.offC + i] = t.c_trial[sh.offC + i];
+}
 }  // namespace rsqp_batch_units

@@ -189,9 +189,8 @@ __global__ void __launch_bounds__(256) batch_handler_update_kernel(HandlerUpdate
     else { k = (int)(e - 3LL * a.sumV); s = 3 + (k >= a.sumC); if (s == 4) k -= a.sumC; }
     // (a constraint entry exists: uniC > 0 where the batch has one shape)
     const int q = member_of(k, isV ? a.uniV : a.uniC, a.nq, [&](int m) { return isV ? a.desc[m].offV : a.desc[m].offC; });
-    int nV, nC, offV, offC;
-    if (a.uniV > 0) { nV = a.uniV; nC = a.uniC; offV = q * nV; offC = q * nC; }
-    else { nV = a.desc[q].nV; nC = a.desc[q].nC; offV = a.desc[q].offV; offC = a.desc[q].offC; }
+    const MemberShape sh = shape_of(a.desc, a.uniV, a.uniC, q);
+    const int nV = sh.nV, nC = sh.nC, offV = sh.offV, offC = sh.offC;
     const int W = a.what[q];
     if (W == 0) return;
     const bool set = (W & RSQP_HU_SET) != 0;
@@ -238,10 +237,8 @@ batch_handler_step_kernel(int nq, const QPDesc *__restrict__ desc, const double 
             for (int i = lane; i < nC; i += G) lam_c[offC + i] = y[offY + nV + i];
         for (int i = n + lane; i < nV; i += G) sm += fabs(x[offV + i]);
     }
-    for (int o = G / 2; o > 0; o >>= 1) {
-        mx = fmax(mx, __shfl_xor(mx, o, G));
-        sm += __shfl_xor(sm, o, G);
-    }
+    mx = group_max<G>(mx);
+    sm = group_sum<G>(sm);
     if (q < nq && lane == 0) {
         if (norm_p) norm_p[q] = mx;
         if (infea) infea[q] = sm;
@@ -278,26 +275,14 @@ extern "C" int rsqp_batch_handler_update(rsqp_batch *b, const rsqp_handler_itera
     HIPCHK(hipSetDevice(b->device));
     HandlerUpdate a;
     std::memset(&a, 0, sizeof(a));
-    if (on_device) {
-        a.what = it->what; a.delta = it->delta; a.rho = it->rho; a.x_k = it->x_k; a.grad = it->grad; a.c_k = it->c_k;
-    } else {
-        // delta | rho | x_k | grad | c_k | what (ints)
-        const size_t nq = (size_t)b->nq, sN = (size_t)b->sumN, sC = (size_t)b->sumC;
-        const size_t o_rho = nq, o_x = 2 * nq, o_g = o_x + sN, o_c = o_g + sN, o_w = o_c + sC, words = o_w + (nq + 1) / 2;
-        const int rc = ensure_staging(b, words);
-        if (rc != RSQP_OK) return rc;
-        std::memcpy(b->pin.p, it->delta, sizeof(double) * nq); std::memcpy(b->pin.p + o_rho, it->rho, sizeof(double) * nq);
-        std::memcpy(b->pin.p + o_x, it->x_k, sizeof(double) * sN);
-        if (it->grad) std::memcpy(b->pin.p + o_g, it->grad, sizeof(double) * sN);
-        if (sC > 0) std::memcpy(b->pin.p + o_c, it->c_k, sizeof(double) * sC);
-        std::memcpy(b->pin.p + o_w, it->what, sizeof(int) * nq);
-        HIPCHK(hipMemcpyAsync(b->scratch.p, b->pin.p, sizeof(double) * words, hipMemcpyHostToDevice, b->stream));
-        double *const d = b->scratch.p;
-        a.delta = d; a.rho = d + o_rho; a.x_k = d + o_x; a.grad = it->grad ? d + o_g : nullptr; a.c_k = d + o_c;
-        a.what = reinterpret_cast<const int *>(d + o_w);
-    }
+    rsqp_handler_iterate d = *it;      // the arrays where the kernel reads them
+    Staging st(b, on_device);
+    if (st.active) stage_iterate(st, d, stage_sizes(b));
+    const int rc = st.up();
+    if (rc != RSQP_OK) return rc;
+    a.what = d.what; a.delta = d.delta; a.rho = d.rho; a.x_k = d.x_k; a.grad = d.grad; a.c_k = d.c_k;
     a.nq = b->nq; a.sumV = (int)b->sumV; a.sumC = (int)b->sumC; a.desc = b->d_desc.p;
-    a.uniV = (b->uniV > 0 && b->uniC >= 0) ? b->uniV : 0; a.uniC = a.uniV > 0 ? b->uniC : 0;
+    a.uniV = uni_shape(b); a.uniC = a.uniV > 0 ? b->uniC : 0;
     a.x_l = b->h_xl.p; a.x_u = b->h_xu.p; a.c_l = b->h_cl.p; a.c_u = b->h_cu.p;
     a.g = b->g.p; a.lb = b->lb.p; a.ub = b->ub.p; a.lbA = b->lbA.p; a.ubA = b->ubA.p;
     const long long n = 3 * b->sumV + 2 * b->sumC;
@@ -312,34 +297,14 @@ extern "C" int rsqp_batch_handler_get_step(rsqp_batch *b, double *p, double *lam
     if (!b) return fail(RSQP_ERR_ARG, "null batch");
     if (!b->have_problem) return fail(RSQP_ERR_ARG, "rsqp_batch_handler_get_step: rsqp_batch_handler_set_problem has not been called");
     HIPCHK(hipSetDevice(b->device));
-    const size_t nq = (size_t)b->nq, sN = (size_t)b->sumN, sC = (size_t)b->sumC;
-    const size_t o_lx = sN, o_lc = 2 * sN, o_in = o_lc + sC, o_np = o_in + nq, words = o_np + nq;
-    double *dp = p, *dlc = lam_c, *dlx = lam_x, *din = infea_model, *dnp = norm_p;
-    if (!on_device) {
-        const int rc = ensure_staging(b, words);
-        if (rc != RSQP_OK) return rc;
-        double *const d = b->scratch.p;
-        dp = p ? d : nullptr; dlx = lam_x ? d + o_lx : nullptr; dlc = lam_c ? d + o_lc : nullptr;
-        din = infea_model ? d + o_in : nullptr; dnp = norm_p ? d + o_np : nullptr;
-    }
-    // hs071-scale members: 8 lanes each, eight members per wavefront
-    const int G = (b->nVmax + b->nCmax <= 16) ? 8 : 64;
-    const dim3 grid((unsigned)(((long long)b->nq * G + 255) / 256)), block(256);
-    if (G == 8)
-        hipLaunchKernelGGL(batch_handler_step_kernel<8>, grid, block, 0, b->stream, b->nq, b->d_desc.p, b->x.p, b->y.p, dp, dlc, dlx, din, dnp);
-    else
-        hipLaunchKernelGGL(batch_handler_step_kernel<64>, grid, block, 0, b->stream, b->nq, b->d_desc.p, b->x.p, b->y.p, dp, dlc, dlx, din, dnp);
-    HIPCHK(hipGetLastError());
-    if (!on_device) HIPCHK(hipMemcpyAsync(b->pin.p, b->scratch.p, sizeof(double) * words, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    if (!on_device) {
-        if (p) std::memcpy(p, b->pin.p, sizeof(double) * sN);
-        if (lam_x) std::memcpy(lam_x, b->pin.p + o_lx, sizeof(double) * sN);
-        if (lam_c) std::memcpy(lam_c, b->pin.p + o_lc, sizeof(double) * sC);
-        if (infea_model) std::memcpy(infea_model, b->pin.p + o_in, sizeof(double) * nq);
-        if (norm_p) std::memcpy(norm_p, b->pin.p + o_np, sizeof(double) * nq);
-    }
-    return RSQP_OK;
+    Staging st(b, on_device);
+    if (st.active) stage_step(st, p, lam_c, lam_x, infea_model, norm_p, stage_sizes(b));
+    int rc;
+    if ((rc = st.up()) != RSQP_OK) return rc;
+    const int nq = b->nq;
+    rc = launch_groups(b, [](auto g) { return batch_handler_step_kernel<decltype(g)::value>; }, nq, b->d_desc.p, b->x.p, b->y.p, p, lam_c,
+                       lam_x, infea_model, norm_p);
+    return rc != RSQP_OK ? rc : st.down();
 }
 
 extern "C" int rsqp_batch_get_vectors(rsqp_batch *b, double *g, double *lb, double *ub, double *lbA, double *ubA) {
@@ -480,18 +445,10 @@ extern "C" int rsqp_batch_handler_set_matrices(rsqp_batch *b, const int *what, c
     }
     HandlerMatrices a;
     std::memset(&a, 0, sizeof(a));
-    if (on_device) {
-        a.what = what; a.jac = jac; a.hess = hess;
-    } else {
-        // what | jac | hess, the arrays that are given alone: one copy up
-        const size_t o_j = (nq + 1) / 2, o_h = o_j + (size_t)nJ, words = o_h + (size_t)nH;
-        if ((rc = ensure_staging(b, words)) != RSQP_OK) return rc;
-        std::memcpy(b->pin.p, what, sizeof(int) * nq);
-        if (jac) std::memcpy(b->pin.p + o_j, jac, sizeof(double) * (size_t)nJ);
-        if (hess) std::memcpy(b->pin.p + o_h, hess, sizeof(double) * (size_t)nH);
-        HIPCHK(hipMemcpyAsync(b->scratch.p, b->pin.p, sizeof(double) * words, hipMemcpyHostToDevice, b->stream));
-        a.what = reinterpret_cast<const int *>(b->scratch.p); a.jac = b->scratch.p + o_j; a.hess = b->scratch.p + o_h;
-    }
+    a.what = what; a.jac = jac; a.hess = hess;
+    Staging st(b, on_device);
+    if (st.active) stage_matrices(st, a.what, a.jac, a.hess, nq, (size_t)nJ, (size_t)nH);
+    if ((rc = st.up()) != RSQP_OK) return rc;
     a.nq = b->nq; a.bits = (jac ? RSQP_HM_JAC : 0) | (hess ? RSQP_HM_HESS : 0);
     a.nJ = nJ; a.nH = nH;
     a.uniJ = b->uni_jn ? b->h_jn[0] : 0; a.uniA = b->uni_annz;

@@ -43,11 +43,10 @@ __global__ void __launch_bounds__(256) batch_nlp_ratio_kernel(NlpRatio a) {
     const int q = (int)(((long long)blockIdx.x * blockDim.x + threadIdx.x) / G), lane = (int)threadIdx.x % G;
     const bool act = q < a.nq && a.t.what[q] != 0;
     MemberShape sh{0, 0, 0, 0};
-    int n = 0, offN = 0;
     double s = 0.0, mx = 0.0;
     if (act) {
         sh = shape_of(a.desc, a.uniV, a.uniC, q);
-        n = sh.nV - 2 * sh.nC; offN = sh.offV - 2 * sh.offC;
+        const int n = sh.nV - 2 * sh.nC;
         s = infea_share<G>(a.t.c_trial + sh.offC, a.c_l + sh.offC, a.c_u + sh.offC, sh.nC, lane);
         for (int i = lane; i < n; i += G) mx = fmax(mx, fabs(a.x[sh.offV + i]));    // getInfNorm of p: exact in any order
     }
@@ -55,29 +54,13 @@ __global__ void __launch_bounds__(256) batch_nlp_ratio_kernel(NlpRatio a) {
     mx = group_max<G>(mx);
     int acc = 0;
     if (act && lane == 0) {
-        const rsqp_nlp_step_options &o = a.o;
         const double f_t = a.t.f_trial[q];
-        const RatioTest r = ratio_test_of(o, a.t.rho[q], a.t.f_k[q], a.t.infea_k[q], f_t, s, a.obj[q]);
-        const double actual = r.actual, pred = r.pred;
+        const RatioTest r = ratio_test_of(a.o, a.t.rho[q], a.t.f_k[q], a.t.infea_k[q], f_t, s, a.obj[q]);
         acc = r.acc;
-        double delta = a.t.delta[q];
-        const bool radius = radius_update(o, actual, pred, mx, delta);
-        if (radius) a.t.delta[q] = delta;
-        if (acc) { a.t.f_k[q] = f_t; a.t.infea_k[q] = s; }
-        if (a.t.actual_reduction) a.t.actual_reduction[q] = actual;
-        if (a.t.pred_reduction) a.t.pred_reduction[q] = pred;
-        if (a.t.infea_trial) a.t.infea_trial[q] = s;
-        if (a.t.accept) a.t.accept[q] = acc;
-        if (a.t.hu_word)
-            a.t.hu_word[q] = acc ? accepted_hu_word(o) : (radius ? RSQP_HU_DELTA : 0);
-        if (a.t.hm_word) a.t.hm_word[q] = acc ? (RSQP_HM_JAC | RSQP_HM_HESS) : 0;
-        if (a.t.exitflag) a.t.exitflag[q] = radius_exitflag(o, delta);
+        write_verdict<TEST_PLAIN>(a.t, a.o, q, r, f_t, s, a.t.delta[q], mx);
     }
     acc = __shfl(acc, 0, G);
-    if (acc) {      // (only lanes of an active member hold 1)
-        for (int i = lane; i < n; i += G) a.t.x_k[offN + i] = a.t.x_k[offN + i] + a.x[sh.offV + i];
-        for (int i = lane; i < sh.nC; i += G) a.t.c_k[sh.offC + i] = a.t.c_trial[sh.offC + i];
-    }
+    if (acc) accept_step<G>(a.t, a.x, sh, lane);      // (only lanes of an active member hold 1)
 }
 
 // classify_single_constraint (src/Utils.cpp:29-45), exactly as written
@@ -173,28 +156,14 @@ extern "C" int rsqp_batch_handler_infeasibility(rsqp_batch *b, const double *c, 
     if (!b || !infea || (b->sumC > 0 && !c)) return fail(RSQP_ERR_ARG, "rsqp_batch_handler_infeasibility: the batch, infea (and c) are required");
     if (!b->have_problem) return fail(RSQP_ERR_ARG, "rsqp_batch_handler_infeasibility: rsqp_batch_handler_set_problem has not been called");
     HIPCHK(hipSetDevice(b->device));
-    const size_t nq = (size_t)b->nq, sC = (size_t)b->sumC, words = sC + nq;      // c | infea
-    const double *dc = c;
-    double *di = infea;
-    if (!on_device) {
-        const int rc = ensure_staging(b, words);
-        if (rc != RSQP_OK) return rc;
-        if (sC > 0) {
-            std::memcpy(b->pin.p, c, sizeof(double) * sC);
-            HIPCHK(hipMemcpyAsync(b->scratch.p, b->pin.p, sizeof(double) * sC, hipMemcpyHostToDevice, b->stream));
-        }
-        dc = b->scratch.p; di = b->scratch.p + sC;
-    }
-    const int G = lanes_per_member(b), uniV = uni_shape(b), uniC = uniV > 0 ? b->uniC : 0;
-    if (G == 8)
-        hipLaunchKernelGGL(batch_nlp_infea_kernel<8>, grid_of(b, G), dim3(256), 0, b->stream, b->nq, uniV, uniC, b->d_desc.p, dc, b->h_cl.p, b->h_cu.p, di);
-    else
-        hipLaunchKernelGGL(batch_nlp_infea_kernel<64>, grid_of(b, G), dim3(256), 0, b->stream, b->nq, uniV, uniC, b->d_desc.p, dc, b->h_cl.p, b->h_cu.p, di);
-    HIPCHK(hipGetLastError());
-    if (!on_device) HIPCHK(hipMemcpyAsync(b->pin.p + sC, b->scratch.p + sC, sizeof(double) * nq, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    if (!on_device) std::memcpy(infea, b->pin.p + sC, sizeof(double) * nq);
-    return RSQP_OK;
+    Staging st(b, on_device);
+    if (st.active) stage_infeasibility(st, c, infea, stage_sizes(b));
+    int rc;
+    if ((rc = st.up()) != RSQP_OK) return rc;
+    const int nq = b->nq, uniV = uni_shape(b), uniC = uniV > 0 ? b->uniC : 0;
+    rc = launch_groups(b, [](auto g) { return batch_nlp_infea_kernel<decltype(g)::value>; }, nq, uniV, uniC, b->d_desc.p, c, b->h_cl.p,
+                       b->h_cu.p, infea);
+    return rc != RSQP_OK ? rc : st.down();
 }
 
 extern "C" int rsqp_batch_handler_ratio_test(rsqp_batch *b, const rsqp_nlp_trial *t, const rsqp_nlp_step_options *o, int on_device) {
@@ -206,62 +175,14 @@ extern "C" int rsqp_batch_handler_ratio_test(rsqp_batch *b, const rsqp_nlp_trial
     NlpRatio a;
     std::memset(&a, 0, sizeof(a));
     a.t = *t; a.o = *o;
-    const size_t nq = (size_t)b->nq, sN = (size_t)b->sumN, sC = (size_t)b->sumC;
-    // up only: what (ints) | rho | f_trial | c_trial; both ways: x_k | c_k | f_k | infea_k | delta | actual | pred | infea_trial |
-    // accept, hu_word, hm_word, exitflag (ints). The outputs go up as well: a member that sits out keeps their bytes
-    const size_t o_rho = int_words(nq), o_ft = o_rho + nq, o_ct = o_ft + nq, o_x = o_ct + sC, o_c = o_x + sN, o_f = o_c + sC, o_in = o_f + nq,
-                 o_d = o_in + nq, o_ar = o_d + nq, o_pr = o_ar + nq, o_it = o_pr + nq, o_w = o_it + nq, words = o_w + int_words(4 * nq);
-    if (!on_device) {
-        const int rc = ensure_staging(b, words);
-        if (rc != RSQP_OK) return rc;
-        double *const h = b->pin.p, *const d = b->scratch.p;
-        int *const hw = reinterpret_cast<int *>(h + o_w), *const dw = reinterpret_cast<int *>(d + o_w);
-        std::memcpy(h, t->what, sizeof(int) * nq);
-        std::memcpy(h + o_rho, t->rho, sizeof(double) * nq); std::memcpy(h + o_ft, t->f_trial, sizeof(double) * nq);
-        std::memcpy(h + o_x, t->x_k, sizeof(double) * sN);
-        if (sC > 0) { std::memcpy(h + o_ct, t->c_trial, sizeof(double) * sC); std::memcpy(h + o_c, t->c_k, sizeof(double) * sC); }
-        std::memcpy(h + o_f, t->f_k, sizeof(double) * nq); std::memcpy(h + o_in, t->infea_k, sizeof(double) * nq);
-        std::memcpy(h + o_d, t->delta, sizeof(double) * nq);
-        if (t->actual_reduction) std::memcpy(h + o_ar, t->actual_reduction, sizeof(double) * nq);
-        if (t->pred_reduction) std::memcpy(h + o_pr, t->pred_reduction, sizeof(double) * nq);
-        if (t->infea_trial) std::memcpy(h + o_it, t->infea_trial, sizeof(double) * nq);
-        if (t->accept) std::memcpy(hw, t->accept, sizeof(int) * nq);
-        if (t->hu_word) std::memcpy(hw + nq, t->hu_word, sizeof(int) * nq);
-        if (t->hm_word) std::memcpy(hw + 2 * nq, t->hm_word, sizeof(int) * nq);
-        if (t->exitflag) std::memcpy(hw + 3 * nq, t->exitflag, sizeof(int) * nq);
-        HIPCHK(hipMemcpyAsync(d, h, sizeof(double) * words, hipMemcpyHostToDevice, b->stream));
-        a.t.what = reinterpret_cast<const int *>(d); a.t.rho = d + o_rho; a.t.f_trial = d + o_ft; a.t.c_trial = d + o_ct;
-        a.t.x_k = d + o_x; a.t.c_k = d + o_c; a.t.f_k = d + o_f; a.t.infea_k = d + o_in; a.t.delta = d + o_d;
-        a.t.actual_reduction = t->actual_reduction ? d + o_ar : nullptr; a.t.pred_reduction = t->pred_reduction ? d + o_pr : nullptr;
-        a.t.infea_trial = t->infea_trial ? d + o_it : nullptr;
-        a.t.accept = t->accept ? dw : nullptr; a.t.hu_word = t->hu_word ? dw + nq : nullptr;
-        a.t.hm_word = t->hm_word ? dw + 2 * nq : nullptr; a.t.exitflag = t->exitflag ? dw + 3 * nq : nullptr;
-    }
+    Staging st(b, on_device);
+    if (st.active) stage_trial(st, a.t, stage_sizes(b));
+    int rc;
+    if ((rc = st.up()) != RSQP_OK) return rc;
     a.nq = b->nq; a.uniV = uni_shape(b); a.uniC = a.uniV > 0 ? b->uniC : 0; a.desc = b->d_desc.p;
     a.c_l = b->h_cl.p; a.c_u = b->h_cu.p; a.x = b->x.p; a.obj = b->obj.p;
-    const int G = lanes_per_member(b);
-    if (G == 8) hipLaunchKernelGGL(batch_nlp_ratio_kernel<8>, grid_of(b, G), dim3(256), 0, b->stream, a);
-    else hipLaunchKernelGGL(batch_nlp_ratio_kernel<64>, grid_of(b, G), dim3(256), 0, b->stream, a);
-    HIPCHK(hipGetLastError());
-    if (!on_device)
-        HIPCHK(hipMemcpyAsync(b->pin.p + o_x, b->scratch.p + o_x, sizeof(double) * (words - o_x), hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    if (!on_device) {
-        const double *const h = b->pin.p;
-        const int *const hw = reinterpret_cast<const int *>(h + o_w);
-        std::memcpy(t->x_k, h + o_x, sizeof(double) * sN);
-        if (sC > 0) std::memcpy(t->c_k, h + o_c, sizeof(double) * sC);
-        std::memcpy(t->f_k, h + o_f, sizeof(double) * nq); std::memcpy(t->infea_k, h + o_in, sizeof(double) * nq);
-        std::memcpy(t->delta, h + o_d, sizeof(double) * nq);
-        if (t->actual_reduction) std::memcpy(t->actual_reduction, h + o_ar, sizeof(double) * nq);
-        if (t->pred_reduction) std::memcpy(t->pred_reduction, h + o_pr, sizeof(double) * nq);
-        if (t->infea_trial) std::memcpy(t->infea_trial, h + o_it, sizeof(double) * nq);
-        if (t->accept) std::memcpy(t->accept, hw, sizeof(int) * nq);
-        if (t->hu_word) std::memcpy(t->hu_word, hw + nq, sizeof(int) * nq);
-        if (t->hm_word) std::memcpy(t->hm_word, hw + 2 * nq, sizeof(int) * nq);
-        if (t->exitflag) std::memcpy(t->exitflag, hw + 3 * nq, sizeof(int) * nq);
-    }
-    return RSQP_OK;
+    rc = launch_groups(b, [](auto g) { return batch_nlp_ratio_kernel<decltype(g)::value>; }, a);
+    return rc != RSQP_OK ? rc : st.down();
 }
 
 extern "C" int rsqp_batch_handler_check_optimality(rsqp_batch *b, const rsqp_nlp_point *pt, const rsqp_nlp_step_options *o,
@@ -273,40 +194,15 @@ extern "C" int rsqp_batch_handler_check_optimality(rsqp_batch *b, const rsqp_nlp
     NlpKkt a;
     std::memset(&a, 0, sizeof(a));
     a.pt = *pt; a.o = *o; a.out = out; a.verdict = verdict;
-    const size_t nq = (size_t)b->nq, sN = (size_t)b->sumN, sC = (size_t)b->sumC;
-    // up only: what (ints) | x_k | grad | c_k | infea; both ways (a member that sits out keeps the bytes): out (5 nq) | verdict (ints)
-    const size_t o_x = int_words(nq), o_g = o_x + sN, o_c = o_g + sN, o_in = o_c + sC, o_out = o_in + nq, o_v = o_out + 5 * nq,
-                 words = o_v + int_words(nq);
     static_assert(sizeof(rsqp_optimality_status) == 5 * sizeof(double), "the records are packed as five doubles");
-    if (!on_device) {
-        const int rc = ensure_staging(b, words);
-        if (rc != RSQP_OK) return rc;
-        double *const h = b->pin.p, *const d = b->scratch.p;
-        std::memcpy(h, pt->what, sizeof(int) * nq);
-        std::memcpy(h + o_x, pt->x_k, sizeof(double) * sN); std::memcpy(h + o_g, pt->grad, sizeof(double) * sN);
-        if (sC > 0) std::memcpy(h + o_c, pt->c_k, sizeof(double) * sC);
-        std::memcpy(h + o_in, pt->infea, sizeof(double) * nq);
-        if (out) std::memcpy(h + o_out, out, sizeof(double) * 5 * nq);
-        if (verdict) std::memcpy(h + o_v, verdict, sizeof(int) * nq);
-        HIPCHK(hipMemcpyAsync(d, h, sizeof(double) * words, hipMemcpyHostToDevice, b->stream));
-        a.pt.what = reinterpret_cast<const int *>(d); a.pt.x_k = d + o_x; a.pt.grad = d + o_g; a.pt.c_k = d + o_c; a.pt.infea = d + o_in;
-        a.out = out ? reinterpret_cast<rsqp_optimality_status *>(d + o_out) : nullptr;
-        a.verdict = verdict ? reinterpret_cast<int *>(d + o_v) : nullptr;
-    }
+    Staging st(b, on_device);
+    if (st.active) stage_point(st, a.pt, a.out, a.verdict, stage_sizes(b));
+    int rc;
+    if ((rc = st.up()) != RSQP_OK) return rc;
     a.nq = b->nq; a.uniV = uni_shape(b); a.uniC = a.uniV > 0 ? b->uniC : 0; a.desc = b->d_desc.p;
     a.uni_pat = b->uni_pat ? 1 : 0; a.uni_annz = b->uni_annz;
     a.x_l = b->h_xl.p; a.x_u = b->h_xu.p; a.c_l = b->h_cl.p; a.c_u = b->h_cu.p;
     a.y = b->y.p; a.Ajc = b->Ajc.p; a.Air = b->Air.p; a.Aval = b->Aval.p;
-    const int G = lanes_per_member(b);
-    if (G == 8) hipLaunchKernelGGL(batch_nlp_kkt_kernel<8>, grid_of(b, G), dim3(256), 0, b->stream, a);
-    else hipLaunchKernelGGL(batch_nlp_kkt_kernel<64>, grid_of(b, G), dim3(256), 0, b->stream, a);
-    HIPCHK(hipGetLastError());
-    if (!on_device && (out || verdict))
-        HIPCHK(hipMemcpyAsync(b->pin.p + o_out, b->scratch.p + o_out, sizeof(double) * (words - o_out), hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    if (!on_device) {
-        if (out) std::memcpy(out, b->pin.p + o_out, sizeof(double) * 5 * nq);
-        if (verdict) std::memcpy(verdict, b->pin.p + o_v, sizeof(int) * nq);
-    }
-    return RSQP_OK;
+    rc = launch_groups(b, [](auto g) { return batch_nlp_kkt_kernel<decltype(g)::value>; }, a);
+    return rc != RSQP_OK ? rc : st.down(out || verdict);      // (neither: nothing comes down)
 }

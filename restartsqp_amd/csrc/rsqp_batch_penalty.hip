@@ -8,7 +8,7 @@
 #pragma clang fp contract(off)
 
 namespace {
-// the call's per-member work (rsqp_batch::pen_i, pen_d): word w of member q at [w * nq + q]
+// the call's per-member work (rsqp_batch::pen)
 enum { PI_PHASE = 0, PI_TAKE_LP, PI_TAKE_QP, PI_HU_LP, PI_ROUNDS, PI_NWSR_QP, PI_NWSR_LP, PEN_INTS };
 enum { PD_RHO_TRIAL = 0, PD_MODEL, PD_MODEL0, PD_INFTY, PD_OBJ0, PEN_DOUBLES };
 // PI_PHASE: where the member stands between two launches
@@ -16,10 +16,9 @@ enum { PH_DONE = 0, PH_LP, PH_LOOP_A, PH_LOOP_B };
 // what lane 0 of a member's group tells the other lanes to do behind the decision
 enum { ACT_ROUND = 1, ACT_SAVE = 2, ACT_RESTORE = 4 };
 
-// the member's shape, the tree sum and the exit flag of an unsolved solve: rsqp_batch_decide.h
-
 struct PenaltyArgs {
-    int nq, uniV, uniC;
+    DecisionView w;                           // nq, and the work: PEN_INTS x nq ints, PEN_DOUBLES x nq doubles
+    int uniV, uniC;
     const QPDesc *desc;
     rsqp_penalty_state s;                     // device addresses
     rsqp_penalty_options o;
@@ -29,14 +28,7 @@ struct PenaltyArgs {
     // the LP batch
     const double *lp_x;
     const int *lp_status, *lp_used;
-    int *wi;                                  // PEN_INTS x nq
-    double *wd;                               // PEN_DOUBLES x nq
-    double *x0;                               // the x of the first solve, pooled like x
-    int *cnt;                                 // [0] members that go on, [1] blocks that have finished
-    int *live;                                // host-mapped: [0] of the finished launch
 };
-__device__ inline int &wi(const PenaltyArgs &a, int w, int q) { return a.wi[(size_t)w * a.nq + q]; }
-__device__ inline double &wd(const PenaltyArgs &a, int w, int q) { return a.wd[(size_t)w * a.nq + q]; }
 
 // the loop conditions of :914-917 and :941-949 before a round: the while test, then `if (rho_trial >= rho_max) break`
 __device__ inline bool loop_goes_on(const PenaltyArgs &a, int q, int phase, double model, double infty, double rho_trial) {
@@ -54,8 +46,8 @@ __device__ inline double start_round(const PenaltyArgs &a, int q, double rho_tri
     const double next = rho_trial * a.o.increase_parm;
     rho_trial = (next < a.o.rho_max) ? next : a.o.rho_max;        // min(rho_max, rho_trial * increase_parm)
     a.s.trial[q] = a.s.trial[q] + 1;
-    wd(a, PD_RHO_TRIAL, q) = rho_trial;
-    wi(a, PI_TAKE_QP, q) = 1;
+    a.w.wd(PD_RHO_TRIAL, q) = rho_trial;
+    a.w.wi(PI_TAKE_QP, q) = 1;
     return rho_trial;
 }
 // where a member leaves the call (:975-1004, and the outputs). broke: it left the loop on an unsolved QP, `flag` its status.
@@ -73,21 +65,21 @@ __device__ inline int leave(const PenaltyArgs &a, int q, double model, double rh
             a.s.rho[q] = rho_trial;
         } else {
             a.s.fail[q] = a.s.fail[q] + 1;
-            model = wd(a, PD_MODEL0, q);
+            model = a.w.wd(PD_MODEL0, q);
             hu = RSQP_HU_PENALTY;
-            a.obj[q] = wd(a, PD_OBJ0, q);
+            a.obj[q] = a.w.wd(PD_OBJ0, q);
             act = ACT_RESTORE;
         }
     }
     if (a.s.infea_model) a.s.infea_model[q] = model;
-    if (a.s.infea_infty && have_infty) a.s.infea_infty[q] = wd(a, PD_INFTY, q);
+    if (a.s.infea_infty && have_infty) a.s.infea_infty[q] = a.w.wd(PD_INFTY, q);
     if (a.s.hu_word) a.s.hu_word[q] = hu;
     if (a.s.exitflag) a.s.exitflag[q] = flag;
-    if (a.s.nwsr_qp) a.s.nwsr_qp[q] = wi(a, PI_NWSR_QP, q);
-    if (a.s.nwsr_lp) a.s.nwsr_lp[q] = wi(a, PI_NWSR_LP, q);
-    if (a.s.rounds) a.s.rounds[q] = wi(a, PI_ROUNDS, q);
-    wi(a, PI_PHASE, q) = PH_DONE;
-    wi(a, PI_TAKE_QP, q) = 0;
+    if (a.s.nwsr_qp) a.s.nwsr_qp[q] = a.w.wi(PI_NWSR_QP, q);
+    if (a.s.nwsr_lp) a.s.nwsr_lp[q] = a.w.wi(PI_NWSR_LP, q);
+    if (a.s.rounds) a.s.rounds[q] = a.w.wi(PI_ROUNDS, q);
+    a.w.wi(PI_PHASE, q) = PH_DONE;
+    a.w.wi(PI_TAKE_QP, q) = 0;
     return act;
 }
 
@@ -98,13 +90,13 @@ __device__ inline int leave(const PenaltyArgs &a, int q, double model, double rh
 template <int G, int STAGE>
 __global__ void __launch_bounds__(256) batch_penalty_kernel(PenaltyArgs a) {
     const int q = (int)(((long long)blockIdx.x * blockDim.x + threadIdx.x) / G), lane = (int)threadIdx.x % G;
-    const bool in = q < a.nq;
+    const bool in = q < a.w.nq;
     int phase = PH_DONE;
     bool act = false;
     if (in) {
         if (STAGE == 0) act = a.s.what[q] != 0 && a.status[q] == QPS_SOLVED;
         else {
-            phase = wi(a, PI_PHASE, q);
+            phase = a.w.wi(PI_PHASE, q);
             act = STAGE == 1 ? phase == PH_LP : (phase == PH_LOOP_A || phase == PH_LOOP_B);
         }
     }
@@ -128,9 +120,9 @@ __global__ void __launch_bounds__(256) batch_penalty_kernel(PenaltyArgs a) {
         if (STAGE == 0) {
             int lp = 0;
             if (act) {
-                wi(a, PI_ROUNDS, q) = 0; wi(a, PI_NWSR_QP, q) = 0; wi(a, PI_NWSR_LP, q) = 0;
+                a.w.wi(PI_ROUNDS, q) = 0; a.w.wi(PI_NWSR_QP, q) = 0; a.w.wi(PI_NWSR_LP, q) = 0;
                 if (sm > a.o.penalty_update_tol) {                                       // :893
-                    wd(a, PD_MODEL, q) = sm; wd(a, PD_MODEL0, q) = sm;
+                    a.w.wd(PD_MODEL, q) = sm; a.w.wd(PD_MODEL0, q) = sm;
                     lp = 1;
                 } else {
                     (void)leave(a, q, sm, a.s.rho[q], false, false, RSQP_EXIT_UNKNOWN);
@@ -138,22 +130,22 @@ __global__ void __launch_bounds__(256) batch_penalty_kernel(PenaltyArgs a) {
             } else if (a.s.what[q] != 0 && a.s.exitflag) {
                 a.s.exitflag[q] = dev_exitflag(a.status[q]);                             // the QP of this iteration is unsolved
             }
-            wi(a, PI_PHASE, q) = lp ? PH_LP : PH_DONE;
-            wi(a, PI_TAKE_LP, q) = lp; wi(a, PI_HU_LP, q) = lp ? RSQP_HU_SET : 0;
-            wi(a, PI_TAKE_QP, q) = 0;
+            a.w.wi(PI_PHASE, q) = lp ? PH_LP : PH_DONE;
+            a.w.wi(PI_TAKE_LP, q) = lp; a.w.wi(PI_HU_LP, q) = lp ? RSQP_HU_SET : 0;
+            a.w.wi(PI_TAKE_QP, q) = 0;
             goes_on = lp;
         } else if (act && STAGE == 1) {
-            wi(a, PI_NWSR_LP, q) = a.lp_used[q];
+            a.w.wi(PI_NWSR_LP, q) = a.lp_used[q];
             if (!solved) {                                                                // :901-904
-                (void)leave(a, q, wd(a, PD_MODEL0, q), a.s.rho[q], false, false, dev_exitflag(a.lp_status[q]));
+                (void)leave(a, q, a.w.wd(PD_MODEL0, q), a.s.rho[q], false, false, dev_exitflag(a.lp_status[q]));
             } else {
-                wd(a, PD_INFTY, q) = sm;
+                a.w.wd(PD_INFTY, q) = sm;
                 phase = (sm <= a.o.penalty_update_tol) ? PH_LOOP_A : PH_LOOP_B;          // :909
                 rho_trial = a.s.rho[q];
-                const double model = wd(a, PD_MODEL, q);
+                const double model = a.w.wd(PD_MODEL, q);
                 if (loop_goes_on(a, q, phase, model, sm, rho_trial)) {
-                    wi(a, PI_PHASE, q) = phase;
-                    wd(a, PD_OBJ0, q) = a.obj[q];
+                    a.w.wi(PI_PHASE, q) = phase;
+                    a.w.wd(PD_OBJ0, q) = a.obj[q];
                     rho_trial = start_round(a, q, rho_trial);
                     todo = ACT_SAVE | ACT_ROUND; goes_on = 1;
                 } else {
@@ -161,14 +153,14 @@ __global__ void __launch_bounds__(256) batch_penalty_kernel(PenaltyArgs a) {
                 }
             }
         } else if (act) {
-            wi(a, PI_ROUNDS, q) = wi(a, PI_ROUNDS, q) + 1;
-            wi(a, PI_NWSR_QP, q) = wi(a, PI_NWSR_QP, q) + a.used[q];
-            rho_trial = wd(a, PD_RHO_TRIAL, q);
+            a.w.wi(PI_ROUNDS, q) = a.w.wi(PI_ROUNDS, q) + 1;
+            a.w.wi(PI_NWSR_QP, q) = a.w.wi(PI_NWSR_QP, q) + a.used[q];
+            rho_trial = a.w.wd(PD_RHO_TRIAL, q);
             if (!solved) {                                                                // :929-932, :963-966
-                todo = leave(a, q, wd(a, PD_MODEL, q), rho_trial, true, true, dev_exitflag(a.status[q]));
+                todo = leave(a, q, a.w.wd(PD_MODEL, q), rho_trial, true, true, dev_exitflag(a.status[q]));
             } else {
-                wd(a, PD_MODEL, q) = sm;
-                if (loop_goes_on(a, q, phase, sm, wd(a, PD_INFTY, q), rho_trial)) {
+                a.w.wd(PD_MODEL, q) = sm;
+                if (loop_goes_on(a, q, phase, sm, a.w.wd(PD_INFTY, q), rho_trial)) {
                     rho_trial = start_round(a, q, rho_trial);
                     todo = ACT_ROUND; goes_on = 1;
                 } else {
@@ -180,13 +172,13 @@ __global__ void __launch_bounds__(256) batch_penalty_kernel(PenaltyArgs a) {
     todo = __shfl(todo, 0, G);
     rho_trial = __shfl(rho_trial, 0, G);
     if (todo & ACT_SAVE)
-        for (int i = lane; i < sh.nV; i += G) a.x0[sh.offV + i] = a.x[sh.offV + i];
+        for (int i = lane; i < sh.nV; i += G) a.w.x0[sh.offV + i] = a.x[sh.offV + i];
     if (todo & ACT_ROUND)
         for (int i = n + lane; i < sh.nV; i += G) a.g[sh.offV + i] = rho_trial;          // update_penalty (QPhandler.cpp:430-441)
     if (todo & ACT_RESTORE)
-        for (int i = lane; i < sh.nV; i += G) a.x[sh.offV + i] = a.x0[sh.offV + i];
+        for (int i = lane; i < sh.nV; i += G) a.x[sh.offV + i] = a.w.x0[sh.offV + i];
     // how many go on: added per member, reported by the block that finishes last
-    report_live(goes_on, a.cnt, a.live);
+    report_live(goes_on, a.w.cnt, a.w.live);
 }
 
 // set_A of setupLP (:703) for the members penalty_begin named: the entries of columns [0, n) of the member's A, slot by slot from the
@@ -212,14 +204,8 @@ batch_penalty_jacobian_kernel(int nq, int uni_pat, int uni_annz, const QPDesc *_
 }
 
 template <int STAGE>
-int launch_decision(rsqp_batch *b, const PenaltyArgs &a, int *live) {
-    const int G = lanes_per_member(b);
-    if (G == 8) hipLaunchKernelGGL((batch_penalty_kernel<8, STAGE>), grid_of(b, G), dim3(256), 0, b->stream, a);
-    else hipLaunchKernelGGL((batch_penalty_kernel<64, STAGE>), grid_of(b, G), dim3(256), 0, b->stream, a);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(b->stream));
-    *live = *b->pen_live.p;
-    return RSQP_OK;
+int decide(rsqp_batch *b, const PenaltyArgs &a, int *live) {
+    return launch_decision(b, b->pen, live, [](auto g) { return batch_penalty_kernel<decltype(g)::value, STAGE>; }, a);
 }
 
 // while the call runs: the LP batch launches on the QP batch's stream, and an inner optimize call of either batch reads the mask a
@@ -274,12 +260,9 @@ extern "C" int rsqp_batch_handler_update_penalty(rsqp_batch *b, const rsqp_penal
     if (!(o->increase_parm > 1.0)) return fail(RSQP_ERR_ARG, "rsqp_batch_handler_update_penalty: increase_parm must exceed 1");
     if (!b->keep_state || !lp->keep_state) return fail(RSQP_ERR_ARG, "rsqp_batch_handler_update_penalty: both batches must keep their state");
     HIPCHK(hipSetDevice(b->device));
-    const size_t nq = (size_t)b->nq, sN = (size_t)b->sumN, sC = (size_t)b->sumC;
+    const size_t nq = (size_t)b->nq;
     int rc;
-    if (!b->pen_i.p) {
-        HIPCHK(b->pen_i.alloc((size_t)PEN_INTS * nq)); HIPCHK(b->pen_d.alloc((size_t)PEN_DOUBLES * nq));
-        HIPCHK(b->pen_x.alloc((size_t)b->sumV)); HIPCHK(b->pen_cnt.alloc(2)); HIPCHK(b->pen_live.alloc(1, true));
-    }
+    if ((rc = b->pen.ensure(PEN_INTS * nq, PEN_DOUBLES * nq, (size_t)b->sumV)) != RSQP_OK) return rc;
     if ((rc = ensure_opt(lp)) != RSQP_OK || (rc = ensure_handler_matrices(lp)) != RSQP_OK) return rc;
     if (!b->used.p) HIPCHK(b->used.alloc(nq, true));
     if (!lp->used.p) HIPCHK(lp->used.alloc(nq, true));
@@ -292,76 +275,35 @@ extern "C" int rsqp_batch_handler_update_penalty(rsqp_batch *b, const rsqp_penal
     PenaltyArgs a;
     std::memset(&a, 0, sizeof(a));
     a.s = *s; a.o = *o;
-    // up only: what (ints) | infea_k | delta | x_k | c_k; both ways (a member that sits out keeps the bytes): rho | eps1 | infea_model |
-    // infea_infty | trial, succ, fail, hu_word, exitflag, nwsr_qp, nwsr_lp, rounds (ints)
-    const size_t o_in = int_words(nq), o_d = o_in + nq, o_x = o_d + nq, o_c = o_x + sN, o_rho = o_c + sC, o_e = o_rho + nq, o_m = o_e + nq,
-                 o_iy = o_m + nq, o_w = o_iy + nq, words = o_w + int_words(8 * nq);
-    int *const outs_h[8] = {s->trial, s->succ, s->fail, s->hu_word, s->exitflag, s->nwsr_qp, s->nwsr_lp, s->rounds};
-    if (!on_device) {
-        if ((rc = ensure_staging(b, words)) != RSQP_OK) return rc;
-        double *const h = b->pin.p, *const d = b->scratch.p;
-        int *const hw = reinterpret_cast<int *>(h + o_w), *const dw = reinterpret_cast<int *>(d + o_w);
-        std::memcpy(h, s->what, sizeof(int) * nq);
-        std::memcpy(h + o_in, s->infea_k, sizeof(double) * nq); std::memcpy(h + o_d, s->delta, sizeof(double) * nq);
-        std::memcpy(h + o_x, s->x_k, sizeof(double) * sN);
-        if (sC > 0) std::memcpy(h + o_c, s->c_k, sizeof(double) * sC);
-        std::memcpy(h + o_rho, s->rho, sizeof(double) * nq); std::memcpy(h + o_e, s->eps1, sizeof(double) * nq);
-        if (s->infea_model) std::memcpy(h + o_m, s->infea_model, sizeof(double) * nq);
-        if (s->infea_infty) std::memcpy(h + o_iy, s->infea_infty, sizeof(double) * nq);
-        for (int k = 0; k < 8; k++)
-            if (outs_h[k]) std::memcpy(hw + k * nq, outs_h[k], sizeof(int) * nq);
-        HIPCHK(hipMemcpyAsync(d, h, sizeof(double) * words, hipMemcpyHostToDevice, b->stream));
-        a.s.what = reinterpret_cast<const int *>(d); a.s.infea_k = d + o_in; a.s.delta = d + o_d; a.s.x_k = d + o_x; a.s.c_k = d + o_c;
-        a.s.rho = d + o_rho; a.s.eps1 = d + o_e;
-        a.s.infea_model = s->infea_model ? d + o_m : nullptr; a.s.infea_infty = s->infea_infty ? d + o_iy : nullptr;
-        a.s.trial = dw; a.s.succ = dw + nq; a.s.fail = dw + 2 * nq;
-        a.s.hu_word = s->hu_word ? dw + 3 * nq : nullptr; a.s.exitflag = s->exitflag ? dw + 4 * nq : nullptr;
-        a.s.nwsr_qp = s->nwsr_qp ? dw + 5 * nq : nullptr; a.s.nwsr_lp = s->nwsr_lp ? dw + 6 * nq : nullptr;
-        a.s.rounds = s->rounds ? dw + 7 * nq : nullptr;
-    }
-    a.nq = b->nq; a.uniV = (b->uniV > 0 && b->uniC >= 0) ? b->uniV : 0; a.uniC = a.uniV > 0 ? b->uniC : 0; a.desc = b->d_desc.p;
+    Staging st(b, on_device);
+    if (st.active) stage_penalty(st, a.s, stage_sizes(b));
+    if ((rc = st.up()) != RSQP_OK) return rc;
+    a.w = b->pen.view(b->nq); a.uniV = uni_shape(b); a.uniC = a.uniV > 0 ? b->uniC : 0; a.desc = b->d_desc.p;
     a.x = b->x.p; a.obj = b->obj.p; a.g = b->g.p; a.status = b->status.p; a.used = b->used.dev;
     a.lp_x = lp->x.p; a.lp_status = lp->status.p; a.lp_used = lp->used.dev;
-    a.wi = b->pen_i.p; a.wd = b->pen_d.p; a.x0 = b->pen_x.p; a.cnt = b->pen_cnt.p; a.live = b->pen_live.dev;
-    int *const take_lp = b->pen_i.p + (size_t)PI_TAKE_LP * nq, *const take_qp = b->pen_i.p + (size_t)PI_TAKE_QP * nq;
+    int *const take_lp = b->pen.i.p + (size_t)PI_TAKE_LP * nq, *const take_qp = b->pen.i.p + (size_t)PI_TAKE_QP * nq;
 
     int live = 0;
-    if ((rc = launch_decision<0>(b, a, &live)) != RSQP_OK) return rc;                   // penalty_begin
+    if ((rc = decide<0>(b, a, &live)) != RSQP_OK) return rc;                   // penalty_begin
     if (live > 0) {
         // setupLP (:700-704): set_bounds + set_g(rho) by the SET word penalty_begin wrote, then set_A from the QP batch's pool
         rsqp_handler_iterate it;
         std::memset(&it, 0, sizeof(it));
-        it.what = b->pen_i.p + (size_t)PI_HU_LP * nq; it.delta = a.s.delta; it.rho = a.s.rho; it.x_k = a.s.x_k; it.c_k = a.s.c_k;
+        it.what = b->pen.i.p + (size_t)PI_HU_LP * nq; it.delta = a.s.delta; it.rho = a.s.rho; it.x_k = a.s.x_k; it.c_k = a.s.c_k;
         if ((rc = rsqp_batch_handler_update(lp, &it, 1)) != RSQP_OK) return rc;
-        const int G = lanes_per_member(b);
         int *const mark = lp->opt.p + (size_t)OPT_UPD * nq;
         const int *const first = lp->opt.p + (size_t)OPT_FIRST * nq;
-        if (G == 8)
-            hipLaunchKernelGGL(batch_penalty_jacobian_kernel<8>, grid_of(b, G), dim3(256), 0, b->stream, b->nq, b->uni_pat ? 1 : 0, b->uni_annz,
-                               b->d_desc.p, take_lp, b->Ajc.p, b->Aval.p, lp->Aval.p, lp->Arv.p, lp->hm_inv.p, mark, first);
-        else
-            hipLaunchKernelGGL(batch_penalty_jacobian_kernel<64>, grid_of(b, G), dim3(256), 0, b->stream, b->nq, b->uni_pat ? 1 : 0, b->uni_annz,
-                               b->d_desc.p, take_lp, b->Ajc.p, b->Aval.p, lp->Aval.p, lp->Arv.p, lp->hm_inv.p, mark, first);
-        HIPCHK(hipGetLastError());
+        rc = launch_groups(b, [](auto g) { return batch_penalty_jacobian_kernel<decltype(g)::value>; }, b->nq, b->uni_pat ? 1 : 0, b->uni_annz,
+                           b->d_desc.p, take_lp, b->Ajc.p, b->Aval.p, lp->Aval.p, lp->Arv.p, lp->hm_inv.p, mark, first);
+        if (rc != RSQP_OK) return rc;
         Loan::lend(lp, take_lp, live);
         if ((rc = rsqp_batch_optimize_lp(lp, nullptr)) != RSQP_OK) return rc;
-        if ((rc = launch_decision<1>(b, a, &live)) != RSQP_OK) return rc;               // penalty_after_lp
+        if ((rc = decide<1>(b, a, &live)) != RSQP_OK) return rc;               // penalty_after_lp
         while (live > 0) {
             Loan::lend(b, take_qp, live);
             if ((rc = rsqp_batch_optimize_qp(b, nullptr)) != RSQP_OK) return rc;
-            if ((rc = launch_decision<2>(b, a, &live)) != RSQP_OK) return rc;           // penalty_round (+ penalty_finish)
+            if ((rc = decide<2>(b, a, &live)) != RSQP_OK) return rc;           // penalty_round (+ penalty_finish)
         }
     }
-    if (!on_device) {
-        HIPCHK(hipMemcpyAsync(b->pin.p + o_rho, b->scratch.p + o_rho, sizeof(double) * (words - o_rho), hipMemcpyDeviceToHost, b->stream));
-        HIPCHK(hipStreamSynchronize(b->stream));
-        const double *const h = b->pin.p;
-        const int *const hw = reinterpret_cast<const int *>(h + o_w);
-        std::memcpy(s->rho, h + o_rho, sizeof(double) * nq); std::memcpy(s->eps1, h + o_e, sizeof(double) * nq);
-        if (s->infea_model) std::memcpy(s->infea_model, h + o_m, sizeof(double) * nq);
-        if (s->infea_infty) std::memcpy(s->infea_infty, h + o_iy, sizeof(double) * nq);
-        for (int k = 0; k < 8; k++)
-            if (outs_h[k]) std::memcpy(outs_h[k], hw + k * nq, sizeof(int) * nq);
-    }
-    return RSQP_OK;
+    return on_device ? RSQP_OK : st.down();      // (every decision has waited for the stream)
 }

@@ -7,7 +7,7 @@
 #pragma clang fp contract(off)
 
 namespace {
-// the calls' per-member work (rsqp_batch::soc_i, soc_d): word w of member q at [w * nq + q]
+// the calls' per-member work (rsqp_batch::soc)
 // SI_TAKE: the member's word in the mask of the inner solve; SI_PEND: soc_begin set it going and soc_end has not seen it yet
 enum { SI_TAKE = 0, SI_PEND, SOC_INTS };
 // the objective of the first solve, the composite qp_obj_ of :1198, and the first test's outputs (written once the correction solved)
@@ -16,7 +16,8 @@ enum { SD_OBJ0 = 0, SD_QPOBJ, SD_ACTUAL, SD_PRED, SD_INFEA, SOC_DOUBLES };
 enum { ACT_ACCEPT = 1, ACT_CORRECT = 2, ACT_RESTORE = 4 };
 
 struct SocArgs {
-    int nq, uniV, uniC;
+    DecisionView w;                           // nq, and the work: SOC_INTS x nq ints, SOC_DOUBLES x nq doubles
+    int uniV, uniC;
     const QPDesc *desc;
     rsqp_soc_trial t;                         // device addresses
     rsqp_nlp_step_options o;
@@ -28,14 +29,7 @@ struct SocArgs {
     const int *status, *used;
     const int *Hjc, *Hir;
     const double *Hval;
-    int *wi;                                  // SOC_INTS x nq
-    double *wd;                               // SOC_DOUBLES x nq
-    double *x0;                               // the x of the first solve, pooled like x
-    int *cnt;                                 // [0] members that go on, [1] blocks that have finished
-    int *live;                                // host-mapped: [0] of the finished launch
 };
-__device__ inline int &wi(const SocArgs &a, int w, int q) { return a.wi[(size_t)w * a.nq + q]; }
-__device__ inline double &wd(const SocArgs &a, int w, int q) { return a.wd[(size_t)w * a.nq + q]; }
 
 // (H_k p)_i over the leading n x n block: from 0, + H_ij * p_j over the entries of row i in increasing j. The canonical pattern holds
 // a row at most once per column, rows ascending: the entry of row i in column j by bisection, no atomics
@@ -60,7 +54,7 @@ __device__ inline double hess_row_times(const int *__restrict__ jc, const int *_
 template <int G>
 __global__ void __launch_bounds__(256) batch_soc_test_kernel(SocArgs a) {
     const int q = (int)(((long long)blockIdx.x * blockDim.x + threadIdx.x) / G), lane = (int)threadIdx.x % G;
-    const bool in = q < a.nq, act = in && a.t.what[q] != 0;
+    const bool in = q < a.w.nq, act = in && a.t.what[q] != 0;
     MemberShape sh{0, 0, 0, 0};
     int n = 0, offN = 0;
     double s = 0.0, mx = 0.0;
@@ -81,37 +75,22 @@ __global__ void __launch_bounds__(256) batch_soc_test_kernel(SocArgs a) {
             const RatioTest r = ratio_test_of(o, a.t.rho[q], a.t.f_k[q], a.t.infea_k[q], f_t, s, a.obj[q]);
             delta = a.t.delta[q];
             if (r.acc || (a.t.what[q] & RSQP_SOC_CORRECT) == 0) {
-                // what rsqp_batch_handler_ratio_test writes, update_radius included
-                const bool radius = radius_update(o, r.actual, r.pred, mx, delta);
-                if (radius) a.t.delta[q] = delta;
-                if (r.acc) { a.t.f_k[q] = f_t; a.t.infea_k[q] = s; todo = ACT_ACCEPT; }
-                if (a.t.actual_reduction) a.t.actual_reduction[q] = r.actual;
-                if (a.t.pred_reduction) a.t.pred_reduction[q] = r.pred;
-                if (a.t.infea_trial) a.t.infea_trial[q] = s;
-                if (a.t.accept) a.t.accept[q] = r.acc;
-                if (a.t.hu_word) a.t.hu_word[q] = r.acc ? accepted_hu_word(o) : (radius ? RSQP_HU_DELTA : 0);
-                if (a.t.hm_word) a.t.hm_word[q] = r.acc ? (RSQP_HM_JAC | RSQP_HM_HESS) : 0;
-                if (a.t.exitflag) a.t.exitflag[q] = radius_exitflag(o, delta);
-                a.t.soc[q] = 0;
-                if (a.t.nwsr_soc) a.t.nwsr_soc[q] = 0;
-                if (a.t.qp_obj) a.t.qp_obj[q] = a.obj[q];
+                write_verdict<TEST_SOC_FIRST>(a.t, o, q, r, f_t, s, delta, mx, a.obj[q]);
+                if (r.acc) todo = ACT_ACCEPT;
             } else {
-                wd(a, SD_OBJ0, q) = a.obj[q];
-                wd(a, SD_ACTUAL, q) = r.actual; wd(a, SD_PRED, q) = r.pred; wd(a, SD_INFEA, q) = s;
+                a.w.wd(SD_OBJ0, q) = a.obj[q];
+                a.w.wd(SD_ACTUAL, q) = r.actual; a.w.wd(SD_PRED, q) = r.pred; a.w.wd(SD_INFEA, q) = s;
                 todo = ACT_CORRECT;
             }
         }
-        wi(a, SI_TAKE, q) = (todo & ACT_CORRECT) ? 1 : 0;
-        wi(a, SI_PEND, q) = 0;
+        a.w.wi(SI_TAKE, q) = (todo & ACT_CORRECT) ? 1 : 0;
+        a.w.wi(SI_PEND, q) = 0;
     }
     todo = __shfl(todo, 0, G);
     delta = __shfl(delta, 0, G);
-    if (todo & ACT_ACCEPT) {      // (only lanes of an active member hold it)
-        for (int i = lane; i < n; i += G) a.t.x_k[offN + i] = a.t.x_k[offN + i] + a.x[sh.offV + i];
-        for (int i = lane; i < sh.nC; i += G) a.t.c_k[sh.offC + i] = a.t.c_trial[sh.offC + i];
-    }
+    if (todo & ACT_ACCEPT) accept_step<G>(a.t, a.x, sh, lane);      // (only lanes of an active member hold it)
     if (todo & ACT_CORRECT) {
-        for (int i = lane; i < sh.nV; i += G) a.x0[sh.offV + i] = a.x[sh.offV + i];
+        for (int i = lane; i < sh.nV; i += G) a.w.x0[sh.offV + i] = a.x[sh.offV + i];
         const int *const jc = a.Hjc + a.desc[q].offHjc, *const ir = a.Hir + a.desc[q].offHnz;
         const double *const val = a.Hval + a.desc[q].offHnz, *const p = a.x + sh.offV;
         for (int i = lane; i < n; i += G) {
@@ -126,7 +105,7 @@ __global__ void __launch_bounds__(256) batch_soc_test_kernel(SocArgs a) {
             if (a.o.refresh_ubA) a.ubA[sh.offC + i] = hu_ubA(a.c_u[sh.offC + i], a.t.c_trial[sh.offC + i]);
         }
     }
-    report_live((in && lane == 0 && (todo & ACT_CORRECT)) ? 1 : 0, a.cnt, a.live);
+    report_live((in && lane == 0 && (todo & ACT_CORRECT)) ? 1 : 0, a.w.cnt, a.w.live);
 }
 
 // soc_step, behind the correction solve: an unsolved member leaves with its status; the others get p + s in the x pool, their second
@@ -134,7 +113,7 @@ __global__ void __launch_bounds__(256) batch_soc_test_kernel(SocArgs a) {
 template <int G>
 __global__ void __launch_bounds__(256) batch_soc_step_kernel(SocArgs a) {
     const int q = (int)(((long long)blockIdx.x * blockDim.x + threadIdx.x) / G), lane = (int)threadIdx.x % G;
-    const bool act = q < a.nq && wi(a, SI_TAKE, q) != 0;
+    const bool act = q < a.w.nq && a.w.wi(SI_TAKE, q) != 0;
     const bool solved = act && a.status[q] == QPS_SOLVED;
     MemberShape sh{0, 0, 0, 0};
     int n = 0, offN = 0;
@@ -143,7 +122,7 @@ __global__ void __launch_bounds__(256) batch_soc_step_kernel(SocArgs a) {
         sh = shape_of(a.desc, a.uniV, a.uniC, q);
         n = sh.nV - 2 * sh.nC; offN = sh.offV - 2 * sh.offC;
         if (!a.t.infea_model)
-            for (int i = n + lane; i < sh.nV; i += G) sm += fabs(a.x0[sh.offV + i]);     // get_infea_measure_model of the first solve
+            for (int i = n + lane; i < sh.nV; i += G) sm += fabs(a.w.x0[sh.offV + i]);     // get_infea_measure_model of the first solve
     }
     sm = group_sum<G>(sm);
     if (act && lane == 0) {
@@ -153,20 +132,20 @@ __global__ void __launch_bounds__(256) batch_soc_step_kernel(SocArgs a) {
             a.t.soc[q] = 0;
         } else {
             const double model = a.t.infea_model ? a.t.infea_model[q] : sm;
-            const double qp_obj = a.obj[q] + (wd(a, SD_OBJ0, q) - a.t.rho[q] * model);    // :1198
-            wd(a, SD_QPOBJ, q) = qp_obj;
+            const double qp_obj = a.obj[q] + (a.w.wd(SD_OBJ0, q) - a.t.rho[q] * model);    // :1198
+            a.w.wd(SD_QPOBJ, q) = qp_obj;
             if (a.t.qp_obj) a.t.qp_obj[q] = qp_obj;
-            if (a.t.actual_reduction) a.t.actual_reduction[q] = wd(a, SD_ACTUAL, q);
-            if (a.t.pred_reduction) a.t.pred_reduction[q] = wd(a, SD_PRED, q);
-            if (a.t.infea_trial) a.t.infea_trial[q] = wd(a, SD_INFEA, q);
+            if (a.t.actual_reduction) a.t.actual_reduction[q] = a.w.wd(SD_ACTUAL, q);
+            if (a.t.pred_reduction) a.t.pred_reduction[q] = a.w.wd(SD_PRED, q);
+            if (a.t.infea_trial) a.t.infea_trial[q] = a.w.wd(SD_INFEA, q);
             if (a.t.accept) a.t.accept[q] = 0;
             a.t.soc[q] = 1;
-            wi(a, SI_PEND, q) = 1;
+            a.w.wi(SI_PEND, q) = 1;
         }
     }
     if (solved)
         for (int i = lane; i < n; i += G) {
-            const double v = a.x0[sh.offV + i] + a.x[sh.offV + i];                        // p_k_->add_vector(s_k) (:1199)
+            const double v = a.w.x0[sh.offV + i] + a.x[sh.offV + i];                        // p_k_->add_vector(s_k) (:1199)
             a.x[sh.offV + i] = v;
             a.t.x_trial[offN + i] = a.t.x_k[offN + i] + v;
         }
@@ -176,17 +155,16 @@ __global__ void __launch_bounds__(256) batch_soc_step_kernel(SocArgs a) {
 template <int G>
 __global__ void __launch_bounds__(256) batch_soc_end_kernel(SocArgs a) {
     const int q = (int)(((long long)blockIdx.x * blockDim.x + threadIdx.x) / G), lane = (int)threadIdx.x % G;
-    const bool act = q < a.nq && a.t.soc[q] != 0 && wi(a, SI_PEND, q) != 0;
+    const bool act = q < a.w.nq && a.t.soc[q] != 0 && a.w.wi(SI_PEND, q) != 0;
     MemberShape sh{0, 0, 0, 0};
-    int n = 0, offN = 0;
     double s = 0.0, mx = 0.0, mx0 = 0.0;
     if (act) {
         sh = shape_of(a.desc, a.uniV, a.uniC, q);
-        n = sh.nV - 2 * sh.nC; offN = sh.offV - 2 * sh.offC;
+        const int n = sh.nV - 2 * sh.nC;
         s = infea_share<G>(a.t.c_trial + sh.offC, a.c_l + sh.offC, a.c_u + sh.offC, sh.nC, lane);
         for (int i = lane; i < n; i += G) {
             mx = fmax(mx, fabs(a.x[sh.offV + i]));       // getInfNorm of p + s ...
-            mx0 = fmax(mx0, fabs(a.x0[sh.offV + i]));    // ... and of the p a rejected member gets back
+            mx0 = fmax(mx0, fabs(a.w.x0[sh.offV + i]));    // ... and of the p a rejected member gets back
         }
     }
     s = group_sum<G>(s);
@@ -197,97 +175,28 @@ __global__ void __launch_bounds__(256) batch_soc_end_kernel(SocArgs a) {
         const rsqp_nlp_step_options &o = a.o;
         const double f_t = a.t.f_trial[q];
         // get_obj_QP() is the correction QP's own objective (:729); composite_pred: the qp_obj_ of :1198
-        const double qp_obj = a.so.composite_pred ? wd(a, SD_QPOBJ, q) : a.obj[q];
+        const double qp_obj = a.so.composite_pred ? a.w.wd(SD_QPOBJ, q) : a.obj[q];
         const RatioTest r = ratio_test_of(o, a.t.rho[q], a.t.f_k[q], a.t.infea_k[q], f_t, s, qp_obj);
         if (r.acc) {
-            a.t.f_k[q] = f_t; a.t.infea_k[q] = s;
             todo = ACT_ACCEPT;
         } else {
-            a.obj[q] = wd(a, SD_OBJ0, q);
-            if (a.t.qp_obj) a.t.qp_obj[q] = wd(a, SD_OBJ0, q);
+            a.obj[q] = a.w.wd(SD_OBJ0, q);
+            if (a.t.qp_obj) a.t.qp_obj[q] = a.w.wd(SD_OBJ0, q);
             todo = ACT_RESTORE;
         }
-        double delta = a.t.delta[q];
-        if (radius_update(o, r.actual, r.pred, r.acc ? mx : mx0, delta)) a.t.delta[q] = delta;
-        if (a.t.actual_reduction) a.t.actual_reduction[q] = r.actual;
-        if (a.t.pred_reduction) a.t.pred_reduction[q] = r.pred;
-        if (a.t.infea_trial) a.t.infea_trial[q] = s;
-        if (a.t.accept) a.t.accept[q] = r.acc;
-        if (a.t.hu_word) a.t.hu_word[q] = accepted_hu_word(o);      // rejected: update_grad + update_bounds at x_k (:1206-1207)
-        if (a.t.hm_word) a.t.hm_word[q] = r.acc ? (RSQP_HM_JAC | RSQP_HM_HESS) : 0;
-        if (a.t.exitflag) a.t.exitflag[q] = radius_exitflag(o, delta);
-        wi(a, SI_PEND, q) = 0;
+        write_verdict<TEST_SOC_SECOND>(a.t, o, q, r, f_t, s, a.t.delta[q], r.acc ? mx : mx0);
+        a.w.wi(SI_PEND, q) = 0;
     }
     todo = __shfl(todo, 0, G);
-    if (todo & ACT_ACCEPT) {
-        for (int i = lane; i < n; i += G) a.t.x_k[offN + i] = a.t.x_k[offN + i] + a.x[sh.offV + i];
-        for (int i = lane; i < sh.nC; i += G) a.t.c_k[sh.offC + i] = a.t.c_trial[sh.offC + i];
-    }
+    if (todo & ACT_ACCEPT) accept_step<G>(a.t, a.x, sh, lane);
     if (todo & ACT_RESTORE)
-        for (int i = lane; i < sh.nV; i += G) a.x[sh.offV + i] = a.x0[sh.offV + i];
+        for (int i = lane; i < sh.nV; i += G) a.x[sh.offV + i] = a.w.x0[sh.offV + i];
 }
 
 __global__ void __launch_bounds__(256)
 batch_set_objective_kernel(int nq, const int *__restrict__ named, const double *__restrict__ src, double *__restrict__ obj) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q < nq && named[q] != 0) obj[q] = src[q];
-}
-
-// the staging block of a host-pointer call, the same for both calls. Up only: what (ints) | rho | f_trial | c_trial | grad |
-// infea_model; both ways (a member that sits out keeps the bytes): x_k | c_k | f_k | infea_k | delta | actual | pred | infea_trial |
-// x_trial | qp_obj | accept, hu_word, hm_word, exitflag, soc, nwsr_soc (ints)
-struct Staging {
-    size_t nq, sN, sC, o_rho, o_ft, o_ct, o_g, o_m, o_x, o_c, o_f, o_in, o_d, o_ar, o_pr, o_it, o_xt, o_q, o_w, words;
-    explicit Staging(const rsqp_batch *b) : nq((size_t)b->nq), sN((size_t)b->sumN), sC((size_t)b->sumC) {
-        o_rho = int_words(nq); o_ft = o_rho + nq; o_ct = o_ft + nq; o_g = o_ct + sC; o_m = o_g + sN; o_x = o_m + nq; o_c = o_x + sN;
-        o_f = o_c + sC; o_in = o_f + nq; o_d = o_in + nq; o_ar = o_d + nq; o_pr = o_ar + nq; o_it = o_pr + nq; o_xt = o_it + nq;
-        o_q = o_xt + sN; o_w = o_q + nq; words = o_w + int_words(6 * nq);
-    }
-};
-inline void put(double *h, size_t off, const void *src, size_t bytes) { if (src && bytes) std::memcpy(h + off, src, bytes); }
-inline void get(void *dst, const double *h, size_t off, size_t bytes) { if (dst && bytes) std::memcpy(dst, h + off, bytes); }
-
-// the caller's arrays into the pinned block and up in one copy; a.t gets the device addresses
-int stage_up(rsqp_batch *b, const Staging &L, const rsqp_soc_trial *t, SocArgs &a) {
-    const int rc = ensure_staging(b, L.words);
-    if (rc != RSQP_OK) return rc;
-    const size_t D = sizeof(double), I = sizeof(int), nq = L.nq;
-    double *const h = b->pin.p, *const d = b->scratch.p;
-    int *const hw = reinterpret_cast<int *>(h + L.o_w), *const dw = reinterpret_cast<int *>(d + L.o_w);
-    put(h, 0, t->what, I * nq); put(h, L.o_rho, t->rho, D * nq); put(h, L.o_ft, t->f_trial, D * nq); put(h, L.o_ct, t->c_trial, D * L.sC);
-    put(h, L.o_g, t->grad, D * L.sN); put(h, L.o_m, t->infea_model, D * nq);
-    put(h, L.o_x, t->x_k, D * L.sN); put(h, L.o_c, t->c_k, D * L.sC); put(h, L.o_f, t->f_k, D * nq); put(h, L.o_in, t->infea_k, D * nq);
-    put(h, L.o_d, t->delta, D * nq); put(h, L.o_ar, t->actual_reduction, D * nq); put(h, L.o_pr, t->pred_reduction, D * nq);
-    put(h, L.o_it, t->infea_trial, D * nq); put(h, L.o_xt, t->x_trial, D * L.sN); put(h, L.o_q, t->qp_obj, D * nq);
-    int *const ints_h[6] = {t->accept, t->hu_word, t->hm_word, t->exitflag, t->soc, t->nwsr_soc};
-    for (int k = 0; k < 6; k++)
-        if (ints_h[k]) std::memcpy(hw + k * nq, ints_h[k], I * nq);
-    HIPCHK(hipMemcpyAsync(d, h, D * L.words, hipMemcpyHostToDevice, b->stream));
-    rsqp_soc_trial &v = a.t;
-    v.what = t->what ? reinterpret_cast<const int *>(d) : nullptr; v.rho = d + L.o_rho; v.f_trial = d + L.o_ft; v.c_trial = d + L.o_ct;
-    v.grad = t->grad ? d + L.o_g : nullptr; v.infea_model = t->infea_model ? d + L.o_m : nullptr;
-    v.x_k = d + L.o_x; v.c_k = d + L.o_c; v.f_k = d + L.o_f; v.infea_k = d + L.o_in; v.delta = d + L.o_d;
-    v.actual_reduction = t->actual_reduction ? d + L.o_ar : nullptr; v.pred_reduction = t->pred_reduction ? d + L.o_pr : nullptr;
-    v.infea_trial = t->infea_trial ? d + L.o_it : nullptr; v.x_trial = t->x_trial ? d + L.o_xt : nullptr;
-    v.qp_obj = t->qp_obj ? d + L.o_q : nullptr;
-    v.accept = t->accept ? dw : nullptr; v.hu_word = t->hu_word ? dw + nq : nullptr; v.hm_word = t->hm_word ? dw + 2 * nq : nullptr;
-    v.exitflag = t->exitflag ? dw + 3 * nq : nullptr; v.soc = t->soc ? dw + 4 * nq : nullptr; v.nwsr_soc = t->nwsr_soc ? dw + 5 * nq : nullptr;
-    return RSQP_OK;
-}
-// ... and what a call may have written down in one copy, into the caller's arrays
-int stage_down(rsqp_batch *b, const Staging &L, const rsqp_soc_trial *t) {
-    HIPCHK(hipMemcpyAsync(b->pin.p + L.o_x, b->scratch.p + L.o_x, sizeof(double) * (L.words - L.o_x), hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    const size_t D = sizeof(double), I = sizeof(int), nq = L.nq;
-    const double *const h = b->pin.p;
-    const int *const hw = reinterpret_cast<const int *>(h + L.o_w);
-    get(t->x_k, h, L.o_x, D * L.sN); get(t->c_k, h, L.o_c, D * L.sC); get(t->f_k, h, L.o_f, D * nq); get(t->infea_k, h, L.o_in, D * nq);
-    get(t->delta, h, L.o_d, D * nq); get(t->actual_reduction, h, L.o_ar, D * nq); get(t->pred_reduction, h, L.o_pr, D * nq);
-    get(t->infea_trial, h, L.o_it, D * nq); get(t->x_trial, h, L.o_xt, D * L.sN); get(t->qp_obj, h, L.o_q, D * nq);
-    int *const ints_h[6] = {t->accept, t->hu_word, t->hm_word, t->exitflag, t->soc, t->nwsr_soc};
-    for (int k = 0; k < 6; k++)
-        if (ints_h[k]) std::memcpy(ints_h[k], hw + k * nq, I * nq);
-    return RSQP_OK;
 }
 
 // what both calls check before any device call; null: fine
@@ -303,12 +212,11 @@ const char *refused(const rsqp_batch *b, const rsqp_soc_trial *t, const rsqp_nlp
 }
 
 void fill(const rsqp_batch *b, SocArgs &a) {
-    a.nq = b->nq; a.uniV = uni_shape(b); a.uniC = a.uniV > 0 ? b->uniC : 0; a.desc = b->d_desc.p;
+    a.w = b->soc.view(b->nq); a.uniV = uni_shape(b); a.uniC = a.uniV > 0 ? b->uniC : 0; a.desc = b->d_desc.p;
     a.x_l = b->h_xl.p; a.x_u = b->h_xu.p; a.c_l = b->h_cl.p; a.c_u = b->h_cu.p;
     a.x = b->x.p; a.obj = b->obj.p; a.g = b->g.p; a.lb = b->lb.p; a.ub = b->ub.p; a.lbA = b->lbA.p; a.ubA = b->ubA.p;
     a.status = b->status.p; a.used = b->used.dev;
     a.Hjc = b->Hjc.p; a.Hir = b->Hir.p; a.Hval = b->Hval.p;
-    a.wi = b->soc_i.p; a.wd = b->soc_d.p; a.x0 = b->soc_x.p; a.cnt = b->soc_cnt.p; a.live = b->soc_live.dev;
 }
 }  // namespace
 
@@ -327,37 +235,27 @@ extern "C" int rsqp_batch_handler_soc_begin(rsqp_batch *b, const rsqp_soc_trial 
     if (correct && !t->grad) return fail(RSQP_ERR_ARG, "rsqp_batch_handler_soc_begin: a word has CORRECT and grad is NULL");
     HIPCHK(hipSetDevice(b->device));
     const size_t nq = (size_t)b->nq;
-    if (!b->soc_i.p) {
-        HIPCHK(b->soc_i.alloc((size_t)SOC_INTS * nq)); HIPCHK(b->soc_d.alloc((size_t)SOC_DOUBLES * nq));
-        HIPCHK(b->soc_x.alloc((size_t)b->sumV)); HIPCHK(b->soc_cnt.alloc(2)); HIPCHK(b->soc_live.alloc(1, true));
-    }
+    int rc;
+    if ((rc = b->soc.ensure(SOC_INTS * nq, SOC_DOUBLES * nq, (size_t)b->sumV)) != RSQP_OK) return rc;
     if (!b->used.p) HIPCHK(b->used.alloc(nq, true));
     MaskLoan loan(b);      // the inner optimize call reads the mask the test kernel writes; put back however the call ends
     SocArgs a;
     std::memset(&a, 0, sizeof(a));
     a.t = *t; a.o = *o; a.so = *so;
-    const Staging L(b);
-    int rc;
-    if (!on_device && (rc = stage_up(b, L, t, a)) != RSQP_OK) return rc;
+    Staging st(b, on_device);
+    if (st.active) stage_trial(st, a.t, stage_sizes(b));
+    if ((rc = st.up()) != RSQP_OK) return rc;
     fill(b, a);
-    const int G = lanes_per_member(b);
-    if (G == 8) hipLaunchKernelGGL(batch_soc_test_kernel<8>, grid_of(b, G), dim3(256), 0, b->stream, a);
-    else hipLaunchKernelGGL(batch_soc_test_kernel<64>, grid_of(b, G), dim3(256), 0, b->stream, a);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(b->stream));
+    int live = 0;
+    if ((rc = launch_decision(b, b->soc, &live, [](auto g) { return batch_soc_test_kernel<decltype(g)::value>; }, a)) != RSQP_OK) return rc;
     b->soc_begun = true;
-    const int live = *b->soc_live.p;
     if (live > 0) {
-        MaskLoan::lend(b, b->soc_i.p + (size_t)SI_TAKE * nq, live);
+        MaskLoan::lend(b, b->soc.i.p + (size_t)SI_TAKE * nq, live);
         if ((rc = rsqp_batch_optimize_qp(b, nullptr)) != RSQP_OK) return rc;
-        if (G == 8) hipLaunchKernelGGL(batch_soc_step_kernel<8>, grid_of(b, G), dim3(256), 0, b->stream, a);
-        else hipLaunchKernelGGL(batch_soc_step_kernel<64>, grid_of(b, G), dim3(256), 0, b->stream, a);
-        HIPCHK(hipGetLastError());
+        if ((rc = launch_groups(b, [](auto g) { return batch_soc_step_kernel<decltype(g)::value>; }, a)) != RSQP_OK) return rc;
         b->results_foreign = true;      // the x pool holds p + s, which is no solve's own x (rsqp_batch_set_results)
     }
-    if (!on_device) return stage_down(b, L, t);
-    HIPCHK(hipStreamSynchronize(b->stream));
-    return RSQP_OK;
+    return st.down();
 }
 
 extern "C" int rsqp_batch_handler_soc_end(rsqp_batch *b, const rsqp_soc_trial *t, const rsqp_nlp_step_options *o,
@@ -368,17 +266,13 @@ extern "C" int rsqp_batch_handler_soc_end(rsqp_batch *b, const rsqp_soc_trial *t
     SocArgs a;
     std::memset(&a, 0, sizeof(a));
     a.t = *t; a.o = *o; a.so = *so;
-    const Staging L(b);
+    Staging st(b, on_device);
+    if (st.active) stage_trial(st, a.t, stage_sizes(b));
     int rc;
-    if (!on_device && (rc = stage_up(b, L, t, a)) != RSQP_OK) return rc;
+    if ((rc = st.up()) != RSQP_OK) return rc;
     fill(b, a);
-    const int G = lanes_per_member(b);
-    if (G == 8) hipLaunchKernelGGL(batch_soc_end_kernel<8>, grid_of(b, G), dim3(256), 0, b->stream, a);
-    else hipLaunchKernelGGL(batch_soc_end_kernel<64>, grid_of(b, G), dim3(256), 0, b->stream, a);
-    HIPCHK(hipGetLastError());
-    if (!on_device) return stage_down(b, L, t);
-    HIPCHK(hipStreamSynchronize(b->stream));
-    return RSQP_OK;
+    rc = launch_groups(b, [](auto g) { return batch_soc_end_kernel<decltype(g)::value>; }, a);
+    return rc != RSQP_OK ? rc : st.down();
 }
 
 extern "C" int rsqp_batch_set_objective(rsqp_batch *b, const int *members, const double *obj) {
