@@ -5,6 +5,7 @@ when the library has not been built (``__graft_entry__.build()`` / ``restartsqp_
 and every call that needs a GPU returns ``RSQP_ERR_DEVICE`` -> ``RsqpError`` without one.
 """
 import ctypes as C
+import functools
 import os
 import sys
 
@@ -199,6 +200,11 @@ SOC_SYMBOLS = {
     "rsqp_batch_handler_soc_end": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "rsqp_batch_set_objective": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
 }
+# every table above by the header under include/ that declares its entry points: lib() binds them all, and a name stands in one table only
+SYMBOL_TABLES = {"rsqp_hip.h": SYMBOLS, "rsqp_hip_lane.h": LANE_SYMBOLS, "rsqp_hip_handover.h": HANDOVER_SYMBOLS,
+                 "rsqp_hip_lane_warm.h": LANE_WARM_SYMBOLS, "rsqp_hip_lane_hot.h": LANE_HOT_SYMBOLS,
+                 "rsqp_hip_dense_check.h": DENSE_CHECK_SYMBOLS, "rsqp_hip_nlp_step.h": NLP_STEP_SYMBOLS,
+                 "rsqp_hip_penalty.h": PENALTY_SYMBOLS, "rsqp_hip_band_check.h": BAND_CHECK_SYMBOLS, "rsqp_hip_soc.h": SOC_SYMBOLS}
 SOC_TEST, SOC_CORRECT = 1, 2                                                                             # RSQP_SOC_*: bits of what[q]
 EXIT_UNKNOWN, EXIT_TRUST_REGION_TOO_SMALL = -99, 4                                                      # RSQP_EXIT_*
 KKT_PRIMAL, KKT_DUAL, KKT_COMPL, KKT_STAT, KKT_FIRST_ORDER_OPT = 1, 2, 4, 8, 16                         # RSQP_KKT_*: the verdict bits
@@ -213,100 +219,94 @@ class OptimalityStatus(C.Structure):
                 ("KKT_error", C.c_double)]
 
 
+def _pointer_struct(rows):
+    """(_fields_, IN, INOUT, OUT, INTS) of a struct of host or device addresses of pooled arguments from its table, one row per field
+    in the header's order: (name, role "in" / "inout" / "out", length "nq" / "sN" (NLP layout) / "sC" (constraint layout), element
+    type "float64" / "int32"). A call converts its "in" arrays and writes the others in place (Batch._pooled)"""
+    names = lambda test: tuple(r[0] for r in rows if test(r))
+    return ([(r[0], C.c_void_p) for r in rows], names(lambda r: r[1] == "in"), names(lambda r: r[1] == "inout"),
+            names(lambda r: r[1] == "out"), names(lambda r: r[3] == "int32"))
+
+
 class HandlerIterate(C.Structure):
     """rsqp_handler_iterate: host or device addresses, as handler_update's on_device says"""
-    _fields_ = [("what", C.c_void_p), ("delta", C.c_void_p), ("rho", C.c_void_p), ("x_k", C.c_void_p), ("grad", C.c_void_p),
-                ("c_k", C.c_void_p)]
+    ROWS = (("what", "in", "nq", "int32"), ("delta", "in", "nq", "float64"), ("rho", "in", "nq", "float64"), ("x_k", "in", "sN", "float64"),
+            ("grad", "in", "sN", "float64"), ("c_k", "in", "sC", "float64"))
+    _fields_, IN, INOUT, OUT, INTS = _pointer_struct(ROWS)
 
 
-class NlpStepOptions(C.Structure):
-    """rsqp_nlp_step_options; a new one holds the defaults of src/Options.cpp:28-42 (rsqp_nlp_step_default_options), keyword
-    arguments override fields"""
-    _fields_ = [(k, C.c_double) for k in ("active_set_tol", "opt_prim_fea_tol", "opt_dual_fea_tol", "opt_compl_tol", "opt_stat_tol",
-                                          "eta_s", "eta_c", "eta_e", "gamma_c", "gamma_e", "delta_min", "delta_max", "tol")] + \
-               [("refresh_ubA", C.c_int)]
+class _Options(C.Structure):
+    """the option structs: a new one holds the library's defaults (the entry point DEFAULTS names), keyword arguments override
+    fields of the C struct C_NAME"""
 
     def __init__(self, **fields):
         super().__init__()
-        check(lib().rsqp_nlp_step_default_options(C.addressof(self)))
+        check(getattr(lib(), self.DEFAULTS)(C.addressof(self)))
         for k, v in fields.items():
             if k not in dict(self._fields_):
-                raise TypeError("rsqp_nlp_step_options has no field %r" % k)
+                raise TypeError("%s has no field %r" % (self.C_NAME, k))
             setattr(self, k, v)
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class NlpStepOptions(_Options):
+    """rsqp_nlp_step_options: the defaults of src/Options.cpp:28-42"""
+    _fields_ = [(k, C.c_double) for k in ("active_set_tol", "opt_prim_fea_tol", "opt_dual_fea_tol", "opt_compl_tol", "opt_stat_tol",
+                                          "eta_s", "eta_c", "eta_e", "gamma_c", "gamma_e", "delta_min", "delta_max", "tol")] + \
+               [("refresh_ubA", C.c_int)]
+    C_NAME, DEFAULTS = "rsqp_nlp_step_options", "rsqp_nlp_step_default_options"
 
 
 class NlpTrial(C.Structure):
     """rsqp_nlp_trial: host or device addresses, as handler_ratio_test's on_device says"""
-    IN = ("what", "rho", "f_trial", "c_trial")
-    INOUT = ("x_k", "c_k", "f_k", "infea_k", "delta")
-    OUT = ("actual_reduction", "pred_reduction", "infea_trial", "accept", "hu_word", "hm_word", "exitflag")
-    INTS = ("what", "accept", "hu_word", "hm_word", "exitflag")
-    _fields_ = [(k, C.c_void_p) for k in IN + INOUT + OUT]
+    ROWS = (("what", "in", "nq", "int32"), ("rho", "in", "nq", "float64"), ("f_trial", "in", "nq", "float64"),
+            ("c_trial", "in", "sC", "float64"), ("x_k", "inout", "sN", "float64"), ("c_k", "inout", "sC", "float64"),
+            ("f_k", "inout", "nq", "float64"), ("infea_k", "inout", "nq", "float64"), ("delta", "inout", "nq", "float64"),
+            ("actual_reduction", "out", "nq", "float64"),
+            ("pred_reduction", "out", "nq", "float64"), ("infea_trial", "out", "nq", "float64"), ("accept", "out", "nq", "int32"),
+            ("hu_word", "out", "nq", "int32"), ("hm_word", "out", "nq", "int32"), ("exitflag", "out", "nq", "int32"))
+    _fields_, IN, INOUT, OUT, INTS = _pointer_struct(ROWS)
 
 
 class NlpPoint(C.Structure):
     """rsqp_nlp_point: host or device addresses, as handler_check_optimality's on_device says"""
-    _fields_ = [(k, C.c_void_p) for k in ("what", "x_k", "grad", "c_k", "infea")]
+    ROWS = (("what", "in", "nq", "int32"), ("x_k", "in", "sN", "float64"), ("grad", "in", "sN", "float64"), ("c_k", "in", "sC", "float64"),
+            ("infea", "in", "nq", "float64"))
+    _fields_, IN, INOUT, OUT, INTS = _pointer_struct(ROWS)
 
 
-class PenaltyOptions(C.Structure):
-    """rsqp_penalty_options; a new one holds the defaults of src/Options.cpp:43-52 (rsqp_penalty_default_options), keyword arguments
-    override fields"""
+class PenaltyOptions(_Options):
+    """rsqp_penalty_options: the defaults of src/Options.cpp:43-52"""
     _fields_ = [("penalty_update_tol", C.c_double), ("increase_parm", C.c_double), ("rho_max", C.c_double), ("penalty_iter_max", C.c_int),
                 ("eps1_change_parm", C.c_double), ("eps2", C.c_double)]
-
-    def __init__(self, **fields):
-        super().__init__()
-        check(lib().rsqp_penalty_default_options(C.addressof(self)))
-        for k, v in fields.items():
-            if k not in dict(self._fields_):
-                raise TypeError("rsqp_penalty_options has no field %r" % k)
-            setattr(self, k, v)
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
+    C_NAME, DEFAULTS = "rsqp_penalty_options", "rsqp_penalty_default_options"
 
 
 class PenaltyState(C.Structure):
     """rsqp_penalty_state: host or device addresses, as handler_update_penalty's on_device says"""
-    IN = ("what", "infea_k", "delta", "x_k", "c_k")
-    INOUT = ("rho", "eps1", "trial", "succ", "fail")
-    OUT = ("infea_model", "infea_infty", "hu_word", "exitflag", "nwsr_qp", "nwsr_lp", "rounds")
-    INTS = ("what", "trial", "succ", "fail", "hu_word", "exitflag", "nwsr_qp", "nwsr_lp", "rounds")
-    _fields_ = [(k, C.c_void_p) for k in IN + INOUT + OUT]
+    ROWS = (("what", "in", "nq", "int32"), ("infea_k", "in", "nq", "float64"), ("delta", "in", "nq", "float64"),
+            ("x_k", "in", "sN", "float64"), ("c_k", "in", "sC", "float64"), ("rho", "inout", "nq", "float64"),
+            ("eps1", "inout", "nq", "float64"), ("trial", "inout", "nq", "int32"), ("succ", "inout", "nq", "int32"),
+            ("fail", "inout", "nq", "int32"), ("infea_model", "out", "nq", "float64"), ("infea_infty", "out", "nq", "float64"),
+            ("hu_word", "out", "nq", "int32"), ("exitflag", "out", "nq", "int32"), ("nwsr_qp", "out", "nq", "int32"),
+            ("nwsr_lp", "out", "nq", "int32"), ("rounds", "out", "nq", "int32"))
+    _fields_, IN, INOUT, OUT, INTS = _pointer_struct(ROWS)
 
 
-class SocOptions(C.Structure):
-    """rsqp_soc_options; a new one holds the defaults (rsqp_soc_default_options: composite_pred = 0, the reference as found),
-    keyword arguments override fields"""
+class SocOptions(_Options):
+    """rsqp_soc_options: composite_pred = 0 by default, the reference as found"""
     _fields_ = [("composite_pred", C.c_int)]
-
-    def __init__(self, **fields):
-        super().__init__()
-        check(lib().rsqp_soc_default_options(C.addressof(self)))
-        for k, v in fields.items():
-            if k not in dict(self._fields_):
-                raise TypeError("rsqp_soc_options has no field %r" % k)
-            setattr(self, k, v)
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
+    C_NAME, DEFAULTS = "rsqp_soc_options", "rsqp_soc_default_options"
 
 
 class SocTrial(C.Structure):
     """rsqp_soc_trial: host or device addresses, as handler_soc_begin's / handler_soc_end's on_device says. The fields of NlpTrial,
-    then grad, infea_model, x_trial, soc, qp_obj, nwsr_soc"""
-    IN = ("what", "rho", "f_trial", "c_trial", "grad", "infea_model")
-    INOUT = ("x_k", "c_k", "f_k", "infea_k", "delta")
-    OUT = ("actual_reduction", "pred_reduction", "infea_trial", "accept", "hu_word", "hm_word", "exitflag", "x_trial", "soc", "qp_obj",
-           "nwsr_soc")
-    INTS = ("what", "accept", "hu_word", "hm_word", "exitflag", "soc", "nwsr_soc")
-    _fields_ = [(k, C.c_void_p) for k in ("what", "rho", "f_trial", "c_trial", "x_k", "c_k", "f_k", "infea_k", "delta",
-                                          "actual_reduction", "pred_reduction", "infea_trial", "accept", "hu_word", "hm_word", "exitflag",
-                                          "grad", "infea_model", "x_trial", "soc", "qp_obj", "nwsr_soc")]
+    then six of its own"""
+    ROWS = NlpTrial.ROWS + (("grad", "in", "sN", "float64"), ("infea_model", "in", "nq", "float64"), ("x_trial", "out", "sN", "float64"),
+                            ("soc", "out", "nq", "int32"), ("qp_obj", "out", "nq", "float64"), ("nwsr_soc", "out", "nq", "int32"))
+    _fields_, IN, INOUT, OUT, INTS = _pointer_struct(ROWS)
 
 
 class RsqpError(RuntimeError):
@@ -327,13 +327,11 @@ def lib():
             raise ImportError("%s not built: run `python -c 'import __graft_entry__ as g; g.build()'`" % LIB_PATH)
         _TORCH_FIRST = "torch" in sys.modules
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SYMBOLS.items()) + list(LANE_SYMBOLS.items()) + list(HANDOVER_SYMBOLS.items()) + \
-                list(LANE_WARM_SYMBOLS.items()) + list(LANE_HOT_SYMBOLS.items()) + list(DENSE_CHECK_SYMBOLS.items()) + \
-                list(NLP_STEP_SYMBOLS.items()) + list(PENALTY_SYMBOLS.items()) + list(BAND_CHECK_SYMBOLS.items()) + \
-                list(SOC_SYMBOLS.items()):
-            f = getattr(L, name)
-            f.restype = res
-            f.argtypes = args
+        for table in SYMBOL_TABLES.values():
+            for name, (res, args) in table.items():
+                f = getattr(L, name)
+                f.restype = res
+                f.argtypes = args
         _LIB = L
     return _LIB
 
@@ -381,9 +379,21 @@ def band_factor(d0, e1, e2):
                 m2i=m2i if built else None, sinv=sinv[:n] if built else None)
 
 
-class BandCheck:
+class _Handle:
+    """the owner of one library handle, _h: close() gives it to the entry point DESTROY names, once -- also on an object whose
+    constructor raised before it had a handle. A class whose objects close when they are collected says __del__ = _Handle.close"""
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(lib(), self.DESTROY)(self._h)
+            self._h = None
+
+
+class BandCheck(_Handle):
     """the uploaded banded factor of one Hessian (rsqp_band_check): apply / apply_q launch the engine's kernels on whole host
     buffers, which are float64 ndarrays WRITTEN IN PLACE (every double of them comes back from the device)"""
+    DESTROY = "rsqp_band_check_destroy"
+    __del__ = _Handle.close
 
     def __init__(self, d0, e1, e2):
         d0, e1, e2 = _d(d0), _d(e1), _d(e2)
@@ -392,13 +402,6 @@ class BandCheck:
         check(lib().rsqp_band_check_create(self.n, _dp(d0), _dp(e1), _dp(e2), C.byref(h)))
         self._h = h
         self.seq = 0        # the tag of the last multi-workgroup product
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().rsqp_band_check_destroy(self._h)
-            self._h = None
-
-    __del__ = close
 
     @staticmethod
     def _whole(a, name):
@@ -515,21 +518,16 @@ def read_qore_dump(path):
     return d
 
 
-class Solver:
+class Solver(_Handle):
     """Thin RAII wrapper over one ``rsqp_solver`` handle."""
+    DESTROY = "rsqp_destroy"
+    __del__ = _Handle.close
 
     def __init__(self, nV, nC, device=-1):
         self.nV, self.nC = nV, nC
         h = C.c_void_p()
         check(lib().rsqp_create(nV, nC, device, C.byref(h)))
         self._h = h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().rsqp_destroy(self._h)
-            self._h = None
-
-    __del__ = close
 
     def write_qp_data(self, path, layout=DUMP_QPOASES):
         """WriteQPDataToFile for the data held by this handle."""
@@ -732,9 +730,11 @@ class Solver:
         return out
 
 
-class Batch:
+class Batch(_Handle):
     """A batch of independent QPs (``rsqp_batch``): problems given as a list of QPData-like
     objects with fields nV, nC, A_jc/A_ir/A_val, H_jc/H_ir/H_val, g, lb, ub, lbA, ubA."""
+    DESTROY = "rsqp_batch_destroy"
+    __del__ = _Handle.close
 
     def __init__(self, problems, device=-1):
         self.problems = problems
@@ -760,12 +760,16 @@ class Batch:
         self.hnnz = np.array([int(p.H_jc[p.nV]) for p in problems], np.int64) if haveH else None
         self.set_vectors_from(problems)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().rsqp_batch_destroy(self._h)
-            self._h = None
+    @functools.cached_property
+    def sizes(self):
+        """(nq, sN, sC, sV): the members, and the pooled entries of the NLP layout (member q owns nV[q] - 2 nC[q]), of the constraint
+        layout (that of lbA) and of the variable layout (that of g); fixed when the batch is created"""
+        sV, sC = int(np.sum(self.nV)), int(np.sum(self.nC))
+        return self.nq, sV - 2 * sC, sC, sV
 
-    __del__ = close
+    def _handler_sizes(self):
+        """(sN, sC) of `sizes`, under the name the tests of the handler calls ask by"""
+        return self.sizes[1:3]
 
     def _mask(self, mask):
         """a per-member mask as nq ints (None stays None: everybody)"""
@@ -805,10 +809,6 @@ class Batch:
             check(lib().rsqp_batch_set_matrix_values_of(self._h, _ip(m), _dp(Aval), _dp(Hval)))
 
     # ---- the QPhandler of every member (rsqp_batch_handler_*): NLP layout = member q owns nV[q] - 2 nC[q] entries, pooled ----
-    def _handler_sizes(self):
-        sV, sC = int(np.sum(self.nV)), int(np.sum(self.nC))
-        return sV - 2 * sC, sC
-
     @staticmethod
     def _sized(a, n, name, dtype=np.float64):
         """a host array of exactly n entries (None stays None)"""
@@ -819,20 +819,62 @@ class Batch:
             raise ValueError("%s has %d entries, the batch needs %d" % (name, a.size, n))
         return a
 
-    @staticmethod
-    def _dev_addr(t, n, name, dtype="float64"):
-        """the address of a device tensor (torch, or anything with data_ptr / numel / dtype / is_contiguous) of n entries"""
-        if t is None:
-            return None
-        if int(t.numel()) != n:
-            raise ValueError("%s has %d entries, the batch needs %d" % (name, int(t.numel()), n))
-        if not str(t.dtype).endswith(dtype) or not t.is_contiguous() or not getattr(t, "is_cuda", True):
-            raise ValueError("%s must be a contiguous %s tensor on the batch's device" % (name, dtype))
-        return int(t.data_ptr())
+    def _addr(self, a, n, name, on_device, dtype="float64", writable=False):
+        """the address of a pooled argument of n entries: a device tensor (torch, or anything with data_ptr / numel / dtype /
+        is_contiguous), or a host array -- which is converted unless the call writes it (then it must be a contiguous ndarray of the
+        right type: it is written in place); (address, what keeps it alive until the call is over), (None, None) for None"""
+        if a is None:
+            return None, None
+        if on_device:
+            if int(a.numel()) != n:
+                raise ValueError("%s has %d entries, the batch needs %d" % (name, int(a.numel()), n))
+            if not str(a.dtype).endswith(dtype) or not a.is_contiguous() or not getattr(a, "is_cuda", True):
+                raise ValueError("%s must be a contiguous %s tensor on the batch's device" % (name, dtype))
+            return int(a.data_ptr()), a
+        if not writable:
+            a = self._sized(a, n, name, dtype)
+        elif not (isinstance(a, np.ndarray) and a.dtype == dtype and a.flags.c_contiguous and a.flags.writeable):
+            raise ValueError("%s is written in place: a contiguous %s ndarray is needed" % (name, dtype))
+        elif a.size != n:
+            raise ValueError("%s has %d entries, the batch needs %d" % (name, a.size, n))
+        return a.ctypes.data, a
+
+    def _new_out(self, n, on_device, dtype="float64", cols=None, fill=True):
+        """a new output of n entries (n rows of `cols`): a host array of zeros, or with on_device a tensor on the batch's device --
+        of zeros, or with fill=False of whatever the memory holds (for a call that writes every entry a caller may read)"""
+        shape = n if cols is None else (n, cols)
+        if not on_device:
+            return np.zeros(shape, dtype)
+        torch = device_torch()
+        dev = "cuda" if getattr(self, "device", -1) < 0 else "cuda:%d" % self.device
+        return (torch.zeros if fill else torch.empty)(shape, dtype=getattr(torch, dtype), device=dev)
+
+    def _pooled(self, cls, given, out, on_device, optional=()):
+        """the pointer struct `cls` of a per-member call, filled from its table: `given` holds the call's inputs and in/out arrays in
+        the order cls.IN + cls.INOUT, each required unless its layout is empty or `optional` names it; an output is the array of
+        `out` where it has one, else a new zero-filled one. Returns (the struct, what keeps the converted inputs alive: hold it
+        until the call is over, `out` complete)"""
+        size = dict(zip(("nq", "sN", "sC"), self.sizes))
+        out = dict(out or {})
+        for k, role, length, dtype in cls.ROWS:
+            if role == "out" and out.get(k) is None:
+                out[k] = self._new_out(size[length], on_device, dtype)
+        given = dict(zip(cls.IN + cls.INOUT, given))
+        s, keep = cls(), []
+        for turn in ("in", "inout", "out"):
+            for k, role, length, dtype in cls.ROWS:
+                if role != turn:
+                    continue
+                a = out[k] if role == "out" else given[k]
+                if a is None and size[length] > 0 and k not in optional:
+                    raise ValueError("%s is required" % k)
+                addr, a = self._addr(a, size[length], k, on_device, dtype, writable=role != "in")
+                setattr(s, k, addr); keep.append(a)
+        return s, keep, out
 
     def handler_set_problem(self, x_l, x_u, c_l=None, c_u=None):
         """the NLP bounds of every member, fixed for a run: x_l, x_u in the NLP layout, c_l, c_u in the layout of lbA"""
-        sN, sC = self._handler_sizes()
+        _, sN, sC, _ = self.sizes
         x_l, x_u = self._sized(x_l, sN, "x_l"), self._sized(x_u, sN, "x_u")
         c_l, c_u = self._sized(c_l, sC, "c_l"), self._sized(c_u, sC, "c_u")
         if x_l is None or x_u is None or (sC > 0 and (c_l is None or c_u is None)):
@@ -843,74 +885,35 @@ class Batch:
         """QPhandler's setters for every member on the device: what[q] = HU_* bits (0: member q is not touched); delta, rho: nq;
         x_k, grad: NLP layout (grad None: the LP handler's set_g(rho)); c_k: the layout of lbA. on_device: every argument is a
         tensor on the batch's device (what: int32, the others float64), complete before the call"""
-        sN, sC = self._handler_sizes()
-        spec = (("what", what, self.nq), ("delta", delta, self.nq), ("rho", rho, self.nq), ("x_k", x_k, sN), ("grad", grad, sN),
-                ("c_k", c_k, sC))
-        if on_device:
-            addr = [self._dev_addr(a, n, name, "int32" if name == "what" else "float64") for name, a, n in spec]
-            keep = None
-        else:
-            keep = [self._sized(a, n, name, np.int32 if name == "what" else np.float64) for name, a, n in spec]
-            addr = [None if a is None else a.ctypes.data for a in keep]
-        for (name, _, n), a in zip(spec, addr):
-            if a is None and name != "grad" and n > 0:
-                raise ValueError("%s is required" % name)
-        it = HandlerIterate(*addr)
+        given = (what, delta, rho, x_k, grad, c_k)
+        it, keep, _ = self._pooled(HandlerIterate, given, None, on_device, optional=HandlerIterate.IN)
+        size = dict(zip(("nq", "sN", "sC"), self.sizes))
+        for (k, _, length, _), a in zip(HandlerIterate.ROWS, given):        # (this call sizes every argument before it misses one)
+            if a is None and k != "grad" and size[length] > 0:
+                raise ValueError("%s is required" % k)
         check(lib().rsqp_batch_handler_update(self._h, C.addressof(it), int(bool(on_device))))
-        del keep
 
     def handler_step(self, on_device=False, out=None):
         """what Algorithm reads from the last solve, as a dict: p, lam_x (NLP layout), lam_c (layout of lbA), infea_model, norm_p
         (nq). on_device: written into float64 tensors on the batch's device -- those of `out` (same keys), else new torch tensors"""
-        sN, sC = self._handler_sizes()
-        sizes = (("p", sN), ("lam_c", sC), ("lam_x", sN), ("infea_model", self.nq), ("norm_p", self.nq))
-        if on_device:
-            if out is None:
-                torch = device_torch()
-                dev = "cuda" if getattr(self, "device", -1) < 0 else "cuda:%d" % self.device
-                out = {k: torch.empty(n, dtype=torch.float64, device=dev) for k, n in sizes}
-            addr = [self._dev_addr(out[k], n, k) for k, n in sizes]
-        else:
-            out = {k: np.zeros(n) for k, n in sizes}
-            addr = [out[k].ctypes.data for k, n in sizes]
+        nq, sN, sC, _ = self.sizes
+        sizes = (("p", sN), ("lam_c", sC), ("lam_x", sN), ("infea_model", nq), ("norm_p", nq))
+        if out is None or not on_device:
+            out = {k: self._new_out(n, on_device, fill=False) for k, n in sizes}
+        addr = [self._addr(out[k], n, k, on_device, writable=True)[0] for k, n in sizes]
         check(lib().rsqp_batch_handler_get_step(self._h, *addr, int(bool(on_device))))
         return out
 
     # ---- the decisions of the SQP loop per member (include/rsqp_hip_nlp_step.h) ----
-    def _addr(self, a, n, name, on_device, ints=False, writable=False):
-        """the address of a pooled argument of n entries: a device tensor, or a host array -- which is converted unless the call
-        writes it (then it must be a contiguous ndarray of the right type: it is written in place); (address, what keeps it alive)"""
-        if a is None:
-            return None, None
-        if on_device:
-            return self._dev_addr(a, n, name, "int32" if ints else "float64"), a
-        dt = np.int32 if ints else np.float64
-        if not writable:
-            a = self._sized(a, n, name, dt)
-        elif not (isinstance(a, np.ndarray) and a.dtype == dt and a.flags.c_contiguous and a.flags.writeable):
-            raise ValueError("%s is written in place: a contiguous %s ndarray is needed" % (name, np.dtype(dt).name))
-        elif a.size != n:
-            raise ValueError("%s has %d entries, the batch needs %d" % (name, a.size, n))
-        return a.ctypes.data, a
-
-    def _new_out(self, n, on_device, ints=False, cols=None):
-        shape = n if cols is None else (n, cols)
-        if on_device:
-            torch = device_torch()
-            dev = "cuda" if getattr(self, "device", -1) < 0 else "cuda:%d" % self.device
-            return torch.zeros(shape, dtype=torch.int32 if ints else torch.float64, device=dev)
-        return np.zeros(shape, np.int32 if ints else np.float64)
-
     def handler_infeasibility(self, c, on_device=False, out=None):
         """cal_infea(c, c_l, c_u) of every member (rsqp_batch_handler_infeasibility): c in the layout of lbA, the result nq entries
         -- `out`, else a new array (on_device: tensors on the batch's device)"""
-        sN, sC = self._handler_sizes()
+        nq, _, sC, _ = self.sizes
         if out is None:
-            out = self._new_out(self.nq, on_device)
+            out = self._new_out(nq, on_device)
         ca, keep = self._addr(c, sC, "c", on_device)
-        oa, _ = self._addr(out, self.nq, "out", on_device, writable=True)
+        oa, _ = self._addr(out, nq, "out", on_device, writable=True)
         check(lib().rsqp_batch_handler_infeasibility(self._h, ca, oa, int(bool(on_device))))
-        del keep
         return out
 
     def handler_ratio_test(self, what, rho, f_trial, c_trial, x_k, c_k, f_k, infea_k, delta, options=None, on_device=False, out=None):
@@ -919,26 +922,9 @@ class Batch:
         members' iterates and are WRITTEN IN PLACE: contiguous float64 ndarrays, or with on_device tensors on the batch's device,
         complete before the call. Returns the outputs as a dict over NlpTrial.OUT (accept, hu_word, hm_word, exitflag: int32) --
         the arrays of `out` where it has them (a member with word 0 keeps their bytes), else new zero-filled ones"""
-        sN, sC = self._handler_sizes()
-        nq = self.nq
-        size = dict(what=nq, rho=nq, f_trial=nq, c_trial=sC, x_k=sN, c_k=sC, f_k=nq, infea_k=nq, delta=nq)
-        given = dict(what=what, rho=rho, f_trial=f_trial, c_trial=c_trial, x_k=x_k, c_k=c_k, f_k=f_k, infea_k=infea_k, delta=delta)
-        out = dict(out or {})
-        for k in NlpTrial.OUT:
-            if out.get(k) is None:
-                out[k] = self._new_out(nq, on_device, ints=k in NlpTrial.INTS)
-        t, keep = NlpTrial(), []
-        for k in NlpTrial.IN + NlpTrial.INOUT:
-            if given[k] is None and size[k] > 0:
-                raise ValueError("%s is required" % k)
-            addr, a = self._addr(given[k], size[k], k, on_device, ints=k in NlpTrial.INTS, writable=k in NlpTrial.INOUT)
-            setattr(t, k, addr); keep.append(a)
-        for k in NlpTrial.OUT:
-            addr, a = self._addr(out[k], nq, k, on_device, ints=k in NlpTrial.INTS, writable=True)
-            setattr(t, k, addr)
+        t, keep, out = self._pooled(NlpTrial, (what, rho, f_trial, c_trial, x_k, c_k, f_k, infea_k, delta), out, on_device)
         o = options or NlpStepOptions()
         check(lib().rsqp_batch_handler_ratio_test(self._h, C.addressof(t), C.addressof(o), int(bool(on_device))))
-        del keep
         return out
 
     def handler_check_optimality(self, what, x_k, grad, c_k, infea, options=None, on_device=False, out=None, verdict=None):
@@ -947,23 +933,16 @@ class Batch:
         x_k, grad: NLP layout; c_k: the layout of lbA; infea: nq. Returns (status, verdict): status [nq, 5] over CERTIFICATE_FIELDS,
         verdict int32 with the KKT_* bits -- `out` / `verdict` where given (a member with word 0 keeps their bytes), else new
         zero-filled ones; on_device: tensors on the batch's device"""
-        sN, sC = self._handler_sizes()
         nq = self.nq
         if out is None:
             out = self._new_out(nq, on_device, cols=5)
         if verdict is None:
-            verdict = self._new_out(nq, on_device, ints=True)
-        p, keep = NlpPoint(), []
-        for k, a, n in (("what", what, nq), ("x_k", x_k, sN), ("grad", grad, sN), ("c_k", c_k, sC), ("infea", infea, nq)):
-            if a is None and n > 0:
-                raise ValueError("%s is required" % k)
-            addr, a = self._addr(a, n, k, on_device, ints=k == "what")
-            setattr(p, k, addr); keep.append(a)
+            verdict = self._new_out(nq, on_device, "int32")
+        p, keep, _ = self._pooled(NlpPoint, (what, x_k, grad, c_k, infea), None, on_device)
         oa, _ = self._addr(out, 5 * nq, "out", on_device, writable=True)
-        va, _ = self._addr(verdict, nq, "verdict", on_device, ints=True, writable=True)
+        va, _ = self._addr(verdict, nq, "verdict", on_device, "int32", writable=True)
         o = options or NlpStepOptions()
         check(lib().rsqp_batch_handler_check_optimality(self._h, C.addressof(p), C.addressof(o), oa, va, int(bool(on_device))))
-        del keep
         return out, verdict
 
     # ---- update_penalty_parameter per member, across this batch and its LP batch (include/rsqp_hip_penalty.h) ----
@@ -981,55 +960,16 @@ class Batch:
         and are WRITTEN IN PLACE: contiguous ndarrays, or with on_device tensors on the batch's device, complete before the call.
         Returns the outputs as a dict over PenaltyState.OUT (infea_model, infea_infty: float64, the others int32) -- the arrays of
         `out` where it has them (a member with word 0 keeps their bytes), else new zero-filled ones"""
-        sN, sC = self._handler_sizes()
-        nq = self.nq
-        size = dict(what=nq, infea_k=nq, delta=nq, x_k=sN, c_k=sC, rho=nq, eps1=nq, trial=nq, succ=nq, fail=nq)
-        given = dict(what=what, infea_k=infea_k, delta=delta, x_k=x_k, c_k=c_k, rho=rho, eps1=eps1, trial=trial, succ=succ, fail=fail)
-        out = dict(out or {})
-        for k in PenaltyState.OUT:
-            if out.get(k) is None:
-                out[k] = self._new_out(nq, on_device, ints=k in PenaltyState.INTS)
-        s, keep = PenaltyState(), []
-        for k in PenaltyState.IN + PenaltyState.INOUT:
-            if given[k] is None and size[k] > 0:
-                raise ValueError("%s is required" % k)
-            addr, a = self._addr(given[k], size[k], k, on_device, ints=k in PenaltyState.INTS, writable=k in PenaltyState.INOUT)
-            setattr(s, k, addr); keep.append(a)
-        for k in PenaltyState.OUT:
-            addr, a = self._addr(out[k], nq, k, on_device, ints=k in PenaltyState.INTS, writable=True)
-            setattr(s, k, addr)
+        s, keep, out = self._pooled(PenaltyState, (what, infea_k, delta, x_k, c_k, rho, eps1, trial, succ, fail), out, on_device)
         o = options or PenaltyOptions()
         check(lib().rsqp_batch_handler_update_penalty(self._h, C.addressof(s), C.addressof(o), int(bool(on_device))))
-        del keep
         return out
 
     # ---- second_order_correction per member (include/rsqp_hip_soc.h) ----
-    def _soc_call(self, fn, begin, what, rho, f_trial, c_trial, x_k, c_k, f_k, infea_k, delta, grad, infea_model, options, soc_options,
-                  on_device, out):
-        sN, sC = self._handler_sizes()
-        nq = self.nq
-        size = dict(what=nq, rho=nq, f_trial=nq, c_trial=sC, grad=sN, infea_model=nq, x_k=sN, c_k=sC, f_k=nq, infea_k=nq, delta=nq)
-        given = dict(what=what, rho=rho, f_trial=f_trial, c_trial=c_trial, grad=grad, infea_model=infea_model, x_k=x_k, c_k=c_k, f_k=f_k,
-                     infea_k=infea_k, delta=delta)
-        optional = ("grad", "infea_model") if begin else ("what", "grad", "infea_model")
-        out = dict(out or {})
-        if not begin and out.get("soc") is None:
-            raise ValueError("soc is required: the array handler_soc_begin wrote")
-        for k in SocTrial.OUT:
-            if out.get(k) is None:
-                out[k] = self._new_out(sN if k == "x_trial" else nq, on_device, ints=k in SocTrial.INTS)
-        t, keep = SocTrial(), []
-        for k in SocTrial.IN + SocTrial.INOUT:
-            if given[k] is None and size[k] > 0 and k not in optional:
-                raise ValueError("%s is required" % k)
-            addr, a = self._addr(given[k], size[k], k, on_device, ints=k in SocTrial.INTS, writable=k in SocTrial.INOUT)
-            setattr(t, k, addr); keep.append(a)
-        for k in SocTrial.OUT:
-            addr, a = self._addr(out[k], sN if k == "x_trial" else nq, k, on_device, ints=k in SocTrial.INTS, writable=True)
-            setattr(t, k, addr)
+    def _soc_call(self, fn, given, optional, options, soc_options, on_device, out):
+        t, keep, out = self._pooled(SocTrial, given, out, on_device, optional)
         o, so = options or NlpStepOptions(), soc_options or SocOptions()
         check(fn(self._h, C.addressof(t), C.addressof(o), C.addressof(so), int(bool(on_device))))
-        del keep
         return out
 
     def handler_soc_begin(self, what, rho, f_trial, c_trial, x_k, c_k, f_k, infea_k, delta, grad=None, infea_model=None, options=None,
@@ -1041,16 +981,19 @@ class Batch:
         NLP layout; accept, hu_word, hm_word, exitflag, soc, nwsr_soc: int32) -- the arrays of `out` where it has them (a member
         with word 0 keeps their bytes), else new zero-filled ones. The members with soc == 1 await f and c at x_trial and
         handler_soc_end"""
-        return self._soc_call(lib().rsqp_batch_handler_soc_begin, True, what, rho, f_trial, c_trial, x_k, c_k, f_k, infea_k, delta, grad,
-                              infea_model, options, soc_options, on_device, out)
+        given = (what, rho, f_trial, c_trial, grad, infea_model, x_k, c_k, f_k, infea_k, delta)
+        return self._soc_call(lib().rsqp_batch_handler_soc_begin, given, ("grad", "infea_model"), options, soc_options, on_device, out)
 
     def handler_soc_end(self, rho, f_trial, c_trial, x_k, c_k, f_k, infea_k, delta, out, options=None, soc_options=None,
                         on_device=False):
         """the second ratio test, the restore of a rejected correction and update_radius for every member with out["soc"][q] != 0
         that the last handler_soc_begin set going (rsqp_batch_handler_soc_end): f_trial, c_trial at the x_trial of that call; `out`
         is the dict that call returned (soc is required) and is returned with this call's outputs"""
-        return self._soc_call(lib().rsqp_batch_handler_soc_end, False, None, rho, f_trial, c_trial, x_k, c_k, f_k, infea_k, delta, None,
-                              None, options, soc_options, on_device, out)
+        if dict(out or {}).get("soc") is None:
+            raise ValueError("soc is required: the array handler_soc_begin wrote")
+        given = (None, rho, f_trial, c_trial, None, None, x_k, c_k, f_k, infea_k, delta)
+        optional = ("what", "grad", "infea_model")
+        return self._soc_call(lib().rsqp_batch_handler_soc_end, given, optional, options, soc_options, on_device, out)
 
     def set_objective(self, obj, members=None):
         """the objective pool of the named members (a mask; None: everybody) := obj (nq entries); nothing else is touched
@@ -1062,7 +1005,7 @@ class Batch:
 
     def get_vectors(self):
         """(g, lb, ub, lbA, ubA) as the pools hold them on the device, in the layout of set_vectors"""
-        sV, sC = int(np.sum(self.nV)), int(np.sum(self.nC))
+        _, _, sC, sV = self.sizes
         v = [np.zeros(sV), np.zeros(sV), np.zeros(sV), np.zeros(sC), np.zeros(sC)]
         check(lib().rsqp_batch_get_vectors(self._h, *[_dp(a) for a in v]))
         return tuple(v)
@@ -1078,20 +1021,15 @@ class Batch:
         no H). on_device: what (int32), jac and hess (float64) are tensors on the batch's device, complete before the call; a
         missing jac / hess then promises that no word carries its bit"""
         nJ, nA, nH = self._matrix_sizes()
-        spec = (("what", what, self.nq), ("jac", jac, nJ), ("hess", None if nH is None else hess, nH))
+        spec = (("what", what, self.nq, "int32"), ("jac", jac, nJ, "float64"), ("hess", None if nH is None else hess, nH, "float64"))
         if what is None:
             raise ValueError("what is required")
-        if on_device:
-            addr = [self._dev_addr(a, n, name, "int32" if name == "what" else "float64") for name, a, n in spec]
-            keep = None
-        else:
-            keep = [self._sized(a, n, name, np.int32 if name == "what" else np.float64) for name, a, n in spec]
-            addr = [None if a is None else a.ctypes.data for a in keep]
+        addr, keep = zip(*[self._addr(a, n, name, on_device, dtype) for name, a, n, dtype in spec])
+        if not on_device:
             seen = int(np.bitwise_or.reduce(keep[0])) if self.nq else 0
             if (seen & HM_JAC and keep[1] is None) or (seen & HM_HESS and nH is not None and keep[2] is None):
                 raise ValueError("a word names a matrix that is not given")
         check(lib().rsqp_batch_handler_set_matrices(self._h, *addr, int(bool(on_device))))
-        del keep
 
     def get_matrix_values(self):
         """(Aval, Hval) as the pools hold them on the device, in the layout the batch was created with; Hval None without H"""
@@ -1273,7 +1211,7 @@ class Batch:
     def allgather_records(self, comm, count_per_rank, all_dev_ptr):
         """native RCCL: pack this rank's records into its slot of the DEVICE buffer at `all_dev_ptr`
         (world * count_per_rank * record_stride doubles) and all-gather in place; returns when done"""
-        check(lib().rsqp_batch_allgather_records(self._h, comm._c, int(count_per_rank), C.c_void_p(all_dev_ptr)))
+        check(lib().rsqp_batch_allgather_records(self._h, comm._h, int(count_per_rank), C.c_void_p(all_dev_ptr)))
 
 
 def rccl_unique_id():
@@ -1283,37 +1221,29 @@ def rccl_unique_id():
     return buf.raw
 
 
-class RcclComm:
-    """an ncclComm_t created through the C ABI (rsqp_rccl_comm_create): one per rank, bound to `device`"""
+class RcclComm(_Handle):
+    """an ncclComm_t created through the C ABI (rsqp_rccl_comm_create): one per rank, bound to `device`; closed by close() alone"""
+    DESTROY = "rsqp_rccl_comm_destroy"
 
     def __init__(self, uid, rank, world, device):
         c = C.c_void_p()
         check(lib().rsqp_rccl_comm_create(C.create_string_buffer(bytes(uid), 128), rank, world, device, C.byref(c)))
-        self._c, self.rank, self.world = c, rank, world
+        self._h, self.rank, self.world = c, rank, world
 
     def broadcast_dev(self, dev_ptr, nbytes, root=0, stream=None):
-        check(lib().rsqp_rccl_broadcast_dev(self._c, C.c_void_p(dev_ptr), int(nbytes), root, C.c_void_p(stream or 0)))
-
-    def close(self):
-        if getattr(self, "_c", None):
-            lib().rsqp_rccl_comm_destroy(self._c)
-            self._c = None
+        check(lib().rsqp_rccl_broadcast_dev(self._h, C.c_void_p(dev_ptr), int(nbytes), root, C.c_void_p(stream or 0)))
 
 
-class SpmvPlan:
+class SpmvPlan(_Handle):
+    DESTROY = "rsqp_spmv_plan_destroy"
+    __del__ = _Handle.close
+
     def __init__(self, nrow, ncol, jc, ir, nbatch, device=-1):
         jc, ir = _i(jc), _i(ir)
         self.nrow, self.ncol, self.nnz, self.nbatch = nrow, ncol, int(jc[ncol]), nbatch
         h = C.c_void_p()
         check(lib().rsqp_spmv_plan_create(nrow, ncol, _ip(jc), _ip(ir), nbatch, device, C.byref(h)))
         self._h = h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().rsqp_spmv_plan_destroy(self._h)
-            self._h = None
-
-    __del__ = close
 
     def upload(self, vals=None, xin=None, transposed=False):
         vals, xin = _d(vals), _d(xin)

@@ -11,6 +11,7 @@ import pytest
 
 import band_cases as bc
 import band_ref as br
+from abi_cases import assert_entry_points
 from conftest import ROOT
 
 NEW = ("rsqp_band_check_factor", "rsqp_band_check_create", "rsqp_band_check_destroy", "rsqp_band_check_apply", "rsqp_band_check_apply_q")
@@ -19,20 +20,7 @@ TH = br.TH
 
 
 def test_entry_points_are_declared_exported_and_bound(capi):
-    main = open(os.path.join(ROOT, "include", "rsqp_hip.h")).read()
-    assert re.search(r'^#include "rsqp_hip_band_check.h"', main, flags=re.M)
-    header = open(os.path.join(ROOT, "include", "rsqp_hip_band_check.h")).read()
-    L = capi.lib()
-    for name in NEW:
-        assert re.search(r"\bint\s+%s\s*\(" % name, header), name
-        assert name in capi.BAND_CHECK_SYMBOLS and hasattr(L, name), name
-        assert getattr(L, name).argtypes == capi.BAND_CHECK_SYMBOLS[name][1]
-        assert not re.search(r"\b%s\s*\(" % name, main), name
-    declared = set(re.findall(r"^\s*int\s+(rsqp_\w+)\s*\(", header, flags=re.M))
-    assert declared == set(capi.BAND_CHECK_SYMBOLS) == set(NEW)
-    for table in (capi.SYMBOLS, capi.LANE_SYMBOLS, capi.HANDOVER_SYMBOLS, capi.LANE_WARM_SYMBOLS, capi.LANE_HOT_SYMBOLS,
-                  capi.DENSE_CHECK_SYMBOLS, capi.NLP_STEP_SYMBOLS, capi.PENALTY_SYMBOLS):
-        assert not declared & set(table)
+    header = assert_entry_points(capi, "rsqp_hip_band_check.h", capi.BAND_CHECK_SYMBOLS, NEW)
     assert int(re.search(r"#define RSQP_BAND_MAX_N (\d+)", header).group(1)) == capi.BAND_MAX_N == 16384
     assert int(re.search(r"#define RSQP_BAND_THREADS (\d+)", header).group(1)) == capi.BAND_THREADS == TH
     words = re.search(r"enum \{ (RSQP_BAND_KERNEL_ENGINE.*?) \};", header).group(1)

@@ -5,13 +5,12 @@ CPU oracle. The behaviour itself needs a GPU:
 tests/test_gpu_batch_handover.py."""
 import copy
 import inspect
-import os
-import re
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, oracle_cold
+from abi_cases import assert_entry_points
+from conftest import oracle_cold
 from restartsqp_amd import problems
 
 NEW = ("rsqp_batch_set_handover", "rsqp_batch_get_handover")
@@ -28,16 +27,7 @@ def test_entry_points_are_declared_exported_and_bound(capi):
     # the two entry points are declared in an extension header of their own, which rsqp_hip.h includes (one include declares the
     # whole C ABI), and bound through a table of their own: header and table name the same entry points, as rsqp_hip.h and
     # capi.SYMBOLS do
-    main = open(os.path.join(ROOT, "include", "rsqp_hip.h")).read()
-    assert re.search(r'^#include "rsqp_hip_handover.h"', main, flags=re.M)
-    header = open(os.path.join(ROOT, "include", "rsqp_hip_handover.h")).read()
-    L = capi.lib()
-    for name in NEW:
-        assert re.search(r"\bint\s+%s\s*\(" % name, header), name
-        assert name in capi.HANDOVER_SYMBOLS and hasattr(L, name), name
-        assert getattr(L, name).argtypes == capi.HANDOVER_SYMBOLS[name][1]
-    declared = set(re.findall(r"^\s*int\s+(rsqp_\w+)\s*\(", header, flags=re.M))
-    assert declared == set(capi.HANDOVER_SYMBOLS) == set(NEW) and not declared & set(capi.SYMBOLS)
+    assert_entry_points(capi, "rsqp_hip_handover.h", capi.HANDOVER_SYMBOLS, NEW)
     assert callable(capi.Batch.set_handover) and callable(capi.Batch.handover)
     from restartsqp_amd import handler
     par = inspect.signature(handler.BatchQPhandler.__init__).parameters

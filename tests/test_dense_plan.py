@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import dense_cases as dc
+from abi_cases import assert_entry_points
 from conftest import ROOT
 
 NEW = ("rsqp_dense_describe_gemm", "rsqp_dense_check_gemm", "rsqp_dense_check_work_create", "rsqp_dense_check_work_destroy",
@@ -19,19 +20,7 @@ SIZES = (1, 8, 64, 65, 128, 129, 2048, 8192, 32641, 65409, 65536)
 
 
 def test_entry_points_are_declared_exported_and_bound(capi):
-    main = open(os.path.join(ROOT, "include", "rsqp_hip.h")).read()
-    assert re.search(r'^#include "rsqp_hip_dense_check.h"', main, flags=re.M)
-    header = open(os.path.join(ROOT, "include", "rsqp_hip_dense_check.h")).read()
-    L = capi.lib()
-    for name in NEW:
-        assert re.search(r"\bint\s+%s\s*\(" % name, header), name
-        assert name in capi.DENSE_CHECK_SYMBOLS and hasattr(L, name), name
-        assert getattr(L, name).argtypes == capi.DENSE_CHECK_SYMBOLS[name][1]
-        assert not re.search(r"\b%s\s*\(" % name, main), name
-    declared = set(re.findall(r"^\s*int\s+(rsqp_\w+)\s*\(", header, flags=re.M))
-    assert declared == set(capi.DENSE_CHECK_SYMBOLS) == set(NEW)
-    for table in (capi.SYMBOLS, capi.LANE_SYMBOLS, capi.HANDOVER_SYMBOLS, capi.LANE_WARM_SYMBOLS, capi.LANE_HOT_SYMBOLS):
-        assert not declared & set(table)
+    header = assert_entry_points(capi, "rsqp_hip_dense_check.h", capi.DENSE_CHECK_SYMBOLS, NEW)
     assert int(re.search(r"#define RSQP_DENSE_PLAN_WORDS (\d+)", header).group(1)) == len(capi.DENSE_PLAN_OUT)
     # the header's words are the binding's, in its order
     words = re.search(r"enum \{ (RSQP_DENSE_GEMM_PLAIN.*?) \};", header).group(1)

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import small_builds as SB
+from abi_cases import assert_entry_points
 from conftest import oracle_cold
 from lane_cases import (FULL, ODD_INCONSISTENT, ODD_INFEASIBLE, ROLES_SEED, assert_ragged_and_full_bits, assert_same_bits,
                         assert_same_solution, continue_hot, lane_cold, members, oracle_handles, oracle_of, pattern, perturbations, ragged_batch)
@@ -70,14 +71,8 @@ def test_the_odd_batch_holds_each_of_its_three_kinds(oracle):
 def test_the_getter_is_declared_exported_and_bound_and_the_plan_words_stay(capi):
     """(no GPU) rsqp_batch_get_lane_shape: declared in include/rsqp_hip_lane.h, which rsqp_hip.h includes, bound in capi.LANE_SYMBOLS;
     the shape word stays out of rsqp_describe_small_launch's words: ("lane", keep, uni, hb) names the build family"""
-    import os, re
-    from conftest import ROOT
-    main = open(os.path.join(ROOT, "include", "rsqp_hip.h")).read()
-    assert re.search(r'^#include "rsqp_hip_lane.h"', main, flags=re.M)
-    header = open(os.path.join(ROOT, "include", "rsqp_hip_lane.h")).read()
-    declared = set(re.findall(r"^\s*int\s+(rsqp_\w+)\s*\(", header, flags=re.M))
-    assert declared == set(capi.LANE_SYMBOLS) == {"rsqp_batch_get_lane_shape"} and not declared & set(capi.SYMBOLS)
-    assert hasattr(capi.lib(), "rsqp_batch_get_lane_shape") and capi.lib().rsqp_batch_get_lane_shape(None) == 0
+    assert_entry_points(capi, "rsqp_hip_lane.h", capi.LANE_SYMBOLS, ("rsqp_batch_get_lane_shape",))
+    assert capi.lib().rsqp_batch_get_lane_shape(None) == 0
     assert "lane_shape" not in capi.SMALL_LAUNCH_OUT and len(capi.SMALL_LAUNCH_OUT) == 20
 
 

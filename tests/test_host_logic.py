@@ -7,6 +7,7 @@ import re
 import numpy as np
 import pytest
 
+from abi_cases import assert_entry_points
 from conftest import ROOT, dump_paths
 from restartsqp_amd import problems
 from restartsqp_amd.qpdump import read_qore_dump, write_qore_dump
@@ -19,13 +20,22 @@ def header_symbols():
 
 
 def test_library_exports_every_declared_symbol(capi):
-    L = capi.lib()
     names = header_symbols()
     assert len(names) >= 40
-    for n in names:
-        assert hasattr(L, n), "librsqp_hip.so does not export %s" % n
-    assert set(names) == set(capi.SYMBOLS), set(names) ^ set(capi.SYMBOLS)
-    assert b"gfx950" in L.rsqp_version()
+    assert_entry_points(capi, "rsqp_hip.h", capi.SYMBOLS, names, structs=(("rsqp_handler_iterate", capi.HandlerIterate),))
+    assert b"gfx950" in capi.lib().rsqp_version()
+
+
+def test_the_tables_are_disjoint_and_together_what_the_library_binds(capi):
+    """one table per header under include/, no name in two of them, and lib() binds their union: nothing else, nothing less"""
+    tables = capi.SYMBOL_TABLES
+    assert sorted(tables) == sorted(os.listdir(os.path.join(ROOT, "include"))) and next(iter(tables)) == "rsqp_hip.h"
+    assert sorted(map(id, tables.values())) == sorted(id(v) for k, v in vars(capi).items() if k.endswith("SYMBOLS")) and len(tables) == 10
+    names = [fn for t in tables.values() for fn in t]
+    assert len(names) == len(set(names))
+    L = capi.lib()
+    bound = {k for k, f in vars(L).items() if k.startswith("rsqp_") and f.argtypes is not None}
+    assert bound == set(names), bound ^ set(names)
 
 
 def test_build_sources_are_the_translation_units_of_csrc():

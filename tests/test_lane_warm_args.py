@@ -3,30 +3,13 @@ lane-per-problem kernel (include/rsqp_hip_lane_warm.h, which include/rsqp_hip.h 
 rsqp_batch_get_lane_warm): declared, exported, bound through a table of their own, and a null batch is an argument error before any
 device call. The behaviour itself needs a GPU: tests/test_gpu_lane_warm.py. (That rsqp_describe_small_launch still reproduces every
 golden plan -- the switch is a word its callers leave at 0 -- is tests/test_small_launch_plan.py's.)"""
-import os
-import re
-
-from conftest import ROOT
+from abi_cases import assert_entry_points
 
 NEW = ("rsqp_batch_set_lane_warm", "rsqp_batch_get_lane_warm")
 
 
 def test_entry_points_are_declared_exported_and_bound(capi):
-    main = open(os.path.join(ROOT, "include", "rsqp_hip.h")).read()
-    assert re.search(r'^#include "rsqp_hip_lane_warm.h"', main, flags=re.M)
-    header = open(os.path.join(ROOT, "include", "rsqp_hip_lane_warm.h")).read()
-    L = capi.lib()
-    for name in NEW:
-        assert re.search(r"\bint\s+%s\s*\(" % name, header), name
-        assert name in capi.LANE_WARM_SYMBOLS and hasattr(L, name), name
-        assert getattr(L, name).argtypes == capi.LANE_WARM_SYMBOLS[name][1]
-    declared = set(re.findall(r"^\s*int\s+(rsqp_\w+)\s*\(", header, flags=re.M))
-    assert declared == set(capi.LANE_WARM_SYMBOLS) == set(NEW)
-    # ... and in no other table: rsqp_hip.h's own declarations and the two older extensions stay what they were
-    for table in (capi.SYMBOLS, capi.LANE_SYMBOLS, capi.HANDOVER_SYMBOLS):
-        assert not declared & set(table)
-    for name in NEW:
-        assert not re.search(r"\b%s\s*\(" % name, main), name
+    assert_entry_points(capi, "rsqp_hip_lane_warm.h", capi.LANE_WARM_SYMBOLS, NEW)
     assert callable(capi.Batch.set_lane_warm) and callable(capi.Batch.lane_warm)
 
 

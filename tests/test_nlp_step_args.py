@@ -6,13 +6,13 @@ committed data before tests/test_gpu_nlp_step.py compares the kernels with them.
 import ctypes as C
 import json
 import os
-import re
 
 import numpy as np
 import pytest
 
+from abi_cases import assert_entry_points
 from restartsqp_amd import handler, problems
-from conftest import GOLDEN, ROOT
+from conftest import GOLDEN
 
 NEW = ("rsqp_nlp_step_default_options", "rsqp_batch_handler_infeasibility", "rsqp_batch_handler_ratio_test",
        "rsqp_batch_handler_check_optimality")
@@ -20,35 +20,13 @@ NLPS = {"hs071": problems.hs071_nlp, "hs035": problems.hs035_nlp, "hs065": probl
 
 
 def test_entry_points_are_declared_exported_and_bound(capi):
-    main = open(os.path.join(ROOT, "include", "rsqp_hip.h")).read()
-    assert re.search(r'^#include "rsqp_hip_nlp_step.h"', main, flags=re.M)
-    header = open(os.path.join(ROOT, "include", "rsqp_hip_nlp_step.h")).read()
-    L = capi.lib()
-    for name in NEW:
-        assert re.search(r"\bint\s+%s\s*\(" % name, header), name
-        assert name in capi.NLP_STEP_SYMBOLS and hasattr(L, name), name
-        assert getattr(L, name).argtypes == capi.NLP_STEP_SYMBOLS[name][1]
-    declared = set(re.findall(r"^\s*int\s+(rsqp_\w+)\s*\(", header, flags=re.M))
-    assert declared == set(capi.NLP_STEP_SYMBOLS) == set(NEW)
-    # ... and in no other table or header
-    for table in (capi.SYMBOLS, capi.LANE_SYMBOLS, capi.HANDOVER_SYMBOLS, capi.LANE_WARM_SYMBOLS, capi.LANE_HOT_SYMBOLS,
-                  capi.DENSE_CHECK_SYMBOLS):
-        assert not declared & set(table)
-    for other in sorted(os.listdir(os.path.join(ROOT, "include"))):
-        if other != "rsqp_hip_nlp_step.h":
-            text = open(os.path.join(ROOT, "include", other)).read()
-            for name in NEW:
-                assert not re.search(r"\b%s\s*\(" % name, text), (other, name)
+    # ... through a table of their own, and the struct layouts of the binding are the header's, field by field and in order
+    header = assert_entry_points(capi, "rsqp_hip_nlp_step.h", capi.NLP_STEP_SYMBOLS, NEW, structs=(
+        ("rsqp_nlp_step_options", capi.NlpStepOptions), ("rsqp_nlp_trial", capi.NlpTrial), ("rsqp_nlp_point", capi.NlpPoint)))
     for method in ("handler_infeasibility", "handler_ratio_test", "handler_check_optimality"):
         assert callable(getattr(capi.Batch, method)), method
     # the header says where the Jacobian comes from and what is not built
     assert "READ IN PLACE" in header and "rsqp_batch_handler_set_matrices" in header and "W_constr_ / W_bounds_" in header
-    # the struct layouts of the binding are the header's, field by field and in order
-    for struct, cls in (("rsqp_nlp_step_options", capi.NlpStepOptions), ("rsqp_nlp_trial", capi.NlpTrial), ("rsqp_nlp_point", capi.NlpPoint)):
-        body = re.search(r"typedef struct \{([^{}]*)\} %s;" % struct, header).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        names = re.findall(r"[\s*](\w+)\s*[,;]", body)
-        assert names == [k for k, _ in cls._fields_], (struct, names)
     assert (capi.EXIT_UNKNOWN, capi.EXIT_TRUST_REGION_TOO_SMALL) == (-99, 4)
     assert "#define RSQP_EXIT_UNKNOWN (-99)" in header and "#define RSQP_EXIT_TRUST_REGION_TOO_SMALL 4" in header
     assert "RSQP_KKT_PRIMAL = 1, RSQP_KKT_DUAL = 2, RSQP_KKT_COMPL = 4, RSQP_KKT_STAT = 8, RSQP_KKT_FIRST_ORDER_OPT = 16" in header

@@ -6,51 +6,28 @@ of tests/penalty_cases.py -- which is asserted here, from that run alone, before
 with it."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
 
 import penalty_cases as PC
+from abi_cases import assert_entry_points
 from conftest import ROOT
 
 NEW = ("rsqp_penalty_default_options", "rsqp_batch_handler_pair_lp", "rsqp_batch_handler_update_penalty")
 
 
 def test_entry_points_are_declared_exported_and_bound(capi):
-    main = open(os.path.join(ROOT, "include", "rsqp_hip.h")).read()
-    assert re.search(r'^#include "rsqp_hip_penalty.h"', main, flags=re.M)
-    header = open(os.path.join(ROOT, "include", "rsqp_hip_penalty.h")).read()
-    L = capi.lib()
-    for name in NEW:
-        assert re.search(r"\bint\s+%s\s*\(" % name, header), name
-        assert name in capi.PENALTY_SYMBOLS and hasattr(L, name), name
-        assert getattr(L, name).argtypes == capi.PENALTY_SYMBOLS[name][1]
-    declared = set(re.findall(r"^\s*int\s+(rsqp_\w+)\s*\(", header, flags=re.M))
-    assert declared == set(capi.PENALTY_SYMBOLS) == set(NEW)
-    # ... and in no other table or header
-    for table in (capi.SYMBOLS, capi.LANE_SYMBOLS, capi.HANDOVER_SYMBOLS, capi.LANE_WARM_SYMBOLS, capi.LANE_HOT_SYMBOLS,
-                  capi.DENSE_CHECK_SYMBOLS, capi.NLP_STEP_SYMBOLS):
-        assert not declared & set(table)
-    for other in sorted(os.listdir(os.path.join(ROOT, "include"))):
-        if other != "rsqp_hip_penalty.h":
-            text = open(os.path.join(ROOT, "include", other)).read()
-            for name in NEW:
-                assert not re.search(r"\b%s\s*\(" % name, text), (other, name)
+    # ... through a table of their own, and the struct layouts of the binding are the header's, field by field and in order
+    header = assert_entry_points(capi, "rsqp_hip_penalty.h", capi.PENALTY_SYMBOLS, NEW, structs=(
+        ("rsqp_penalty_options", capi.PenaltyOptions), ("rsqp_penalty_state", capi.PenaltyState)))
     for method in ("handler_pair_lp", "handler_update_penalty"):
         assert callable(getattr(capi.Batch, method)), method
     # the header says where J comes from, which layouts are refused, and what the failure path restores and what it leaves
     assert "READ IN PLACE" in header and "NON-CANONICAL LAYOUT" in header and "THE ASYMMETRY" in header
     assert "ARE PUT BACK TO THE FIRST SOLVE'S" in header
-    # the struct layouts of the binding are the header's, field by field and in order
-    for struct, cls in (("rsqp_penalty_options", capi.PenaltyOptions), ("rsqp_penalty_state", capi.PenaltyState)):
-        body = re.search(r"typedef struct \{([^{}]*)\} %s;" % struct, header).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        names = re.findall(r"[\s*](\w+)\s*[,;]", body)
-        assert names == [k for k, _ in cls._fields_], (struct, names)
     types = dict(capi.PenaltyOptions._fields_)
     assert types["penalty_iter_max"] is C.c_int and all(t is C.c_double for k, t in types.items() if k != "penalty_iter_max")
-    assert set(capi.PenaltyState.IN + capi.PenaltyState.INOUT + capi.PenaltyState.OUT) == {k for k, _ in capi.PenaltyState._fields_}
     # the sentence of rsqp_hip_nlp_step.h about the penalty bit points at the call
     assert "rsqp_batch_handler_update_penalty" in open(os.path.join(ROOT, "include", "rsqp_hip_nlp_step.h")).read()
 

@@ -12,46 +12,25 @@ import numpy as np
 import pytest
 
 import soc_cases as SC
+from abi_cases import assert_entry_points
 from conftest import ROOT
 
 NEW = ("rsqp_soc_default_options", "rsqp_batch_handler_soc_begin", "rsqp_batch_handler_soc_end", "rsqp_batch_set_objective")
 
 
 def test_entry_points_are_declared_exported_and_bound(capi):
-    main = open(os.path.join(ROOT, "include", "rsqp_hip.h")).read()
-    assert re.search(r'^#include "rsqp_hip_soc.h"', main, flags=re.M)
-    header = open(os.path.join(ROOT, "include", "rsqp_hip_soc.h")).read()
-    L = capi.lib()
-    for name in NEW:
-        assert re.search(r"\bint\s+%s\s*\(" % name, header), name
-        assert name in capi.SOC_SYMBOLS and hasattr(L, name), name
-        assert getattr(L, name).argtypes == capi.SOC_SYMBOLS[name][1]
-    declared = set(re.findall(r"^\s*int\s+(rsqp_\w+)\s*\(", header, flags=re.M))
-    assert declared == set(capi.SOC_SYMBOLS) == set(NEW)
-    # ... and in no other table or header
-    for table in (capi.SYMBOLS, capi.LANE_SYMBOLS, capi.HANDOVER_SYMBOLS, capi.LANE_WARM_SYMBOLS, capi.LANE_HOT_SYMBOLS,
-                  capi.DENSE_CHECK_SYMBOLS, capi.NLP_STEP_SYMBOLS, capi.PENALTY_SYMBOLS, capi.BAND_CHECK_SYMBOLS):
-        assert not declared & set(table)
-    for other in sorted(os.listdir(os.path.join(ROOT, "include"))):
-        if other != "rsqp_hip_soc.h":
-            text = open(os.path.join(ROOT, "include", other)).read()
-            for name in NEW:
-                assert not re.search(r"\b%s\s*\(" % name, text), (other, name)
+    # ... through a table of their own, and the struct layouts of the binding are the header's, field by field and in order
+    header = assert_entry_points(capi, "rsqp_hip_soc.h", capi.SOC_SYMBOLS, NEW, structs=(
+        ("rsqp_soc_options", capi.SocOptions), ("rsqp_soc_trial", capi.SocTrial)))
     for method in ("handler_soc_begin", "handler_soc_end", "set_objective"):
         assert callable(getattr(capi.Batch, method)), method
     # the header says which objective the second test reads, where H comes from, and what is saved and put back
     assert "THE CORRECTION QP'S OWN OBJECTIVE" in header and "composite_pred" in header and "READ IN PLACE" in header
     assert "ARE SAVED" in header and "ARE PUT BACK TO THE SAVED FIRST SOLVE'S" in header and "INSTEAD OF" in header
     assert (capi.SOC_TEST, capi.SOC_CORRECT) == (1, 2) and re.search(r"RSQP_SOC_TEST = 1, RSQP_SOC_CORRECT = 2", header)
-    # the struct layouts of the binding are the header's, field by field and in order; the trial begins as rsqp_nlp_trial does
-    for struct, cls in (("rsqp_soc_options", capi.SocOptions), ("rsqp_soc_trial", capi.SocTrial)):
-        body = re.search(r"typedef struct \{([^{}]*)\} %s;" % struct, header).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        names = re.findall(r"[\s*](\w+)\s*[,;]", body)
-        assert names == [k for k, _ in cls._fields_], (struct, names)
+    # the trial begins as rsqp_nlp_trial does
     nlp = [k for k, _ in capi.NlpTrial._fields_]
     assert [k for k, _ in capi.SocTrial._fields_][:len(nlp)] == nlp
-    assert set(capi.SocTrial.IN + capi.SocTrial.INOUT + capi.SocTrial.OUT) == {k for k, _ in capi.SocTrial._fields_}
     assert dict(capi.SocOptions._fields_)["composite_pred"] is C.c_int
     # the unit is built with the library, contraction off
     from restartsqp_amd import build
