@@ -68,10 +68,60 @@ extern "C" void rsqp_debug_lane_stamps(unsigned long long *out, int reset) {
 #ifndef RSQP_LANE_XVOTE
 #define RSQP_LANE_XVOTE 1
 #endif
+// the stores of a full wave's results and kept state (WaveRun): bit 0 x, y and the working sets, bit 1 the state's tableau, bit 2 the
+// state's tail go out write-through; a bit that is off keeps the plain store (tuning builds screen them, -DRSQP_LANE_WT=<bits>)
+#ifndef RSQP_LANE_WT
+#define RSQP_LANE_WT 7
+#endif
+// timing-only builds that price those stores (never shipped: they leave the pools unwritten): bit 0 gives a full wave's result pools
+// and its five per-lane words, bit 1 its state pool a buffer descriptor of ZERO records -- the range check drops every store through
+// it, the instruction stream and the waits stay. The launch's time against the product's is what the bytes cost, dirty lines included
+#ifndef RSQP_LANE_NOSTORE
+#define RSQP_LANE_NOSTORE 0
+#endif
 
 namespace {
 
 constexpr int MV = 8, WL = 64;
+typedef double v2d __attribute__((ext_vector_type(2)));
+typedef int v4i __attribute__((ext_vector_type(4)));
+typedef unsigned int v2u __attribute__((ext_vector_type(2)));
+typedef unsigned int v4u __attribute__((ext_vector_type(4)));
+// ---- a full wave's run of a pool (its 64 members' consecutive elements) as the target of its stores. WT: write-through (sc1) -- the
+// line leaves the L2 as the store is issued. A plain store leaves it there dirty until the launch ends; the write-back then runs
+// with every CU idle and the next launch of the stream waits for it (13.6 MB behind the headline launch, 111 MB, of which the L2s
+// hold 32 MiB, with the state kept; DESIGN.md 4.3b, "The results' stores"). The kernel that reads the pools next finds them in HBM,
+// not in this launch's L2. Operands, order and values are those of the plain store. The descriptor is the wave's own (base = its
+// run, records = the run's bytes): offsets stay small whatever the batch, and a store beyond the run is dropped, not performed
+template <bool WT, bool DROP = false> struct WaveRun {
+    static constexpr bool BUF = WT || DROP;
+    __amdgpu_buffer_rsrc_t r;
+    char *base;
+    __device__ __forceinline__ WaveRun(void *b, int bytes) {
+        if constexpr (BUF) {
+            // (wave-uniform by construction -- kernel arguments and blockIdx --; the descriptor wants that provable)
+            const unsigned long long a = (unsigned long long)b;
+            const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
+            r = __builtin_amdgcn_make_buffer_rsrc((void *)(((unsigned long long)hi << 32) | lo), 0,
+                                                  DROP ? 0 : __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
+        } else base = (char *)b;
+    }
+    static constexpr int AUX = WT ? 16 : 0;                 // (16: sc1)
+    // element k of the run, counted in 16 / 8 / 4 bytes
+    template <class V> __device__ __forceinline__ void put16(int k, V v) const {
+        static_assert(sizeof(V) == 16, "16 bytes per lane");
+        if constexpr (BUF) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, v), r, k * 16, 0, AUX);
+        else reinterpret_cast<V *>(base)[k] = v;
+    }
+    template <class V> __device__ __forceinline__ void put8(int k, V v) const {
+        static_assert(sizeof(V) == 8, "8 bytes per lane");
+        if constexpr (BUF) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, v), r, k * 8, 0, AUX);
+        else reinterpret_cast<V *>(base)[k] = v;
+    }
+#if RSQP_LANE_NOSTORE
+    __device__ __forceinline__ void put4(int k, int v) const { __builtin_amdgcn_raw_buffer_store_b32(v, r, k * 4, 0, AUX); }
+#endif
+};
 // loops over slots with COMPILE-TIME indices: the register arrays of the solver state are split into scalars before any other
 // transformation sees them (a run-time loop, even one that is fully unrolled later, leaves selects between member addresses
 // behind, and the whole state goes to scratch memory)
@@ -333,32 +383,33 @@ struct LaneT {
     }
     // the reverse for results: x / y as pairs in the order p(j); the working sets (the low halves of their slots) four ints at a time
     // in natural lane order (a 4-byte read is served in groups of 32 lanes, and four consecutive ints mostly share an owner)
-    template <int CH, bool EVEN> __device__ __forceinline__ void put_pairs(double *dst, int n, int p, const ldouble *T, int s0) const {
+    template <int CH, bool EVEN, bool WT> __device__ __forceinline__ void put_pairs(double *dst, int n, int p, const ldouble *T, int s0) const {
         static_assert((CH & 1) == 0, "pairs");
         Walk wk = walk<2>(n, p);
-        double2 *d2 = reinterpret_cast<double2 *>(dst) + p;
+        const WaveRun<WT, (RSQP_LANE_NOSTORE & 1) != 0> d2(dst, n * WL * 8);
         SFOR(c, CH / 2, if (2 * c < n) {
                  if (EVEN || c * WL + p < 32 * n) {
                      const ldouble *a = T + (s0 + wk.e) * WL + wk.qq;
-                     double2 v;
+                     v2d v;
                      v.x = a[0];
                      if constexpr (EVEN) v.y = a[WL];
                      else v.y = (wk.e + 1 == n ? T + s0 * WL + wk.qq + 1 : a + WL)[0];
-                     d2[c * WL] = v;
+                     d2.put16(c * WL + p, v);
                  }
                  next_group(wk, n);
              });
     }
-    template <int CH> __device__ __forceinline__ void put_quads(int *dst, int n, int lane, const ldouble *T, int s0) const {
+    template <int CH, bool WT> __device__ __forceinline__ void put_quads(int *dst, int n, int lane, const ldouble *T, int s0) const {
         typedef const __attribute__((address_space(3))) int clint;
         Walk wk = walk<4>(n, lane);
-        int4 *d4 = reinterpret_cast<int4 *>(dst) + lane;
+        const WaveRun<WT, (RSQP_LANE_NOSTORE & 1) != 0> d4(dst, n * WL * 4);
         SFOR(c, (CH + 3) / 4, if (4 * c < n) {
                  if (c * WL + lane < 16 * n) {
                      int v[4], qq = wk.qq, e = wk.e;
                      SFOR(u, 4, v[u] = ((clint *)(T + (s0 + e) * WL + qq))[0];
                           const bool wrap = e + 1 == n; e = wrap ? 0 : e + 1; qq = wrap ? qq + 1 : qq;);
-                     d4[c * WL] = make_int4(v[0], v[1], v[2], v[3]);
+                     v4i w; w.x = v[0]; w.y = v[1]; w.z = v[2]; w.w = v[3];
+                     d4.put16(c * WL + lane, w);
                  }
                  next_group(wk, n);
              });
@@ -371,10 +422,13 @@ struct LaneT {
     // of blocks (two doubles of one problem per instruction, consecutive lanes consecutive pairs): 0.075 ms.
     // The tableau part: both triangles in HBM (what the 8-lane kernel holds), from the upper one in the LDS slots
     // (live, WARM: bit qq = problem qq of the wave is in the launch; the others' blocks stay as they are)
-    __device__ __forceinline__ void state_put_tableau(double *sbase, long long stride, int nqw, int lane, const ldouble *T,
-                                                      unsigned long long live = ~0ull) const {
+    // (FULL: a full wave with every member in the launch -- no store of its is masked, and they go write-through by the run of the
+    //  pool, WaveRun)
+    template <bool FULL> __device__ __forceinline__ void state_put_tableau(double *sbase, long long stride, int nqw, int lane, const ldouble *T,
+                                                                           unsigned long long live = ~0ull) const {
         static_assert((N & 1) == 0, "pairs of a row");
         constexpr int PAIRS = N * N / 2;
+        const WaveRun<FULL && (RSQP_LANE_WT & 2), FULL && (RSQP_LANE_NOSTORE & 2)> run(sbase, (int)stride * WL * 8);
         // (a run-time loop: nothing here indexes a register array, and 50 unrolled trips were hoisted in front of each other until
         //  1 493 registers spilled)
 #pragma unroll 5
@@ -382,25 +436,32 @@ struct LaneT {
             const int m = t * WL + lane;
             const int qq = m / PAIRS, e = (m - qq * PAIRS) * 2, r = e / N, k = e - r * N;            // entries (r, k), (r, k + 1)
             const int hi0 = r > k ? r : k, lo0 = r > k ? k : r, hi1 = r > k + 1 ? r : k + 1, lo1 = r > k + 1 ? k + 1 : r;
-            double2 v;
+            v2d v;
             v.x = T[(((hi0 * (hi0 + 1)) >> 1) + lo0) * WL + qq]; v.y = T[(((hi1 * (hi1 + 1)) >> 1) + lo1) * WL + qq];
-            bool mine = qq < nqw;
-            if constexpr (WARM != 0) mine = mine && ((live >> (qq & 63)) & 1) != 0;
-            if (mine) *reinterpret_cast<double2 *>(sbase + (long long)qq * stride + e) = v;
+            if constexpr (FULL) run.put16((qq * (int)stride + e) >> 1, v);
+            else {
+                bool mine = qq < nqw;
+                if constexpr (WARM != 0) mine = mine && ((live >> (qq & 63)) & 1) != 0;
+                if (mine) *reinterpret_cast<v2d *>(sbase + (long long)qq * stride + e) = v;
+            }
         }
     }
     // the slot state + status words behind it: TAILD doubles (the ints as pairs), staged in LDS slots 0 .. in two halves
     static constexpr int TAILD = 96 + 10, THALF = TAILD / 2;
     static_assert(THALF <= NT, "the halves of the slot state pass through the tableau's slots");
-    __device__ __forceinline__ void state_put_tail_half(double *sbase, long long stride, int nqw, int lane, const ldouble *T, int half,
-                                                        unsigned long long live = ~0ull) const {
+    template <bool FULL> __device__ __forceinline__ void state_put_tail_half(double *sbase, long long stride, int nqw, int lane, const ldouble *T, int half,
+                                                                             unsigned long long live = ~0ull) const {
+        const WaveRun<FULL && (RSQP_LANE_WT & 4), FULL && (RSQP_LANE_NOSTORE & 2)> run(sbase, (int)stride * WL * 8);
 #pragma unroll 4
         for (int t = 0; t < THALF; t++) {
             const int m = t * WL + lane;
             const int qq = m / THALF, f = m - qq * THALF;
-            bool mine = qq < nqw;
-            if constexpr (WARM != 0) mine = mine && ((live >> (qq & 63)) & 1) != 0;
-            if (mine) sbase[(long long)qq * stride + N * N + half * THALF + f] = T[f * WL + qq];
+            if constexpr (FULL) run.put8(qq * (int)stride + N * N + half * THALF + f, (double)T[f * WL + qq]);
+            else {
+                bool mine = qq < nqw;
+                if constexpr (WARM != 0) mine = mine && ((live >> (qq & 63)) & 1) != 0;
+                if (mine) sbase[(long long)qq * stride + N * N + half * THALF + f] = T[f * WL + qq];
+            }
         }
     }
     // my slot state as the TAILD doubles behind the tableau: f < 48 field f / 8 (x g lo up gy y) of variable slot f % 8; f < 80 field
@@ -1602,21 +1663,27 @@ __device__ __forceinline__ void lane_qp_body(const QPPools &P, int nq, int maxWS
     double obj = 0.0;
     if (!results_first) obj = E.finish(refine);
     LSTAMP(3);
+    // what a full wave stores write-through (RSQP_LANE_WT)
+    constexpr bool WTR = (RSQP_LANE_WT & 1) != 0;
+    constexpr bool WTS = (RSQP_LANE_WT & 6) != 0 || (RSQP_LANE_NOSTORE & 2) != 0;
     if constexpr (KEEP) {
         // ---- the state first (its tableau part IS the LDS slots the rest is about to pass through)
         double *sbase = P.state + (long long)q0 * P.uni_state;
         double dg[N];
         SFOR(k, N, dg[k] = E.G[tri(k, k) * WL];);
+        // (a full wave, every member in the launch: write-through by the wave's run of the pool; any other wave masks its stores)
+        const bool full_state = nqw == WL && (!WARM || live_state == ~0ull) && (((size_t)P.state | (size_t)(P.uni_state << 3)) & 15) == 0;
+#define BYFULL(...) do { if (WTS && full_state) { constexpr bool FULL = true; __VA_ARGS__ } else { constexpr bool FULL = false; __VA_ARGS__ } } while (0)
         E.wave_sync();
-        E.state_put_tableau(sbase, P.uni_state, nqw, lane, T, live_state);
+        BYFULL(E.template state_put_tableau<FULL>(sbase, P.uni_state, nqw, lane, T, live_state););
         E.wave_sync();
         E.template tail_put_half<0>(E.G, dg, pivots);
         E.wave_sync();
-        E.state_put_tail_half(sbase, P.uni_state, nqw, lane, T, 0, live_state);
+        BYFULL(E.template state_put_tail_half<FULL>(sbase, P.uni_state, nqw, lane, T, 0, live_state););
         E.wave_sync();
         E.template tail_put_half<1>(E.G, dg, pivots);
         E.wave_sync();
-        E.state_put_tail_half(sbase, P.uni_state, nqw, lane, T, 1, live_state);
+        BYFULL(E.template state_put_tail_half<FULL>(sbase, P.uni_state, nqw, lane, T, 1, live_state););
         LSTAMP(15);
     }
     // ---- results (x, y = [bounds; constraints], working set, status / nWSR / objective): the member-major vectors leave through the
@@ -1634,10 +1701,10 @@ __device__ __forceinline__ void lane_qp_body(const QPPools &P, int nq, int maxWS
         if (nqw == WL && (!WARM || live == ~0ull) && (((size_t)P.x | (size_t)P.y | (size_t)P.ws_b | (size_t)P.ws_c) & 15) == 0) {
             // (a full wave: 16 bytes per lane, as it was staged)
             const int pp = ENG::pair_of(lane);
-            BYPARITY(nV, E.template put_pairs<MV, EV>(P.x + (long long)q0 * nV, nV, pp, T, SX););
-            BYPARITY(nV + nC, E.template put_pairs<MV + MC, EV>(P.y + (long long)q0 * (nV + nC), nV + nC, pp, T, SY););
-            E.template put_quads<MV>(P.ws_b + (long long)q0 * nV, nV, lane, T, SB);
-            if (nC > 0) E.template put_quads<MC>(P.ws_c + (long long)q0 * nC, nC, lane, T, SW);
+            BYPARITY(nV, E.template put_pairs<MV, EV, WTR>(P.x + (long long)q0 * nV, nV, pp, T, SX););
+            BYPARITY(nV + nC, E.template put_pairs<MV + MC, EV, WTR>(P.y + (long long)q0 * (nV + nC), nV + nC, pp, T, SY););
+            E.template put_quads<MV, WTR>(P.ws_b + (long long)q0 * nV, nV, lane, T, SB);
+            if (nC > 0) E.template put_quads<MC, WTR>(P.ws_c + (long long)q0 * nC, nC, lane, T, SW);
         } else {
         E.template put_block<MV>(P.x + (long long)q0 * nV, nV, nqw * nV, lane, T, SX, live);
         E.template put_block<MV + MC>(P.y + (long long)q0 * (nV + nC), nV + nC, nqw * (nV + nC), lane, T, SY, live);
@@ -1651,8 +1718,17 @@ __device__ __forceinline__ void lane_qp_body(const QPPools &P, int nq, int maxWS
     }
     if (q < nq && run) {
         const int st = E.status;
+#if RSQP_LANE_NOSTORE & 1
+        if (nqw == WL) {
+            const WaveRun<false, true> ws(P.status + q0, 0), wr(P.ret + q0, 0), wn(P.nwsr + q0, 0), wf(P.nflips + q0, 0), wo(P.obj + q0, 0);
+            ws.put4(lane, E.infeasible ? 100 + st : (E.unbounded ? 200 + st : st));
+            wr.put4(lane, rcode); wn.put4(lane, nWSR); wf.put4(lane, E.nflips); wo.put8(lane, obj);
+        } else
+#endif
+        {
         P.status[q] = E.infeasible ? 100 + st : (E.unbounded ? 200 + st : st);
         P.ret[q] = rcode; P.nwsr[q] = nWSR; P.nflips[q] = E.nflips; P.obj[q] = obj;
+        }
     }
     LSTAMP(4);
 }

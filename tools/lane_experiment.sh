@@ -1,6 +1,7 @@
 #!/bin/bash
 # Quick-turnaround tuning build of the lane-per-problem kernel (qp_lane.hip) into restartsqp_amd/lib/librsqp_exp.so;
-# select it with RSQP_LIB=<path>. Extra compiler flags as arguments (e.g. -DRSQP_STAMPS, -DRSQP_LANE_XVOTE=<bits>).
+# select it with RSQP_LIB=<path>. Extra compiler flags as arguments (e.g. -DRSQP_STAMPS, -DRSQP_LANE_XVOTE=<bits>,
+# -DRSQP_LANE_WT=<bits>, -DRSQP_LANE_NOSTORE=<bits>: a timing-only build that leaves its pools unwritten).
 set -e
 cd "$(dirname "$0")/.."
 OBJ=restartsqp_amd/lib/obj
